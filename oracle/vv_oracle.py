@@ -102,7 +102,9 @@ def dpm_set_timesteps(alphas_cumprod: Tensor, n: int):
     num_train = alphas_cumprod.shape[0]
     last_timestep = num_train  # lambda_min_clipped = -inf -> clipped_idx = 0 (dpm_solver.py:353-354)
     timesteps = np.linspace(0, last_timestep - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
-    sigmas = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy()
+    # the fp32 square root correctly rounded (float64 sqrt, rounded once): torch's vectorised fp32 `** 0.5` is not, and its last bit
+    # differs between CPU instruction sets, which would tie the fixtures to the CPU they were made on
+    sigmas = np.sqrt(((1 - alphas_cumprod) / alphas_cumprod).numpy().astype(np.float64)).astype(np.float32)
     sigmas = np.interp(timesteps, np.arange(0, len(sigmas)), sigmas)
     sigmas = np.concatenate([sigmas, [0]]).astype(np.float32)
     return timesteps, torch.from_numpy(sigmas)

@@ -1,6 +1,7 @@
 """End-to-end bf16 'mid' generate against the fp32 oracle with the fused Block1D kernel on and off (per-frame rel RMS)."""
 import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from conftest import rel_rms
 from test_hip_parity import _Tok
 from oracle import vv_oracle as O

@@ -1,5 +1,6 @@
 import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from conftest import load_golden, rel_rms
 from vibevoice_rocm_amd.config import VVConfig
 from vibevoice_rocm_amd.synth import synth_state_dict

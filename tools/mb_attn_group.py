@@ -1,5 +1,6 @@
 import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from vibevoice_rocm_amd import _lib as L
 from vibevoice_rocm_amd.config import VVConfig

@@ -1,6 +1,7 @@
 """Row-group balance of the streaming GEMV: persistent grid sizes that give every wave the same number of row groups."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 def bench(m, n, k, dual, blocks, iters=300):

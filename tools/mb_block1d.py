@@ -1,6 +1,7 @@
 """In-graph time of one fused Block1D launch (vv_block1d) at the per-frame shapes of the narrow conv stages."""
 import sys, time, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 L.check(lib.vv_init(), "init")

@@ -1,7 +1,8 @@
 """Where a streaming frame of the acoustic decoder / semantic encoder spends its time: vv_linear calls by shape (vv_prof, eager,
 HIP events) and, when run under rocprofv3 --kernel-trace --stats, every kernel by name."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 from vibevoice_rocm_amd.config import VVConfig
 from vibevoice_rocm_amd.modeling import VibeVoiceForConditionalGenerationInference

@@ -1,6 +1,7 @@
 """Streaming GEMV: bf16 weights vs weight-only fp8 (e4m3fn codes, 8-byte loads per lane), eager back-to-back launches on fresh weights."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 def bench(m, n, k, dual, f8, iters=200):

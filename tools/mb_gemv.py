@@ -1,5 +1,6 @@
 import sys, ctypes as C, torch, time
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 def bench(m, n, k, dual, blocks, iters=300, pro=1, mod=True, flags=0, copies=None):

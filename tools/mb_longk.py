@@ -1,6 +1,7 @@
 """Long-K down-projection GEMV (m=2 n=1536 k=8960, residual epilogue): waves that split K x persistent grid size."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 def bench(m, n, k, iters=300):

@@ -1,7 +1,8 @@
 """The hoisted adaLN modulation GEMM of the diffusion head (40 rows x [4608, 1536] bf16): fp32 x staged through LDS vs bf16 x
 streamed from global, 32- or 64-row tiles."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 def bench(m, n, k, xb, mt, iters=100):

@@ -1,5 +1,6 @@
 import sys, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd.config import VVConfig
 from vibevoice_rocm_amd.modeling import VibeVoiceForConditionalGenerationInference
 from vibevoice_rocm_amd.synth import synth_state_dict_torch

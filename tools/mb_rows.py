@@ -1,6 +1,7 @@
 import sys
 sys.argv=['x']
-sys.path.insert(0,'/root/repo/tools')
+import os
+sys.path.insert(0,os.path.dirname(os.path.abspath(__file__)))
 import mb_chain_lin as M
 L=M.L
 for m in (1,2,4):

@@ -1,7 +1,8 @@
 """Row-count scaling of the two GEMV kernels (VALU vs matrix-core) on the frame's big shapes: what batching dialogues into rows would cost."""
 import sys
 sys.argv = ['x']
-sys.path.insert(0, '/root/repo/tools')
+import os
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mb_chain_lin as M
 L = M.L
 for name, a, kw in (("head gate/up", (4608, 1536, True, 4), dict(mod=True, flags=L.LIN_W_REUSED)), ("head down", (1536, 4608, False, 4), dict(pro=0, epi=True, flags=L.LIN_W_REUSED)),

@@ -1,7 +1,8 @@
 """Steady-state vs per-call streaming rate of the GEMV kernels: the same kernel on a 16x taller matrix shows what the memory
 pipe sustains once launch ramp and tail are amortised (the gap is what a persistent chained kernel could recover)."""
 import sys, ctypes as C, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vibevoice_rocm_amd import _lib as L
 lib = L.load()
 

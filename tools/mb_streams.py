@@ -1,6 +1,7 @@
 """Throughput experiment: S independent utterances on one GPU, one Engine + HIP stream + host thread each (weights shared)."""
 import sys, time, threading, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from vibevoice_rocm_amd.config import VVConfig
 from vibevoice_rocm_amd.modeling import VibeVoiceForConditionalGenerationInference

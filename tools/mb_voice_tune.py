@@ -1,6 +1,7 @@
 """voice-prompt encode time (27 s prompt, no profiler) under vv_tune settings: python tools/mb_voice_tune.py key=value ..."""
 import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from vibevoice_rocm_amd.config import VVConfig
 from vibevoice_rocm_amd.modeling import VibeVoiceForConditionalGenerationInference

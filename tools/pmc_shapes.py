@@ -9,7 +9,8 @@ SHAPES = [(2, 4608, 1536, True), (2, 8960, 1536, True), (2, 1536, 4608, False), 
 N = 12
 if sys.argv[1] == "run":
     import ctypes as C, torch
-    sys.path.insert(0, "/root/repo")
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from vibevoice_rocm_amd import _lib as L
     lib = L.load()
     s = torch.cuda.current_stream().cuda_stream
