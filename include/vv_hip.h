@@ -262,13 +262,22 @@ int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const 
                    const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, void* ws,
                    const float* sde_noise /* [n_steps, latent] per-step variance noise of the SDE solver (dpm_solver.py:993-998) or NULL */,
                    vv_stream_t stream);
-/* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary, bf16 weights): cond[2 B, cond_dim] = rows
+/* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights): cond[2 B, cond_dim] = rows
  * {positive, negative} of utterance b at 2 b, 2 b + 1; noise[b * ld_noise ..], latent_out[b * ld_latent ..].  Every head matrix is streamed once
  * per solver step for all utterances.  ws: vv_head_ws_bytes_batch(h, n_steps, B) bytes. */
 size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B);
 int vv_head_sample_batch(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
                          const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
                          vv_stream_t stream);
+/* The same with the SDE solver (sde-dpmsolver++, coef[i].cn != 0): sde_noise[B][n_steps][latent] (utterance b at b * ld_sde, step i at
+ * i * latent) is the per-step variance noise, step i of utterance b adding coef[i].cn * sde_noise[b][i] to x - the row vv_head_sample takes
+ * at sde_noise + i * latent, so both give the same sample.  One launch before the step loop maps all of it into the solver state
+ * ([noisy_proj n ; n]); the fused boundary adds it in its epilogue.  sde_noise == NULL: the ODE solver, bit-identical to vv_head_sample_batch.
+ * ws: vv_head_ws_bytes_batch_sde(h, n_steps, B) bytes. */
+size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int B);
+int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                             const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
+                             const float* sde_noise, int64_t ld_sde, vv_stream_t stream);
 /* VibeVoiceDiffusionHead.forward alone (parity tests): x[R, latent], temb_rows[R, D], cond[R, cond_dim] -> v[R, latent] */
 int vv_head_forward(const vv_head* h, const float* x, const float* temb_rows, const float* cond, int R, float* v,
                     void* ws, vv_stream_t stream);

@@ -48,7 +48,9 @@ int vv_head_boundary_fused(const vv_head* h, const float* hrows, int64_t ldh, co
                            const vv_dpm_coef* k, float* Xs, float* Ms, float* h_out, int64_t ldh_out, float* latent_out, hipStream_t s);
 int vv_head_boundary_batch(const vv_head* h, const float* hrows, int64_t ldh, const float* shift, const float* scale, int64_t ld_mod, float cfg,
                            const vv_dpm_coef* k, float* Xs, float* Ms, int64_t state_stride, float* h_out, int64_t ldh_out, float* latent_out,
-                           int64_t latent_stride, int B, hipStream_t s);   // B dialogues per launch: rows 2 b, 2 b + 1; state / sample of b at b * stride
+                           int64_t latent_stride, int B, hipStream_t s,   // B dialogues per launch: rows 2 b, 2 b + 1; state / sample of b at b * stride
+                           const float* nx = nullptr, int64_t nx_stride = 0);   // SDE: + k->cn * (this step's NX of b at nx + b * nx_stride)
+int vv_head_sde_proj_fused(const vv_head* h, const float* sde_noise, int64_t ld_sde, int n_steps, int B, float* NX, hipStream_t s);   // NX[b][i] = [P n ; n], n = sde_noise + b * ld_sde + i * latent
 int vv_fused_init();
 int vv_head_pre_fused(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, int n_steps, void* c_bf16, const float* noise,
                       float* Xs, float* Ms, float* h0, int64_t ldh, hipStream_t s);   // cond_proj + silu(c0 + temb) rows (bf16) + solver-state init in one launch; 1 launched, 0 not covered

@@ -51,6 +51,29 @@ __global__ __launch_bounds__(256) void head_init_kernel(const WT* P, const float
   Ms[n] = 0.f;
 }
 
+// SDE solver: the variance noise of every step of every utterance mapped into the state space in ONE launch before the step loop,
+// NX[u][n] = [P n_u ; n_u] for the rows n_u = noise + (u / n_steps) * ld_noise + (u % n_steps) * latent (u = b * n_steps + i, blockIdx.y).
+// The boundary of step i then adds cn_i NX[b][i] to the state: P is linear, so X' = ... + cn [P n ; n] is x' = ... + cn n (dpm_solver.py:993-998).
+template <typename WT>
+__global__ __launch_bounds__(256) void head_sde_proj_kernel(const WT* P, const float* noise, int64_t ld_noise, int n_steps, int D, int latent, float* NX) {
+  extern __shared__ float nz[];
+  const int u = blockIdx.y, N = D + latent;
+  const float* nr = noise + (int64_t)(u / n_steps) * ld_noise + (int64_t)(u % n_steps) * latent;
+  for (int i = threadIdx.x; i < latent; i += blockDim.x) nz[i] = nr[i];
+  __syncthreads();
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float s;
+  if (n < D) {
+    s = 0.f;
+    const WT* pr = P + (int64_t)n * latent;
+    for (int j = 0; j < latent; ++j) s = fmaf(ldw(pr + j), nz[j], s);
+  } else {
+    s = nz[n - D];
+  }
+  NX[(int64_t)u * N + n] = s;
+}
+
 struct BoundaryArgs {
   const float* G;          // [D + latent, D] fp32
   const float* h; int64_t ldh;                      // [2, D] hidden rows after the last head layer {cond, uncond}
@@ -63,14 +86,17 @@ struct BoundaryArgs {
   int D, latent;
   // dialogues batched into one launch (blockIdx.y = b): hidden / modulation rows 2 b, 2 b + 1; solver state and sample of b at these strides
   int64_t state_stride, latent_stride;
+  // SDE instantiation only: this step's variance noise in state space, NX of b at nx + b * nx_stride ([D + latent]; head_sde_proj_kernel)
+  const float* nx; int64_t nx_stride;
 };
 
-template <int KU>
+template <int KU, bool SDE>
 __global__ __launch_bounds__(256) void head_boundary_kernel(BoundaryArgs a) {
   {
     const int b = blockIdx.y;
     a.h += 2 * b * a.ldh; a.shift += 2 * b * a.ld_mod; a.scale += 2 * b * a.ld_mod;
     a.Xs += b * a.state_stride; a.Ms += b * a.state_stride; a.h_out += 2 * b * a.ldh_out; a.latent_out += b * a.latent_stride;
+    if constexpr (SDE) a.nx += b * a.nx_stride;
   }
   __shared__ __attribute__((aligned(16))) float ys[KU * 512];
   __shared__ float red[4][2];
@@ -105,8 +131,11 @@ __global__ __launch_bounds__(256) void head_boundary_kernel(BoundaryArgs a) {
     }
   };
   float xs_cur = a.Xs[g < N ? g : 0], ms_cur = a.Ms[g < N ? g : 0];
+  float nx_cur = 0.f, nx_nxt = 0.f;
+  if constexpr (SDE) nx_cur = a.nx[g < N ? g : 0];
   issue(cur, g);
   float xs_nxt = a.Xs[g + gstride < N ? g + gstride : 0], ms_nxt = a.Ms[g + gstride < N ? g + gstride : 0];
+  if constexpr (SDE) nx_nxt = a.nx[g + gstride < N ? g + gstride : 0];
   issue(nxt, g + gstride);
   __builtin_amdgcn_sched_barrier(0);
 #define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
@@ -170,6 +199,7 @@ __global__ __launch_bounds__(256) void head_boundary_kernel(BoundaryArgs a) {
       const float x0 = a.k.alpha_s * xs_cur - a.k.sigma_s * z;
       float xt = a.k.cx * xs_cur - a.k.cd * x0;
       if (a.k.order == 2) xt -= 0.5f * a.k.cd * (a.k.rinv * (x0 - ms_cur));
+      if constexpr (SDE) xt = fmaf(a.k.cn, nx_cur, xt);        // variance noise of this step, as vv_dpm_proj adds it to x
       a.Xs[g] = xt;
       a.Ms[g] = x0;
       if (g < D) { a.h_out[g] = xt; a.h_out[a.ldh_out + g] = xt; }
@@ -179,7 +209,12 @@ __global__ __launch_bounds__(256) void head_boundary_kernel(BoundaryArgs a) {
 #pragma unroll
     for (int u = 0; u < KU; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; }
     xs_cur = xs_nxt; ms_cur = ms_nxt;
-    if (g + gstride < N) { xs_nxt = a.Xs[g + gstride]; ms_nxt = a.Ms[g + gstride]; issue(nxt, g + gstride); }
+    if constexpr (SDE) nx_cur = nx_nxt;
+    if (g + gstride < N) {
+      xs_nxt = a.Xs[g + gstride]; ms_nxt = a.Ms[g + gstride];
+      if constexpr (SDE) nx_nxt = a.nx[g + gstride];
+      issue(nxt, g + gstride);
+    }
   }
 }
 
@@ -188,7 +223,8 @@ template <int KU> void launch_boundary(const BoundaryArgs& a, int B, hipStream_t
   int blocks = (n + 3) / 4;
   if (blocks > 512) blocks = 512;
   if (B > 1 && blocks > 256) blocks = 256;         // B dialogues share the chip
-  hipLaunchKernelGGL((head_boundary_kernel<KU>), dim3(blocks, B), dim3(256), 0, s, a);
+  if (a.nx) hipLaunchKernelGGL((head_boundary_kernel<KU, true>), dim3(blocks, B), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((head_boundary_kernel<KU, false>), dim3(blocks, B), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -780,6 +816,18 @@ int vv_head_init_fused(const vv_head* h, const float* noise, float* Xs, float* M
   return 0;
 }
 
+int vv_head_sde_proj_fused(const vv_head* h, const float* sde_noise, int64_t ld_sde, int n_steps, int B, float* NX, hipStream_t s) {
+  const int n = h->D + h->latent;
+  const dim3 grid((n + 255) / 256, B * n_steps);
+  const size_t lds = (size_t)h->latent * sizeof(float);
+  if (h->wdt == VV_F32)
+    hipLaunchKernelGGL((head_sde_proj_kernel<float>), grid, dim3(256), lds, s, (const float*)h->noisy_proj, sde_noise, ld_sde, n_steps, h->D, h->latent, NX);
+  else
+    hipLaunchKernelGGL((head_sde_proj_kernel<bf16_t>), grid, dim3(256), lds, s, (const bf16_t*)h->noisy_proj, sde_noise, ld_sde, n_steps, h->D, h->latent, NX);
+  VV_CHECK_LAUNCH("vv_head_sde_proj_fused");
+  return 0;
+}
+
 bool vv_head_boundary_supported(const vv_head* h) {
   return h->fused_g != nullptr && h->D % 8 == 0 && h->D <= 4096 && ((uintptr_t)h->fused_g % 16 == 0);
 }
@@ -792,9 +840,10 @@ int vv_head_boundary_fused(const vv_head* h, const float* hrows, int64_t ldh, co
 // B dialogues in one launch: hidden rows [2 B] (dialogue b: rows 2 b, 2 b + 1), modulation rows likewise, solver state / sample of b at b * stride
 int vv_head_boundary_batch(const vv_head* h, const float* hrows, int64_t ldh, const float* shift, const float* scale, int64_t ld_mod, float cfg,
                            const vv_dpm_coef* k, float* Xs, float* Ms, int64_t state_stride, float* h_out, int64_t ldh_out, float* latent_out,
-                           int64_t latent_stride, int B, hipStream_t s) {
+                           int64_t latent_stride, int B, hipStream_t s, const float* nx, int64_t nx_stride) {
   BoundaryArgs a;
   a.state_stride = state_stride; a.latent_stride = latent_stride;
+  a.nx = k->cn != 0.f ? nx : nullptr; a.nx_stride = nx_stride;     // cn == 0 (the ODE solver, the SDE solver's last step): the ODE instantiation
   a.G = h->fused_g; a.h = hrows; a.ldh = ldh; a.shift = shift; a.scale = scale; a.ld_mod = ld_mod; a.eps = h->eps; a.cfg = cfg; a.k = *k;
   a.Xs = Xs; a.Ms = Ms; a.h_out = h_out; a.ldh_out = ldh_out; a.latent_out = latent_out; a.D = h->D; a.latent = h->latent;
   switch ((h->D + 511) / 512) {

@@ -356,15 +356,31 @@ extern "C" size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B) {
          al(vv_gemv_rows_part_floats(h->D, 0)) + al(vv_gemv_rows_tickets(h->ffn));
 }
 
-extern "C" int vv_head_sample_batch(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
-                                    const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
-                                    vv_stream_t stream) {
-  if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "vv_head_sample_batch: null pointer");
-  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 4) return vv_set_error(VV_E_ARG, "vv_head_sample_batch: n_steps=%d layers=%d B=%d (1..4)", n_steps, h->layers, B);
-  for (int i = 0; i < n_steps; ++i)
-    if (coef[i].cn != 0.f) return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: the SDE solver is served per utterance (vv_head_sample)");
+// the SDE form: the same workspace with the variance noise of every step of every utterance in state space, NX [B][n_steps][D + latent], at its end
+extern "C" size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int B) {
+  const size_t base = vv_head_ws_bytes_batch(h, n_steps, B);
+  if (!base) return 0;
+  return base + al((size_t)B * n_steps * (h->D + h->latent));
+}
+
+// sde_noise == NULL: the ODE solver (every launch identical to vv_head_sample_batch's); else [B][n_steps][latent] at utterance stride ld_sde,
+// step i of utterance b adding coef[i].cn * sde_noise[b][i] to x (the noise vv_head_sample takes after step i).  sde_fn == NULL: the ODE-only
+// entry point vv_head_sample_batch, which refuses SDE coefficients
+static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                             const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
+                             const float* sde_noise, int64_t ld_sde, vv_stream_t stream) {
+  const char* fn = sde_fn ? sde_fn : "vv_head_sample_batch";
+  if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
+  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 4) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..4)", fn, n_steps, h->layers, B);
+  if (!sde_fn)
+    for (int i = 0; i < n_steps; ++i)
+      if (coef[i].cn != 0.f) return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: the SDE solver is served by vv_head_sample_batch_sde");
+  if (sde_noise && ld_sde < (int64_t)n_steps * h->latent) return vv_set_error(VV_E_ARG, "%s: ld_sde=%lld < n_steps * latent", fn, (long long)ld_sde);
+  if (!sde_noise)
+    for (int i = 0; i < n_steps; ++i)
+      if (coef[i].cn != 0.f) return vv_set_error(VV_E_ARG, "%s: the SDE solver step needs its variance noise", fn);
   if (h->wdt != VV_BF16 || !vv_head_boundary_supported(h) || h->D % 32)
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: needs bf16 weights and the fused solver boundary (vv_head.fused_g)");
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: needs bf16 weights and the fused solver boundary (vv_head.fused_g)", fn);
   hipStream_t s = (hipStream_t)stream;
   const int D = h->D, R2 = 2 * B;
   const size_t R = (size_t)R2 * n_steps;
@@ -382,7 +398,9 @@ extern "C" int vv_head_sample_batch(const vv_head* h, const float* cond, int64_t
   const size_t rpart_n = vv_gemv_rows_part_floats(h->D, 0), rtick_n = vv_gemv_rows_tickets(h->ffn);
   float* rpart = cv.take(rpart_n);
   int* rtick = reinterpret_cast<int*>(cv.take(rtick_n));
-  if (hipMemsetAsync(rtick, 0, rtick_n * sizeof(int), s) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_head_sample_batch: memset");
+  if (hipMemsetAsync(rtick, 0, rtick_n * sizeof(int), s) != hipSuccess) return vv_set_error(VV_E_HIP, "%s: memset", fn);
+  float* NX = sde_noise ? cv.take((size_t)B * n_steps * sst) : nullptr;        // carved last: the ODE layout is that of vv_head_ws_bytes_batch
+  if (NX) VV_TRY(vv_head_sde_proj_fused(h, sde_noise, ld_sde, n_steps, B, NX, s));
   // step-invariant work: cond_proj on all rows, silu(cond_proj(cond) + t_emb(t_i)) as bf16 rows [step][2 B], every adaLN modulation
   vv_lin_args a = lin_base(cond, ld_cond, R2, h->cond_proj, D, h->cond_dim, h->wdt, c0, D);
   VV_TRY(vv_linear_ws(&a, nullptr, nullptr, rpart, rpart_n, rtick, rtick_n, stream));
@@ -405,9 +423,24 @@ extern "C" int vv_head_sample_batch(const vv_head* h, const float* cond, int64_t
       VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream));
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
-    VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s));
+    VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,
+                                  NX ? NX + (size_t)i * sst : nullptr, (int64_t)n_steps * sst));
   }
   return 0;
+}
+
+extern "C" int vv_head_sample_batch(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                                    const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
+                                    vv_stream_t stream) {
+  return head_sample_batch(nullptr, h, cond, ld_cond, noise, ld_noise, temb, coef, n_steps, cfg_scale, latent_out, ld_latent, B, ws,
+                           nullptr, 0, stream);
+}
+
+extern "C" int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                                        const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
+                                        const float* sde_noise, int64_t ld_sde, vv_stream_t stream) {
+  return head_sample_batch("vv_head_sample_batch_sde", h, cond, ld_cond, noise, ld_noise, temb, coef, n_steps, cfg_scale, latent_out, ld_latent, B, ws,
+                           sde_noise, ld_sde, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

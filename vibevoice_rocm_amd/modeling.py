@@ -290,7 +290,7 @@ class VibeVoiceForConditionalGenerationInference:
                 raise NotImplementedError("refresh_negative=False is built for batch size 1 only")
             rb = kwargs.get("row_batch", self.row_batch)
             fn = self._generate_lockstep
-            if rb and self.row_batch_min <= B <= 16 and sample_fn is None and self.dtype == torch.bfloat16 and self.weight_quant is None and not self.engine.sde:
+            if rb and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and self.weight_quant is None:
                 fn = self._generate_rowbatch      # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py)
             return fn(input_ids, attention_mask, speech_input_mask, conn_all, special, cfg_scale, max_new_tokens, max_length_times,
                                            forced_tokens, None if noise is None else torch.as_tensor(noise), None if sde_noise is None else torch.as_tensor(sde_noise),
@@ -343,9 +343,10 @@ class VibeVoiceForConditionalGenerationInference:
             n = len(self._lanes)             # lanes past LANES_IN_FLIGHT share the stream of lane n % LANES_IN_FLIGHT: see _generate_lockstep
             eng = Engine(self.config, None, device=self.device, dtype=self.dtype, use_graphs=self._use_graphs, weight_quant=self.weight_quant,
                          stream=self._lanes[n % LANES_IN_FLIGHT].stream if n >= LANES_IN_FLIGHT else None, weights_from=self.engine)
-            eng.scheduler = self.engine.scheduler
             self._lanes.append(eng)
         eng = self._lanes[b]
+        # a new lane starts on its own (ODE) schedule: taking over the main engine's scheduler goes through set_steps, which rebuilds the
+        # solver tables (sde-dpmsolver++ included) - assigning the object alone would leave the lane's tables on the old solver
         if eng.scheduler is not self.engine.scheduler or eng.n_steps != self.engine.n_steps:
             eng.scheduler = self.engine.scheduler
             eng.set_steps(self.engine.n_steps)
@@ -555,8 +556,9 @@ class VibeVoiceForConditionalGenerationInference:
         (rowbatch.RowBatch: one Qwen2 decode step with 2 B rows, one diffusion sampling with 2 B rows; the conv tokenizers stay per dialogue on
         their lanes' streams).  5..16 dialogues run as ceil(B / 4) row batches inside the same loop, all on the main stream: each step enqueues A and
         H of every batch, then the conv tails - a batch's tails overlap the other batches' A and H.  Token handling, the draws' order, speculation and rollback
-        are those of the lock-step loop; results agree with the lanes to the rounding of the matrix-core GEMV (activations as bf16 hi + lo,
-        ~2e-6 relative per product)."""
+        are those of the lock-step loop: with do_sample every row batch's logits are read back once per step and the tokens drawn in ascending
+        dialogue order, then the noise rows (SDE solver: n_steps more per step), so a seeded call draws what the lanes draw; results agree with the
+        lanes to the rounding of the matrix-core GEMV (activations as bf16 hi + lo, ~2e-6 relative per product)."""
         from .rowbatch import RowBatch
         cfg = self.config
         B, Lp = input_ids.shape
@@ -590,6 +592,8 @@ class VibeVoiceForConditionalGenerationInference:
         per_list = forced_tokens is not None and len(forced_tokens) > 0 and isinstance(forced_tokens[0], (list, tuple))
         ftok = [(forced_tokens[b] if per_list else forced_tokens) for b in range(B)]
         nz = [(noise[b] if (noise is not None and noise.dim() == 3) else noise) for b in range(B)]
+        snz = [(sde_noise[b] if (sde_noise is not None and sde_noise.dim() == 4) else sde_noise) for b in range(B)]
+        sde = lanes[0].sde
         x0s, off = [], 0
         with torch.cuda.stream(self.engine.stream):
             for b in range(B):
@@ -609,7 +613,7 @@ class VibeVoiceForConditionalGenerationInference:
         prev_tok = [None] * B
         pending = []
         ours = [False] * max(B, getattr(audio_streamer, "batch_size", B) if audio_streamer is not None else B)
-        speculate = self.speculative_frames and self._use_graphs
+        speculate = self.speculative_frames and sample_fn is None and self._use_graphs
 
         def deliver():
             if audio_streamer is None or not pending:
@@ -653,9 +657,28 @@ class VibeVoiceForConditionalGenerationInference:
                 for b in live:
                     rb_of[b].prefill(loc[b], x0s[b], chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=st_embed)
                 for b in live:
-                    toks[b] = rb_of[b].first_token(loc[b], forced[b])
+                    toks[b] = rb_of[b].first_token(loc[b], forced[b], sample_fn)
                     if toks[b] == SD:
                         rb_of[b].commit_negative(loc[b])
+            elif sample_fn is not None:
+                # do_sample: A1 of every row batch, ONE wait for all their logits, the tokens drawn in ascending dialogue order (the lanes' order),
+                # then A2 with them as forced tokens.  No speculation (the token is known only once the host has drawn it), as on the lanes
+                plan = []
+                for rb, idxs in groups:
+                    lv = [b for b in idxs if b in forced]
+                    if lv:
+                        rb.decode_logits()
+                        plan.append((rb, lv))
+                deliver()
+                lg = {}
+                for rb, lv in plan:
+                    lh = rb.logits_end()
+                    lg.update({b: lh[loc[b]] for b in lv})
+                for b in live:
+                    rb = rb_of[b]
+                    toks[b] = forced[b] if forced[b] is not None else int(sample_fn(lg[b][: len(rb.valid_ids)].clone(), rb.valid_ids))
+                for rb, lv in plan:
+                    rb.decode_commit(ST, SD, {loc[b]: toks[b] for b in lv})
             else:
                 # graph A of every row batch; a batch in its steady state (every live dialogue diffusing, noise injected) gets its diffusion
                 # sampling enqueued speculatively behind it.  The conv tails follow once all A / H are queued: each batch's tails are enqueued
@@ -665,10 +688,12 @@ class VibeVoiceForConditionalGenerationInference:
                     lv = [b for b in idxs if b in forced]
                     if not lv:
                         continue
-                    spec = speculate and all(prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) for b in lv)
+                    spec = speculate and all(prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
+                                             (not sde or (snz[b] is not None and frame[b] < len(snz[b]))) for b in lv)
                     rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv})
                     if spec:
-                        rb.speech_begin([loc[b] for b in lv], {loc[b]: nz[b][frame[b]] for b in lv})
+                        rb.speech_begin([loc[b] for b in lv], {loc[b]: nz[b][frame[b]] for b in lv},
+                                        {loc[b]: snz[b][frame[b]] for b in lv} if sde else None)
                     plan.append((rb, lv, spec))
                 deliver()                  # the previous step's chunks (their copies completed long ago), before the host waits for a sampler
                 for rb, lv, spec in plan:
@@ -704,12 +729,18 @@ class VibeVoiceForConditionalGenerationInference:
             todo = [b for b in diffusing if b not in speculated]
             if todo:
                 need = [b for b in todo if nz[b] is None or frame[b] >= len(nz[b])]
-                drawn = torch.randn(2 * len(need), cfg.latent)[: len(need)] if need else None     # the reference's draw for n diffusing samples (:699)
+                drawn, sdrawn = None, None
+                if need:       # the reference's draws for n diffusing samples (:699; SDE: n_steps more, dpm_solver.py:993-998), as _generate_lockstep's draw()
+                    n = len(need)
+                    drawn = torch.randn(2 * n, cfg.latent)[:n]
+                    if sde:
+                        sdrawn = torch.stack([torch.randn(2 * n, cfg.latent)[:n] for _ in range(lanes[0].n_steps)], dim=1)
                 rows = {b: (drawn[need.index(b)] if b in need else nz[b][frame[b]]) for b in todo}
+                srows = {b: (sdrawn[need.index(b)] if b in need else snz[b][frame[b]]) for b in todo} if sde else None
                 for rb, idxs in groups:
                     mine = [b for b in todo if rb_of[b] is rb]
                     if mine:
-                        rb.speech([loc[b] for b in mine], {loc[b]: rows[b] for b in mine})
+                        rb.speech([loc[b] for b in mine], {loc[b]: rows[b] for b in mine}, {loc[b]: srows[b] for b in mine} if sde else None)
             for rb, _ in groups:
                 rb.flush()                 # the conv tails are enqueued from worker threads: the chunk copies below must queue behind them
             for b in diffusing:                                                                     # :571-670

@@ -6,8 +6,11 @@ B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in on
   graph A   Qwen2 decode step with R = 2 B rows (dialogue b = rows {2 b: positive, 2 b + 1: negative} of x, lens and one KV cache with 2 B
             rows): every weight matrix is read once for all dialogues (4..8 rows: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
             fragment-major weight copies), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
-            bookkeeping per dialogue;
-  graph H   vv_head_sample_batch: the CFG diffusion sampler for all B utterances, 2 B rows through every head matrix per solver step.
+            bookkeeping per dialogue.  With do_sample it splits as Engine.step_decode does: A1 = the decode step and the constrained logits
+            (no position bookkeeping), one host read-back of every row batch's logits, the tokens drawn on the host, A2 = the bookkeeping with
+            those tokens as forced tokens;
+  graph H   vv_head_sample_batch(_sde): the CFG diffusion sampler for all B utterances, 2 B rows through every head matrix per solver step
+            (the SDE solver: with the per-step variance noise of every utterance, uploaded with the initial noise).
 
 The conv tokenizers (acoustic decode, semantic encode) and the connectors stay per dialogue - each has its own streaming state - and run as
 B concurrent hipGraphs on the lanes' streams between H and the next A (events fork / join them), exactly the launch sequences the lanes use.
@@ -73,6 +76,7 @@ class RowBatch:
             self.forced_dev = torch.full((B,), -1, **i32)
             self.active_dev = torch.ones(B, **i32)
             self.logits = torch.zeros(B, 8, **f32)
+            self.logits_host = torch.zeros(B, 8, dtype=torch.float32).pin_memory()
             self.noise_dev = torch.zeros(B, cfg.latent, **f32)
             self.latent = torch.zeros(B, cfg.latent, **f32)
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
@@ -98,7 +102,10 @@ class RowBatch:
         self._kv_t = None
         self._graphs: Dict[tuple, int] = {}
         self._head_ws = None
-        self._head_steps = 0
+        self._head_temb = None          # the lane's t_embedder table the head workspace / noise buffers were sized for (a new one on any set_steps)
+        self.sde = False
+        self.sde_noise_dev = None
+        self.sde_noise_host = None
         self.valid_ids: List[int] = []
         self._w_valid = None
         self._ids_dev = None
@@ -180,9 +187,17 @@ class RowBatch:
                 self._ck(self.lib.vv_gather_rows(eng.w.lm_head.data_ptr(), eng.w.wdt, cfg.hidden, arr, len(ids), self._w_valid.data_ptr(), self.sp), "vv_gather_rows")
                 self._ids_dev = torch.tensor(ids, dtype=torch.int32, device=self.device)
                 self._drop_graphs()
-            if self._head_steps != eng.n_steps:
-                self._head_ws = torch.empty(self.lib.vv_head_ws_bytes_batch(C.byref(eng.w.head), eng.n_steps, B), dtype=torch.uint8, device=self.device)
-                self._head_steps = eng.n_steps
+            if self._head_temb is not eng.temb:
+                # a new schedule (step count or solver): graph H captured the old t_embedder table, coefficients and buffers
+                self.sde = eng.sde
+                ws_bytes = (self.lib.vv_head_ws_bytes_batch_sde if self.sde else self.lib.vv_head_ws_bytes_batch)(C.byref(eng.w.head), eng.n_steps, B)
+                self._head_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+                if self.sde:
+                    self.sde_noise_dev = torch.zeros(B, eng.n_steps, cfg.latent, dtype=torch.float32, device=self.device)
+                    self.sde_noise_host = torch.zeros(2, B, eng.n_steps, cfg.latent, dtype=torch.float32).pin_memory()
+                else:
+                    self.sde_noise_dev = self.sde_noise_host = None
+                self._head_temb = eng.temb
                 self._drop_graphs()
             self.lens.zero_()
             self.frame_ctr.zero_()
@@ -235,16 +250,20 @@ class RowBatch:
         with torch.cuda.stream(self.stream):
             self.lens[2 * b + 1] = 1
 
-    def first_token(self, b: int, forced: Optional[int]) -> int:
-        """Token selection right after the prefill of dialogue b (hidden[2 b] holds its last prompt state)."""
+    def first_token(self, b: int, forced: Optional[int], sample_fn=None) -> int:
+        """Token selection right after the prefill of dialogue b (hidden[2 b] holds its last prompt state).  With `sample_fn(logits, ids) -> token`
+        (do_sample) the constrained logits are read back and the drawn token is selected as a forced one (Engine.first_token)."""
         nv = len(self.valid_ids)
         with torch.cuda.stream(self.stream):
-            self._set_forced({b: forced})
             a = L.LinArgs()
             a.x, a.ldx, a.m = self.hidden[2 * b].data_ptr(), self.cfg.hidden, 1
             a.w, a.n, a.k, a.wdt = self._w_valid.data_ptr(), nv, self.cfg.hidden, L.VV_BF16
             a.out, a.ldo = self.logits[b].data_ptr(), nv
             self._ck(self.lib.vv_linear(C.byref(a), self.sp), "lm_head")
+        if sample_fn is not None and forced is None:
+            forced = int(sample_fn(self.read_logits()[b, :nv].clone(), self.valid_ids))
+        with torch.cuda.stream(self.stream):
+            self._set_forced({b: forced})
             self._ck(self.lib.vv_argmax_ids(self.logits[b].data_ptr(), nv, self._ids_dev.data_ptr(), self.token_dev[b:].data_ptr(),
                                             self.forced_dev[b:].data_ptr(), self.sp), "vv_argmax_ids")
             self.token_host.copy_(self.token_dev, non_blocking=True)
@@ -283,8 +302,32 @@ class RowBatch:
                                             self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.active_dev.data_ptr(), self.sp),
                  "vv_llm_tail_batch")
 
+    def _seq_A1(self):
+        """the decode step and the constrained logits of every dialogue; positions stay (lens / frame_counter NULL)"""
+        eng, B, H = self.main, self.B, self.cfg.hidden
+        self._ck(self.lib.vv_llm_forward(C.byref(eng.w.llm), C.byref(self.kv), self.x.data_ptr(), H, 2 * B, self.lens.data_ptr(), None, None, 0,
+                                         self._llm_ws.data_ptr(), self.sp), "vv_llm_forward")
+        self._ck(self.lib.vv_llm_tail_batch(C.byref(eng.w.llm), self._llm_ws.data_ptr(), H, B, self.hidden.data_ptr(), H, self._w_valid.data_ptr(),
+                                            len(self.valid_ids), self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(), None,
+                                            None, 0, 0, None, None, self.sp), "vv_llm_tail_batch")
+
+    def _seq_A2(self, tok_start, tok_diff):
+        """the tail again on the same rows (deterministic: hidden / logits are rewritten with the same values), now with the drawn tokens forced
+        and the position bookkeeping of every live dialogue"""
+        eng, B, H = self.main, self.B, self.cfg.hidden
+        self._ck(self.lib.vv_llm_tail_batch(C.byref(eng.w.llm), self._llm_ws.data_ptr(), H, B, self.hidden.data_ptr(), H, self._w_valid.data_ptr(),
+                                            len(self.valid_ids), self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(),
+                                            self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(),
+                                            self.active_dev.data_ptr(), self.sp), "vv_llm_tail_batch")
+
     def _seq_H(self, cfg_scale):
         eng, cfg = self.main, self.cfg
+        if self.sde:
+            self._ck(self.lib.vv_head_sample_batch_sde(C.byref(eng.w.head), self.hidden.data_ptr(), cfg.hidden, self.noise_dev.data_ptr(), cfg.latent,
+                                                       eng.temb.data_ptr(), eng._coefs, eng.n_steps, cfg_scale, self.latent.data_ptr(), cfg.latent, self.B,
+                                                       self._head_ws.data_ptr(), self.sde_noise_dev.data_ptr(), eng.n_steps * cfg.latent, self.sp),
+                     "vv_head_sample_batch_sde")
+            return
         self._ck(self.lib.vv_head_sample_batch(C.byref(eng.w.head), self.hidden.data_ptr(), cfg.hidden, self.noise_dev.data_ptr(), cfg.latent,
                                                eng.temb.data_ptr(), eng._coefs, eng.n_steps, cfg_scale, self.latent.data_ptr(), cfg.latent, self.B,
                                                self._head_ws.data_ptr(), self.sp), "vv_head_sample_batch")
@@ -339,20 +382,55 @@ class RowBatch:
         self._tok_event.synchronize()
         return [int(t) for t in self.token_host]
 
-    def speech(self, which: List[int], noise: Dict[int, torch.Tensor]):
+    def decode_logits(self):
+        """do_sample, first half: graph A1 for all dialogues + the asynchronous copy of their constrained logits; the caller enqueues this for
+        every row batch of the step before it waits for any (`logits_end`), then hands the drawn tokens to `decode_commit`."""
+        with torch.cuda.stream(self.stream):
+            self._join_lanes()
+            self._run("A1", self._seq_A1)
+            self.logits_host.copy_(self.logits, non_blocking=True)
+            self._tok_event.record(self.stream)
+
+    def logits_end(self) -> torch.Tensor:
+        """[B][8] constrained logits of the step (row b: dialogue b, columns: valid_ids)"""
+        self._tok_event.synchronize()
+        return self.logits_host
+
+    def read_logits(self) -> torch.Tensor:
+        with torch.cuda.stream(self.stream):
+            self.logits_host.copy_(self.logits, non_blocking=True)
+            self._tok_event.record(self.stream)
+        return self.logits_end()
+
+    def decode_commit(self, tok_start: int, tok_diff: int, tokens: Dict[int, int]):
+        """do_sample, second half: graph A2 with `tokens` (every live dialogue's drawn or forced token) as forced tokens"""
+        with torch.cuda.stream(self.stream):
+            self._set_forced(tokens)
+            self._run("A2", self._seq_A2, int(tok_start), int(tok_diff))
+            self._tok_event.record(self.stream)
+
+    def speech(self, which: List[int], noise: Dict[int, torch.Tensor], sde_noise: Optional[Dict[int, torch.Tensor]] = None):
         """Diffusion sampling for the whole batch (graph H), then the conv tail of the dialogues in `which`, each on its own stream."""
-        self.speech_begin(which, noise)
+        self.speech_begin(which, noise, sde_noise)
         self.speech_tails(which)
 
-    def speech_begin(self, which: List[int], noise: Dict[int, torch.Tensor]):
-        """noise upload + graph H on the main stream"""
+    def speech_begin(self, which: List[int], noise: Dict[int, torch.Tensor], sde_noise: Optional[Dict[int, torch.Tensor]] = None):
+        """noise upload (the SDE solver: with every step's variance noise [n_steps, latent] per dialogue) + graph H on the main stream"""
         cfg = self.cfg
+        if self.sde and (sde_noise is None or any(b not in sde_noise or sde_noise[b] is None for b in which)):
+            raise L.VVError("the SDE solver needs the per-step variance noise [n_steps, latent] of every diffusing dialogue")
         with torch.cuda.stream(self.stream):
             self._noise_k ^= 1
             nh = self.noise_host[self._noise_k]
             for b in which:
                 nh[b].copy_(noise[b].reshape(-1)[: cfg.latent])
             self.noise_dev.copy_(nh, non_blocking=True)
+            if self.sde:
+                sh = self.sde_noise_host[self._noise_k]
+                n_steps = sh.shape[1]
+                for b in which:
+                    sh[b].copy_(sde_noise[b].reshape(n_steps, -1)[:, : cfg.latent])
+                self.sde_noise_dev.copy_(sh, non_blocking=True)
             self._run("H", self._seq_H, float(self.cfg_scale))
             self._head_event.record(self.stream)
             if self._timing is not None and self._tcur is not None:
