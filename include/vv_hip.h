@@ -28,15 +28,16 @@ extern "C" {
 
 typedef void* vv_stream_t; /* hipStream_t */
 
-enum { VV_F32 = 0, VV_BF16 = 1, VV_FP8 = 2 /* e4m3fn bytes + per-output-row fp32 scale (vv_lin_args.wscale); streaming GEMV (m <= 2) only */ };
+enum { VV_F32 = 0, VV_BF16 = 1, VV_FP8 = 2 /* e4m3fn bytes + per-output-row fp32 scale (vv_lin_args.wscale); streaming GEMV (m <= 2, row-major) or
+                                             3..8-row matrix-core GEMV (VV_LIN_W_FRAG, fp8 fragment-major) only */ };
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
 /* vv_lin_args.flags: bf16 activation hand-off between two matrix-core GEMMs (x / out point at bf16 [m, ld] arrays, no
  * prologue on a bf16 x), a hint that the weights are re-read soon (keep them cacheable instead of streaming them
  * non-temporally: the diffusion head's matrices are reused by every one of the N solver steps of a frame), and
- * VV_LIN_W_FRAG: w / w2 point at the fragment-major copies of the matrices (vv_llm_layer.f_*; 3..8 rows, bf16, n % 16 == 0,
- * k % 32 == 0 - any other call with this flag is an error) */
+ * VV_LIN_W_FRAG: w / w2 point at the fragment-major copies of the matrices (vv_llm_layer.f_*; 3..8 rows, n % 16 == 0, bf16 with k % 32 == 0 or
+ * fp8 codes with k % 64 == 0 and wscale (w2scale) - any other call with this flag is an error) */
 enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8 };
 
 const char* vv_last_error(void);
@@ -177,8 +178,13 @@ typedef struct vv_llm_layer {
   const void* wdown; /* [hidden, inter] */
   vv_w8 q_qkv, q_o, q_gate, q_up, q_down;
   /* optional fragment-major copies of the five matrices (NULL: none) for a row-batched decode step (4..8 rows = {positive, negative} x 2..4
-   * dialogues, vv_gemv_rows.hip): [N / 16][K / 32][4][16][8], i.e. element (16 g + n, 32 j + 8 c + e) of the row-major matrix at
-   * ((g * K/32 + j) * 64 + 16 c + n) * 8 + e - one matrix-core B fragment per 1 KB of contiguous memory.  N % 16 == 0, K % 32 == 0. */
+   * dialogues, vv_gemv_rows.hip).
+   *   bf16 (the matrix has no fp8 companion, q_*.q == NULL): [N / 16][K / 32][4][16][8] bf16, i.e. element (16 g + n, 32 j + 8 c + e) of the
+   *   row-major matrix at ((g * K/32 + j) * 64 + 16 c + n) * 8 + e - one matrix-core B fragment per 1 KB of contiguous memory.  N % 16 == 0,
+   *   K % 32 == 0.
+   *   fp8 (the matrix HAS an fp8 companion, q_*.q != NULL): f_* is then the fragment-major copy of the companion's e4m3fn CODES (its scale is
+   *   q_*.scale), [N / 16][K / 64][4][16][2][8] bytes, i.e. code (16 g + n, 64 j + 32 h + 8 c + e) at ((g * K/64 + j) * 64 + 16 c + n) * 16 +
+   *   8 h + e - one 1 KB wave load carries the B fragments of two 32-wide k steps.  N % 16 == 0, K % 64 == 0.  Never a bf16 copy. */
   const void* f_qkv; const void* f_o; const void* f_gate; const void* f_up; const void* f_down;
 } vv_llm_layer;
 
@@ -221,7 +227,7 @@ typedef struct vv_head_layer {
   const void* wdown;  /* [D, ffn] */
   const void* adaln;  /* [3D, D]: shift | scale | gate */
   vv_w8 q_gate, q_up, q_down;
-  const void* f_gate; const void* f_up; const void* f_down;   /* optional fragment-major copies (see vv_llm_layer) */
+  const void* f_gate; const void* f_up; const void* f_down;   /* optional fragment-major copies, bf16 or - with q_*.q set - fp8 codes (see vv_llm_layer) */
 } vv_head_layer;
 
 typedef struct vv_head {
@@ -262,7 +268,8 @@ int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const 
                    const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, void* ws,
                    const float* sde_noise /* [n_steps, latent] per-step variance noise of the SDE solver (dpm_solver.py:993-998) or NULL */,
                    vv_stream_t stream);
-/* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights): cond[2 B, cond_dim] = rows
+/* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights, with
+ * their fp8 companions' fragment-major codes where the layers carry them): cond[2 B, cond_dim] = rows
  * {positive, negative} of utterance b at 2 b, 2 b + 1; noise[b * ld_noise ..], latent_out[b * ld_latent ..].  Every head matrix is streamed once
  * per solver step for all utterances.  ws: vv_head_ws_bytes_batch(h, n_steps, B) bytes. */
 size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B);

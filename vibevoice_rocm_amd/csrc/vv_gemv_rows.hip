@@ -12,7 +12,14 @@
 //                       one wave instruction reads 1 KB of contiguous memory and a wave's steps are one contiguous run.  From the row-major
 //                       matrix the same instruction gathers 16 rows x 64 B (measured: 16.9 vs 14.0 us on the head's SwiGLU GEMV, 24.1 vs
 //                       18.4 us on the LLM's, tools/mb_rows8.py).
-//   workgroup (g, s)    = 16 weight rows (row group g)  x  K slice s of `ksplit`;  its NW waves split the slice into `spw` 32-wide k steps each
+//   fp8 weights         (VV_FP8 + VV_LIN_W_FRAG, weight-only) the e4m3fn codes in the fragment-major copy [N / 16][K / 64][64 lanes][16 B]: lane
+//                       (n, c) of 64-wide k step j of row group g finds W[16 g + n][64 j + 8 c ..+8] in bytes 0 .. 7 and W[16 g + n][64 j + 32 + 8 c ..+8]
+//                       in bytes 8 .. 15 at ((g * K/64 + j) * 64 + lane) * 16: one 1 KB wave load carries the B fragments of two 32-wide k steps.  The
+//                       codes are decoded to bf16 in registers with the lane's row scale folded in (v_cvt_scalef32_pk_bf16_fp8; a power of two, so
+//                       code * scale is exact in bf16) and meet the same hi / lo activation fragments on the same bf16 MFMA: the products and their
+//                       summation order are those of the bf16 kernel on the effective matrix code * scale, bit for bit.
+//   workgroup (g, s)    = 16 weight rows (row group g)  x  K slice s of `ksplit`;  its NW waves split the slice into `spw` weight loads each (32-wide
+//                       k steps; 64-wide for fp8)
 //   prologue            the block's x slice [8, K / ksplit] is fetched once (fp32), RMSNorm statistics over the block's columns, norm weight and
 //                       adaLN shift / scale applied, split into hi / lo and laid out in LDS in fragment order; every wave then holds its A
 //                       fragments in registers.  All of it is REQUESTED before the weights (loads return in order) and computed while the
@@ -39,6 +46,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned bf_bits(float f) {     // round to nearest even (finite activations)
   const unsigned u = __float_as_uint(f);
@@ -54,7 +62,7 @@ struct RowsAux {
   int dbg;           // timing experiments (wrong results): 2 = no ticket merge, 4 = no activation loads
   float* part;       // [n_groups][ksplit][PST] partial tiles (ksplit > 1)
   int* tickets;      // [n_groups], zero on entry, left zero
-  int ksplit, spw;   // K slices per row group; 32-wide k steps per wave
+  int ksplit, spw;   // K slices per row group; weight loads per wave (32-wide k steps, 64-wide for fp8)
   int n_groups;
 };
 
@@ -62,15 +70,29 @@ constexpr int MAXSPLIT = 16;
 
 struct EpiOps { float b, g, r; };
 
-template <bool DUAL, int NW, int KS, bool PERS>
+// 16 e4m3fn codes (one fp8 fragment-major lane load) -> the bf16 B fragments of two 32-wide k steps, times the row scale s (a power of two)
+__device__ __forceinline__ void fp8_frags(const u32x4 w, float s, bf16x8& b0, bf16x8& b1) {
+  bf16x2 p[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    p[2 * i] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], s, false);
+    p[2 * i + 1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], s, true);
+  }
+  b0 = bf16x8{p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], p[3][0], p[3][1]};
+  b1 = bf16x8{p[4][0], p[4][1], p[5][0], p[5][1], p[6][0], p[6][1], p[7][0], p[7][1]};
+}
+
+// F8: fp8 fragment-major weights, KS 64-wide weight loads per wave (KA = 2 KS activation fragments); else bf16, KS = KA 32-wide loads
+template <bool DUAL, int NW, int KS, bool PERS, bool F8>
 __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a, const RowsAux x) {
   constexpr int T = NW * 64;
-  constexpr int NCH = (KS + 7) / 8;                 // 4-column chunks per thread per activation row
+  constexpr int KA = F8 ? 2 * KS : KS;              // 32-wide A fragments per wave
+  constexpr int NCH = (KA + 7) / 8;                 // 4-column chunks per thread per activation row
   constexpr int NM = DUAL ? 2 : 1;
   constexpr int PST = 128 * NM + 8;                 // floats per partial tile: [NM][8][16] sums + 8 partial sums of squares
   constexpr bool MOD_OK = NCH == 1;                 // adaLN shift / scale rows: only the instantiations whose slice is one chunk per thread (registers)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* xa = reinterpret_cast<u32x4*>(smem);       // [NW][KS][64] A fragments (16 B per lane)
+  u32x4* xa = reinterpret_cast<u32x4*>(smem);       // [NW][KA][64] A fragments (16 B per lane)
   __shared__ float red[PERS ? 2 : 1][NW][NM][256];  // per wave: the 16 x 16 accumulator tile(s); ping-pong when the block walks row groups
   __shared__ float ssr[NW][8];
   __shared__ float s_tot[8];
@@ -80,8 +102,10 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   const int ks = blockIdx.y;
   const int K = a.k, N = a.n, mr = a.m;
   const int spw = x.spw, ksplit = x.ksplit, n_groups = x.n_groups;
+  const int spa = F8 ? 2 * spw : spw;               // 32-wide k steps per wave
   const int steps_total = K >> 5;
-  const int step0 = ks * NW * spw;                  // first k step of this block
+  const int wsteps_total = F8 ? K >> 6 : steps_total;
+  const int step0 = ks * NW * spa;                  // first 32-wide k step of this block
   const int k0 = step0 << 5;
   const bool rms = a.pro == VV_PRO_RMSNORM;
   const bool has_nw = rms && a.norm_w != nullptr, has_mod = MOD_OK && a.mod_scale != nullptr;
@@ -94,7 +118,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
 #pragma unroll
   for (int cc = 0; cc < NCH; ++cc) {
     const int q = tid + cc * T;
-    cval[cc] = q < NW * spw * 8 && (k0 + 4 * q) < K;
+    cval[cc] = q < NW * spa * 8 && (k0 + 4 * q) < K;
     const int kk = (cval[cc] && !(x.dbg & 4)) ? k0 + 4 * q : 4 * (tid & 7);
 #pragma unroll
     for (int m = 0; m < 8; ++m) xv[m][cc] = *reinterpret_cast<const float4*>(a.x + (int64_t)(m < mr ? m : mr - 1) * a.ldx + kk);
@@ -122,19 +146,22 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
     e.b = *pb; e.g = *pg; e.r = *pr;
     return e;
   };
-  const int sb = step0 + wave * spw;                // this wave's first k step
+  const int sb = step0 + wave * spa;                // this wave's first 32-wide k step
+  const int sbw = F8 ? sb >> 1 : sb;                // ... and its first weight load
   const bf16_t* __restrict__ W = reinterpret_cast<const bf16_t*>(a.w);
   const bf16_t* __restrict__ W2 = reinterpret_cast<const bf16_t*>(a.w2);
+  // fp8: the row scale of this lane's weight row (n) in row group grp; N % 16 == 0, so the clamped group is in bounds
+  auto wscale_of = [&](const float* sc, int grp) { return F8 ? sc[min(grp, n_groups - 1) * 16 + n] : 1.0f; };
   auto issue = [&](u32x4 (&w)[KS], u32x4 (&w2)[DUAL ? KS : 1], int grp) {
     const bool glive = grp < n_groups;
-    int64_t base;
-    if (frag) base = ((int64_t)grp * steps_total) * 512 + lane * 8;
+    int64_t base;                                   // in bf16 elements (fp8: two codes per element)
+    if (frag) base = ((int64_t)grp * wsteps_total) * 512 + lane * 8;
     else base = (int64_t)min(grp * 16 + n, N - 1) * K + c * 8;
     const int64_t sstep = frag ? 512 : 32;
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
-      const bool live = glive && j < spw && sb + j < steps_total;
-      const int64_t off = live ? base + (int64_t)(sb + j) * sstep : 0;
+      const bool live = glive && j < spw && sbw + j < wsteps_total;
+      const int64_t off = live ? base + (int64_t)(sbw + j) * sstep : 0;
       const u32x4* p1 = reinterpret_cast<const u32x4*>(W + off);
       const u32x4* p2 = reinterpret_cast<const u32x4*>(W2 + off);
       if (reused) {
@@ -151,9 +178,12 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   u32x4 wc[KS], wc2[DUAL ? KS : 1];
   u32x4 wn[PERS ? KS : 1], wn2[(PERS && DUAL) ? KS : 1];
   EpiOps eo = load_eo(g), eo_n = eo;
+  float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;
+  if constexpr (F8) { sc = wscale_of(a.wscale, g); if (DUAL) sc2 = wscale_of(a.w2scale, g); }
   issue(wc, wc2, g);
   if constexpr (PERS) {
     eo_n = load_eo(g + gstride);
+    if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
     issue(wn, wn2, g + gstride);
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -204,11 +234,11 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
 #pragma unroll
   for (int cc = 0; cc < NCH; ++cc) {
     const int q = tid + cc * T;
-    if (q >= NW * KS * 8) continue;
-    const int js = q >> 3, wv = js / spw, j = js - wv * spw;        // block-relative k step -> (wave, step of the wave)
+    if (q >= NW * KA * 8) continue;
+    const int js = q >> 3, wv = js / spa, j = js - wv * spa;        // block-relative k step -> (wave, step of the wave)
     if (wv >= NW) continue;
     const int cq = (q & 7) >> 1, half = q & 1;
-    unsigned char* base = smem + ((size_t)((wv * KS + j) * 64 + cq * 16) * 16 + half * 8);
+    unsigned char* base = smem + ((size_t)((wv * KA + j) * 64 + cq * 16) * 16 + half * 8);
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
       float4 v = xv[m][cc];
@@ -235,9 +265,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
     }
   }
   __syncthreads();
-  u32x4 af[KS];
+  u32x4 af[KA];
 #pragma unroll
-  for (int j = 0; j < KS; ++j) af[j] = xa[(wave * KS + j) * 64 + lane];
+  for (int j = 0; j < KA; ++j) af[j] = xa[(wave * KA + j) * 64 + lane];
 
   // ---- the weights meet the fragments: one row group per pass -------------------------------------------------------------------------
   int pp_ = 0;
@@ -245,9 +275,21 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
-      if (j < spw && sb + j < steps_total) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc[j]), acc, 0, 0, 0);
-        if (DUAL) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc2[j]), acc2, 0, 0, 0);
+      if (j < spw && sbw + j < wsteps_total) {
+        if constexpr (F8) {              // the two 32-wide halves in k order: the summation order of the bf16 kernel
+          bf16x8 b0, b1;
+          fp8_frags(wc[j], sc, b0, b1);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j]), b0, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j + 1]), b1, acc, 0, 0, 0);
+          if (DUAL) {
+            fp8_frags(wc2[j], sc2, b0, b1);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j]), b0, acc2, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j + 1]), b1, acc2, 0, 0, 0);
+          }
+        } else {
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc[j]), acc, 0, 0, 0);
+          if (DUAL) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc2[j]), acc2, 0, 0, 0);
+        }
       }
     }
     // accumulator: lane (n, c) holds fragment rows 4 c + i of weight row n
@@ -331,10 +373,12 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
       g += gstride;
       pp_ ^= 1;                                        // ping-pong: one barrier per row group is enough
       eo = eo_n;
+      sc = sn; sc2 = sn2;
 #pragma unroll
       for (int j = 0; j < KS; ++j) { wc[j] = wn[j]; if (DUAL) wc2[j] = wn2[j]; }
       if (g + gstride < n_groups) {
         eo_n = load_eo(g + gstride);
+        if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
         issue(wn, wn2, g + gstride);
       }
     }
@@ -348,17 +392,66 @@ int g_rows_pers = 192;      // persistent blocks of the whole-row SwiGLU kernels
 int g_rows_dbg = 0;
 int g_rows_atomic = 1;      // tuning hook "gemv_rows_atomic": 0 = always fold K slices through the ticket (deterministic summation order)
 
-template <bool DUAL, int NW, int KS, bool PERS>
+template <bool DUAL, int NW, int KS, bool PERS, bool F8 = false>
 int launch_cfg(const vv_lin_args& a, RowsAux x, int n_groups, hipStream_t s) {
-  const size_t lds = (size_t)NW * KS * 64 * 16;        // the LDS limit of every instantiation is raised in vv_gemv_rows_init (not capturable)
+  const size_t lds = (size_t)NW * (F8 ? 2 * KS : KS) * 64 * 16;   // the LDS limit of every instantiation is raised in vv_gemv_rows_init (not capturable)
   int gx = n_groups;
   if (PERS && gx > g_rows_pers) {                       // the same number of row groups for every block
     const int per = (n_groups + g_rows_pers - 1) / g_rows_pers;
     gx = (n_groups + per - 1) / per;
   }
   x.n_groups = n_groups;
-  hipLaunchKernelGGL((gemv_rows_kernel<DUAL, NW, KS, PERS>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
+  hipLaunchKernelGGL((gemv_rows_kernel<DUAL, NW, KS, PERS, F8>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
   return 1;
+}
+
+// fp8 fragment-major weights.  A 64-wide weight load costs 4 VGPRs per matrix (8 in flight per persistent buffer pair) and its two activation
+// fragments 8: KS = 4 holds the whole K <= 2048 row in 8 waves and leaves the persistent dual form 64 weight + 32 fragment VGPRs, so fp8 runs
+// persistent at every whole-row width; the single-matrix split-K form goes up to 8 loads (8 KB in flight per wave, as the bf16 form's 8 - 12).
+int launch_fp8(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s) {
+  const bool dual = a.w2 != nullptr;
+  const int steps = a.k / 64, n_groups = a.n / 16;
+  RowsAux x;
+  x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = n_groups; x.atomic = 0;
+  if (steps <= 32) {                                  // K <= 2048: whole rows per block
+    x.ksplit = 1;
+    x.spw = (steps + 7) / 8;
+    if (dual) {
+      if (n_groups > g_rows_pers) {
+        if (x.spw <= 2) return launch_cfg<true, 8, 2, true, true>(a, x, n_groups, s);
+        return launch_cfg<true, 8, 4, true, true>(a, x, n_groups, s);
+      }
+      if (x.spw <= 2) return launch_cfg<true, 8, 2, false, true>(a, x, n_groups, s);
+      return launch_cfg<true, 8, 4, false, true>(a, x, n_groups, s);
+    }
+    if (x.spw <= 2) return launch_cfg<false, 8, 2, false, true>(a, x, n_groups, s);
+    return launch_cfg<false, 8, 4, false, true>(a, x, n_groups, s);
+  }
+  if (a.mod_scale) return 0;
+  const int NW = dual ? 8 : 4, kscap = dual ? 4 : 6, ksmax = dual ? 4 : 8;
+  int ksplit = 0, spw = 0;
+  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
+    const int w = (steps + sp * NW - 1) / (sp * NW);
+    if (w <= kscap && ((long)n_groups * sp >= g_rows_blocks || w <= 2)) { ksplit = sp; spw = w; }
+  }
+  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
+    const int w = (steps + sp * NW - 1) / (sp * NW);
+    if (w <= ksmax) { ksplit = sp; spw = w; }
+  }
+  if (!ksplit) return 0;
+  while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;
+  const size_t pst = dual ? 264 : 136;
+  x.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
+  if (!x.atomic && (!part || !tickets || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return 0;
+  x.ksplit = ksplit; x.spw = spw;
+  if (dual) {
+    if (spw <= 2) return launch_cfg<true, 8, 2, false, true>(a, x, n_groups, s);
+    return launch_cfg<true, 8, 4, false, true>(a, x, n_groups, s);
+  }
+  if (spw <= 2) return launch_cfg<false, 4, 2, false, true>(a, x, n_groups, s);
+  if (spw <= 4) return launch_cfg<false, 4, 4, false, true>(a, x, n_groups, s);
+  if (spw <= 6) return launch_cfg<false, 4, 6, false, true>(a, x, n_groups, s);
+  return launch_cfg<false, 4, 8, false, true>(a, x, n_groups, s);
 }
 
 }  // namespace
@@ -377,26 +470,36 @@ size_t vv_gemv_rows_tickets(int n) { return (size_t)((n + 15) / 16); }
 
 // every kernel's LDS attribute is set before any graph capture (hipFuncSetAttribute is not capturable)
 int vv_gemv_rows_init() {
-#define VV_ROWS_ATTR(D, NW, KS, P)                                                                                                        \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<D, NW, KS, P>), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                          NW * KS * 64 * 16) != hipSuccess)                                                                               \
+#define VV_ROWS_ATTR_F(D, NW, KS, P, F8)                                                                                                  \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<D, NW, KS, P, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                          NW * (F8 ? 2 * KS : KS) * 64 * 16) != hipSuccess)                                                              \
     return vv_set_error(VV_E_HIP, "gemv_rows: cannot raise the dynamic LDS limit");
+#define VV_ROWS_ATTR(D, NW, KS, P) VV_ROWS_ATTR_F(D, NW, KS, P, false)
   VV_ROWS_ATTR(false, 4, 3, false) VV_ROWS_ATTR(false, 4, 6, false) VV_ROWS_ATTR(false, 4, 9, false) VV_ROWS_ATTR(false, 4, 12, false)
   VV_ROWS_ATTR(false, 8, 4, false) VV_ROWS_ATTR(false, 8, 6, false) VV_ROWS_ATTR(false, 8, 8, false)
   VV_ROWS_ATTR(true, 8, 4, false) VV_ROWS_ATTR(true, 8, 6, false) VV_ROWS_ATTR(true, 8, 8, false)
   VV_ROWS_ATTR(true, 8, 4, true) VV_ROWS_ATTR(true, 8, 6, true)
+  VV_ROWS_ATTR_F(false, 8, 2, false, true) VV_ROWS_ATTR_F(false, 8, 4, false, true)
+  VV_ROWS_ATTR_F(true, 8, 2, false, true) VV_ROWS_ATTR_F(true, 8, 4, false, true) VV_ROWS_ATTR_F(true, 8, 2, true, true) VV_ROWS_ATTR_F(true, 8, 4, true, true)
+  VV_ROWS_ATTR_F(false, 4, 2, false, true) VV_ROWS_ATTR_F(false, 4, 4, false, true) VV_ROWS_ATTR_F(false, 4, 6, false, true) VV_ROWS_ATTR_F(false, 4, 8, false, true)
 #undef VV_ROWS_ATTR
+#undef VV_ROWS_ATTR_F
   return 0;
 }
 
 // 1 launched, 0 not covered (the caller falls back), < 0 error.  part / tickets: split-K workspace (tickets zeroed by the caller once; every
-// launch leaves them zero) or null (then only shapes that need no K split are taken).
+// launch leaves them zero) or null (then only shapes that need no K split are taken).  fp8 weights: fragment-major only (VV_LIN_W_FRAG).
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s) {
-  if (!g_rows_on || a.wdt != VV_BF16 || a.m < 3 || a.m > 8 || a.k % 32 || a.k < 32) return 0;
+  const bool f8 = a.wdt == VV_FP8;
+  if (!g_rows_on || (a.wdt != VV_BF16 && !f8) || a.m < 3 || a.m > 8 || a.k % 32 || a.k < 32) return 0;
   if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return 0;
   if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16 || a.ldx % 4) return 0;
   if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
   if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return 0;
+  if (f8) {
+    if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale)) return 0;
+    return launch_fp8(a, part, part_floats, tickets, n_tickets, s);
+  }
   if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return 0;
   const bool dual = a.w2 != nullptr;
   const int steps = a.k / 32, n_groups = (a.n + 15) / 16;

@@ -640,7 +640,11 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   if (a->act != VV_ACT_SWIGLU && a->w2) return vv_set_error(VV_E_ARG, "vv_linear: w2 given without SWIGLU");
   if (a->mod_scale && (!a->mod_shift || a->pro != VV_PRO_RMSNORM)) return vv_set_error(VV_E_ARG, "vv_linear: modulate needs RMSNORM prologue and shift");
   if (a->m > 8 && a->ldx == 0) return vv_set_error(VV_E_ARG, "vv_linear: broadcast rows (ldx=0) only for m<=8");
-  if ((a->flags & VV_LIN_W_FRAG) && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
+  if ((a->flags & VV_LIN_W_FRAG) && a->wdt == VV_FP8 &&
+      (a->m < 3 || a->m > 8 || a->n % 16 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
+    return vv_set_error(VV_E_ARG, "vv_linear: fp8 VV_LIN_W_FRAG weights need 3..8 rows, n %% 16 == 0, k %% 64 == 0 and wscale (w2scale) (m=%d n=%d k=%d)",
+                        a->m, a->n, a->k);
+  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
     return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..8 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
     return vv_set_error(VV_E_ARG, "vv_linear: bf16 activation hand-off needs bf16 weights, m > 8 and k %% 16 == 0");
@@ -655,6 +659,12 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   }
   if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
+  else if (a->wdt == VV_FP8 && (a->flags & VV_LIN_W_FRAG)) {
+    // fp8 fragment-major weights: the 3..8-row matrix-core GEMV (process-wide split-K scratch as for bf16, see rows_scratch)
+    rc = g_rows_part ? vv_launch_gemv_rows(*a, g_rows_part, G_ROWS_PART_FLOATS, g_rows_tk, G_ROWS_TICKETS, s) : 0;
+    rc = rc < 0 ? rc : rc == 1 ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)",
+                                                 a->m, a->n, a->k);
+  }
   else if (a->wdt == VV_FP8) {
     // weight-only fp8 exists for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix
     rc = vv_launch_gemv_stream(*a, s) ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 weights need m <= 2, k %% 8 == 0, scales and 8-byte aligned rows (m=%d k=%d)", a->m, a->k);
@@ -667,11 +677,19 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 }
 
 // vv_linear for the composites of a row-batched step: 3..8 rows go to the matrix-core GEMV with the caller's split-K workspace, on the
-// fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices
-int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream) {
+// fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices.
+// q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*)
+int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
+                 const vv_w8* q1, const vv_w8* q2) {
   if (a && a->wdt == VV_BF16 && a->m > 2 && a->m <= 8 && a->x && a->w && a->out) {
     vv_lin_args b = *a;
-    if (f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
+    const bool f8 = q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
+    if (f8) {                 // fp8 companions: their fragment-major codes or nothing (never a bf16 read of an fp8 copy)
+      if (f1 && (!b.w2 || f2)) {
+        b.w = f1; b.wscale = q1->scale; b.wdt = VV_FP8; b.flags |= VV_LIN_W_FRAG;
+        if (b.w2) { b.w2 = f2; b.w2scale = q2->scale; }
+      }
+    } else if (f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
     const int rc = vv_launch_gemv_rows(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream);
     if (rc < 0) return rc;
     if (rc == 1) { VV_CHECK_LAUNCH("vv_linear(rows)"); return 0; }

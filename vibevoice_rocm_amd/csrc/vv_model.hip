@@ -119,9 +119,10 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     VV_TRY(vv_copy_rows(x, ldx, h, H, R, H, stream));
     hin = h; ldh = H;
   }
-  auto lin = [&](vv_lin_args& a, const void* f1, const void* f2) -> int {
+  // rows8 with fp8 companions: f_* are the fragment-major copies of their codes (vv_llm_layer)
+  auto lin = [&](vv_lin_args& a, const void* f1, const void* f2, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr) -> int {
     if (!rows8) return vv_linear(&a, stream);
-    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream);
+    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, q1, q2);
   };
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
@@ -135,7 +136,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln1; a.eps = m->rms_eps; a.bias = L.bqkv;
       if (!rows8) use_w8(a, L.q_qkv);
     }
-    VV_TRY(lin(a, L.f_qkv, nullptr));
+    VV_TRY(lin(a, L.f_qkv, nullptr, &L.q_qkv));
     if (decode) {
       VV_TRY(vv_attn_decode_ws(qkv, qkvd, R, m->heads, kv, l, rope, lens, att, qd, att_part, att_tickets, att_split, VV_ATT_PART_SPLITS, stream));   // decode: RoPE + append fused
     } else {
@@ -151,7 +152,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       if (!rows8) use_w8(a, L.q_o);
     }
     a.res = hin; a.ldres = ldh;
-    VV_TRY(lin(a, L.f_o, nullptr));
+    VV_TRY(lin(a, L.f_o, nullptr, &L.q_o));
     hin = h; ldh = H;
     if (prefill) {
       VV_TRY(vv_cast_rows_bf16(h, H, R, H, VV_PRO_RMSNORM, L.ln2, m->rms_eps, xb, H, stream));
@@ -166,7 +167,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     if (prefill) {            // the SwiGLU output is handed to the down projection in bf16: no separate cast pass
       a.out = reinterpret_cast<float*>(xb2); a.ldo = m->inter; a.flags |= VV_LIN_OUT_BF16;
     }
-    VV_TRY(lin(a, L.f_gate, L.f_up));
+    VV_TRY(lin(a, L.f_gate, L.f_up, &L.q_gate, &L.q_up));
     if (prefill) {
       a = lin_base((const float*)xb2, m->inter, R, L.wdown, H, m->inter, m->wdt, h, H);
       a.flags = VV_LIN_X_BF16;
@@ -175,7 +176,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       if (!rows8) use_w8(a, L.q_down);
     }
     a.res = h; a.ldres = H;
-    VV_TRY(lin(a, L.f_down, nullptr));
+    VV_TRY(lin(a, L.f_down, nullptr, &L.q_down));
   }
   if (!out) return 0;       // the caller runs the final norm itself (vv_llm_tail: norm + logits + token + bookkeeping in one launch)
   return vv_rmsnorm_rows(h, H, m->final_norm, m->rms_eps, R, H, out, ldo, s);
@@ -417,10 +418,10 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
       a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
       a.w2 = L.wup; a.act = VV_ACT_SWIGLU; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream));
+      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, &L.q_gate, &L.q_up));
       a = lin_base(act, h->ffn, R2, L.wdown, D, h->ffn, h->wdt, hc, D);
       a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hc; a.ldres = D; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream));
+      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, &L.q_down));
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
     VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,

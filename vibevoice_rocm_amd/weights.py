@@ -84,6 +84,9 @@ class DeviceWeights:
         self._fp8_names = set(fp8_matrix_names(cfg)) if quant == "fp8" else set()
         self.wdt = _wdt(wdtype)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
+        # the fragment-major copies (ensure_frag) live here: one dict object shared by every fork, as the ctypes layer arrays they are
+        # written into are, so they are built once per process whichever fork asks first
+        self._frag_state: Dict[str, object] = {"done": False, "tensors": []}
         self._sd = sd
         self.state_tensors: Dict[str, List[torch.Tensor]] = {"acoustic_dec": [], "semantic_enc": []}
         # every streaming-state tensor (conv left contexts, mixer histories) is a 256-byte aligned view into ONE arena, so the
@@ -185,39 +188,56 @@ class DeviceWeights:
             return None
         return w.view(n // 16, 16, k // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
 
+    @staticmethod
+    def frag_major_fp8(q: torch.Tensor) -> Optional[torch.Tensor]:
+        """[N, K] e4m3fn codes (uint8) -> the fp8 fragment-major copy [N / 16][K / 64][64 lanes][16 B] (include/vv_hip.h, vv_llm_layer.f_*): lane
+        16 c + n of 64-wide k step j of row group g holds W[16 g + n][64 j + 8 c ..+8] then W[16 g + n][64 j + 32 + 8 c ..+8], i.e. element
+        (16 g + n, 64 j + 32 h + 8 c + e) at ((g * K/64 + j) * 64 + 16 c + n) * 16 + 8 h + e."""
+        n, k = q.shape
+        if n % 16 or k % 64 or q.dtype != torch.uint8:
+            return None
+        return q.view(n // 16, 16, k // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
+
     def ensure_frag(self) -> None:
         """Fragment-major copies of the LLM's and the diffusion head's per-frame matrices for the row-batched decode step (rowbatch.py): built
-        once, on first use, next to the row-major matrices (which the prefill GEMMs and the 1..4-row GEMVs keep using); +2.9 GB at 1.5B."""
-        if getattr(self, "_frag_done", False) or self.wdtype != torch.bfloat16:
+        once per process (for this weight set and all its forks), on first use, next to the row-major matrices (which the prefill GEMMs and the
+        1..4-row GEMVs keep using).  bf16: copies of the bf16 matrices, +2.9 GB at 1.5B.  weight_quant="fp8": copies of the e4m3 codes of the
+        matrices' fp8 companions instead (+1.45 GB at 1.5B) - a layer's f_* then points at fp8 codes (the vv_llm_layer rule); a matrix whose
+        shape the fp8 form cannot take (N % 16, K % 64) gets no copy and keeps the row-major fallback."""
+        st = self._frag_state
+        if st["done"] or self.wdtype != torch.bfloat16:
             return
         by_ptr = {t.data_ptr(): t for t in self._keep if isinstance(t, torch.Tensor)}
 
-        def frag_of(p, n, k):
-            t = by_ptr.get(int(p)) if p else None
+        def frag_of(p, w8, n, k):
+            if w8.q:          # fp8 companion: the copy is of its codes, or none
+                t, fm = by_ptr.get(int(w8.q)), self.frag_major_fp8
+            else:
+                t, fm = (by_ptr.get(int(p)) if p else None), self.frag_major
             if t is None or tuple(t.shape) != (n, k):
                 return None
-            f = self.frag_major(t)
+            f = fm(t)
             if f is None:
                 return None
             f = self._aligned(f)
-            self._keep.append(f)
+            st["tensors"].append(f)
             return f.data_ptr()
 
         cfg = self.cfg
         qkvd = (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim
         for l in range(cfg.layers):
             lay = self.llm.layer[l]
-            lay.f_qkv = frag_of(lay.wqkv, qkvd, cfg.hidden)
-            lay.f_o = frag_of(lay.wo, cfg.hidden, cfg.heads * cfg.head_dim)
-            lay.f_gate = frag_of(lay.wgate, cfg.inter, cfg.hidden)
-            lay.f_up = frag_of(lay.wup, cfg.inter, cfg.hidden)
-            lay.f_down = frag_of(lay.wdown, cfg.hidden, cfg.inter)
+            lay.f_qkv = frag_of(lay.wqkv, lay.q_qkv, qkvd, cfg.hidden)
+            lay.f_o = frag_of(lay.wo, lay.q_o, cfg.hidden, cfg.heads * cfg.head_dim)
+            lay.f_gate = frag_of(lay.wgate, lay.q_gate, cfg.inter, cfg.hidden)
+            lay.f_up = frag_of(lay.wup, lay.q_up, cfg.inter, cfg.hidden)
+            lay.f_down = frag_of(lay.wdown, lay.q_down, cfg.hidden, cfg.inter)
         for l in range(cfg.head_layers):
             lay = self.head.layer[l]
-            lay.f_gate = frag_of(lay.wgate, cfg.head_ffn, cfg.head_hidden)
-            lay.f_up = frag_of(lay.wup, cfg.head_ffn, cfg.head_hidden)
-            lay.f_down = frag_of(lay.wdown, cfg.head_hidden, cfg.head_ffn)
-        self._frag_done = True
+            lay.f_gate = frag_of(lay.wgate, lay.q_gate, cfg.head_ffn, cfg.head_hidden)
+            lay.f_up = frag_of(lay.wup, lay.q_up, cfg.head_ffn, cfg.head_hidden)
+            lay.f_down = frag_of(lay.wdown, lay.q_down, cfg.head_hidden, cfg.head_ffn)
+        st["done"] = True
 
     def state_blob(self) -> torch.Tensor:
         """All streaming state of the speech path as one flat fp32 tensor."""
@@ -229,7 +249,8 @@ class DeviceWeights:
         return t
 
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep if isinstance(t, torch.Tensor))
+        ts = [t for t in self._keep if isinstance(t, torch.Tensor)] + list(self._frag_state["tensors"])
+        return sum(t.numel() * t.element_size() for t in ts)
 
     # ---- Qwen2 ---------------------------------------------------------------------------------------------------
     def _build_llm(self):
