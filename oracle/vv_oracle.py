@@ -488,10 +488,79 @@ class GenerateResult:
         self.reach_max_step = False
 
 
+def batch_negative_replacements(schedules: List[List[int]], special: dict) -> List[set]:
+    """The reference's batched negative branch (modeling_vibevoice_inference.py:547-563, :575-622) run symbolically on the forced token
+    schedules of a batch: every negative KV row is labelled with the step that computed it, the attention mask and the rows are shifted
+    exactly as written (the mask guard `start_idx + 1 < seq_len - 1`, the KV guard `start_idx + 1 < k_cache.shape[2] - 1`).  Per
+    sample, the steps whose row stays visible although the sample did not diffuse in that step: where the two guards disagree
+    (correct_cnt == kv_len - 2) the mask moves one slot right over rows that did not, so the row just computed replaces the one
+    before it.  Every other step matches the per-sample semantics of `generate` (pinned by tests/golden/loop_trace_batch_*)."""
+    ST, D, EOS = special["speech_start"], special["speech_diffusion"], special["eos"]
+    B = len(schedules)
+    mask = [[1] for _ in range(B)]
+    rows = [[] for _ in range(B)]
+    cnt = [0] * B
+    finished = [False] * B
+    out = [set() for _ in range(B)]
+    for step in range(max(len(s) for s in schedules)):
+        if all(finished):
+            break
+        tok = [EOS if finished[b] or step >= len(schedules[b]) else schedules[b][step] for b in range(B)]
+        finished = [f or t == EOS for f, t in zip(finished, tok)]
+        for b in range(B):
+            if not finished[b] and tok[b] == ST:
+                mask[b] = [0] * len(mask[b])
+                mask[b][-1] = 1
+                if rows[b]:
+                    rows[b][-1] = rows[b][0]
+        if not any(not finished[b] and tok[b] == D for b in range(B)):
+            continue
+        for b in range(B):
+            rows[b].append(step)
+            mask[b].append(1)
+        for b in range(B):
+            if finished[b] or tok[b] == D:
+                continue
+            s, seq_len, kv_len = cnt[b], len(mask[b]), len(rows[b])
+            if s + 1 < seq_len - 1:
+                mask[b][s + 1:] = mask[b][s:-1]
+            mask[b][s] = 0
+            if s + 1 < kv_len - 1:
+                rows[b][s + 1:] = rows[b][s:-1]
+            cnt[b] += 1
+            if any(m and r == step for m, r in zip(mask[b], rows[b])):
+                out[b].add(step)
+    return out
+
+
+def batch_conv_restarts(schedules: List[List[int]], special: dict) -> List[set]:
+    """The streaming tokenizer cache of the batched loop: decode / encode run on the diffusing subset with sample_indices, and the cache's
+    get() returns None - a fresh state for EVERY sample of the call - as soon as one of them has no state yet
+    (modular_vibevoice_tokenizer.py:198-207; set_to_zero keeps the keys).  Per sample, the steps at which it diffuses next to a sample
+    that diffuses for the first time, after having diffused itself before."""
+    D, EOS = special["speech_diffusion"], special["eos"]
+    B = len(schedules)
+    seen = [False] * B
+    finished = [False] * B
+    out = [set() for _ in range(B)]
+    for step in range(max(len(s) for s in schedules)):
+        tok = [EOS if finished[b] or step >= len(schedules[b]) else schedules[b][step] for b in range(B)]
+        finished = [f or t == EOS for f, t in zip(finished, tok)]
+        diff = [b for b in range(B) if not finished[b] and tok[b] == D]
+        if any(not seen[b] for b in diff):
+            for b in diff:
+                if seen[b]:
+                    out[b].add(step)
+        for b in diff:
+            seen[b] = True
+    return out
+
+
 def generate(W, cfg: dict, input_ids: List[int], speech_input_mask: Optional[Tensor], speech_embeds: Optional[Tensor],
              special: dict, noise: Tensor, cfg_scale: float = 1.3, n_steps: int = 10, max_length_times: float = 2.0,
              forced_tokens: Optional[List[int]] = None, max_new_tokens: Optional[int] = None,
-             keep_trace: bool = False, bf16_t: bool = False, refresh_negative: bool = True) -> GenerateResult:
+             keep_trace: bool = False, bf16_t: bool = False, refresh_negative: bool = True,
+             neg_replace_steps: Optional[set] = None, conv_restart_steps: Optional[set] = None) -> GenerateResult:
     """Batch-1 restatement of generate().  `special` = dict(speech_start, speech_end, speech_diffusion, eos[, bos]).
     `noise` [F, latent] is consumed one row per diffusion frame (replaces the CPU randn at :699).
     `forced_tokens` overrides the argmax (bench / random-weight runs) but the logits
@@ -502,7 +571,11 @@ def generate(W, cfg: dict, input_ids: List[int], speech_input_mask: Optional[Ten
     `bf16_t`: the timestep roundings of the reference's bf16 run (see timestep_embedding).
     `refresh_negative=False` (:501-515): the negative branch instead consumes EVERY step's input embedding right after the token
     choice (a single speech_start at step 0, where inputs_embeds is still None), is never reset on speech_start, and the
-    diffusion branch uses that step's negative hidden state (batch 1: the correction of :588-622 touches no sample)."""
+    diffusion branch uses that step's negative hidden state (batch 1: the correction of :588-622 touches no sample).
+    `neg_replace_steps`: the steps at which the reference's BATCHED loop keeps this sample's negative row although the sample did not
+    diffuse, in place of its last visible row (see batch_negative_replacements); empty for a batch of one.
+    `conv_restart_steps`: the steps at which the batched loop restarts this sample's acoustic / semantic streaming state before the frame
+    (see batch_conv_restarts); empty for a batch of one."""
     res = GenerateResult()
     emb = W[LLM + "embed_tokens.weight"]
     ids = list(input_ids)
@@ -540,11 +613,21 @@ def generate(W, cfg: dict, input_ids: List[int], speech_input_mask: Optional[Ten
             nhidden = llm_forward(W, cfg, neg_in, neg_kv, neg_kv.length)[-1]
         if refresh_negative and not finished and tok == special["speech_start"]:   # :547-563
             neg_kv.truncate(0)
+        if neg_replace_steps and step in neg_replace_steps:                         # :588-622 in a batch: mask shifted, KV not
+            neg_in = x_in[-1:] if step > 0 else emb[special["speech_start"]].float()[None]
+            n_vis = neg_kv.length
+            assert n_vis >= 1, "a replacement needs a visible row to replace"
+            llm_forward(W, cfg, neg_in, neg_kv, n_vis)
+            for i in range(len(neg_kv.k)):
+                neg_kv.k[i] = torch.cat([neg_kv.k[i][:, : n_vis - 1], neg_kv.k[i][:, n_vis:]], dim=1)
+                neg_kv.v[i] = torch.cat([neg_kv.v[i][:, : n_vis - 1], neg_kv.v[i][:, n_vis:]], dim=1)
         next_embeds = emb[tok].float()[None]                                       # :567
         if not finished and tok == special["speech_diffusion"]:                    # :571-670
             if refresh_negative:
                 neg_in = x_in[-1:] if step > 0 else emb[special["speech_start"]].float()[None]
                 nhidden = llm_forward(W, cfg, neg_in, neg_kv, neg_kv.length)[-1]   # :575-587
+            if conv_restart_steps and step in conv_restart_steps:
+                ac_state, sem_state = ConvState(), ConvState()
             latent = sample_speech_tokens(W, cfg, hidden[None], nhidden[None], noise[frame][None], cfg_scale,
                                           n_steps, tables, bf16_t=bf16_t)          # :627-631
             scaled = latent / W["model.speech_scaling_factor"].float() - W["model.speech_bias_factor"].float()

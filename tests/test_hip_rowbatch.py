@@ -324,7 +324,7 @@ def test_generate_row_batch_mid_bf16_vs_oracle():
         assert e_rows < 2e-2, f"row-batched dialogue {b}: waveform rel RMS {e_rows:.3e} vs oracle (lanes: {e_lane:.3e})"
 
 
-@pytest.mark.parametrize("B", [6, 8, 9])
+@pytest.mark.parametrize("B", [6, 8, 9, 12, 16])
 def test_generate_two_row_batches_vs_lanes(big, B):
     """5..16 dialogues: ceil(B / 4) row batches (3 + 3, 4 + 4, 3 + 3 + 3) inside one lock-step loop, both on the main stream, their conv tails on the three side
     streams (two lanes per stream, one launch worker per stream) - against the lanes: same sequences, waveforms to the bf16 noise floor."""

@@ -412,3 +412,41 @@ def test_bench_under_torchrun_two_ranks():
     assert r.returncode == 0, r.stderr[-800:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2, r.stdout
+
+
+def test_batch_coupling_matches_reference_rules():
+    """modeling._BatchCoupling (the counters generate() keeps for B > 1) against the oracle's literal symbolic run of the reference's
+    batched negative-branch mask / KV surgery and streaming cache (batch_negative_replacements, batch_conv_restarts), on random
+    schedules of 2..4 samples: same dialogues replaced / restarted at the same steps."""
+    import random
+    from oracle import vv_oracle as O
+    from vibevoice_rocm_amd.modeling import _BatchCoupling
+    ST, E, D, EOS = 150, 151, 152, 153
+    special = dict(speech_start=ST, speech_end=E, speech_diffusion=D, eos=EOS)
+    rng = random.Random(5)
+    hits = [0, 0]
+    for _ in range(3000):
+        B = rng.randint(2, 4)
+        sch = [[rng.choice([D, D, D, E, ST]) for _ in range(rng.randint(1, 12))] + [EOS] for _ in range(B)]
+        want_r, want_c = O.batch_negative_replacements(sch, special), O.batch_conv_restarts(sch, special)
+        got_r, got_c = [set() for _ in range(B)], [set() for _ in range(B)]
+        cp = _BatchCoupling(B, ST, D)
+        finished = [False] * B
+        for step in range(max(len(s) for s in sch)):
+            live = [b for b in range(B) if not finished[b]]
+            if not live:
+                break
+            toks = {b: sch[b][step] for b in live}
+            going = [b for b in live if toks[b] != EOS]
+            rep, res = cp.step(toks, going)
+            for b in rep:
+                got_r[b].add(step)
+            for b in res:
+                got_c[b].add(step)
+            for b in live:
+                finished[b] = toks[b] == EOS
+        assert got_r == want_r, (sch, got_r, want_r)
+        assert got_c == want_c, (sch, got_c, want_c)
+        hits[0] += sum(map(len, want_r))
+        hits[1] += sum(map(len, want_c))
+    assert min(hits) > 100, hits

@@ -214,3 +214,59 @@ def test_oracle_vs_reference_components_fp32_and_bf16_floor():
     for key in ("wav", "sem", "prefill_hidden", "decode_hidden"):
         floor = rel_rms(g[key + "_bf16"], g[key + "_fp32"])
         assert 6e-3 < floor < 1.2e-2, f"{key}: reference bf16 vs fp32 floor {floor:.3e}"
+
+
+def _batch_trace_inputs(g, entry, b, cfg, W):
+    """sample b of a loop_trace_batch entry, unpadded, with its own voice prompt encoded through the oracle"""
+    keep = g[f"{entry}_attention_mask"][b].astype(bool)
+    _, conn = O.process_speech_inputs(W, cfg, t(g[f"{entry}_voice"][b:b + 1]), t(g[f"{entry}_speech_masks"][b:b + 1]),
+                                      t(g[f"{entry}_std_noise"][b:b + 1]), t(g[f"{entry}_eps_noise"][b:b + 1]))
+    return g[f"{entry}_ids"][b][keep].tolist(), t(g[f"{entry}_speech_input_mask"][b][keep]), conn
+
+
+@pytest.mark.parametrize("preset", ["tiny", "mid"])
+def test_generate_loop_trace_batch(preset):
+    """tests/golden/loop_trace_batch_*.npz: the reference's BATCHED loop, hand-driven with its own negative-branch mask / KV surgery and its
+    own streaming tokenizer cache for all samples at once, left-padded prompts of different lengths, one voice prompt per sample.  Every
+    sample against a per-sample oracle run.  Entry a (interleaved segments, an early EOS, a speech_start while another sample diffuses)
+    needs no batch rule; entry b trips the guard disagreement of :595 / :607 (batch_negative_replacements), entry c the streaming cache's
+    all-or-nothing get() (batch_conv_restarts).  For b and c the plain per-sample run is checked to DIFFER from the fixture, so the rules
+    are needed, not decoration."""
+    from vibevoice_rocm_amd.config import VVConfig
+    from vibevoice_rocm_amd.synth import synth_state_dict
+    vc = VVConfig.preset(preset)
+    g = load_golden(f"loop_trace_batch_{preset}")
+    cfg = vc.as_dict()
+    W = {k: torch.from_numpy(v) for k, v in synth_state_dict(vc, 1234).items()}
+    if int(g["weights_bf16"]):
+        W = {k: (v.to(torch.bfloat16).float() if v.dim() >= 1 else v) for k, v in W.items()}
+    ST, E, D, EOS = [int(v) for v in g["special"]]
+    special = dict(speech_start=ST, speech_end=E, speech_diffusion=D, eos=EOS)
+    valid = sorted([ST, E, D, EOS])
+    lm = O.lm_head_weight(W, cfg)[valid].double()
+    for entry, n_repl, n_restart in (("a", 0, 0), ("b", 1, 0), ("c", 0, 1)):
+        B = g[f"{entry}_ids"].shape[0]
+        forced = [g[f"{entry}_s{b}_forced"].tolist() for b in range(B)]
+        repl = O.batch_negative_replacements(forced, special)
+        rest = O.batch_conv_restarts(forced, special)
+        assert sum(len(r) for r in repl) == n_repl and sum(len(r) for r in rest) == n_restart, (entry, repl, rest)
+        assert int(g[f"{entry}_n_guard"]) > 0 or not n_repl        # a replacement needs a guard disagreement (a has harmless ones)
+        for b in range(B):
+            ids, sp, conn = _batch_trace_inputs(g, entry, b, cfg, W)
+            runs = [(repl[b], rest[b])] + ([(set(), set())] if (repl[b] or rest[b]) else [])
+            for k, (rs, cs) in enumerate(runs):
+                res = O.generate(W, cfg, ids, sp, conn, special, t(g[f"{entry}_s{b}_noise"]), cfg_scale=float(g["cfg_scale"]),
+                                 n_steps=int(g["n_steps"]), forced_tokens=forced[b], keep_trace=True, neg_replace_steps=rs, conv_restart_steps=cs)
+                assert res.sequences[len(ids):] == g[f"{entry}_s{b}_tokens"].tolist()
+                frames = [r for r in res.trace if "latent" in r]
+                assert len(frames) == g[f"{entry}_s{b}_latent"].shape[0]
+                e_wav = rel_rms(torch.cat(res.audio).numpy(), g[f"{entry}_s{b}_wav"].reshape(-1))
+                if k == 1:
+                    assert e_wav > 1e-2, f"{entry} sample {b}: the per-sample semantics alone already match ({e_wav:.2e})"
+                    continue
+                for i, r in enumerate(frames):
+                    assert rel_rms(r["cond"].numpy(), g[f"{entry}_s{b}_cond"][i]) < 1e-4, (entry, b, i)
+                    assert rel_rms(r["ncond"].numpy(), g[f"{entry}_s{b}_ncond"][i]) < 1e-4, (entry, b, i)
+                    assert rel_rms(r["latent"].numpy(), g[f"{entry}_s{b}_latent"][i]) < 2e-4, (entry, b, i)
+                    assert rel_rms(r["wav"].numpy(), g[f"{entry}_s{b}_wav"][i]) < 5e-4, (entry, b, i)
+                assert e_wav < 5e-4, (entry, b, e_wav)

@@ -103,6 +103,58 @@ def save_checkpoint_dir(path: str, config: VVConfig, state_dict: Dict[str, torch
         json.dump({"metadata": {"total_size": total}, "weight_map": weight_map}, f, indent=2)
 
 
+class _BatchCoupling:
+    """Where the reference's BATCHED loop does not treat a sample as if it ran alone; the host knows every step's tokens, so it can say.
+    (1) Negative branch (modeling_vibevoice_inference.py:575-622): one negative forward for all samples whenever any diffuses, then the
+        non-diffusing ones are shifted out from their correct_cnt.  The mask guard tests seq_len - 1, the KV guard k_cache.shape[2] - 1,
+        one row shorter: with correct_cnt == kv_len - 2 the mask moves one slot right and the rows do not, so the row just computed for
+        the sample stays visible in place of its last visible one.  `replace` lists those dialogues: their negative row of this step
+        (computed by every decode step anyway, at slot lens[1]) is copied over slot lens[1] - 1 and lens[1] stays.
+    (2) Streaming tokenizer cache (modular_vibevoice_tokenizer.py:198-207): get() returns None - a fresh conv state for the whole call -
+        when one sample of the diffusing subset has no state yet.  `restart` lists the dialogues whose conv states are zeroed before
+        this frame's tail because they diffuse next to a first-time diffuser.
+    Neither applies to a batch of one.  Restated symbolically, literal to the reference, by the CPU restatement the tests use (batch_negative_replacements,
+    batch_conv_restarts) and pinned by tests/golden/loop_trace_batch_*."""
+
+    def __init__(self, B: int, tok_start: int, tok_diff: int):
+        self.ST, self.SD = tok_start, tok_diff
+        self.n_fwd = 0                 # negative forwards so far (the batch-wide negative cache length)
+        self.cnt = [0] * B             # correct_cnt
+        self.vis = [0] * B             # visible negative rows of each dialogue (= its lens[1])
+        self.seen = [False] * B        # has a streaming tokenizer state
+
+    def step(self, toks: Dict[int, int], going: List[int]):
+        """toks: this step's token of every dialogue live at its start; going: those still unfinished after it (no EOS, no max length).
+        Returns (replace, restart)."""
+        diff = [b for b in going if toks[b] == self.SD]
+        for b in going:
+            if toks[b] == self.ST:
+                self.vis[b] = 0
+        replace, restart = [], []
+        if diff:
+            self.n_fwd += 1
+            for b in going:
+                if toks[b] != self.SD:
+                    if self.cnt[b] == self.n_fwd - 2 and self.vis[b] >= 1:
+                        replace.append(b)
+                    self.cnt[b] += 1
+            if not all(self.seen[b] for b in diff):
+                restart = [b for b in diff if self.seen[b]]
+            for b in diff:
+                self.seen[b] = True
+                self.vis[b] += 1
+        return replace, restart
+
+
+def _copy_kv_slot(k: torch.Tensor, v: torch.Tensor, vt: Optional[torch.Tensor], row: int, src: int, dst: int) -> None:
+    """slot src -> slot dst of KV cache row `row` in every layer ([layers, rows, kv_heads, s_max, head_dim]; vt: the transposed value
+    copy in 32-key tiles [layers, rows, kv_heads, s_max / 32, head_dim, 32])"""
+    k[:, row, :, dst].copy_(k[:, row, :, src])
+    v[:, row, :, dst].copy_(v[:, row, :, src])
+    if vt is not None:
+        vt[:, row, :, dst // 32, :, dst % 32].copy_(vt[:, row, :, src // 32, :, src % 32])
+
+
 def _make_sampler(gen_cfg: dict):
     """do_sample path (modeling_vibevoice_inference.py:491-494): softmax over the constrained logits + multinomial, with the
     HF warpers the reference's callers configure (temperature, top_k, top_p; main.py:1187-1196) applied in HF order.
@@ -418,6 +470,7 @@ class VibeVoiceForConditionalGenerationInference:
             s_ = torch.stack([torch.randn(2 * n, cfg.latent)[:n] for _ in range(lanes[0].n_steps)], dim=1) if sde else None
             return a, s_
 
+        coupling = _BatchCoupling(B, ST, SD)
         pool = None
         if B > 1 and os.environ.get("VV_LANE_THREADS", "1") != "0":
             from concurrent.futures import ThreadPoolExecutor
@@ -483,11 +536,18 @@ class VibeVoiceForConditionalGenerationInference:
                 deliver()                  # the previous step's chunks: their copies completed long before this step's tokens
                 for b in live:
                     toks[b] = lanes[b].decode_end()
+            going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
+            replace, restart = coupling.step(toks, going)
+            for b in replace:
+                e = lanes[b]
+                with torch.cuda.stream(e.stream):
+                    _copy_kv_slot(e._kv_t[0], e._kv_t[1], e._kv_vt if e.kv.vt else None, 1, coupling.vis[b], coupling.vis[b] - 1)
             diffusing = []
             for b in live:
                 tok = toks[b]
-                if b in speculated and tok != SD:
+                if b in speculated and (tok != SD or b in restart):
                     lanes[b].rollback_speech_state()
+                    speculated.discard(b)
                 prev_tok[b] = tok
                 seq[b].append(tok)
                 if tok == EOS:                                                                      # :517-526
@@ -512,6 +572,9 @@ class VibeVoiceForConditionalGenerationInference:
                         lanes[b].reset_speech_caches()
                 if tok == SD:
                     diffusing.append(b)
+                    if b in restart:
+                        with torch.cuda.stream(lanes[b].stream):
+                            lanes[b].reset_speech_caches()
                 else:
                     lanes[b].step_embed()                                                           # :567
             need = [b for b in diffusing if b not in speculated and (nz[b] is None or frame[b] >= len(nz[b]))]
@@ -623,6 +686,8 @@ class VibeVoiceForConditionalGenerationInference:
             audio_streamer.put(torch.stack([lanes[b].take_chunk(k)[None] for b, k in pending]), torch.tensor(idx))   # one put per step, all samples (:644-653)
             pending.clear()
 
+        coupling = _BatchCoupling(B, ST, SD)
+
         def finish(b):
             finished[b] = True
             rb_of[b].set_active(loc[b], False)
@@ -703,12 +768,19 @@ class VibeVoiceForConditionalGenerationInference:
                 for rb, lv, spec in plan:
                     tk = rb.decode_end()
                     toks.update({b: tk[loc[b]] for b in lv})
+            going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
+            replace, restart = coupling.step(toks, going)
+            for b in replace:
+                rb = rb_of[b]
+                with torch.cuda.stream(rb.stream):
+                    _copy_kv_slot(rb._kv_t[0], rb._kv_t[1], rb._kv_vt if rb.kv.vt else None, 2 * loc[b] + 1, coupling.vis[b], coupling.vis[b] - 1)
             diffusing = []
             for b in live:
                 tok = toks[b]
                 rb = rb_of[b]
-                if b in speculated and tok != SD:
+                if b in speculated and (tok != SD or b in restart):
                     rb.rollback(loc[b])
+                    speculated.discard(b)
                 prev_tok[b] = tok
                 seq[b].append(tok)
                 if tok == EOS:                                                                      # :517-526
@@ -724,6 +796,8 @@ class VibeVoiceForConditionalGenerationInference:
                     rb.reset_speech(loc[b])
                 if tok == SD:
                     diffusing.append(b)
+                    if b in restart:
+                        rb.reset_speech(loc[b])
                 else:
                     rb.embed(loc[b])                                                                # :567
             todo = [b for b in diffusing if b not in speculated]

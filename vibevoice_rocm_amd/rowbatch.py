@@ -471,6 +471,9 @@ class RowBatch:
         if late and inline:
             self._head_event.synchronize()
         for b in inline:
+            e = self.lanes[b]
+            if e.use_graphs and ("RBconv", b, self.uid) not in e._graphs:
+                _wait_all_jobs()   # first use captures on the main stream: no worker may still be waiting on _head_event (recorded there)
             tail(b)             # this dialogue's tail rides the main stream, behind H
 
     def embed(self, b: int):
