@@ -12,10 +12,18 @@ timed region.  With N GPUs every rank synthesises its own dialogue (weak scaling
 weights are broadcast from rank 0 and waveforms gathered to rank 0 over RCCL.
 
 The JSON line also carries
-  roofline      the dominant kernel (the streamed-weight GEMV) timed with HIP events on its launch stream,
-                algorithmic bytes = its weight matrix, against the 8 TB/s HBM3E peak;
   frame         algorithmic bytes per frame (SURVEY.md §8d formula) / measured seconds per frame;
-  cpu_baseline  the CPU oracle (oracle/vv_oracle.py, kind "port") timed on this host on a bounded sample.
+  rccl          (N > 1) the checkpoint broadcast and the per-step waveform gather.
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+adds the diagnostic legs, each a run of its own after the timed steps (N = 1 only):
+  first_chunk_latency   generate() entry to the first audio chunk on the host, + the matrix-core legs of it;
+  roofline, kernels     the dominant kernel (the streamed-weight GEMV) timed with HIP events on its launch stream,
+                        algorithmic bytes = its weight matrix, against the 8 TB/s HBM3E peak;
+  batched_generate(_x8), concurrent_streams, fp8_weights
+                        serving extras on the headline shape (cfg2 only);
+  cpu_baseline          the CPU oracle (oracle/vv_oracle.py, kind "port") timed on this host on a bounded sample.
 """
 import argparse
 import ctypes as C
@@ -379,7 +387,7 @@ def cpu_baseline_leg(sd_dev, cfg, frames=4, timed_runs=3):
     """BASELINE.md section 3 / SURVEY.md section 8d cfg 1 restated on the CPU oracle (kind "port"): VibeVoice-1.5B shapes, fp32, CFG = 1.0,
     10 solver steps, 1 speaker with a 70-frame voice prompt through process_speech_inputs, a ~170-token prompt, forced speech_diffusion
     frames.  One warm-up + `timed_runs` timed passes of the frame loop (median), per-component seconds per frame; the once-per-utterance
-    legs (voice encode, prefill) are timed once.  Bounded to a few frames so that the default bench run stays within minutes: the
+    legs (voice encode, prefill) are timed once.  Bounded to a few frames so that a --full bench run stays within minutes: the
     per-frame cost does not depend on how many frames follow (KV growth over 4 frames is negligible)."""
     from oracle import vv_oracle as O
     cores = min(len(os.sched_getaffinity(0)), 16)       # a 1-GPU box's CPU share is 16 cores even when the mask lists the whole host
@@ -623,13 +631,16 @@ def main():
     ap.add_argument("--cfg-scale", type=float, default=2.0)
     ap.add_argument("--ddpm-steps", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--no-fp8-leg", dest="fp8_leg", action="store_false", help="skip the extra weight-only-fp8 leg")
-    ap.add_argument("--concurrent", type=int, default=3, help="extra leg: N independent dialogues concurrently on one GPU (0/1 = skip)")
-    ap.add_argument("--batched", type=int, default=4, help="extra leg: one generate() call on a batch of N dialogues (0/1 = skip)")
-    ap.add_argument("--first-chunk-runs", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the diagnostic legs (first-chunk latency, roofline, batched / concurrent / fp8 extras, "
+                         "CPU baseline); a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline leg")
+    ap.add_argument("--no-fp8-leg", dest="fp8_leg", action="store_false", help="--full: skip the extra weight-only-fp8 leg")
+    ap.add_argument("--concurrent", type=int, default=3, help="--full: N independent dialogues concurrently on one GPU (0/1 = skip)")
+    ap.add_argument("--batched", type=int, default=4, help="--full: one generate() call on a batch of N dialogues (0/1 = skip)")
+    ap.add_argument("--first-chunk-runs", type=int, default=5, help="--full: generate() calls the first-chunk latency is the median of")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one's generate() returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
@@ -676,8 +687,8 @@ def main():
     model = VibeVoiceForConditionalGenerationInference(cfg, sd, device=device, torch_dtype=dtype, use_graphs=not args.no_graphs,
                                                        weight_quant=W["quant"] if dtype == torch.bfloat16 else None)
     log(f"engine ready ({model.engine.w.nbytes() / 1e9:.2f} GB resident)")
-    single = world == 1            # the diagnostic legs run at N = 1 only (other ranks would just wait at the final barrier)
-    keep_sd = rank == 0 and single and headline and (not args.no_cpu_baseline or args.concurrent > 1 or args.fp8_leg)
+    extras = args.full and world == 1      # the diagnostic legs run at N = 1 only (other ranks would just wait at the final barrier)
+    keep_sd = rank == 0 and extras and headline and (not args.no_cpu_baseline or args.concurrent > 1 or args.fp8_leg)
     if not keep_sd:
         del sd
         sd = None
@@ -758,14 +769,14 @@ def main():
         rccl["note"] = ("one broadcast of the packed checkpoint before the timed region, one ragged gather of the fp32 waveforms per step inside "
                         "it (wall time on rank 0: includes waiting for the slowest rank); no collective inside generate()")
         result["rccl"] = rccl
-    if rank == 0 and single:
+    if rank == 0 and extras:
         result["first_chunk_latency"] = first_chunk_leg(model, wl, args.cfg_scale, runs=args.first_chunk_runs, gen_kw=gen_kw)
         log(f"first-chunk latency p50 {result['first_chunk_latency']['p50_ms']} ms")
         try:
             result["first_chunk_latency"]["matrix_core_legs"] = first_chunk_parts(model, wl, cfg)
         except Exception as e:      # noqa: BLE001
             result["first_chunk_latency"]["matrix_core_legs"] = {"error": repr(e)}
-    if rank == 0 and single and not args.no_roofline:
+    if rank == 0 and extras and not args.no_roofline:
         ents = roofline_leg(model, wl, args.cfg_scale)
         log("roofline leg done")
         D, F = cfg.head_hidden, cfg.head_ffn
@@ -791,7 +802,7 @@ def main():
             result["roofline_hbm_stream"] = entry(hbm_ents[0])
         result["kernels"] = [{k: (round(v, 2) if isinstance(v, float) else v) for k, v in e.items()} for e in ents[:8]]
     # the extra legs never take the headline line down with them
-    if rank == 0 and single and headline and args.batched > 1:
+    if rank == 0 and extras and headline and args.batched > 1:
         try:
             result["batched_generate"] = batched_leg(model, cfg, args, args.batched)
             log(f"batched x{args.batched}: {result['batched_generate']['value']} audio-sec/s aggregate")
@@ -807,21 +818,21 @@ def main():
         except Exception as e:      # noqa: BLE001
             result["batched_generate"] = {"error": repr(e)}
             log(f"batched leg failed: {e!r}")
-    if rank == 0 and single and headline and args.concurrent > 1:
+    if rank == 0 and extras and headline and args.concurrent > 1:
         try:
             result["concurrent_streams"] = concurrent_leg(model, cfg, sd, dtype, device, args, args.concurrent)
             log(f"concurrent x{args.concurrent}: {result['concurrent_streams']['value']} audio-sec/s aggregate")
         except Exception as e:      # noqa: BLE001
             result["concurrent_streams"] = {"error": repr(e)}
             log(f"concurrent leg failed: {e!r}")
-    if rank == 0 and single and headline and args.fp8_leg and dtype == torch.bfloat16 and sd is not None:
+    if rank == 0 and extras and headline and args.fp8_leg and dtype == torch.bfloat16 and sd is not None:
         try:
             result["fp8_weights"] = fp8_leg(cfg, sd, device, args, wl)
             log(f"fp8 weights: {result['fp8_weights']['value']} audio-sec/s")
         except Exception as e:      # noqa: BLE001
             result["fp8_weights"] = {"error": repr(e)}
             log(f"fp8 leg failed: {e!r}")
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if rank == 0 and extras and not args.no_cpu_baseline:
         if sd is None or args.model != "1.5b":
             cfg15 = VVConfig.preset("1.5b")
             sd15 = synth_state_dict_torch(cfg15, 1234, device=device, dtype=dtype)
