@@ -30,6 +30,18 @@ typedef void* vv_stream_t; /* hipStream_t */
 
 enum { VV_F32 = 0, VV_BF16 = 1, VV_FP8 = 2 /* e4m3fn bytes + per-output-row fp32 scale (vv_lin_args.wscale); streaming GEMV (m <= 2, row-major) or
                                              3..8-row matrix-core GEMV (VV_LIN_W_FRAG, fp8 fragment-major) only */ };
+/* VV_NF4: weight-only 4-bit NF4 (bitsandbytes' blockwise NF4 table, one fp32 absmax per 64 consecutive k of a row), streaming GEMV only:
+ * m <= 2, k % 64 == 0, no VV_LIN_W_FRAG.  Effective weight W[n][k] = bf16_rne(table[code] * absmax) (bf16 compute dtype).
+ *   w / w2:           packed codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B], 16-byte aligned: code of (4 q + r, 512 u + 8 l + i) is
+ *                     nibble i (bits 4 i .. 4 i + 3) of dword r of the 16 bytes at ((q * ceil(K/512) + u) * 64 + l) * 16
+ *   wscale / w2scale: absmax [ceil(N/4)][ceil(K/512)][4 rows][8 blocks] fp32: block b of unit u covers k = 512 u + 64 b .. + 63
+ * Padding (rows past N, k past K) holds code 0 and scale 0.  Any other NF4 call (m > 2, GEMM shapes, VV_LIN_W_FRAG, missing scales) is an error. */
+enum { VV_NF4 = 3 };
+/* vv_llm.wdt, vv_head.wdt, vv_convnet.wdt: VV_WQ_NF4 ORed into the matrix dtype says the layers' vv_w8 companions hold NF4 (codes in q, block
+ * absmax in scale, the VV_NF4 layouts above) instead of fp8.  The 1..2-row GEMVs then stream them; every 3..8-row path (vv_linear_ws,
+ * vv_llm_forward with R in 3..8, vv_head_sample_batch(_sde), vv_llm_tail_batch) uses the bf16 matrices (row-major or their bf16 fragment-major
+ * f_* copies), which hold the same effective values. */
+enum { VV_WQ_NF4 = 0x100 };
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };

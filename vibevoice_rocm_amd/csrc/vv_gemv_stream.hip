@@ -6,8 +6,8 @@
 // workgroups are persistent: each wave walks its row groups with the next group's loads already in flight while
 // it reduces the current one (register double buffering), so the memory pipe never drains between rows.
 // Row sums use DPP row reductions (vv_wave_sum), every output's epilogue (bias / GELU / SwiGLU / gate / residual) runs in its own
-// lane on operands fetched one row group ahead, M <= 2 has an fp8 (e4m3fn codes + row scale) instantiation, M = 8 covers the
-// T = 8 conv stage when K splits to <= 2 units per wave.
+// lane on operands fetched one row group ahead, M <= 2 has an fp8 (e4m3fn codes + row scale) and an NF4 (4-bit codes + per-64 block
+// scale, see below) instantiation, M = 8 covers the T = 8 conv stage when K splits to <= 2 units per wave.
 //   KSPLIT == 1        a wave owns RW whole weight rows per step (block = 4 independent waves)        K <= 2560
 //   KSPLIT == 4/8/16   the block's 4/8/16 waves split K (interleaved 512-element units) and combine through LDS
 //                      in a fixed order (long K: 1.5B down-projections, every 7B matrix)
@@ -80,13 +80,34 @@ __device__ __forceinline__ void epi_pre(const vv_lin_args& a, int m, int n, floa
   a.out[(int64_t)m * a.ldo + n] = v;
 }
 
+// NF4 (VV_NF4, weight-only 4-bit): the instantiation streams FOUR weight rows per step so that each lane's 16-byte load carries the 32 codes
+// of its own 8-wide k slice of one 512-wide unit in each of the 4 rows (codes [N/4][K/512][64 lanes][4 rows][8 nibbles], include/vv_hip.h).
+// Decode: every (row, 64-block) of a unit pair gets its 16-entry table bf16(table[c] * absmax) built ONCE by one lane (lane = table index:
+// 16 multiplies and 8 packed converts, which also do the bf16 rounding the definition asks for) into the wave's LDS slot; every weight is
+// then one nibble extract, one ds_read_u16 and one shift into the high half of an fp32.  The scales of a unit pair are one 4-byte load per lane.
+__constant__ float c_nf4_table[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
+                                      -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,
+                                      0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f,
+                                      0.7229568362236023f, 1.0f};
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void nf4_build_lut(float s, unsigned int* dst) {   // dst: this lane's 8 dwords (16 bf16) in the wave's LDS slot
+  unsigned int e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const f32x2 v = {c_nf4_table[2 * j] * s, c_nf4_table[2 * j + 1] * s};
+    e[j] = __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_t));   // v_cvt_pk_bf16_f32: round to nearest even
+  }
+  *reinterpret_cast<u32x4*>(dst) = u32x4{e[0], e[1], e[2], e[3]};
+  *reinterpret_cast<u32x4*>(dst + 4) = u32x4{e[4], e[5], e[6], e[7]};
+}
+
 int g_blocks_override = 0;   // tuning hook (vv_tune)
 int g_waves_override = 0;    // tuning hook "gemv_waves": waves per block of the whole-row (KSPLIT == 1) kernels, 3 .. 8
 int g_opt = 13;              // tuning hook "gemv_opt": bit 0 / 1 = batched prologue for RMSNorm / no prologue, bit 2 = straight-line epilogue-operand loads, bit 3 = block-staged RMSNorm prologue (KSPLIT == 1)
 int g_long_cap = 512;        // persistent blocks for K-split launches with K > 6144 (tuning hook)
 int g_long_ku = 5;           // K units per wave allowed for rows longer than 12 units (tuning hook: 3 -> 8 waves split K)
 
-template <int M, bool DUAL, int KSPLIT, int KU, int RW, bool F8>
+template <int M, bool DUAL, int KSPLIT, int KU, int RW, int WQ>   // WQ: 0 bf16, 1 fp8, 2 NF4 (RW == 4)
 __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_kernel(const vv_lin_args a, const int n_groups, const int opt) {
   constexpr int NW = (KSPLIT == 1) ? 8 : KSPLIT;     // waves per block (KSPLIT == 1: at most; the launcher picks 3 .. 8 so that the row groups divide evenly)
   __shared__ float red[NW * M];
@@ -109,7 +130,10 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     if (!kval[u]) koff[u] = 0;                    // any valid address; the activation there is forced to 0
   }
   const bool reused = (a.flags & VV_LIN_W_REUSED) != 0 || (opt & 16);    // opt bit 4 (tuning): every matrix with cacheable loads
-  constexpr bool f8 = F8;                        // weight-only fp8 is its own instantiation: the bf16 kernels carry none of it
+  constexpr bool f8 = WQ == 1;                   // weight-only fp8 / NF4 are instantiations of their own: the bf16 kernels carry none of it
+  constexpr bool nf4 = WQ == 2;
+  static_assert(!nf4 || (RW == 4 && M <= 2), "NF4: 4 rows per 16-byte code load, decode rows only");
+  const int units_k = (K + 511) >> 9;            // NF4: 512-wide units per row in the packed layout
   // the first row group's weight loads are issued before the activation prologue so both latencies overlap
   const int gstride = (KSPLIT == 1) ? gridDim.x * nwv : gridDim.x;
   int g = (KSPLIT == 1) ? blockIdx.x * nwv + wave : blockIdx.x;
@@ -124,6 +148,23 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
       const int n = min(grp * RW + r, N - 1);
 #pragma unroll
       for (int u = 0; u < KU; ++u) {
+        if constexpr (nf4) {     // r == 0: this lane's 16 B of codes (4 rows); r == 1, u < (KU + 1) / 2: the scale dword of unit pair u
+          const int uu = (r == 0) ? u : 2 * u + (lane >> 5);
+          const int unit = (KSPLIT == 1) ? uu : (wave + NW * uu);
+          const bool ok = live && uu < KU && unit < units_k;
+          if (r == 0) {
+            const int64_t co = ok ? (((int64_t)grp * units_k + unit) * 64 + lane) * 16 : 0;
+            const u32x4* p1 = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(a.w) + co);
+            const u32x4* p2 = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(a.w2) + co);
+            if (reused) { b[0][u] = *p1; if (DUAL) b2[0][u] = *p2; }
+            else { b[0][u] = __builtin_nontemporal_load(p1); if (DUAL) b2[0][u] = __builtin_nontemporal_load(p2); }
+          } else if (r == 1 && 2 * u < KU) {
+            const int64_t so = ok ? ((int64_t)grp * units_k + unit) * 32 + (lane & 31) : 0;
+            b[1][u].x = __float_as_uint(a.wscale[so]);
+            if constexpr (DUAL) b2[1][u].x = __float_as_uint(a.w2scale[so]);
+          }
+          continue;
+        }
         const int64_t off = live ? (int64_t)n * K + koff[u] : 0;
         if (f8) {                // e4m3fn bytes: this lane's 8 weights are 8 bytes
           const u32x2 t = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(a.w) + off));
@@ -421,6 +462,44 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     for (int r = 0; r < RW; ++r)
 #pragma unroll
       for (int m = 0; m < M; ++m) { pacc[r][m] = vf2{0.f, 0.f}; if (DUAL) pacc2[r][m] = vf2{0.f, 0.f}; }
+    if constexpr (nf4) {
+      // per wave: 64 tables (unit half h, row r, block b at index 32 h + 8 r + b) x 16 bf16, one slot per weight stream
+      __shared__ __attribute__((aligned(16))) unsigned int lut[NW][DUAL ? 2 : 1][64 * 8];
+      const int lb = (lane >> 3) * 8;            // this lane's block within a unit, in dwords of its tables
+#pragma unroll
+      for (int p = 0; p < (KU + 1) / 2; ++p) {
+        nf4_build_lut(__uint_as_float(cur[1][p].x), &lut[wave][0][lane * 8]);
+        if constexpr (DUAL) nf4_build_lut(__uint_as_float(cur2[1][p].x), &lut[wave][DUAL ? 1 : 0][lane * 8]);
+        __builtin_amdgcn_wave_barrier();         // keeps the reads below the writes; a wave's LDS operations complete in order
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int u = 2 * p + h;
+          if (u >= KU) break;
+#pragma unroll
+          for (int r = 0; r < RW; ++r) {
+            const unsigned short* t1 = reinterpret_cast<const unsigned short*>(&lut[wave][0][(h * 32 + r * 8) * 8 + lb]);
+            const unsigned short* t2 = reinterpret_cast<const unsigned short*>(&lut[wave][DUAL ? 1 : 0][(h * 32 + r * 8) * 8 + lb]);
+            const unsigned int c1 = cur[0][u][r], c2 = DUAL ? cur2[0][u][r] : 0u;
+            float w[8], w2[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              w[i] = __uint_as_float((unsigned int)t1[(c1 >> (4 * i)) & 15u] << 16);
+              if (DUAL) w2[i] = __uint_as_float((unsigned int)t2[(c2 >> (4 * i)) & 15u] << 16);
+            }
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+#pragma unroll
+              for (int j = 0; j < 8; j += 2) {
+                const vf2 xp = {xr[m][u][j], xr[m][u][j + 1]};
+                pacc[r][m] = __builtin_elementwise_fma(vf2{w[j], w[j + 1]}, xp, pacc[r][m]);
+                if (DUAL) pacc2[r][m] = __builtin_elementwise_fma(vf2{w2[j], w2[j + 1]}, xp, pacc2[r][m]);
+              }
+            }
+          }
+        }
+        __builtin_amdgcn_wave_barrier();         // the next pair's tables overwrite these only after every read above was issued
+      }
+    } else {
 #pragma unroll
     for (int u = 0; u < KU; ++u) {
 #pragma unroll
@@ -438,6 +517,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
           }
         }
       }
+    }
     }
     float acc[RW][M], acc2[DUAL ? RW : 1][M];
 #pragma unroll
@@ -509,32 +589,41 @@ void launch_rw(const vv_lin_args& a, hipStream_t s) {
   int blocks = work < cap ? work : cap;
   if (g_blocks_override > 0) blocks = g_blocks_override < work ? g_blocks_override : work;
   const int threads = KSPLIT == 1 ? 64 * waves : 64 * KSPLIT;
+  if constexpr (RW == 4) {                       // NF4 weights (launch_one): 4 rows per code load
+    hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 2>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+    return;
+  }
   if constexpr (M <= 2) {                        // fp8 weights: decode rows only
     if (a.wdt == VV_FP8) {
-      hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, true>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+      hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 1>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
       return;
     }
   }
-  hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, false>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+  hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 0>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
 }
 
 int g_small_rw = 2;           // rows per wave step for narrow non-dual matrices (tuning hook)
 
 template <int M, bool DUAL, int KSPLIT, int KU>
-void launch_one(const vv_lin_args& a, hipStream_t s) {
+bool launch_one(const vv_lin_args& a, hipStream_t s) {
+  if (a.wdt == VV_NF4) {   // NF4: <= 2 rows, <= 8 waves (LDS), the dual kernel at <= 4 units per wave (registers); never a bf16 read of codes
+    if constexpr (M <= 2 && KSPLIT <= 8 && !(DUAL && KU > 4)) { launch_rw<M, DUAL, KSPLIT, KU, 4>(a, s); return true; }
+    return false;
+  }
   if (DUAL && g_dual_rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, s);
   else if (!DUAL && KSPLIT == 1 && a.n <= 4096 && g_small_rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, s);
   else launch_rw<M, DUAL, KSPLIT, KU, 2>(a, s);
+  return true;
 }
 
 template <int M, bool DUAL, int KSPLIT>
 bool launch_kus(const vv_lin_args& a, hipStream_t s, int ku) {
   switch (ku) {
-    case 1: if constexpr (KSPLIT == 1) { launch_one<M, DUAL, KSPLIT, 1>(a, s); return true; } else return false;
-    case 2: launch_one<M, DUAL, KSPLIT, 2>(a, s); return true;
-    case 3: launch_one<M, DUAL, KSPLIT, 3>(a, s); return true;
-    case 4: if constexpr (!DUAL || KSPLIT == 1) { launch_one<M, DUAL, KSPLIT, 4>(a, s); return true; } else return false;
-    case 5: if constexpr (!DUAL || KSPLIT == 1) { launch_one<M, DUAL, KSPLIT, 5>(a, s); return true; } else return false;
+    case 1: if constexpr (KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 1>(a, s); else return false;
+    case 2: return launch_one<M, DUAL, KSPLIT, 2>(a, s);
+    case 3: return launch_one<M, DUAL, KSPLIT, 3>(a, s);
+    case 4: if constexpr (!DUAL || KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 4>(a, s); else return false;
+    case 5: if constexpr (!DUAL || KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 5>(a, s); else return false;
   }
   return false;
 }
@@ -575,7 +664,11 @@ void vv_gemv_stream_set_small_rw(int r) { g_small_rw = r; }
 
 // returns 1 when the call was launched here, 0 when the shape/alignment is not covered (caller falls back)
 int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
-  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8) || a.m > 8 || a.k % 8) return 0;
+  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4) || a.m > 8 || a.k % 8) return 0;
+  // NF4: decode rows only, whole 64-blocks, scales for every matrix, 16-byte aligned codes (vv_hip.h)
+  if (a.wdt == VV_NF4 && (a.m > 2 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) ||
+                          (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4) || (a.flags & VV_LIN_W_FRAG)))
+    return 0;
   if (a.wdt == VV_FP8 && (a.m > 2 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 8 || (a.w2 && (uintptr_t)a.w2 % 8))) return 0;
   if (a.m > 4) {
     if (a.w2 || a.wdt != VV_BF16) return 0;
@@ -601,7 +694,7 @@ int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
   // smallest wave count whose per-wave slice fits the register-resident activation fragment (KU <= 5 units; <= 3 for the
   // dual kernel when K is split, its registers hold two weight streams)
   int ksplit = 1, ku = units;
-  if (units > 5) {
+  if (units > ((a.wdt == VV_NF4 && dual) ? 4 : 5)) {   // the NF4 SwiGLU kernel holds two code streams and their tables: <= 4 units
     const int kumax = dual ? 3 : (units > 12 ? g_long_ku : 5);
     ksplit = 0;
     for (int w : {4, 8, 16}) {
@@ -610,6 +703,7 @@ int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
     if (!ksplit) return 0;
     if (ku < 2) ku = 2;
   }
+  if (a.wdt == VV_NF4 && ksplit > 8) return 0;   // 16 waves of table slots would not fit the block's LDS: not built
   bool ok;
   if (a.m == 1) ok = dual ? launch_ku<1, true>(a, s, ksplit, ku) : launch_ku<1, false>(a, s, ksplit, ku);
   else if (a.m == 2) ok = dual ? launch_ku<2, true>(a, s, ksplit, ku) : launch_ku<2, false>(a, s, ksplit, ku);

@@ -644,6 +644,9 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
       (a->m < 3 || a->m > 8 || a->n % 16 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_ARG, "vv_linear: fp8 VV_LIN_W_FRAG weights need 3..8 rows, n %% 16 == 0, k %% 64 == 0 and wscale (w2scale) (m=%d n=%d k=%d)",
                         a->m, a->n, a->k);
+  if (a->wdt == VV_NF4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights exist for the streaming GEMV alone: m <= 2, k %% 64 == 0, wscale (w2scale), "
+                        "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
   if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
     return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..8 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
@@ -668,6 +671,10 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   else if (a->wdt == VV_FP8) {
     // weight-only fp8 exists for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix
     rc = vv_launch_gemv_stream(*a, s) ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 weights need m <= 2, k %% 8 == 0, scales and 8-byte aligned rows (m=%d k=%d)", a->m, a->k);
+  }
+  else if (a->wdt == VV_NF4) {
+    // weight-only NF4: the streaming GEMV's NF4 instantiation (<= 2 rows); GEMM-shaped calls use the bf16 matrix of the effective weights
+    rc = vv_launch_gemv_stream(*a, s) ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights need m <= 2, k %% 64 == 0, scales and 16-byte aligned codes (m=%d k=%d)", a->m, a->k);
   }
   else return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (rc) return rc;

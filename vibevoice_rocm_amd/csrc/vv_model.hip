@@ -33,12 +33,22 @@ inline vv_lin_args lin_base(const float* x, int64_t ldx, int m, const void* w, i
 // ---------------------------------------------------------------------------------------------------------------
 // Qwen2 decoder stack
 // ---------------------------------------------------------------------------------------------------------------
-// weight-only fp8 companions (vv_w8) replace the bf16 matrix on the weight-streaming GEMVs (<= 2 activation rows)
-static inline void use_w8(vv_lin_args& a, const vv_w8& q, const vv_w8* q2 = nullptr) {
+// weight-only fp8 or NF4 companions (vv_w8; wq = VV_FP8 / VV_NF4, the descriptor's kind) replace the bf16 matrix on the weight-streaming
+// GEMVs (<= 2 activation rows)
+static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q2 = nullptr) {
   if (a.m > 2 || !q.q || !q.scale || (a.w2 && (!q2 || !q2->q || !q2->scale))) return;
-  a.w = q.q; a.wscale = q.scale; a.wdt = VV_FP8;
+  a.w = q.q; a.wscale = q.scale; a.wdt = wq;
   if (a.w2) { a.w2 = q2->q; a.w2scale = q2->scale; }
 }
+
+// VV_WQ_NF4 (vv_hip.h) rides on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
+// the matrix dtype, and keeps the companions' kind in `wq`
+#define VV_WQ_STRIP(T, p)                                                   \
+  T p##_plain_ = *(p);                                                      \
+  const int wq = (p##_plain_.wdt & VV_WQ_NF4) ? VV_NF4 : VV_FP8;            \
+  p##_plain_.wdt &= ~VV_WQ_NF4;                                             \
+  p = &p##_plain_;                                                          \
+  (void)wq
 
 // from this many rows on, a bf16-weight LLM forward is a prompt prefill: activations are cast to bf16 once per GEMM and both
 // operands stream from global on the matrix cores with 128-row tiles (every weight fragment reused by 4 row tiles)
@@ -77,6 +87,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
   if (R <= 0) return vv_set_error(VV_E_ARG, "vv_llm_forward: R=%d", R);
   if (kv->layers != m->layers || kv->kv_heads != m->kv_heads || kv->head_dim != m->head_dim)
     return vv_set_error(VV_E_ARG, "vv_llm_forward: kv cache shape does not match the model");
+  VV_WQ_STRIP(vv_llm, m);
   hipStream_t s = (hipStream_t)stream;
   const int H = m->hidden, d = m->head_dim, qd = m->heads * d, qkvd = (m->heads + 2 * m->kv_heads) * d;
   Carver c(ws);
@@ -122,7 +133,8 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
   // rows8 with fp8 companions: f_* are the fragment-major copies of their codes (vv_llm_layer)
   auto lin = [&](vv_lin_args& a, const void* f1, const void* f2, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr) -> int {
     if (!rows8) return vv_linear(&a, stream);
-    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, q1, q2);
+    // NF4 companions never reach the 3..8-row kernel: f1 / f2 are then bf16 fragment-major copies of the effective matrices (or NULL)
+    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr);
   };
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
@@ -134,7 +146,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     } else {
       a = lin_base(hin, ldh, R, L.wqkv, qkvd, H, m->wdt, qkv, qkvd);
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln1; a.eps = m->rms_eps; a.bias = L.bqkv;
-      if (!rows8) use_w8(a, L.q_qkv);
+      if (!rows8) use_w8(a, wq, L.q_qkv);
     }
     VV_TRY(lin(a, L.f_qkv, nullptr, &L.q_qkv));
     if (decode) {
@@ -149,7 +161,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       a.flags = VV_LIN_X_BF16;
     } else {
       a = lin_base(att, qd, R, L.wo, H, qd, m->wdt, h, H);
-      if (!rows8) use_w8(a, L.q_o);
+      if (!rows8) use_w8(a, wq, L.q_o);
     }
     a.res = hin; a.ldres = ldh;
     VV_TRY(lin(a, L.f_o, nullptr, &L.q_o));
@@ -163,7 +175,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln2; a.eps = m->rms_eps;
     }
     a.w2 = L.wup; a.act = VV_ACT_SWIGLU;
-    if (!prefill && !rows8) use_w8(a, L.q_gate, &L.q_up);
+    if (!prefill && !rows8) use_w8(a, wq, L.q_gate, &L.q_up);
     if (prefill) {            // the SwiGLU output is handed to the down projection in bf16: no separate cast pass
       a.out = reinterpret_cast<float*>(xb2); a.ldo = m->inter; a.flags |= VV_LIN_OUT_BF16;
     }
@@ -173,7 +185,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
       a.flags = VV_LIN_X_BF16;
     } else {
       a = lin_base(act, m->inter, R, L.wdown, H, m->inter, m->wdt, h, H);
-      if (!rows8) use_w8(a, L.q_down);
+      if (!rows8) use_w8(a, wq, L.q_down);
     }
     a.res = h; a.ldres = H;
     VV_TRY(lin(a, L.f_down, nullptr, &L.q_down));
@@ -187,6 +199,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" size_t vv_head_ws_bytes(const vv_head* h, int n_steps) {
   if (!h || n_steps <= 0) return 0;
+  VV_WQ_STRIP(vv_head, h);
   const size_t R = 2 * (size_t)n_steps > 8 ? 2 * (size_t)n_steps : 8;
   const size_t D = h->D;
   return al(8 * D) /*c0*/ + al(R * D) /*c*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + al(8 * D) /*hcur*/ +
@@ -195,7 +208,7 @@ extern "C" size_t vv_head_ws_bytes(const vv_head* h, int n_steps) {
 }
 
 // shared body: rows R (<= 8), modulation tables mod[l] [*, 3D] / modf [*, 2D] with row offset `mrow`
-static int head_body(const vv_head* h, const float* x, int64_t ldx, int R, float* const* mod, const float* modf, int64_t mrow,
+static int head_body(const vv_head* h, int wq, const float* x, int64_t ldx, int R, float* const* mod, const float* modf, int64_t mrow,
                      float* hcur, float* act, float* v, vv_stream_t stream) {
   const int D = h->D;
   vv_lin_args a;
@@ -210,11 +223,11 @@ static int head_body(const vv_head* h, const float* x, int64_t ldx, int R, float
     a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
     a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
     a.w2 = L.wup; a.act = VV_ACT_SWIGLU;
-    use_w8(a, L.q_gate, &L.q_up);
+    use_w8(a, wq, L.q_gate, &L.q_up);
     VV_TRY(vv_linear(&a, stream));
     a = lin_base(act, h->ffn, R, L.wdown, D, h->ffn, h->wdt, hcur, D);
     a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hcur; a.ldres = D;
-    use_w8(a, L.q_down);
+    use_w8(a, wq, L.q_down);
     VV_TRY(vv_linear(&a, stream));
   }
   const float* mf = modf + mrow * 2 * D;
@@ -248,6 +261,7 @@ extern "C" int vv_head_forward(const vv_head* h, const float* x, const float* te
                                void* ws, vv_stream_t stream) {
   if (!h || !x || !temb_rows || !cond || !v || !ws) return vv_set_error(VV_E_ARG, "vv_head_forward: null pointer");
   if (R <= 0 || R > 8 || h->layers > 16) return vv_set_error(VV_E_ARG, "vv_head_forward: R=%d (1..8)", R);
+  VV_WQ_STRIP(vv_head, h);
   const int D = h->D;
   Carver cv(ws);
   float* c0 = cv.take(8 * (size_t)D);
@@ -262,7 +276,7 @@ extern "C" int vv_head_forward(const vv_head* h, const float* x, const float* te
   // c[r] = c0[r] + temb_rows[r]: rows_b = R with a single "step" whose b-row is row r -> use add_rows twice-free form
   for (int r = 0; r < R; ++r) VV_TRY(vv_add_rows(c0 + (size_t)r * D, D, temb_rows + (size_t)r * D, D, c + (size_t)r * D, 1, 1, D, stream));
   VV_TRY(head_modulations(h, c, R, mod, modf, false, false, stream));
-  return head_body(h, x, h->latent, R, mod, modf, 0, hcur, act, v, stream);
+  return head_body(h, wq, x, h->latent, R, mod, modf, 0, hcur, act, v, stream);
 }
 
 extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const float* noise, const float* temb,
@@ -270,6 +284,7 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
                               const float* sde_noise, vv_stream_t stream) {
   if (!h || !cond2 || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "vv_head_sample: null pointer");
   if (n_steps <= 0 || h->layers > 16) return vv_set_error(VV_E_ARG, "vv_head_sample: bad n_steps/layers");
+  VV_WQ_STRIP(vv_head, h);
   hipStream_t s = (hipStream_t)stream;
   const int D = h->D;
   const size_t R = 2 * (size_t)n_steps > 8 ? 2 * (size_t)n_steps : 8;
@@ -322,11 +337,11 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
         a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
         a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
         a.w2 = L.wup; a.act = VV_ACT_SWIGLU; a.flags = VV_LIN_W_REUSED;
-        use_w8(a, L.q_gate, &L.q_up);
+        use_w8(a, wq, L.q_gate, &L.q_up);
         VV_TRY(vv_linear(&a, stream));
         a = lin_base(act, h->ffn, 2, L.wdown, D, h->ffn, h->wdt, hc, D);
         a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hc; a.ldres = D; a.flags = VV_LIN_W_REUSED;
-        use_w8(a, L.q_down);
+        use_w8(a, wq, L.q_down);
         VV_TRY(vv_linear(&a, stream));
       }
       const float* mf = modf + (size_t)2 * i * 2 * D;
@@ -342,7 +357,7 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
                        i == n_steps ? nullptr : h->noisy_proj, h->wdt, h->latent, D, hcur, D, 2,
                        (sde_noise && i > 0) ? sde_noise + (size_t)(i - 1) * h->latent : nullptr, stream));
     if (i == n_steps) break;
-    VV_TRY(head_body(h, nullptr, 0, 2, mod, modf, 2 * (int64_t)i, hcur, act, v, stream));
+    VV_TRY(head_body(h, wq, nullptr, 0, 2, mod, modf, 2 * (int64_t)i, hcur, act, v, stream));
   }
   (void)s;
   return 0;
@@ -351,6 +366,7 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
 // B utterances per call: rows [2 B] everywhere the single-utterance sampler has 2; conditioning rows laid out [step][2 B]
 extern "C" size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B) {
   if (!h || n_steps <= 0 || B <= 0 || B > 4) return 0;
+  VV_WQ_STRIP(vv_head, h);
   const size_t R = (size_t)2 * B * n_steps, D = h->D;
   return al(8 * D) /*c0*/ + al(R * D) /*c (bf16 rows fit)*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + 2 * al(8 * D) /*hidden rows x 2*/ +
          al(8 * (size_t)h->ffn) + 2 * al((size_t)B * (D + h->latent)) /*solver state X, M*/ +
@@ -373,6 +389,8 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
   const char* fn = sde_fn ? sde_fn : "vv_head_sample_batch";
   if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
   if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 4) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..4)", fn, n_steps, h->layers, B);
+  VV_WQ_STRIP(vv_head, h);
+  const bool f8q = wq == VV_FP8;                  // NF4 companions: the bf16 matrices (and their bf16 fragment-major copies) serve these rows
   if (!sde_fn)
     for (int i = 0; i < n_steps; ++i)
       if (coef[i].cn != 0.f) return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: the SDE solver is served by vv_head_sample_batch_sde");
@@ -418,10 +436,10 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
       a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
       a.w2 = L.wup; a.act = VV_ACT_SWIGLU; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, &L.q_gate, &L.q_up));
+      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_gate : nullptr, f8q ? &L.q_up : nullptr));
       a = lin_base(act, h->ffn, R2, L.wdown, D, h->ffn, h->wdt, hc, D);
       a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hc; a.ldres = D; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, &L.q_down));
+      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_down : nullptr));
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
     VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,
@@ -499,6 +517,7 @@ static size_t convnet_pad_floats(const vv_convnet* net, int64_t t_in, size_t* of
 
 extern "C" size_t vv_convnet_ws_bytes(const vv_convnet* net, int64_t t_in, int decoder) {
   if (!net || t_in <= 0) return 0;
+  VV_WQ_STRIP(vv_convnet, net);
   size_t a, h;
   convnet_sizes(net, t_in, decoder, &a, &h);
   return 2 * al(a) + al(h) + (convnet_streaming(net) ? al(convnet_pad_floats(net, t_in, nullptr)) + al(VV_ROW_HIST_FLOATS) : 0);
@@ -508,7 +527,7 @@ extern "C" size_t vv_convnet_ws_bytes(const vv_convnet* net, int64_t t_in, int d
 // that it becomes the next conv's padded input; *pad_out is that buffer.  Unfused block (mixer -> other, lin1 -> hid, lin2): the
 // dead input buffer is the only one free, so the result goes there, shifted.  Fused block (one launch reads its input while
 // other row tiles already write): the result must not overlap the input; `other` is free (no mixer output) and takes it.
-static int run_blocks(const vv_convnet* net, int stage, int64_t T, int C, float*& cur, float*& other, float* hid,
+static int run_blocks(const vv_convnet* net, int wq, int stage, int64_t T, int C, float*& cur, float*& other, float* hid,
                       int nctx, float** pad_out, vv_stream_t stream, float* next_pad = nullptr, float* row_hist = nullptr,
                       vv_conv_ctx_item* items = nullptr, int* n_items = nullptr, int* row_stage = nullptr) {
   // row_hist / items (streaming nets): scratch for the new histories of the one-row stage's blocks and the list of state moves that the
@@ -545,7 +564,7 @@ static int run_blocks(const vv_convnet* net, int stage, int64_t T, int C, float*
         float* dst1 = (last && final_dst) ? final_dst : other;
         vv_lin_args a1 = lin_base(hid, 4 * C, 1, B.w2, C, 4 * C, net->wdt, dst1, C);
         a1.bias = B.b2; a1.gate = B.ffn_gamma; a1.gate_ld = 0; a1.res = other; a1.ldres = C;
-        use_w8(a1, B.q_w2);
+        use_w8(a1, wq, B.q_w2);
         VV_TRY(vv_linear(&a1, stream));
         if (dst1 == other) { float* t = cur; cur = other; other = t; }
         else { cur = nullptr; }
@@ -587,13 +606,13 @@ static int run_blocks(const vv_convnet* net, int stage, int64_t T, int C, float*
       a.pro = VV_PRO_RMSNORM; a.norm_w = B.ffn_norm_w; a.eps = net->eps; a.bias = B.b1; a.act = VV_ACT_GELU;
     }
     if (handoff) a.flags |= VV_LIN_OUT_BF16;
-    use_w8(a, B.q_w1);
+    use_w8(a, wq, B.q_w1);
     VV_TRY(vv_linear(&a, stream));
     float* dst = (j == nb - 1 && final_dst) ? final_dst : other;
     a = lin_base(hid, 4 * C, (int)T, B.w2, C, 4 * C, net->wdt, dst, C);
     if (handoff) a.flags |= VV_LIN_X_BF16;
     a.bias = B.b2; a.gate = B.ffn_gamma; a.gate_ld = 0; a.res = other; a.ldres = C;
-    use_w8(a, B.q_w2);
+    use_w8(a, wq, B.q_w2);
     VV_TRY(vv_linear(&a, stream));
     if (dst == other) { float* t = cur; cur = other; other = t; }   // result now in `cur`
     else { cur = nullptr; }                                           // result went to final_dst
@@ -615,6 +634,7 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
                                   void* ws, vv_stream_t stream) {
   if (!net || !latent || !wav || !ws) return vv_set_error(VV_E_ARG, "vv_decoder_forward: null pointer");
   if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "vv_decoder_forward: bad T/stages");
+  VV_WQ_STRIP(vv_convnet, net);
   size_t ael, hel;
   convnet_sizes(net, T0, 1, &ael, &hel);
   Carver cvr(ws);
@@ -678,7 +698,7 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
       // the last block writes straight into the next conv's padded input; which buffer that is depends on block parity:
       // block j reads cur -> writes other, then they swap.  The last block's mixer output sits in `other_last`, its
       // result may go anywhere except that buffer and hid: use the buffer holding the (dead) input of that block.
-      VV_TRY(run_blocks(net, i, T, C, cur, other, hid, nctx, &pad, stream, next_pad, row_hist, items, &n_items, &row_stage));
+      VV_TRY(run_blocks(net, wq, i, T, C, cur, other, hid, nctx, &pad, stream, next_pad, row_hist, items, &n_items, &row_stage));
     } else {
       float* dstb = next_pad ? next_pad : other;
       hipError_t e = hipMemcpyAsync(dstb + (size_t)nctx * C, cur, (size_t)T * C * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
@@ -698,6 +718,7 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
 extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64_t T0, float* feat, void* ws, vv_stream_t stream) {
   if (!net || !wav || !feat || !ws) return vv_set_error(VV_E_ARG, "vv_encoder_forward: null pointer");
   if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "vv_encoder_forward: bad T/stages");
+  VV_WQ_STRIP(vv_convnet, net);
   hipStream_t s = (hipStream_t)stream;
   size_t ael, hel;
   convnet_sizes(net, T0, 0, &ael, &hel);
@@ -783,7 +804,7 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
     const int nctx = conv_ctx_of(nxt);
     float* next_pad = streaming ? pads + poff[i + 1] : nullptr;
     if (net->n_blocks[i] > 0) {
-      VV_TRY(run_blocks(net, i, T, C, cur, other, hid, nctx, &pad, stream, next_pad, row_hist, items, &n_items, &row_stage));
+      VV_TRY(run_blocks(net, wq, i, T, C, cur, other, hid, nctx, &pad, stream, next_pad, row_hist, items, &n_items, &row_stage));
     } else {
       float* dstb = next_pad ? next_pad : other;
       e = hipMemcpyAsync(dstb + (size_t)nctx * C, cur, (size_t)T * C * 4, hipMemcpyDeviceToDevice, s);
@@ -797,6 +818,7 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
 
 extern "C" int vv_convnet_reset(const vv_convnet* net, vv_stream_t stream) {
   if (!net) return vv_set_error(VV_E_ARG, "vv_convnet_reset: null");
+  VV_WQ_STRIP(vv_convnet, net);
   hipStream_t s = (hipStream_t)stream;
   for (int i = 0; i <= net->n_stages; ++i) {
     const vv_conv& cv = (i == net->n_stages) ? net->head : net->sample[i];

@@ -52,7 +52,38 @@ def load_state_dict_from_dir(path: str) -> Dict[str, torch.Tensor]:
     sd: Dict[str, torch.Tensor] = {}
     for fn in files:
         sd.update(load_file(os.path.join(path, fn)))
+    bnb = [k for k in sd if k.endswith((".weight.absmax", ".weight.quant_map", ".weight.quant_state.bitsandbytes__nf4",
+                                        ".weight.quant_state.bitsandbytes__fp4", ".weight.nested_absmax"))]
+    if bnb:
+        raise NotImplementedError(f"{path!r} is a pre-quantized bitsandbytes 4-bit checkpoint ({bnb[0]!r}, ...): loading that format is not built. "
+                                  "Quantize on the fly instead: from_pretrained(<the bf16 checkpoint>, quantization_config=BitsAndBytesConfig("
+                                  "load_in_4bit=True, bnb_4bit_quant_type='nf4')) or weight_quant='nf4'")
     return sd
+
+
+def weight_quant_from_config(quantization_config, weight_quant: Optional[str] = None) -> Optional[str]:
+    """Map a transformers BitsAndBytesConfig - or any object or dict with its attribute names - onto this engine's weight_quant.
+    load_in_4bit with bnb_4bit_quant_type "nf4" -> "nf4" (weights and activations stay bf16 whatever torch_dtype / bnb_4bit_compute_dtype says:
+    the engine has no fp16 path; bnb_4bit_use_double_quant is accepted, the block scales stay fp32).  fp4 and 8-bit loads are not built."""
+    if quantization_config is None:
+        return weight_quant
+
+    def get(name, default=None):
+        if isinstance(quantization_config, dict):
+            return quantization_config.get(name, default)
+        return getattr(quantization_config, name, default)
+
+    built = "built: 4-bit NF4 (load_in_4bit=True, bnb_4bit_quant_type='nf4', or weight_quant='nf4') and weight-only fp8 (weight_quant='fp8')"
+    if get("load_in_8bit", False):
+        raise NotImplementedError(f"load_in_8bit is not built; {built}")
+    if not get("load_in_4bit", False):
+        raise NotImplementedError(f"quantization_config without load_in_4bit is not built; {built}")
+    qt = str(get("bnb_4bit_quant_type", "fp4")).lower()     # bitsandbytes' default 4-bit type is fp4
+    if qt != "nf4":
+        raise NotImplementedError(f"bnb_4bit_quant_type={qt!r} is not built; {built}")
+    if weight_quant not in (None, "nf4"):
+        raise ValueError(f"quantization_config asks for nf4 but weight_quant={weight_quant!r}: give one or the other")
+    return "nf4"
 
 
 def save_checkpoint_dir(path: str, config: VVConfig, state_dict: Dict[str, torch.Tensor], max_shard_bytes: int = 2 * 10 ** 9,
@@ -194,7 +225,8 @@ class VibeVoiceForConditionalGenerationInference:
         self.row_batch = os.environ.get("VV_ROW_BATCH", "1") != "0"
         self.row_batch_min = int(os.environ.get("VV_ROW_BATCH_MIN", "2"))      # 2 dialogues: 64 vs 58 audio-sec/s on the lanes
         self._rowbatch = {}
-        # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs
+        # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
+        # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant)
         self.device = self.engine.device
@@ -217,13 +249,16 @@ class VibeVoiceForConditionalGenerationInference:
         path = str(pretrained_model_name_or_path)
         if not os.path.isdir(path):
             raise OSError(f"{path!r} is not a local checkpoint directory (this build has no hub access)")
+        wq = weight_quant_from_config(kw.get("quantization_config"), kw.get("weight_quant"))
+        if wq == "nf4" and kw.get("quantization_config") is not None:
+            torch_dtype = torch.bfloat16        # bnb's fp16 / bf16 compute dtype is served as bf16 (no fp16 path)
         cfg = VVConfig.from_pretrained(path)
         device = device_map if isinstance(device_map, (str, torch.device)) and str(device_map) not in ("auto", "cpu") else "cuda:0"
         if str(device) == "cuda":
             device = "cuda:0"
         return cls(cfg, load_state_dict_from_dir(path), device=device, torch_dtype=torch_dtype,
                    attn_implementation=attn_implementation or "hip_gfx950", use_graphs=kw.get("use_graphs", True),
-                   weight_quant=kw.get("weight_quant"))
+                   weight_quant=wq)
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):

@@ -71,18 +71,94 @@ def fp8_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict
     return out
 
 
+# bitsandbytes' NF4 code book (index = 4-bit code), in this order
+NF4_TABLE = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
+             -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+             0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0)
+NF4_BLOCK = 64
+
+
+def _nf4_thresholds() -> torch.Tensor:
+    """The 15 decision thresholds of bnb's dQuantizeNF4: midpoints of neighbouring table entries (fp64 midpoint, fp32 constant)."""
+    t = torch.tensor(NF4_TABLE, dtype=torch.float64)
+    return ((t[1:] + t[:-1]) / 2).float()
+
+
+def quantize_nf4(w: torch.Tensor):
+    """Weight-only blockwise NF4 of a [N, K] matrix (K % 64 == 0), bitsandbytes' definition restated:
+      * blocks are 64 consecutive weights along K within an output row;
+      * absmax = fp32 max |w| over the block (w = the weight widened to fp32);
+      * code = index of the table entry nearest to w * (1 / absmax) (fp32), ties to the lower code (bnb compares x > midpoint);
+      * a block with absmax == 0 gets code 7 (0.0) and scale 0;
+      * effective weight = bf16_rne(fp32(table[code]) * absmax): bnb's dequantisation with bf16 as compute dtype (there is no fp16 path).
+    Double quantisation of the scales is not reproduced: absmax stays fp32.
+    Returns (codes uint8 [N, K], absmax fp32 [N, K / 64], effective weights fp32 [N, K], every value exactly bf16-representable)."""
+    n, k = w.shape
+    if k % NF4_BLOCK:
+        raise ValueError(f"NF4 needs K % {NF4_BLOCK} == 0 (K={k})")
+    wf = w.detach().float().reshape(n, k // NF4_BLOCK, NF4_BLOCK)
+    absmax = wf.abs().amax(dim=2)
+    zero = absmax == 0
+    inv = torch.where(zero, torch.zeros_like(absmax), torch.reciprocal(absmax))
+    x = (wf * inv[..., None]).contiguous()
+    codes = torch.searchsorted(_nf4_thresholds().to(x.device), x, right=False).to(torch.uint8)   # number of thresholds t with x > t
+    codes = torch.where(zero[..., None], torch.full_like(codes, 7), codes)
+    table = torch.tensor(NF4_TABLE, dtype=torch.float32, device=x.device)
+    eff = (table[codes.long()] * absmax[..., None]).to(torch.bfloat16).float()
+    return codes.reshape(n, k).contiguous(), absmax.contiguous(), eff.reshape(n, k).contiguous()
+
+
+def pack_nf4(codes: torch.Tensor, absmax: torch.Tensor):
+    """(codes uint8 [N, K], absmax fp32 [N, K / 64]) -> the streaming GEMV's VV_NF4 layout (include/vv_hip.h), padded with code 0 / scale 0:
+    codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B] - nibble i of dword r of lane l's 16 bytes is code (4 q + r, 512 u + 8 l + i) -
+    and absmax [ceil(N/4)][ceil(K/512)][4 rows][8 blocks].  Returns (uint8 1-D, fp32 1-D)."""
+    n, k = codes.shape
+    nq, ku = (n + 3) // 4, (k + 511) // 512
+    c = torch.zeros(nq * 4, ku * 512, dtype=torch.uint8, device=codes.device)
+    c[:n, :k] = codes
+    c = c.view(nq, 4, ku, 64, 4, 2).permute(0, 2, 3, 1, 4, 5)           # [q, u, lane, r, byte, nibble]
+    packed = (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
+    s = torch.zeros(nq * 4, ku * 8, dtype=torch.float32, device=absmax.device)
+    s[:n, : k // NF4_BLOCK] = absmax
+    scales = s.view(nq, 4, ku, 8).permute(0, 2, 1, 3).contiguous().view(-1)
+    return packed, scales
+
+
+def unpack_nf4(packed: torch.Tensor, scales: torch.Tensor, n: int, k: int):
+    """Inverse of pack_nf4: (codes uint8 [N, K], absmax fp32 [N, K / 64])."""
+    nq, ku = (n + 3) // 4, (k + 511) // 512
+    b = packed.view(nq, ku, 64, 4, 4)
+    c = torch.stack([b & 15, b >> 4], dim=-1)                           # [q, u, lane, r, byte, nibble]
+    codes = c.permute(0, 3, 1, 2, 4, 5).reshape(nq * 4, ku * 512)[:n, :k].contiguous()
+    absmax = scales.view(nq, ku, 4, 8).permute(0, 2, 1, 3).reshape(nq * 4, ku * 8)[:n, : k // NF4_BLOCK].contiguous()
+    return codes, absmax
+
+
+def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The state dict a weight_quant="nf4" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
+    K % 64 == 0 replaced by the effective NF4 weights of its bf16 rounding bf16(table[code] * absmax) (fp32 tensors; q/k/v quantise the same fused or apart, the
+    blocks lie inside rows)."""
+    out = dict(sd)
+    for name in fp8_matrix_names(cfg):
+        if sd[name].shape[1] % NF4_BLOCK == 0:
+            out[name] = quantize_nf4(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
+    return out
+
+
 class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
     def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None):
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
-        if quant not in (None, "fp8"):
-            raise ValueError(f"weight_quant {quant!r}: only None or 'fp8' (weight-only e4m3, decode GEMVs) is built")
-        if quant == "fp8" and wdtype != torch.bfloat16:
-            raise ValueError("weight_quant='fp8' keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
+        if quant not in (None, "fp8", "nf4"):
+            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3) or 'nf4' (weight-only 4-bit NF4), decode GEMVs, is built")
+        if quant is not None and wdtype != torch.bfloat16:
+            raise ValueError(f"weight_quant={quant!r} keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
         self.quant = quant
-        self._fp8_names = set(fp8_matrix_names(cfg)) if quant == "fp8" else set()
+        self._fp8_names = set(fp8_matrix_names(cfg)) if quant is not None else set()     # the matrices that get a companion
         self.wdt = _wdt(wdtype)
+        # the descriptors' wdt: VV_WQ_NF4 marks their vv_w8 companions as NF4 (vv_hip.h); self.wdt stays the plain matrix dtype
+        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
         # the fragment-major copies (ensure_frag) live here: one dict object shared by every fork, as the ctypes layer arrays they are
         # written into are, so they are built once per process whichever fork asks first
@@ -122,8 +198,17 @@ class DeviceWeights:
         return t
 
     def _mat_q(self, t: torch.Tensor, quantise: bool):
-        """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales)."""
+        """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
+        mode it holds the effective weights bf16(table[code] * absmax) and the companion the packed codes and block scales (pack_nf4).
+        An NF4 matrix with K % 64 != 0 gets no companion."""
         w8 = L.W8()
+        if self.quant == "nf4" and quantise and t.shape[1] % NF4_BLOCK == 0:
+            codes, absmax, eff = quantize_nf4(t.to(device=self.device, dtype=torch.bfloat16))    # the bf16 weight, widened
+            packed, scales = pack_nf4(codes, absmax)
+            packed = self._aligned(packed)
+            self._keep.append(packed)
+            w8.q, w8.scale = L.ptr(packed), L.ptr(self._vec(scales))
+            return self._mat(eff), w8
         if not (quantise and self.quant == "fp8"):
             return self._mat(t), w8
         codes, scale, eff = quantize_e4m3_pow2(t.to(self.device))
@@ -210,7 +295,7 @@ class DeviceWeights:
         by_ptr = {t.data_ptr(): t for t in self._keep if isinstance(t, torch.Tensor)}
 
         def frag_of(p, w8, n, k):
-            if w8.q:          # fp8 companion: the copy is of its codes, or none
+            if w8.q and self.quant == "fp8":    # fp8 companion: the copy is of its codes, or none (NF4: the bf16 effective matrix)
                 t, fm = by_ptr.get(int(w8.q)), self.frag_major_fp8
             else:
                 t, fm = (by_ptr.get(int(p)) if p else None), self.frag_major
@@ -261,7 +346,7 @@ class DeviceWeights:
         layers = (L.LlmLayer * cfg.layers)()
         for l in range(cfg.layers):
             q = f"{p}layers.{l}."
-            qz = self.quant == "fp8"
+            qz = self.quant is not None
             lay = layers[l]
             wqkv, lay.q_qkv = self._mat_q(torch.cat([sd[q + "self_attn.q_proj.weight"], sd[q + "self_attn.k_proj.weight"],
                                                     sd[q + "self_attn.v_proj.weight"]], dim=0), qz)
@@ -279,7 +364,7 @@ class DeviceWeights:
         inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, cfg.head_dim, 2, dtype=torch.float) / cfg.head_dim))
         self.inv_freq = self._vec(inv_freq)
         m = L.Llm()
-        m.wdt, m.hidden, m.inter, m.layers = self.wdt, cfg.hidden, cfg.inter, cfg.layers
+        m.wdt, m.hidden, m.inter, m.layers = self.desc_wdt, cfg.hidden, cfg.inter, cfg.layers
         m.heads, m.kv_heads, m.head_dim, m.rms_eps = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.rms_eps
         m.inv_freq = L.ptr(self.inv_freq)
         m.final_norm = L.ptr(self._vec(sd[p + "norm.weight"]))
@@ -298,12 +383,12 @@ class DeviceWeights:
             lay.norm_w = L.ptr(self._vec(sd[q + "norm.weight"]))
             for field, qf, key in (("wgate", "q_gate", "ffn.gate_proj.weight"), ("wup", "q_up", "ffn.up_proj.weight"),
                                    ("wdown", "q_down", "ffn.down_proj.weight")):
-                wm, w8 = self._mat_q(sd[q + key], self.quant == "fp8")
+                wm, w8 = self._mat_q(sd[q + key], self.quant is not None)
                 setattr(lay, field, L.ptr(wm))
                 setattr(lay, qf, w8)
             lay.adaln = L.ptr(self._mat(sd[q + "adaLN_modulation.1.weight"]))
         h = L.Head()
-        h.wdt, h.D, h.ffn, h.layers, h.latent, h.cond_dim = self.wdt, cfg.head_hidden, cfg.head_ffn, cfg.head_layers, cfg.latent, cfg.hidden
+        h.wdt, h.D, h.ffn, h.layers, h.latent, h.cond_dim = self.desc_wdt, cfg.head_hidden, cfg.head_ffn, cfg.head_layers, cfg.latent, cfg.hidden
         h.eps = cfg.head_eps
         h.noisy_proj = L.ptr(self._mat(sd[p + "noisy_images_proj.weight"]))
         h.cond_proj = L.ptr(self._mat(sd[p + "cond_proj.weight"]))
@@ -385,7 +470,7 @@ class DeviceWeights:
         if n > L.VV_MAX_STAGES:
             raise ValueError("too many tokenizer stages")
         net = L.ConvNet()
-        net.wdt, net.n_stages, net.eps = self.wdt, n, eps
+        net.wdt, net.n_stages, net.eps = self.desc_wdt, n, eps
         if decoder:
             depths = list(reversed(depths_enc))
             for i in range(n):
