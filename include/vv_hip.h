@@ -382,6 +382,32 @@ typedef struct vv_prof_entry { int m, n, k, dual, wdt, count; double total_ms; }
 int vv_prof_begin(int max_records);
 int vv_prof_end(vv_prof_entry* out, int max_out, int* n_out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * vv_nf4_import — one matrix of a pre-quantized bitsandbytes 4-bit NF4 checkpoint (functional.quantize_4bit storage, QuantState.as_dict)
+ * into the engine's layouts, in one pass over its packed bytes.  Load time only.
+ *   packed:  ceil(n * k / 2) bytes over the row-major flattened [n, k] weight; element 2 i is the HIGH nibble of byte i, 2 i + 1 the low one
+ *   absmax:  one scale per `blocksize` consecutive flattened elements (blocks may straddle rows): fp32 [nblocks], or with double quantisation
+ *            (nested_absmax != NULL) uint8 codes [nblocks] decoded as (nested_map[code] * nested_absmax[b / nested_blocksize]) + nested_offset
+ *   value:   bf16_rne(quant_map[code] * absmax[j / blocksize]) in fp32, each operation rounded on its own (no FMA contraction)
+ * Writes rows row0 .. row0 + n - 1 of the destination (a fused [q|k|v] matrix takes q, k and v as three calls), which has rows_total rows:
+ *   w:              bf16 [rows_total][ldw] row-major (ldw >= k)
+ *   cq / cs:        optional (both or neither) VV_NF4 companion of the whole destination (codes and block absmax, the vv_linear layouts above,
+ *                   ceil(rows_total / 4) * ceil(k / 512) * 1024 bytes and * 32 floats, zeroed by the caller: padding stays code 0 / scale 0).
+ *                   Only when the companion holds the file's numbers exactly: k % 64 == 0, blocksize % 64 == 0 and k % blocksize == 0 (a block of
+ *                   128 or 256 becomes 2 or 4 64-blocks repeating one scale); anything else with cq / cs is VV_E_ARG.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct vv_nf4_src {
+  const uint8_t* packed;
+  const void* absmax;            /* fp32, or uint8 codes when nested_absmax != NULL */
+  const float* quant_map;        /* [16] */
+  const float* nested_absmax;    /* [ceil(nblocks / nested_blocksize)] or NULL */
+  const float* nested_map;       /* [256] (the stored dynamic map) */
+  float nested_offset;
+  int nested_blocksize;
+  int n, k, blocksize;
+} vv_nf4_src;
+int vv_nf4_import(const vv_nf4_src* src, void* w, int64_t ldw, int row0, int rows_total, void* cq, float* cs, vv_stream_t stream);
+
 /* struct sizes, for the ctypes mirror's self-check */
 size_t vv_sizeof(const char* struct_name);
 

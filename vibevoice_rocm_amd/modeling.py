@@ -36,9 +36,7 @@ class VibeVoiceGenerationOutput:
     reach_max_step_sample: Optional[torch.BoolTensor] = None
 
 
-def load_state_dict_from_dir(path: str) -> Dict[str, torch.Tensor]:
-    """HF sharded-safetensors checkpoint as the reference's converter writes it
-    (vibevoice/scripts/convert_nnscaler_checkpoint_to_transformers.py:116-123)."""
+def _read_safetensors_dir(path: str) -> Dict[str, torch.Tensor]:
     from safetensors.torch import load_file
     idx = os.path.join(path, "model.safetensors.index.json")
     files = []
@@ -52,13 +50,30 @@ def load_state_dict_from_dir(path: str) -> Dict[str, torch.Tensor]:
     sd: Dict[str, torch.Tensor] = {}
     for fn in files:
         sd.update(load_file(os.path.join(path, fn)))
+    return sd
+
+
+def load_state_dict_from_dir(path: str) -> Dict[str, torch.Tensor]:
+    """HF sharded-safetensors checkpoint as the reference's converter writes it
+    (vibevoice/scripts/convert_nnscaler_checkpoint_to_transformers.py:116-123).  Plain tensors only: a pre-quantized bitsandbytes checkpoint is
+    refused here (load_prequantized_dir reads it)."""
+    sd = _read_safetensors_dir(path)
     bnb = [k for k in sd if k.endswith((".weight.absmax", ".weight.quant_map", ".weight.quant_state.bitsandbytes__nf4",
                                         ".weight.quant_state.bitsandbytes__fp4", ".weight.nested_absmax"))]
     if bnb:
-        raise NotImplementedError(f"{path!r} is a pre-quantized bitsandbytes 4-bit checkpoint ({bnb[0]!r}, ...): loading that format is not built. "
-                                  "Quantize on the fly instead: from_pretrained(<the bf16 checkpoint>, quantization_config=BitsAndBytesConfig("
-                                  "load_in_4bit=True, bnb_4bit_quant_type='nf4')) or weight_quant='nf4'")
+        raise NotImplementedError(f"{path!r} is a pre-quantized bitsandbytes 4-bit checkpoint ({bnb[0]!r}, ...): this plain-tensor loader does not "
+                                  "read it. Use load_prequantized_dir(path), which returns the plain tensors and the NF4 matrices as they are, or "
+                                  "VibeVoiceForConditionalGenerationInference.from_pretrained(path), which detects the format and runs it as "
+                                  "weight_quant='nf4'")
     return sd
+
+
+def load_prequantized_dir(path: str):
+    """(plain tensors, {weight key: bnb.BnbNF4}) of a checkpoint directory: a pre-quantized bitsandbytes NF4 checkpoint (what save_pretrained
+    writes after a BitsAndBytesConfig(load_in_4bit=True, bnb_4bit_quant_type="nf4") load; format in bnb.py) gives its quantised matrices as
+    records and every other tensor as it is; a plain checkpoint gives an empty record dict."""
+    from .bnb import split_prequantized
+    return split_prequantized(_read_safetensors_dir(path))
 
 
 def weight_quant_from_config(quantization_config, weight_quant: Optional[str] = None) -> Optional[str]:
@@ -212,8 +227,17 @@ def _make_sampler(gen_cfg: dict):
 
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
-                 attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None):
-        missing = [k for k in state_dict_shapes(config) if k not in state_dict]
+                 attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None):
+        # prequant: the NF4 matrices of a pre-quantized bitsandbytes checkpoint ({weight key: bnb.BnbNF4}, load_prequantized_dir); they run as
+        # weight_quant="nf4" with bf16 compute, codes and scales taken as the file holds them
+        shapes = state_dict_shapes(config)
+        if prequant:
+            from .bnb import check_shapes
+            check_shapes(prequant, shapes)
+            if weight_quant not in (None, "nf4"):
+                raise ValueError(f"a pre-quantized bitsandbytes NF4 checkpoint runs as weight_quant='nf4', not {weight_quant!r}")
+            weight_quant, torch_dtype = "nf4", torch.bfloat16
+        missing = [k for k in shapes if k not in state_dict and k not in (prequant or {})]
         if missing:
             raise KeyError(f"state dict is missing {len(missing)} tensors, e.g. {missing[:4]}")
         self.config = config
@@ -228,7 +252,8 @@ class VibeVoiceForConditionalGenerationInference:
         # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         self.weight_quant = weight_quant
-        self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant)
+        self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
+                             prequant=prequant)
         self.device = self.engine.device
         # batches run in lock step on one Engine per sample (own HIP stream, KV cache and conv state; matrices already in the streamed
         # dtype on the device are shared, not copied): lanes beyond the first are built on first use from this state dict
@@ -243,22 +268,39 @@ class VibeVoiceForConditionalGenerationInference:
     # ---- construction ----------------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, torch_dtype=torch.bfloat16, device_map=None,
-                        attn_implementation: Optional[str] = None, **kw):
+                        attn_implementation: Optional[str] = None, subfolder: Optional[str] = None, config=None, quantization_config=None,
+                        local_files_only=None, cache_dir=None, **kw):
         """Load a local checkpoint directory (config.json + safetensors shards).  `attn_implementation` is accepted for
-        call compatibility; attention always runs on the hand-written gfx950 kernel."""
+        call compatibility; attention always runs on the hand-written gfx950 kernel.  `subfolder` joins the path; `config` (the shim's
+        VibeVoiceConfig, a VVConfig or a config.json dict) overrides the directory's config.json.  A pre-quantized bitsandbytes NF4 checkpoint
+        is detected from its tensors, with or without `quantization_config`, and runs as weight_quant="nf4" in bf16.  `local_files_only` and
+        `cache_dir` are accepted and ignored: paths are local directories only."""
         path = str(pretrained_model_name_or_path)
+        if subfolder:
+            path = os.path.join(path, subfolder)
         if not os.path.isdir(path):
             raise OSError(f"{path!r} is not a local checkpoint directory (this build has no hub access)")
-        wq = weight_quant_from_config(kw.get("quantization_config"), kw.get("weight_quant"))
-        if wq == "nf4" and kw.get("quantization_config") is not None:
+        wq = weight_quant_from_config(quantization_config, kw.get("weight_quant"))
+        if wq == "nf4" and quantization_config is not None:
             torch_dtype = torch.bfloat16        # bnb's fp16 / bf16 compute dtype is served as bf16 (no fp16 path)
-        cfg = VVConfig.from_pretrained(path)
+        if config is None:
+            cfg = VVConfig.from_pretrained(path)
+        elif isinstance(config, VVConfig):
+            cfg = config
+        elif isinstance(config, dict):
+            cfg = VVConfig.from_json_dict(config)
+        else:
+            cfg = VVConfig.from_json_dict(config.to_dict())
+        sd, prequant = load_prequantized_dir(path)
+        if prequant:
+            if kw.get("weight_quant") not in (None, "nf4"):
+                raise ValueError(f"{path!r} is a pre-quantized bitsandbytes NF4 checkpoint: weight_quant={kw.get('weight_quant')!r} cannot apply")
+            wq, torch_dtype = "nf4", torch.bfloat16
         device = device_map if isinstance(device_map, (str, torch.device)) and str(device_map) not in ("auto", "cpu") else "cuda:0"
         if str(device) == "cuda":
             device = "cuda:0"
-        return cls(cfg, load_state_dict_from_dir(path), device=device, torch_dtype=torch_dtype,
-                   attn_implementation=attn_implementation or "hip_gfx950", use_graphs=kw.get("use_graphs", True),
-                   weight_quant=wq)
+        return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
+                   use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None)
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):

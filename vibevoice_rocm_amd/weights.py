@@ -148,13 +148,19 @@ def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict
 class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
-    def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None):
+    def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None,
+                 prequant: Optional[Dict[str, object]] = None):
+        """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
+        are imported as they are (vv_nf4_import) and need quant="nf4"."""
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
         if quant not in (None, "fp8", "nf4"):
             raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3) or 'nf4' (weight-only 4-bit NF4), decode GEMVs, is built")
         if quant is not None and wdtype != torch.bfloat16:
             raise ValueError(f"weight_quant={quant!r} keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
+        if prequant and quant != "nf4":
+            raise ValueError(f"a pre-quantized bitsandbytes NF4 checkpoint runs as weight_quant='nf4', not {quant!r}")
         self.quant = quant
+        self._pre = dict(prequant or {})
         self._fp8_names = set(fp8_matrix_names(cfg)) if quant is not None else set()     # the matrices that get a companion
         self.wdt = _wdt(wdtype)
         # the descriptors' wdt: VV_WQ_NF4 marks their vv_w8 companions as NF4 (vv_hip.h); self.wdt stays the plain matrix dtype
@@ -185,6 +191,7 @@ class DeviceWeights:
         self.speech_scale = float(sd["model.speech_scaling_factor"].float().item())
         self.speech_bias = float(sd["model.speech_bias_factor"].float().item())
         self._sd = None
+        self._pre = {}
 
     # ---- helpers -------------------------------------------------------------------------------------------------
     @staticmethod
@@ -196,6 +203,35 @@ class DeviceWeights:
         t = self._aligned(t.detach().to(device=self.device, dtype=self.wdtype).contiguous())
         self._keep.append(t)
         return t
+
+    def _w(self, key: str) -> torch.Tensor:
+        """A weight as the checkpoint holds it: the plain tensor, or for a pre-quantized bnb matrix its bf16 effective values (vv_nf4_import,
+        no companion) in its quant_state shape."""
+        r = self._pre.get(key)
+        if r is None:
+            return self._sd[key]
+        from .bnb import import_nf4
+        return import_nf4([r], self.device, companion=False)[0].view(r.shape)
+
+    def _mat_q_keys(self, keys: List[str], quantise: bool):
+        """_mat_q of the named matrices stacked along N (one key, or q / k / v for the fused [q|k|v] matrix).  Matrices that a pre-quantized
+        checkpoint holds in bnb form are imported as they are - with the VV_NF4 companion when `quantise` and every part fits it exactly; a
+        companion-set matrix that such a checkpoint holds unquantized runs bf16, without a companion (it is not quantised on the fly)."""
+        if not self._pre:
+            t = self._sd[keys[0]] if len(keys) == 1 else torch.cat([self._sd[k] for k in keys], dim=0)
+            return self._mat_q(t, quantise)
+        w8 = L.W8()
+        parts = [self._pre.get(k) for k in keys]
+        if all(p is not None for p in parts):
+            from .bnb import import_nf4
+            comp = quantise and all(p.companion_exact() for p in parts)
+            w, packed, scales = import_nf4(parts, self.device, companion=comp)
+            if comp:
+                self._keep.append(packed)
+                w8.q, w8.scale = L.ptr(packed), L.ptr(self._vec(scales))
+            return self._mat(w), w8
+        t = torch.cat([self._w(k).to(self.device, self.wdtype) for k in keys], dim=0)
+        return self._mat(t), w8
 
     def _mat_q(self, t: torch.Tensor, quantise: bool):
         """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
@@ -341,15 +377,15 @@ class DeviceWeights:
     def _build_llm(self):
         cfg, sd = self.cfg, self._sd
         p = "model.language_model."
-        self.embed = self._mat(sd[p + "embed_tokens.weight"])
-        self.lm_head = self.embed if (cfg.tie or "lm_head.weight" not in sd) else self._mat(sd["lm_head.weight"])
+        self.embed = self._mat(self._w(p + "embed_tokens.weight"))
+        has_head = "lm_head.weight" in sd or "lm_head.weight" in self._pre
+        self.lm_head = self.embed if (cfg.tie or not has_head) else self._mat(self._w("lm_head.weight"))
         layers = (L.LlmLayer * cfg.layers)()
         for l in range(cfg.layers):
             q = f"{p}layers.{l}."
             qz = self.quant is not None
             lay = layers[l]
-            wqkv, lay.q_qkv = self._mat_q(torch.cat([sd[q + "self_attn.q_proj.weight"], sd[q + "self_attn.k_proj.weight"],
-                                                    sd[q + "self_attn.v_proj.weight"]], dim=0), qz)
+            wqkv, lay.q_qkv = self._mat_q_keys([q + f"self_attn.{n}_proj.weight" for n in "qkv"], qz)
             bqkv = self._vec(torch.cat([sd[q + "self_attn.q_proj.bias"], sd[q + "self_attn.k_proj.bias"],
                                         sd[q + "self_attn.v_proj.bias"]], dim=0))
             lay.ln1 = L.ptr(self._vec(sd[q + "input_layernorm.weight"]))
@@ -357,7 +393,7 @@ class DeviceWeights:
             lay.wqkv, lay.bqkv = L.ptr(wqkv), L.ptr(bqkv)
             for field, qf, key in (("wo", "q_o", "self_attn.o_proj.weight"), ("wgate", "q_gate", "mlp.gate_proj.weight"),
                                    ("wup", "q_up", "mlp.up_proj.weight"), ("wdown", "q_down", "mlp.down_proj.weight")):
-                wm, w8 = self._mat_q(sd[q + key], qz)
+                wm, w8 = self._mat_q_keys([q + key], qz)
                 setattr(lay, field, L.ptr(wm))
                 setattr(lay, qf, w8)
         # Qwen2RotaryEmbedding.compute_default_rope_parameters, same fp32 ops as the reference stack
@@ -383,29 +419,29 @@ class DeviceWeights:
             lay.norm_w = L.ptr(self._vec(sd[q + "norm.weight"]))
             for field, qf, key in (("wgate", "q_gate", "ffn.gate_proj.weight"), ("wup", "q_up", "ffn.up_proj.weight"),
                                    ("wdown", "q_down", "ffn.down_proj.weight")):
-                wm, w8 = self._mat_q(sd[q + key], self.quant is not None)
+                wm, w8 = self._mat_q_keys([q + key], self.quant is not None)
                 setattr(lay, field, L.ptr(wm))
                 setattr(lay, qf, w8)
-            lay.adaln = L.ptr(self._mat(sd[q + "adaLN_modulation.1.weight"]))
+            lay.adaln = L.ptr(self._mat(self._w(q + "adaLN_modulation.1.weight")))
         h = L.Head()
         h.wdt, h.D, h.ffn, h.layers, h.latent, h.cond_dim = self.desc_wdt, cfg.head_hidden, cfg.head_ffn, cfg.head_layers, cfg.latent, cfg.hidden
         h.eps = cfg.head_eps
-        h.noisy_proj = L.ptr(self._mat(sd[p + "noisy_images_proj.weight"]))
-        h.cond_proj = L.ptr(self._mat(sd[p + "cond_proj.weight"]))
-        h.final_adaln = L.ptr(self._mat(sd[p + "final_layer.adaLN_modulation.1.weight"]))
-        h.final_linear = L.ptr(self._mat(sd[p + "final_layer.linear.weight"]))
+        h.noisy_proj = L.ptr(self._mat(self._w(p + "noisy_images_proj.weight")))
+        h.cond_proj = L.ptr(self._mat(self._w(p + "cond_proj.weight")))
+        h.final_adaln = L.ptr(self._mat(self._w(p + "final_layer.adaLN_modulation.1.weight")))
+        h.final_linear = L.ptr(self._mat(self._w(p + "final_layer.linear.weight")))
         h.layer = C.cast(layers, C.POINTER(L.HeadLayer))
         self._keep.append(layers)
         # G = [P F ; F] (fp32, built once in fp64 from the matrices the kernels stream: bf16-rounded in bf16 mode): every solver-step
         # boundary - final linear, CFG, DPM-Solver++ update, next noisy_images_proj, all linear in the modulated hidden state - is
         # one GEMV over it (csrc/vv_fused.hip); P (F y) == (P F) y up to fp32 rounding
-        P = sd[p + "noisy_images_proj.weight"].to(device=self.device, dtype=self.wdtype).double()
-        F = sd[p + "final_layer.linear.weight"].to(device=self.device, dtype=self.wdtype).double()
+        P = self._w(p + "noisy_images_proj.weight").to(device=self.device, dtype=self.wdtype).double()
+        F = self._w(p + "final_layer.linear.weight").to(device=self.device, dtype=self.wdtype).double()
         self.head_g = self._vec(torch.cat([P @ F, F], dim=0).float())
         h.fused_g = L.ptr(self.head_g)
         self.head = h
-        self.t_mlp0 = self._mat(sd[p + "t_embedder.mlp.0.weight"])
-        self.t_mlp2 = self._mat(sd[p + "t_embedder.mlp.2.weight"])
+        self.t_mlp0 = self._mat(self._w(p + "t_embedder.mlp.0.weight"))
+        self.t_mlp2 = self._mat(self._w(p + "t_embedder.mlp.2.weight"))
 
     # ---- conv tokenizers -----------------------------------------------------------------------------------------
     def _conv(self, w: torch.Tensor, b: torch.Tensor, stride: int, transposed: bool, state_key) -> L.Conv:
@@ -446,15 +482,15 @@ class DeviceWeights:
             b.dw_w = L.ptr(self._vec(sd[q + "mixer.conv.conv.conv.weight"].reshape(ch, 7)))
             b.dw_b = L.ptr(self._vec(sd[q + "mixer.conv.conv.conv.bias"]))
             qz = state_key is not None and (q + "ffn.linear1.weight") in self._fp8_names
-            w1m, b.q_w1 = self._mat_q(sd[q + "ffn.linear1.weight"], qz)
-            w2m, b.q_w2 = self._mat_q(sd[q + "ffn.linear2.weight"], qz)
+            w1m, b.q_w1 = self._mat_q_keys([q + "ffn.linear1.weight"], qz)
+            w2m, b.q_w2 = self._mat_q_keys([q + "ffn.linear2.weight"], qz)
             b.w1, b.b1 = L.ptr(w1m), L.ptr(self._vec(sd[q + "ffn.linear1.bias"]))
             b.w2, b.b2 = L.ptr(w2m), L.ptr(self._vec(sd[q + "ffn.linear2.bias"]))
             if state_key is not None:
                 h = self._state_zeros(6, ch)
                 self.state_tensors[state_key].append(h)
                 b.hist = L.ptr(h)
-                if ch == 2048 and not qz:
+                if ch == 2048 and not b.q_w1.q:
                     # the one-row stage: the history part of the depthwise conv is carried as state (hs = sum_k<6 tap_k * hist_k, zero with
                     # hist, inside the same arena so reset / snapshot / rollback cover it) and the newest row's tap is packed
                     b.dw_last = L.ptr(self._vec(sd[q + "mixer.conv.conv.conv.weight"].reshape(ch, 7)[:, 6].contiguous()))
@@ -477,10 +513,10 @@ class DeviceWeights:
                 ch = filters * 2 ** (n - 1 - i)
                 if i == 0:
                     q = prefix + "upsample_layers.0.0.conv.conv."
-                    net.sample[i] = self._conv(sd[q + "weight"], sd[q + "bias"], 1, False, state_key)
+                    net.sample[i] = self._conv(self._w(q + "weight"), sd[q + "bias"], 1, False, state_key)
                 else:
                     q = prefix + f"upsample_layers.{i}.0.convtr.convtr."
-                    net.sample[i] = self._conv(sd[q + "weight"], sd[q + "bias"], ratios[i - 1], True, state_key)
+                    net.sample[i] = self._conv(self._w(q + "weight"), sd[q + "bias"], ratios[i - 1], True, state_key)
                 net.n_blocks[i] = depths[i]
                 arr = self._blocks(prefix + f"stages.{i}.", depths[i], ch, state_key)
                 net.blocks[i] = C.cast(arr, C.POINTER(L.Block))
@@ -489,19 +525,19 @@ class DeviceWeights:
             for i in range(n):
                 ch = filters * 2 ** i
                 q = prefix + f"downsample_layers.{i}.0.conv.conv."
-                net.sample[i] = self._conv(sd[q + "weight"], sd[q + "bias"], 1 if i == 0 else rr[i - 1], False, state_key)
+                net.sample[i] = self._conv(self._w(q + "weight"), sd[q + "bias"], 1 if i == 0 else rr[i - 1], False, state_key)
                 net.n_blocks[i] = depths_enc[i]
                 arr = self._blocks(prefix + f"stages.{i}.", depths_enc[i], ch, state_key)
                 net.blocks[i] = C.cast(arr, C.POINTER(L.Block))
         q = prefix + "head.conv.conv."
-        net.head = self._conv(sd[q + "weight"], sd[q + "bias"], 1, False, state_key)
+        net.head = self._conv(self._w(q + "weight"), sd[q + "bias"], 1, False, state_key)
         return net
 
     def _build_connector(self, prefix, din) -> L.Connector:
         sd = self._sd
         c = L.Connector()
         c.wdt, c.din, c.hidden = self.wdt, din, self.cfg.hidden
-        c.fc1, c.b1 = L.ptr(self._mat(sd[prefix + "fc1.weight"])), L.ptr(self._vec(sd[prefix + "fc1.bias"]))
+        c.fc1, c.b1 = L.ptr(self._mat(self._w(prefix + "fc1.weight"))), L.ptr(self._vec(sd[prefix + "fc1.bias"]))
         c.norm_w = L.ptr(self._vec(sd[prefix + "norm.weight"]))
-        c.fc2, c.b2 = L.ptr(self._mat(sd[prefix + "fc2.weight"])), L.ptr(self._vec(sd[prefix + "fc2.bias"]))
+        c.fc2, c.b2 = L.ptr(self._mat(self._w(prefix + "fc2.weight"))), L.ptr(self._vec(sd[prefix + "fc2.bias"]))
         return c
