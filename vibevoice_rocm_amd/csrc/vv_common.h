@@ -21,6 +21,13 @@ int vv_set_error(int code, const char* fmt, ...);
   } while (0)
 
 int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s);   // vv_gemv_stream.hip: 1 = launched, 0 = not covered
+// vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
+// kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
+// template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.
+struct vv_gemv_hot_shape { const char* name; int m, n, k, dual, pro, mod, bias, gate, res, act, flags; };
+extern "C" int vv_gemv_hot_shapes(vv_gemv_hot_shape* out, int cap);   // copies up to cap entries, returns the table's length (exported for the tests; not in vv_hip.h)
+int vv_launch_gemv_hot(const vv_lin_args& a, hipStream_t s);      // 1 = launched on a shape-specialised kernel, 0 = no enabled table entry matches
+void vv_gemv_hot_set(int mask);                                   // tuning hook "gemv_hot"
 // vv_gemv_rows.hip: 3..8 activation rows on the matrix cores; 1 launched, 0 not covered, < 0 error.  part / tickets: split-K workspace
 // (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry, left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
