@@ -408,6 +408,14 @@ typedef struct vv_nf4_src {
 } vv_nf4_src;
 int vv_nf4_import(const vv_nf4_src* src, void* w, int64_t ldw, int row0, int rows_total, void* cq, float* cs, vv_stream_t stream);
 
+/* The conv tokenizers' shape-specialised kernels (csrc/vv_conv_hot.hip): the table of call sites that have one, in the bit order of
+ * vv_tune("conv_hot").  kind GEMV: a vv_linear call with exactly these m, n, k and epilogue operands (bf16 weights, no prologue, gate per
+ * output column); kind ROW: the first FFN half of a one-row Block1D with C = k.  Copies up to cap entries, returns the table's length. */
+#define VV_CONV_HOT_GEMV 0
+#define VV_CONV_HOT_ROW 1
+typedef struct vv_conv_hot_shape { const char* name; int kind, m, n, k, bias, gate, res; } vv_conv_hot_shape;
+int vv_conv_hot_shapes(vv_conv_hot_shape* out, int cap);
+
 /* struct sizes, for the ctypes mirror's self-check */
 size_t vv_sizeof(const char* struct_name);
 

@@ -151,6 +151,7 @@ PROTOTYPES = {
     "vv_graph_launch": (C.c_int, [vp, vp]),
     "vv_graph_destroy": (C.c_int, [vp]),
     "vv_nf4_import": (C.c_int, [C.POINTER(Nf4Src), vp, i64, C.c_int, C.c_int, vp, vp, vp]),
+    "vv_conv_hot_shapes": (C.c_int, [vp, C.c_int]),
     "vv_sizeof": (C.c_size_t, [C.c_char_p]),
     "vv_prof_begin": (C.c_int, [C.c_int]),
     "vv_prof_end": (C.c_int, [C.POINTER(ProfEntry), C.c_int, C.POINTER(C.c_int)]),

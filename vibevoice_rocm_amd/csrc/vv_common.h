@@ -28,6 +28,11 @@ struct vv_gemv_hot_shape { const char* name; int m, n, k, dual, pro, mod, bias, 
 extern "C" int vv_gemv_hot_shapes(vv_gemv_hot_shape* out, int cap);   // copies up to cap entries, returns the table's length (exported for the tests; not in vv_hip.h)
 int vv_launch_gemv_hot(const vv_lin_args& a, hipStream_t s);      // 1 = launched on a shape-specialised kernel, 0 = no enabled table entry matches
 void vv_gemv_hot_set(int mask);                                   // tuning hook "gemv_hot"
+// vv_conv_hot.hip: the conv tokenizers' one-row stage and hand-over GEMVs on kernels of their own (table: vv_conv_hot_shapes, vv_hip.h); bit i of
+// vv_tune("conv_hot") switches entry i.  1 = launched, 0 = no enabled entry matches (the caller goes on to today's path)
+int vv_launch_conv_hot_gemv(const vv_lin_args& a, hipStream_t s);
+int vv_launch_conv_hot_row(const vv_block& B, const float* x, float* y, float* hidden, float* hist_new, int C, float eps, hipStream_t s);
+void vv_conv_hot_set(int mask);                                   // tuning hook "conv_hot"
 // vv_gemv_rows.hip: 3..8 activation rows on the matrix cores; 1 launched, 0 not covered, < 0 error.  part / tickets: split-K workspace
 // (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry, left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);

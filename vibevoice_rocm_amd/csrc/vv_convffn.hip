@@ -626,7 +626,8 @@ int vv_launch_ffn_in_row_hs(const vv_block& B, int wdt, const float* x, float* y
   if (!a16(B.w1) || !a16(B.b1) || !a16(B.gamma) || !a16(B.norm_w) || !a16(B.ffn_norm_w) || !a16(B.dw_b) || !a16(B.dw_last) || !a16(B.hs) || !a16(x) ||
       !a16(y) || !a16(hidden) || !a16(hist_new) || !a16(B.hist) || x == y)
     return 0;
-  hipLaunchKernelGGL(ffn_in_row_kernel, dim3(4 * 2048 / 32), dim3(256), 0, s, x, y, hidden, hist_new, B, eps);
+  if (!vv_launch_conv_hot_row(B, x, y, hidden, hist_new, C, eps, s))          // its own kernel when vv_tune "conv_hot" bit 1 is set (vv_conv_hot.hip)
+    hipLaunchKernelGGL(ffn_in_row_kernel, dim3(4 * 2048 / 32), dim3(256), 0, s, x, y, hidden, hist_new, B, eps);
   return hipGetLastError() == hipSuccess ? 1 : vv_set_error(VV_E_HIP, "vv_convffn: launch failed");
 }
 

@@ -690,6 +690,7 @@ int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
   if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
   if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return 0;
   if (a.m == 2 && a.wdt == VV_BF16 && vv_launch_gemv_hot(a, s)) return 1;   // the six hot 1.5B shapes: their own kernels (vv_gemv_hot.hip)
+  if (a.m == 1 && a.wdt == VV_BF16 && vv_launch_conv_hot_gemv(a, s)) return 1;   // the conv tokenizers' one-row W2 and hand-over GEMVs (vv_conv_hot.hip)
   const int units = (a.k + 511) / 512;
   const bool dual = a.w2 != nullptr;
   // smallest wave count whose per-wave slice fits the register-resident activation fragment (KU <= 5 units; <= 3 for the

@@ -88,6 +88,7 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
   if (key && !strcmp(key, "gemv_dual_rw")) { vv_gemv_stream_set_dual_rw(value); return 0; }
   if (key && !strcmp(key, "gemv_small_rw")) { vv_gemv_stream_set_small_rw(value); return 0; }
   if (key && !strcmp(key, "gemv_hot")) { vv_gemv_hot_set(value); return 0; }
+  if (key && !strcmp(key, "conv_hot")) { vv_conv_hot_set(value); return 0; }
   if (key && !strcmp(key, "mixer_rows")) { vv_mixer_set_rows(value); return 0; }
   if (key && !strcmp(key, "block1d_fused")) { vv_block1d_set_fused(value); return 0; }
   if (key && !strcmp(key, "block1d_blocks")) { vv_block1d_set_blocks(value); return 0; }
