@@ -82,6 +82,32 @@ def test_lanes_fp32_vs_reference_batch_trace(tiny_cfg, tiny_weights, graphs, ent
     _check(g, entry, out, B, 1e-3, f"generate() lanes fp32 tiny, graphs={graphs}, vs reference batched loop")
 
 
+def test_lanes_do_sample_streams_every_chunk_as_it_returns_it(tiny_cfg, tiny_weights):
+    """do_sample on the lanes with an AudioStreamer: every step delivers the previous step's chunks, so 12 frames - more than the 8 slots of
+    a lane's host ring - reach the streamer as the samples generate() returns, bit for bit.  (Forced tokens: the non-sampling kernels
+    under the sample_fn branch of the loop.)"""
+    _need_gpu()
+    from vibevoice_rocm_amd.modeling import VibeVoiceForConditionalGenerationInference
+    from vibevoice_rocm_amd.streamer import AudioStreamer
+    g = load_golden("loop_trace_batch_tiny")
+    ST, E, D, EOS = [int(v) for v in g["special"]]
+    m = VibeVoiceForConditionalGenerationInference(tiny_cfg, tiny_weights, device="cuda:0", torch_dtype=torch.float32, use_graphs=True)
+    st = AudioStreamer(batch_size=2, timeout=5)
+    try:
+        m.set_ddpm_inference_steps(int(g["n_steps"]))
+        out = m.generate(input_ids=torch.from_numpy(g["a_ids"])[:2], attention_mask=torch.from_numpy(g["a_attention_mask"])[:2],
+                         tokenizer=_Tok(ST, E, D, EOS), cfg_scale=float(g["cfg_scale"]), forced_tokens=[D] * 12 + [E, EOS],
+                         noise=torch.randn(2, 12, tiny_cfg.latent, generator=torch.Generator().manual_seed(3)),
+                         generation_config={"do_sample": True}, audio_streamer=st, row_batch=False)
+    finally:
+        _drop(m)
+    assert out.sequences[:, -14:].tolist() == [[D] * 12 + [E, EOS]] * 2
+    for b in range(2):
+        got = list(st.get_stream(b))
+        assert len(got) == 12, (b, len(got))
+        assert torch.equal(torch.cat([c.reshape(-1) for c in got]), out.speech_outputs[b][0].float().cpu()), b
+
+
 def _drop(m):
     """release a model's engines NOW: an Engine collected later by the garbage collector synchronises its stream in __del__, which
     invalidates a graph capture another test may have running on another stream at that moment"""

@@ -450,3 +450,238 @@ def test_batch_coupling_matches_reference_rules():
         hits[0] += sum(map(len, want_r))
         hits[1] += sum(map(len, want_c))
     assert min(hits) > 100, hits
+
+
+_ST, _E, _D, _EOS, _PAD = 150, 151, 152, 153, 7
+
+
+class _FakeDriver:
+    """Recording stand-in for the lanes / row batches behind batchloop.run: returns the forced tokens, speculates every eligible dialogue,
+    hands out small CPU tensors as chunks (value = 100 * dialogue + frame) and logs every call as (step, name, dialogue)."""
+
+    def __init__(self, sde=False, n_steps=3):
+        self.sde, self.n_steps = sde, n_steps
+        self.log, self.step, self.deliveries = [], -1, 0
+
+    def _rec(self, name, b=None):
+        self.log.append((self.step, name, b))
+
+    def begin(self, prompts, voices, max_steps, valid):
+        self.frames = [0] * len(prompts)
+        self.ring = {}
+        assert valid == [_ST, _E, _D, _EOS] and all(v is None for v in voices)
+
+    def first_tokens(self, live, forced, sample_fn):
+        self.step = 0
+        return {b: forced[b] for b in live}
+
+    def decode(self, live, forced, eligible, sample_fn, deliver):
+        self.step += 1
+        assert set(eligible) <= set(live) == set(forced)
+        for b in eligible:
+            self._rec("spec", b)
+        deliver()
+        self.deliveries += 1
+        return {b: forced[b] for b in live}, set(eligible)
+
+    def replace_negative(self, b, src, dst):
+        assert dst == src - 1 >= 0
+        self._rec("replace", b)
+
+    def rollback(self, b):
+        self._rec("rollback", b)
+
+    def reset_speech(self, b):
+        self._rec("reset", b)
+
+    def embed(self, b):
+        self._rec("embed", b)
+
+    def finished(self, b):
+        self._rec("finished", b)
+
+    def speech(self, rows):
+        for b, (n_row, s_row) in rows.items():
+            assert n_row.shape == (4,) and (s_row.shape == (self.n_steps, 4) if self.sde else s_row is None)
+            self._rec("speech", b)
+
+    def chunk(self, b):
+        self._rec("chunk", b)
+        self.frames[b] += 1
+        return torch.full((2,), 100.0 * b + self.frames[b] - 1)
+
+    def stage_chunk(self, b):
+        self.ring[(b, self.frames[b] - 1)] = torch.full((2,), 100.0 * b + self.frames[b] - 1)
+        return self.frames[b] - 1
+
+    def take_chunk(self, b, slot):
+        return self.ring.pop((b, slot))
+
+    def synchronize(self):
+        self._rec("sync")
+
+
+def _spy_streamer(B, events, driver):
+    from vibevoice_rocm_amd.streamer import AudioStreamer
+
+    class Spy(AudioStreamer):
+        def put(self, audio_chunks, sample_indices):
+            events.append((driver.step, "put", [int(i) for i in sample_indices], [float(c.mean()) for c in audio_chunks]))
+            super().put(audio_chunks, sample_indices)
+
+        def end(self, sample_indices=None):
+            events.append((driver.step, "end", None if sample_indices is None else [int(i) for i in sample_indices], None))
+            super().end(sample_indices)
+    return Spy(batch_size=B)
+
+
+def _run_loop(sch, driver, L0=None, **kw):
+    """batchloop.run on left-padded prompts of L0[b] tokens with the schedules as forced tokens"""
+    from vibevoice_rocm_amd import batchloop
+    B = len(sch)
+    L0 = L0 or [3 + b for b in range(B)]
+    Lp = max(L0)
+    ids = torch.full((B, Lp), _PAD, dtype=torch.long)
+    am = torch.zeros(B, Lp, dtype=torch.long)
+    for b in range(B):
+        ids[b, Lp - L0[b]:] = torch.arange(10 + b, 10 + b + L0[b])
+        am[b, Lp - L0[b]:] = 1
+    kw.setdefault("max_length_times", 50)
+    call = batchloop.BatchCall(special=dict(speech_start=_ST, speech_end=_E, speech_diffusion=_D, eos=_EOS, bos=None), pad_id=_PAD, max_pos=4096,
+                               latent=4, forced_tokens=[list(s) for s in sch], **kw)
+    return batchloop.run(driver, ids, am, None, None, call), ids, am
+
+
+def test_batch_loop_under_a_recording_driver():
+    """batchloop.run - the one host loop of batched generate() - under a fake driver, on the random schedules of
+    test_batch_coupling_matches_reference_rules: sequences, where KV slots are replaced and conv states reset (the oracle's literal symbolic
+    run of the reference's batched loop), rollback before anything else touches a mis-speculated dialogue, no frame both speculated and
+    sampled, one put per step with exactly the previous step's diffusing dialogues, end([b]) once and after the last chunk, and - without
+    injected noise - exactly the reference's draws (2 n (1 + n_steps sde) rows of randn per step with n diffusing dialogues)."""
+    import random
+    from oracle import vv_oracle as O
+    special = dict(speech_start=_ST, speech_end=_E, speech_diffusion=_D, eos=_EOS)
+    rng = random.Random(11)
+    hits = [0, 0, 0]
+    for it in range(1200):
+        B = rng.randint(2, 4)
+        sch = [[rng.choice([_D, _D, _D, _E, _ST]) for _ in range(rng.randint(1, 12))] + [_EOS] for _ in range(B)]
+        want_r, want_c = O.batch_negative_replacements(sch, special), O.batch_conv_restarts(sch, special)
+        sde = bool(it % 2)
+        n_frames = [s.count(_D) for s in sch]
+        # ---- noise injected (speculation eligible), with a streamer
+        drv, events = _FakeDriver(sde), []
+        st = _spy_streamer(B, events, drv)
+        out, ids, am = _run_loop(sch, drv, noise=torch.zeros(B, 12, 4), sde_noise=torch.zeros(B, 12, 3, 4) if sde else None, audio_streamer=st)
+        Lp = ids.shape[1]
+        assert out.sequences.shape == (B, max(Lp + len(s) for s in sch))                               # padded prompt + longest schedule
+        for b in range(B):                                                                             # 1
+            want = ids[b].tolist() + sch[b]
+            assert out.sequences[b].tolist() == want + [_PAD] * (out.sequences.shape[1] - len(want)), (sch, b)
+            assert (out.speech_outputs[b] is None) == (n_frames[b] == 0)
+            if n_frames[b]:
+                assert out.speech_outputs[b][0, ::2].tolist() == [100.0 * b + f for f in range(n_frames[b])]
+        assert not out.reach_max_step_sample.any()
+        by = lambda name: [set(s for s, n, b_ in drv.log if n == name and b_ == b) for b in range(B)]      # noqa: E731
+        assert by("replace") == want_r, (sch, by("replace"), want_r)                                   # 2
+        ends = [set(i for i, t in enumerate(s) if t == _E) for s in sch]
+        assert by("reset") == [want_c[b] | ends[b] for b in range(B)], (sch, by("reset"), want_c)      # 3
+        n_steps = max(len(s) for s in sch)
+        diffusing = []
+        for step in range(n_steps):
+            calls = [(n, b) for s, n, b in drv.log if s == step]
+            spec = {b for n, b in calls if n == "spec"}
+            diffusing.append([b for b in range(B) if step < len(sch[b]) and sch[b][step] == _D])
+            for b in range(B):
+                tok = sch[b][step] if step < len(sch[b]) else None
+                mine = [n for n, b_ in calls if b_ == b and n not in ("spec", "replace")]
+                if b in spec and (tok != _D or step in want_c[b]):                                     # 4
+                    assert mine[0] == "rollback", (sch, step, b, mine)
+                    mine = mine[1:]
+                    hits[2] += 1
+                else:
+                    assert not (b in spec and "speech" in mine), (sch, step, b, mine)                  # 5
+                assert "rollback" not in mine, (sch, step, b, mine)
+                if tok == _D:
+                    assert ("speech" in mine) == (b not in spec or step in want_c[b]) and mine[-1] == "chunk" and "embed" not in mine
+                elif tok in (_E, _ST):
+                    assert mine[-1] == "embed" and "speech" not in mine and "chunk" not in mine
+                elif tok == _EOS:
+                    assert mine == ["finished"]
+                else:
+                    assert mine == []
+            assert [n for n, _ in calls if n in ("speech", "chunk")] == sorted([n for n, _ in calls if n in ("speech", "chunk")], reverse=True)
+        puts = {s: (idx, vals) for s, n, idx, vals in events if n == "put"}                              # 6
+        assert len(puts) == len([e for e in events if e[1] == "put"])
+        assert {s: idx for s, (idx, _) in puts.items()} == {s + 1: d for s, d in enumerate(diffusing) if d}, (sch, events)
+        got = {b: [] for b in range(B)}
+        for s, (idx, vals) in sorted(puts.items()):
+            for b, v in zip(idx, vals):
+                got[b].append(v)
+        assert got == {b: [100.0 * b + f for f in range(n_frames[b])] for b in range(B)}
+        for b in range(B):                                                                             # 7
+            e_at = [i for i, e in enumerate(events) if e[1] == "end" and e[2] == [b]]
+            p_at = [i for i, e in enumerate(events) if e[1] == "put" and b in e[2]]
+            assert len(e_at) == 1 and all(i < e_at[0] for i in p_at), (sch, events)
+        assert events[-1][1:3] == ("end", None) and drv.log[-1][1] == "sync" and not drv.ring
+        assert drv.deliveries == n_steps - 1
+        # ---- nothing injected: nobody is speculated, every frame's rows are drawn in the reference's order                  # 8
+        drv2 = _FakeDriver(sde)
+        torch.manual_seed(it)
+        out2, _, _ = _run_loop(sch, drv2)
+        state = torch.get_rng_state()
+        torch.manual_seed(it)
+        rows = 0
+        for d in diffusing:
+            if d:
+                for _ in range(1 + (drv2.n_steps if sde else 0)):
+                    torch.randn(2 * len(d), 4)
+                    rows += 2 * len(d)
+        assert rows == sum(2 * len(d) * (1 + drv2.n_steps * sde) for d in diffusing)
+        assert torch.equal(state, torch.get_rng_state()), sch
+        assert not [x for x in drv2.log if x[1] in ("spec", "rollback")] and out2.sequences.tolist() == out.sequences.tolist()
+        assert [x for x in drv2.log if x[1] == "speech"] == [(s, "speech", b) for s, d in enumerate(diffusing) for b in d]
+        hits[0] += sum(map(len, want_r))
+        hits[1] += sum(map(len, want_c))
+    assert min(hits) > 100, hits
+
+
+def test_batch_loop_stop_external_finish_and_max_new_tokens():
+    sch = [[_D] * 6 + [_E, _EOS], [_D] * 4 + [_E, _EOS]]
+    # stop_check_fn fires at step 3: every stream ends, the chunks of step 2 are delivered first
+    drv, events, calls = _FakeDriver(), [], []
+    st = _spy_streamer(2, events, drv)
+    out, ids, _ = _run_loop(sch, drv, audio_streamer=st, stop_check_fn=lambda: calls.append(0) or len(calls) == 4)
+    assert [s[ids.shape[1]:].tolist() for s in out.sequences] == [[_D] * 3, [_D] * 3] and not out.reach_max_step_sample.any()
+    assert [e[1:3] for e in events] == [("put", [0, 1])] * 3 + [("end", None), ("end", None)]
+    assert st.finished_flags == [True, True] and [q.qsize() for q in st.audio_queues] == [4, 4]
+    assert [t.shape for t in out.speech_outputs] == [(1, 6), (1, 6)]
+    # a stream ended by someone else stops the batch at the next step; one ended by the loop itself (dialogue 1's EOS) does not
+    drv, events = _FakeDriver(), []
+    st = _spy_streamer(2, events, drv)
+    out, ids, _ = _run_loop(sch, drv, audio_streamer=st)
+    assert [s[ids.shape[1]:].tolist() for s in out.sequences] == [sch[0], sch[1] + [_PAD, _PAD]]
+    drv, events = _FakeDriver(), []
+    st = _spy_streamer(3, events, drv)           # a third stream nobody generates for
+
+    def embed(b, orig=drv.embed):
+        orig(b)
+        st.end([2])
+    drv.embed = embed                            # first embed: dialogue 1's speech_end at step 4
+    out, ids, _ = _run_loop(sch, drv, audio_streamer=st)
+    assert [s[ids.shape[1]:].tolist() for s in out.sequences] == [[_D] * 5, [_D] * 4 + [_E]]
+    assert [e[1:3] for e in events if e[1] == "put"] == [("put", [0, 1])] * 4 + [("put", [0])]
+    # max_new_tokens shorter than the schedule: the loop runs out of steps and, like the reference (max_steps <= every max_step_per_sample
+    # when max_new_tokens is the binding limit, modeling_vibevoice_inference.py:420-421,529; pinned on the GPU for a single dialogue by
+    # test_generate_properties_1p5b), reach_max_step_sample stays False
+    out, ids, _ = _run_loop(sch, _FakeDriver(), max_new_tokens=5)
+    assert [s[ids.shape[1]:].tolist() for s in out.sequences] == [[_D] * 5, [_D] * 4 + [_E]]
+    assert out.reach_max_step_sample.tolist() == [False, False]
+    # the flag is the per-sample step limit (:421, :528-537): prompts of 3 and 4 tokens, max_length_times 2 -> 6 and 8 steps; dialogue 0
+    # is cut at its 7th token, its stream ended then and its last chunk delivered before
+    drv, events = _FakeDriver(), []
+    st = _spy_streamer(2, events, drv)
+    out, ids, _ = _run_loop([[_D] * 9 + [_EOS], [_D] * 3 + [_E, _EOS]], drv, max_length_times=2, audio_streamer=st)
+    assert [s[ids.shape[1]:].tolist() for s in out.sequences] == [[_D] * 7, [_D] * 3 + [_E, _EOS, _PAD, _PAD]]
+    assert out.reach_max_step_sample.tolist() == [True, False] and out.speech_outputs[0].shape == (1, 12)
+    assert [e[1:3] for e in events][-3:] == [("put", [0]), ("end", [0]), ("end", None)]

@@ -1,0 +1,256 @@
+"""The batched generate() loop (reference: modeling_vibevoice_inference.py:430-673 with batch_size > 1), written once, and the small host
+helpers the batch-of-one path shares with it (valid ids, limits, output packing).
+
+`run` is host bookkeeping only - limits, the token state machine, the batch coupling, which frames may be speculated, the reference-order
+noise draws, chunk collection and streaming.  It makes no torch.cuda call and knows no Engine, RowBatch or stream: all of that sits behind a
+driver (modeling._LaneDriver: one Engine lane per dialogue; modeling._RowDriver: RowBatch groups of 2..4 dialogues), so the loop runs under
+a recording fake on a machine without a GPU (tests/test_host_cpu.py).  A driver has the attributes `sde`, `n_steps` and the methods
+
+  begin(prompts, voices, max_steps, valid)   fresh sequences; prompt embeddings with the voice rows `(mask, rows)` scattered in
+  first_tokens(live, forced, sample_fn)      step 0: prefill of every live dialogue, first token, negative prompt committed where it diffuses
+  decode(live, forced, eligible, sample_fn, deliver)
+                                             one LLM step: {dialogue: token} and the set of dialogues whose frame it speculated (a subset of
+                                             `eligible` = {dialogue: (noise row, SDE rows)}); calls deliver() once, before it first waits
+  replace_negative(b, src, dst)              negative KV slot src -> dst            rollback(b)      undo a mis-speculated frame
+  reset_speech(b)                            zero the conv states                   embed(b)         next input = embedding of its token
+  finished(b)                                the dialogue takes no more steps
+  speech(rows)                               the frame of every dialogue in {dialogue: (noise row, SDE rows)}; all launches enqueued on return
+  chunk(b) / stage_chunk(b) / take_chunk(b, slot)     the frame's samples (device), its copy to the host ring, the host samples
+  synchronize()"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional
+
+import torch
+
+
+@dataclass
+class VibeVoiceGenerationOutput:
+    sequences: torch.LongTensor = None
+    speech_outputs: Optional[List[Optional[torch.Tensor]]] = None
+    reach_max_step_sample: Optional[torch.BoolTensor] = None
+
+
+@dataclass
+class BatchCall:
+    """What one generate() call fixes for its batched loop.  `forced_tokens` / `noise` / `sde_noise` may be given per sample (list / leading
+    batch dimension) or once for all."""
+    special: dict                         # speech_start / speech_end / speech_diffusion / eos [/ bos] ids
+    pad_id: int
+    max_pos: int
+    latent: int
+    max_new_tokens: Optional[int] = None
+    max_length_times: float = 2
+    forced_tokens: Optional[list] = None
+    noise: Optional[torch.Tensor] = None
+    sde_noise: Optional[torch.Tensor] = None
+    audio_streamer: object = None
+    stop_check_fn: Optional[Callable[[], bool]] = None
+    verbose: bool = False
+    sample_fn: Optional[Callable] = None
+    speculate: bool = True                # frames may be launched before their token is known (never with sample_fn)
+    return_speech: bool = True
+    in_dev: object = "cpu"
+
+
+def valid_token_ids(special: dict) -> List[int]:
+    """the ids generation is constrained to (modeling_vibevoice_inference.py:53-66)"""
+    return [special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]] + \
+        ([special["bos"]] if special.get("bos") is not None else [])
+
+
+def limits(max_pos: int, prompt_len: int, max_new_tokens: Optional[int], max_length_times: float):
+    """(max_length, max_steps) of a call whose (padded) prompt has prompt_len tokens"""
+    max_length = max_pos if max_new_tokens is None else prompt_len + int(max_new_tokens)            # :370-371
+    return max_length, min(max_length - prompt_len, int(max_length_times * prompt_len))            # :420
+
+
+def pack_output(rows: List[torch.Tensor], audios, reach: List[bool], pad_id: int, in_dev, return_speech: bool) -> VibeVoiceGenerationOutput:
+    """rows: every sample's ids (left padding included), right-padded here to the longest"""
+    seq_t = torch.full((len(rows), max(r.shape[0] for r in rows)), int(pad_id), dtype=torch.long)
+    for b, r in enumerate(rows):
+        seq_t[b, : r.shape[0]] = r
+    return VibeVoiceGenerationOutput(sequences=seq_t.to(in_dev), speech_outputs=audios if return_speech else None,
+                                     reach_max_step_sample=torch.tensor(reach, dtype=torch.bool))
+
+
+class _BatchCoupling:
+    """Where the reference's BATCHED loop does not treat a sample as if it ran alone; the host knows every step's tokens, so it can say.
+    (1) Negative branch (modeling_vibevoice_inference.py:575-622): one negative forward for all samples whenever any diffuses, then the
+        non-diffusing ones are shifted out from their correct_cnt.  The mask guard tests seq_len - 1, the KV guard k_cache.shape[2] - 1,
+        one row shorter: with correct_cnt == kv_len - 2 the mask moves one slot right and the rows do not, so the row just computed for
+        the sample stays visible in place of its last visible one.  `replace` lists those dialogues: their negative row of this step
+        (computed by every decode step anyway, at slot lens[1]) is copied over slot lens[1] - 1 and lens[1] stays.
+    (2) Streaming tokenizer cache (modular_vibevoice_tokenizer.py:198-207): get() returns None - a fresh conv state for the whole call -
+        when one sample of the diffusing subset has no state yet.  `restart` lists the dialogues whose conv states are zeroed before
+        this frame's tail because they diffuse next to a first-time diffuser.
+    Neither applies to a batch of one.  Restated symbolically, literal to the reference, by the CPU restatement the tests use (batch_negative_replacements,
+    batch_conv_restarts) and pinned by tests/golden/loop_trace_batch_*."""
+
+    def __init__(self, B: int, tok_start: int, tok_diff: int):
+        self.ST, self.SD = tok_start, tok_diff
+        self.n_fwd = 0                 # negative forwards so far (the batch-wide negative cache length)
+        self.cnt = [0] * B             # correct_cnt
+        self.vis = [0] * B             # visible negative rows of each dialogue (= its lens[1])
+        self.seen = [False] * B        # has a streaming tokenizer state
+
+    def step(self, toks: Dict[int, int], going: List[int]):
+        """toks: this step's token of every dialogue live at its start; going: those still unfinished after it (no EOS, no max length).
+        Returns (replace, restart)."""
+        diff = [b for b in going if toks[b] == self.SD]
+        for b in going:
+            if toks[b] == self.ST:
+                self.vis[b] = 0
+        replace, restart = [], []
+        if diff:
+            self.n_fwd += 1
+            for b in going:
+                if toks[b] != self.SD:
+                    if self.cnt[b] == self.n_fwd - 2 and self.vis[b] >= 1:
+                        replace.append(b)
+                    self.cnt[b] += 1
+            if not all(self.seen[b] for b in diff):
+                restart = [b for b in diff if self.seen[b]]
+            for b in diff:
+                self.seen[b] = True
+                self.vis[b] += 1
+        return replace, restart
+
+
+def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_input_mask, conn_all, call: BatchCall) -> VibeVoiceGenerationOutput:
+    """One host loop drives B dialogues in lock step, as the reference's batched generate() does: every live sample takes its LLM step (all
+    of them enqueued before any token is awaited), tokens are handled per sample (:517-563), the samples that emitted speech_diffusion are
+    sampled / decoded / re-embedded (:571-670) and their chunks reach the AudioStreamer together, once per step (:644-653).  The random
+    draws follow the reference's order (randn(2 n, latent) per step for the n diffusing samples, rows [:n] used, :699; SDE solver: n_steps
+    more of the same, dpm_solver.py:993-998) - only for the dialogues that diffuse, were not speculated and have no injected row, in ascending order."""
+    B, Lp = input_ids.shape
+    special, streamer, sample_fn = call.special, call.audio_streamer, call.sample_fn
+    ST, SE, SD, EOS = special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]
+    keep = attention_mask.bool()
+    L0 = keep.sum(-1).tolist()
+    max_length, max_steps = limits(call.max_pos, Lp, call.max_new_tokens, call.max_length_times)     # padded length, as the reference
+    max_step_per_sample = [min(max_length - l, int(call.max_length_times * l)) for l in L0]         # :421
+    forced_tokens, noise, sde_noise = call.forced_tokens, call.noise, call.sde_noise
+    per_list = forced_tokens is not None and len(forced_tokens) > 0 and isinstance(forced_tokens[0], (list, tuple))
+    ftok = [(forced_tokens[b] if per_list else forced_tokens) for b in range(B)]
+    nz = [(noise[b] if (noise is not None and noise.dim() == 3) else noise) for b in range(B)]
+    snz = [(sde_noise[b] if (sde_noise is not None and sde_noise.dim() == 4) else sde_noise) for b in range(B)]
+    prompts = [input_ids[b][keep[b]] for b in range(B)]
+    voices, off = [None] * B, 0
+    if speech_input_mask is not None and conn_all is not None:
+        for b in range(B):
+            sp_b = speech_input_mask[b][keep[b]].bool()
+            n_b = int(sp_b.sum())
+            if n_b:
+                voices[b] = (sp_b, conn_all[off: off + n_b])
+                off += n_b
+    driver.begin(prompts, voices, max_steps, valid_token_ids(special))
+    sde, n_steps = driver.sde, driver.n_steps
+    seq = [p.tolist() for p in prompts]
+    chunks = [[] for _ in range(B)]
+    frame = [0] * B
+    finished = [False] * B
+    reach = [False] * B
+    prev_tok = [None] * B
+    pending = []                      # (sample, ring slot) of chunks not yet handed to the streamer
+    ours = [False] * max(B, getattr(streamer, "batch_size", B) if streamer is not None else B)   # streams ended by this loop
+    speculate = call.speculate and sample_fn is None
+    coupling = _BatchCoupling(B, ST, SD)
+
+    def deliver():
+        if streamer is not None and pending:
+            streamer.put(torch.stack([driver.take_chunk(b, k)[None] for b, k in pending]), torch.tensor([b for b, _ in pending]))   # one put per step, all samples (:644-653)
+        pending.clear()
+
+    def finish(b):
+        finished[b] = True
+        driver.finished(b)
+        if streamer is not None:
+            deliver()
+            ours[b] = True
+            streamer.end(torch.tensor([b]))
+
+    for step in range(max_steps):
+        if call.stop_check_fn is not None and call.stop_check_fn():                                 # :432-438
+            if call.verbose:
+                print(f"Generation stopped externally at step {step + 1}")
+            deliver()
+            if streamer is not None:
+                streamer.end()
+            break
+        if streamer is not None and hasattr(streamer, "finished_flags") and any(f and not ours[i] for i, f in enumerate(streamer.finished_flags)):
+            break           # :441-445 "stopped externally".  Deviation, on purpose: the reference tests any(finished_flags), which its own
+                            # end(new_eos_indices) at :526 also sets - a batch with a streamer then stops at the FIRST sample's EOS; here
+                            # only streams ended by someone else stop the batch, streams this loop ended itself (EOS / max length) do not
+        if all(finished):
+            break
+        if Lp + step >= max_length:                                                                 # :452-457
+            for b in range(B):
+                reach[b] = reach[b] or not finished[b]
+            break
+        live = [b for b in range(B) if not finished[b]]
+        forced = {b: (ftok[b][step] if (ftok[b] is not None and step < len(ftok[b])) else None) for b in live}
+        if step == 0:
+            toks, speculated = driver.first_tokens(live, forced, sample_fn), set()
+        else:
+            # a dialogue in its steady state may get its diffusion tail enqueued speculatively behind its LLM step when its noise is injected
+            # (drawn noise depends on how many samples diffuse in this step, which is only known once the tokens are)
+            eligible = {b: (nz[b][frame[b]], snz[b][frame[b]] if sde else None) for b in live
+                        if speculate and prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
+                        (not sde or (snz[b] is not None and frame[b] < len(snz[b])))}
+            toks, speculated = driver.decode(live, forced, eligible, sample_fn, deliver)
+        going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
+        replace, restart = coupling.step(toks, going)
+        for b in replace:
+            driver.replace_negative(b, coupling.vis[b], coupling.vis[b] - 1)
+        diffusing = []
+        for b in live:
+            tok = toks[b]
+            if b in speculated and (tok != SD or b in restart):
+                driver.rollback(b)
+                speculated.discard(b)
+            prev_tok[b] = tok
+            seq[b].append(tok)
+            if tok == EOS:                                                                          # :517-526
+                if call.verbose:
+                    print(f"Samples [{b}] reached EOS token at step {step + 1}.", flush=True)
+                finish(b)
+                continue
+            if step >= max_step_per_sample[b]:                                                      # :528-537
+                reach[b] = True
+                finish(b)
+                continue
+            if tok == SE:                                                                           # :540-544
+                driver.reset_speech(b)
+            if tok == SD:
+                diffusing.append(b)
+                if b in restart:
+                    driver.reset_speech(b)
+            else:
+                driver.embed(b)                                                                     # :567
+        need = [b for b in diffusing if b not in speculated and (nz[b] is None or frame[b] >= len(nz[b]))]
+        if need:
+            n = len(need)
+            drawn = torch.randn(2 * n, call.latent)[:n]
+            sdrawn = torch.stack([torch.randn(2 * n, call.latent)[:n] for _ in range(n_steps)], dim=1) if sde else None
+        rows = {}
+        for b in diffusing:                                                                         # :571-670
+            if b in need:
+                i = need.index(b)
+                rows[b] = (drawn[i], sdrawn[i] if sde else None)
+            elif b not in speculated:
+                rows[b] = (nz[b][frame[b]], snz[b][frame[b]] if sde else None)
+        driver.speech(rows)
+        for b in diffusing:
+            chunks[b].append(driver.chunk(b))
+            if streamer is not None:
+                pending.append((b, driver.stage_chunk(b)))
+            frame[b] += 1
+    deliver()
+    driver.synchronize()
+    if streamer is not None:
+        streamer.end()
+    rows = [torch.cat([input_ids[b][~keep[b]], torch.tensor(seq[b], dtype=torch.long)]) for b in range(B)]
+    audios = [(torch.cat(c)[None] if c else None) for c in chunks]
+    return pack_output(rows, audios, reach, call.pad_id, call.in_dev, call.return_speech)

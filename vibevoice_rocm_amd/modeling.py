@@ -7,14 +7,13 @@ tokenizer=, generation_config={'do_sample': False}, verbose=, audio_streamer=, s
 `.model.language_model.config._attn_implementation`, `.ddpm_inference_steps`, `.device`, `.model.noise_scheduler` —
 and returns the same `VibeVoiceGenerationOutput(sequences, speech_outputs, reach_max_step_sample)`
 (reference: vibevoice/modular/modeling_vibevoice_inference.py:38-51,68-147,326-693).
-The loop below restates :364-693 for one utterance per engine; a batch is served utterance by utterance
-(they are independent: SURVEY.md §8e).
+`_generate_one` restates :364-693 for one utterance on one engine; a batch runs through the one batched loop of batchloop.py, which drives
+the dialogues through `_LaneDriver` (one Engine lane each) or `_RowDriver` (row batches, rowbatch.py).
 """
 from __future__ import annotations
 
 import json
 import os
-from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional
 
@@ -22,18 +21,13 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import batchloop
+from .batchloop import VibeVoiceGenerationOutput, _BatchCoupling      # noqa: F401  (public names of this module)
 from .config import VVConfig
 from .engine import Engine
 from .synth import state_dict_shapes
 
-LANES_IN_FLIGHT = 4       # lock-step batches: lanes (one HIP stream each) enqueued concurrently; see _generate_lockstep
-
-
-@dataclass
-class VibeVoiceGenerationOutput:
-    sequences: torch.LongTensor = None
-    speech_outputs: Optional[List[Optional[torch.Tensor]]] = None
-    reach_max_step_sample: Optional[torch.BoolTensor] = None
+LANES_IN_FLIGHT = 4       # lock-step batches: lanes (one HIP stream each) enqueued concurrently; see _LaneDriver
 
 
 def _read_safetensors_dir(path: str) -> Dict[str, torch.Tensor]:
@@ -149,49 +143,6 @@ def save_checkpoint_dir(path: str, config: VVConfig, state_dict: Dict[str, torch
         json.dump({"metadata": {"total_size": total}, "weight_map": weight_map}, f, indent=2)
 
 
-class _BatchCoupling:
-    """Where the reference's BATCHED loop does not treat a sample as if it ran alone; the host knows every step's tokens, so it can say.
-    (1) Negative branch (modeling_vibevoice_inference.py:575-622): one negative forward for all samples whenever any diffuses, then the
-        non-diffusing ones are shifted out from their correct_cnt.  The mask guard tests seq_len - 1, the KV guard k_cache.shape[2] - 1,
-        one row shorter: with correct_cnt == kv_len - 2 the mask moves one slot right and the rows do not, so the row just computed for
-        the sample stays visible in place of its last visible one.  `replace` lists those dialogues: their negative row of this step
-        (computed by every decode step anyway, at slot lens[1]) is copied over slot lens[1] - 1 and lens[1] stays.
-    (2) Streaming tokenizer cache (modular_vibevoice_tokenizer.py:198-207): get() returns None - a fresh conv state for the whole call -
-        when one sample of the diffusing subset has no state yet.  `restart` lists the dialogues whose conv states are zeroed before
-        this frame's tail because they diffuse next to a first-time diffuser.
-    Neither applies to a batch of one.  Restated symbolically, literal to the reference, by the CPU restatement the tests use (batch_negative_replacements,
-    batch_conv_restarts) and pinned by tests/golden/loop_trace_batch_*."""
-
-    def __init__(self, B: int, tok_start: int, tok_diff: int):
-        self.ST, self.SD = tok_start, tok_diff
-        self.n_fwd = 0                 # negative forwards so far (the batch-wide negative cache length)
-        self.cnt = [0] * B             # correct_cnt
-        self.vis = [0] * B             # visible negative rows of each dialogue (= its lens[1])
-        self.seen = [False] * B        # has a streaming tokenizer state
-
-    def step(self, toks: Dict[int, int], going: List[int]):
-        """toks: this step's token of every dialogue live at its start; going: those still unfinished after it (no EOS, no max length).
-        Returns (replace, restart)."""
-        diff = [b for b in going if toks[b] == self.SD]
-        for b in going:
-            if toks[b] == self.ST:
-                self.vis[b] = 0
-        replace, restart = [], []
-        if diff:
-            self.n_fwd += 1
-            for b in going:
-                if toks[b] != self.SD:
-                    if self.cnt[b] == self.n_fwd - 2 and self.vis[b] >= 1:
-                        replace.append(b)
-                    self.cnt[b] += 1
-            if not all(self.seen[b] for b in diff):
-                restart = [b for b in diff if self.seen[b]]
-            for b in diff:
-                self.seen[b] = True
-                self.vis[b] += 1
-        return replace, restart
-
-
 def _copy_kv_slot(k: torch.Tensor, v: torch.Tensor, vt: Optional[torch.Tensor], row: int, src: int, dst: int) -> None:
     """slot src -> slot dst of KV cache row `row` in every layer ([layers, rows, kv_heads, s_max, head_dim]; vt: the transposed value
     copy in 32-key tiles [layers, rows, kv_heads, s_max / 32, head_dim, 32])"""
@@ -223,6 +174,246 @@ def _make_sampler(gen_cfg: dict):
         p = torch.softmax(z, -1)
         return ids[int(torch.multinomial(p.float(), 1))]
     return sample
+
+
+def _embed_prompt(eng: Engine, ids: torch.Tensor, voice, after: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Prompt embeddings of one dialogue on eng's stream, the voice rows `(mask, rows)` scattered over their placeholders (`after`: the
+    stream that produced the rows)."""
+    with torch.cuda.stream(eng.stream):
+        x0 = eng.embed_ids(ids)
+        if voice is not None:
+            if after is not None:
+                eng.stream.wait_stream(after)
+            x0[voice[0].to(eng.device)] = voice[1]                                              # :221-224
+    return x0
+
+
+class _LaneDriver:
+    """batchloop driver: one Engine lane per dialogue (own HIP stream, KV cache and conv state).  Phase A of every live sample is enqueued
+    before any token is awaited, so the B dependent chains fill each other's bubbles on the GPU; a sample is the same computation as in a
+    batch of one - bit for bit with injected noise."""
+
+    def __init__(self, model, B: int, cfg_scale: float, ST: int, SD: int):
+        self.model, self.cfg_scale, self.ST, self.SD = model, float(cfg_scale), ST, SD
+        self.lanes = [model._lane(b) for b in range(B)]
+        for e in self.lanes[1:]:
+            e.sync_in()
+        self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
+        self.pool = None
+        if os.environ.get("VV_LANE_THREADS", "1") != "0":
+            from concurrent.futures import ThreadPoolExecutor
+            self.pool = ThreadPoolExecutor(max_workers=min(B, LANES_IN_FLIGHT))
+
+    def begin(self, prompts, voices, max_steps, valid):
+        self.x0 = []
+        for eng, ids, voice in zip(self.lanes, prompts, voices):
+            eng.cfg_scale = self.cfg_scale
+            eng.begin_sequence(len(ids) + max(max_steps, 1) + 8, valid)
+            self.x0.append(_embed_prompt(eng, ids, voice, after=self.model.engine.stream))     # conn_all was produced on lane 0's stream
+
+    def first_tokens(self, live, forced, sample_fn):
+        lanes, toks = self.lanes, {}
+        for b in live:
+            lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])))
+        for b in live:
+            toks[b] = lanes[b].first_token(self.ST, self.SD, forced[b], sample_fn)
+            if toks[b] == self.SD:
+                lanes[b].commit_negative_prompt()
+        return toks
+
+    def decode(self, live, forced, eligible, sample_fn, deliver):
+        lanes = self.lanes
+        if sample_fn is not None:
+            deliver()                  # step_decode waits inside: the previous step's chunks go out ahead of it
+            return {b: lanes[b].step_decode(self.ST, self.SD, forced[b], sample_fn) for b in live}, set()
+        # a frame is ~600 graph nodes and the runtime enqueues them node by node: the lanes' launches go out from one host
+        # thread each (the HIP calls release the GIL), or the host becomes the bottleneck at batch > 2
+        # at most LANES_IN_FLIGHT lanes run at once: more streams than that serialise badly on MI355X (8 streams in flight are
+        # slower than 4), so lane b of a larger batch shares the HIP stream of lane b % LANES_IN_FLIGHT and stream order queues
+        # it behind that lane's frame.  One host thread per stream (never two threads on one stream: first use captures graphs).
+        def begin(s_):
+            for b in live:
+                if b % LANES_IN_FLIGHT == s_:
+                    lanes[b].decode_begin(self.ST, self.SD, forced[b], eligible.get(b))
+        slots = sorted({b % LANES_IN_FLIGHT for b in live})
+        if self.pool is not None and len(slots) > 1:
+            list(self.pool.map(begin, slots))
+        else:
+            for s_ in slots:
+                begin(s_)
+        deliver()                      # the previous step's chunks: their copies completed long before this step's tokens
+        return {b: lanes[b].decode_end() for b in live}, set(eligible)
+
+    def replace_negative(self, b, src, dst):
+        e = self.lanes[b]
+        with torch.cuda.stream(e.stream):
+            _copy_kv_slot(e._kv_t[0], e._kv_t[1], e._kv_vt if e.kv.vt else None, 1, src, dst)
+
+    def rollback(self, b):
+        self.lanes[b].rollback_speech_state()
+
+    def reset_speech(self, b):
+        with torch.cuda.stream(self.lanes[b].stream):
+            self.lanes[b].reset_speech_caches()
+
+    def embed(self, b):
+        self.lanes[b].step_embed()
+
+    def finished(self, b):
+        pass
+
+    def speech(self, rows):
+        for b, (n_row, s_row) in rows.items():
+            self.lanes[b].step_speech(n_row, s_row)
+
+    def chunk(self, b):
+        with torch.cuda.stream(self.lanes[b].stream):
+            return self.lanes[b].wav.clone()
+
+    def stage_chunk(self, b):
+        return self.lanes[b].stage_chunk()
+
+    def take_chunk(self, b, slot):
+        return self.lanes[b].take_chunk(slot)
+
+    def synchronize(self):
+        for e in self.lanes:
+            e.stream.synchronize()
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown()
+
+
+class _RowDriver:
+    """batchloop driver: the B dialogues batched into the ROW dimension of the weight-heavy half of a frame (rowbatch.RowBatch: one Qwen2
+    decode step with 2 B rows, one diffusion sampling with 2 B rows; the conv tokenizers stay per dialogue on their lanes' streams).  5..16
+    dialogues run as ceil(B / 4) row batches, all on the main stream: each step enqueues A and H of every batch, then the conv tails - a
+    batch's tails overlap the other batches' A and H.  With do_sample every row batch's logits are read back once per step and the tokens
+    drawn in ascending dialogue order, so a seeded call draws what the lanes draw; results agree with the lanes to the rounding of the
+    matrix-core GEMV (activations as bf16 hi + lo, ~2e-6 relative per product)."""
+
+    def __init__(self, model, B: int, cfg_scale: float, ST: int, SD: int):
+        self.model, self.main, self.cfg_scale, self.ST, self.SD = model, model.engine, float(cfg_scale), ST, SD
+        if B > 4:
+            # two row batches: no dialogue's conv tail on the main stream (lanes 0, 4, 8, ... live there) - the main stream then runs A and H of
+            # the two batches back to back while all tails run beside it on the three side streams (8 dialogues: 108 -> 119 audio-sec/s, 6: 88 -> 99)
+            self.lanes = [model._lane(i) for i in [i for i in range(3 * B) if i % LANES_IN_FLIGHT][:B]]
+        else:
+            self.lanes = [model._lane(b) for b in range(B)]
+        self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
+        self.groups, self.at = [], {}          # (row batch, its dialogues); dialogue -> (row batch, index in it)
+
+    def begin(self, prompts, voices, max_steps, valid):
+        from .rowbatch import RowBatch
+        model, lanes, B, off = self.model, self.lanes, len(self.lanes), 0
+        n_groups = -(-B // 4)                                                                       # row batches of <= 4 dialogues, sizes balanced
+        for n in [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]:
+            idxs = list(range(off, off + n))
+            key = (n, off) if lanes[0] is model._lanes[0] else (n, off, "side")
+            rb = model._rowbatch.get(key)
+            if rb is None:
+                rb = model._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.main.stream)
+            rb.begin(max(len(prompts[b]) for b in idxs) + max(max_steps, 1) + 8, valid, self.cfg_scale)
+            self.groups.append((rb, idxs))
+            for b in idxs:
+                self.at[b] = (rb, b - off)
+            off += n
+        self.x0 = [_embed_prompt(self.main, ids, voice) for ids, voice in zip(prompts, voices)]
+
+    def first_tokens(self, live, forced, sample_fn):
+        at, toks = self.at, {}
+        st_embed = self.main.embed_ids(torch.tensor([self.ST]))
+        for b in live:
+            at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed)
+        for b in live:
+            rb, loc = at[b]
+            toks[b] = rb.first_token(loc, forced[b], sample_fn)
+            if toks[b] == self.SD:
+                rb.commit_negative(loc)
+        return toks
+
+    def decode(self, live, forced, eligible, sample_fn, deliver):
+        at, ST, SD = self.at, self.ST, self.SD
+        loc = {b: at[b][1] for b in live}
+        plan = [(rb, [b for b in idxs if b in forced]) for rb, idxs in self.groups]
+        plan = [(rb, lv) for rb, lv in plan if lv]
+        toks, speculated = {}, set()
+        if sample_fn is not None:
+            # do_sample: A1 of every row batch, ONE wait for all their logits, the tokens drawn in ascending dialogue order (the lanes' order),
+            # then A2 with them as forced tokens.  No speculation (the token is known only once the host has drawn it), as on the lanes
+            for rb, lv in plan:
+                rb.decode_logits()
+            deliver()
+            lg = {}
+            for rb, lv in plan:
+                lh = rb.logits_end()
+                lg.update({b: lh[loc[b]] for b in lv})
+            for b in live:
+                rb = at[b][0]
+                toks[b] = forced[b] if forced[b] is not None else int(sample_fn(lg[b][: len(rb.valid_ids)].clone(), rb.valid_ids))
+            for rb, lv in plan:
+                rb.decode_commit(ST, SD, {loc[b]: toks[b] for b in lv})
+            return toks, speculated
+        # graph A of every row batch; a batch in its steady state (every live dialogue diffusing, noise injected) gets its diffusion
+        # sampling enqueued speculatively behind it.  The conv tails follow once all A / H are queued: each batch's tails are enqueued
+        # when ITS sampler has finished (RowBatch.speech_tails) and run while the main stream works on the next batch
+        for rb, lv in plan:
+            rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv})
+            if all(b in eligible for b in lv):
+                rb.speech_begin([loc[b] for b in lv], {loc[b]: eligible[b][0] for b in lv}, {loc[b]: eligible[b][1] for b in lv} if self.sde else None)
+                speculated.update(lv)
+        deliver()                      # the previous step's chunks (their copies completed long ago), before the host waits for a sampler
+        for rb, lv in plan:
+            if lv[0] in speculated:
+                rb.speech_tails([loc[b] for b in lv])
+        for rb, lv in plan:
+            tk = rb.decode_end()
+            toks.update({b: tk[loc[b]] for b in lv})
+        return toks, speculated
+
+    def replace_negative(self, b, src, dst):
+        rb, loc = self.at[b]
+        with torch.cuda.stream(rb.stream):
+            _copy_kv_slot(rb._kv_t[0], rb._kv_t[1], rb._kv_vt if rb.kv.vt else None, 2 * loc + 1, src, dst)
+
+    def rollback(self, b):
+        self.at[b][0].rollback(self.at[b][1])
+
+    def reset_speech(self, b):
+        self.at[b][0].reset_speech(self.at[b][1])
+
+    def embed(self, b):
+        self.at[b][0].embed(self.at[b][1])
+
+    def finished(self, b):
+        self.at[b][0].set_active(self.at[b][1], False)
+
+    def speech(self, rows):
+        for rb, idxs in self.groups:
+            mine = [b for b in idxs if b in rows]
+            if mine:
+                loc = {b: self.at[b][1] for b in mine}
+                rb.speech([loc[b] for b in mine], {loc[b]: rows[b][0] for b in mine}, {loc[b]: rows[b][1] for b in mine} if self.sde else None)
+        for rb, _ in self.groups:
+            rb.flush()                 # the conv tails are enqueued from worker threads: the chunk copies must queue behind them
+
+    def chunk(self, b):
+        with torch.cuda.stream(self.lanes[b].stream):
+            return self.lanes[b].wav.clone()
+
+    def stage_chunk(self, b):
+        return self.lanes[b].stage_chunk()
+
+    def take_chunk(self, b, slot):
+        return self.lanes[b].take_chunk(slot)
+
+    def synchronize(self):
+        for rb, _ in self.groups:
+            rb.synchronize()
+
+    def close(self):
+        pass
 
 
 class VibeVoiceForConditionalGenerationInference:
@@ -396,6 +587,8 @@ class VibeVoiceForConditionalGenerationInference:
         noise = kwargs.get("noise")                          # extension: injected diffusion noise [F, latent]
         speech_noise = kwargs.get("speech_noise")            # extension: (std_noise [S], eps_noise [S, F, 64])
         sde_noise = kwargs.get("sde_noise")                  # extension: injected variance noise of the SDE solver [F, n_steps, latent]
+        noise = None if noise is None else torch.as_tensor(noise)
+        sde_noise = None if sde_noise is None else torch.as_tensor(sde_noise)
         input_ids = torch.as_tensor(input_ids)
         in_dev = input_ids.device                            # callers may hand over device tensors (the reference moves them itself, modeling_vibevoice_inference.py:288,305-307)
         input_ids = input_ids.cpu()                          # ids / masks drive host-side bookkeeping only
@@ -408,6 +601,9 @@ class VibeVoiceForConditionalGenerationInference:
         special = dict(speech_start=tokenizer.speech_start_id, speech_end=tokenizer.speech_end_id,
                        speech_diffusion=tokenizer.speech_diffusion_id, eos=tokenizer.eos_token_id,
                        bos=getattr(tokenizer, "bos_token_id", None))
+        pad_id = getattr(tokenizer, "pad_id", None)
+        if pad_id is None:
+            pad_id = special["eos"]
         conn_all = None
         if speech_tensors is not None and speech_masks is not None:
             sn = speech_noise or (None, None)
@@ -417,46 +613,33 @@ class VibeVoiceForConditionalGenerationInference:
                 # with refresh_negative=False the reference's batched loop couples the samples (a non-diffusing sample's negative step is
                 # dropped only in steps where some OTHER sample diffuses, :588-622): served per sample here would not reproduce that
                 raise NotImplementedError("refresh_negative=False is built for batch size 1 only")
-            rb = kwargs.get("row_batch", self.row_batch)
-            fn = self._generate_lockstep
-            if rb and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and self.weight_quant in (None, "fp8"):
-                fn = self._generate_rowbatch      # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py)
-            return fn(input_ids, attention_mask, speech_input_mask, conn_all, special, cfg_scale, max_new_tokens, max_length_times,
-                                           forced_tokens, None if noise is None else torch.as_tensor(noise), None if sde_noise is None else torch.as_tensor(sde_noise),
-                                           audio_streamer, stop_check_fn, verbose, sample_fn, tokenizer, return_speech, in_dev)
-        seqs, audios, reach = [], [], []
-        off = 0
-        for b in range(B):
-            keep = attention_mask[b].bool()
-            ids_b = input_ids[b][keep]                       # left padding carries no information (position_ids = cumsum(mask)-1)
-            sp_b = None
-            conn_b = None
-            if speech_input_mask is not None:
-                sp_b = torch.as_tensor(speech_input_mask)[b][keep].bool()
-                n_b = int(sp_b.sum())
-                if n_b and conn_all is not None:
-                    conn_b = conn_all[off: off + n_b]
-                    off += n_b
-            r = self._generate_one(ids_b, sp_b, conn_b, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
-                                   None if noise is None else torch.as_tensor(noise), audio_streamer, stop_check_fn, b, verbose, sample_fn,
-                                   None if sde_noise is None else torch.as_tensor(sde_noise), refresh_negative=refresh_negative)
-            seqs.append(torch.cat([input_ids[b][~keep], r["sequence"]]))
-            audios.append(r["audio"])
-            reach.append(r["reach_max"])
+            # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py), or one engine lane each
+            rows = kwargs.get("row_batch", self.row_batch) and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and \
+                self.weight_quant in (None, "fp8")
+            driver = (_RowDriver if rows else _LaneDriver)(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"])
+            call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
+                                       max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
+                                       sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
+                                       sample_fn=sample_fn, speculate=self.speculative_frames and self._use_graphs, return_speech=return_speech,
+                                       in_dev=in_dev)
+            try:
+                return batchloop.run(driver, input_ids, attention_mask, speech_input_mask, conn_all, call)
+            finally:
+                driver.close()         # the lanes' host threads, also when the loop raises
+        keep = attention_mask[0].bool()
+        ids = input_ids[0][keep]                             # left padding carries no information (position_ids = cumsum(mask)-1)
+        sp, conn = None, None
+        if speech_input_mask is not None:
+            sp = speech_input_mask[0][keep].bool()
+            if int(sp.sum()) and conn_all is not None:
+                conn = conn_all[: int(sp.sum())]
+        r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
+                               stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative)
         if audio_streamer is not None:
             audio_streamer.end()
-        mx = max(s.shape[0] for s in seqs)
-        pad_id = getattr(tokenizer, "pad_id", None)
-        if pad_id is None:
-            pad_id = special["eos"]
-        seq_t = torch.full((B, mx), int(pad_id), dtype=torch.long)
-        for b, s in enumerate(seqs):
-            seq_t[b, : s.shape[0]] = s
-        return VibeVoiceGenerationOutput(sequences=seq_t.to(in_dev), speech_outputs=audios if return_speech else None,
-                                         reach_max_step_sample=torch.tensor(reach, dtype=torch.bool))
+        return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
 
-
-    # ---- batches: lock step over samples (modeling_vibevoice_inference.py:430-673 with batch_size > 1) ---------------------
+    # ---- batches: lock step over samples (batchloop.run through _LaneDriver / _RowDriver) -----------------------------------
     def release_lanes(self) -> None:
         """Drop the engines of earlier batched calls (lanes, row batches): their HIP streams go back to the recycle pool (engine.py, _IDLE_STREAMS)."""
         for rb in self._rowbatch.values():
@@ -469,7 +652,7 @@ class VibeVoiceForConditionalGenerationInference:
 
     def _lane(self, b: int) -> Engine:
         while len(self._lanes) <= b:
-            n = len(self._lanes)             # lanes past LANES_IN_FLIGHT share the stream of lane n % LANES_IN_FLIGHT: see _generate_lockstep
+            n = len(self._lanes)             # lanes past LANES_IN_FLIGHT share the stream of lane n % LANES_IN_FLIGHT: see _LaneDriver
             eng = Engine(self.config, None, device=self.device, dtype=self.dtype, use_graphs=self._use_graphs, weight_quant=self.weight_quant,
                          stream=self._lanes[n % LANES_IN_FLIGHT].stream if n >= LANES_IN_FLIGHT else None, weights_from=self.engine)
             self._lanes.append(eng)
@@ -480,444 +663,6 @@ class VibeVoiceForConditionalGenerationInference:
             eng.scheduler = self.engine.scheduler
             eng.set_steps(self.engine.n_steps)
         return eng
-
-    def _generate_lockstep(self, input_ids, attention_mask, speech_input_mask, conn_all, special, cfg_scale, max_new_tokens, max_length_times,
-                           forced_tokens, noise, sde_noise, audio_streamer, stop_check_fn, verbose, sample_fn, tokenizer, return_speech, in_dev):
-        """One host loop drives B engines in lock step, as the reference's batched generate() does: every live sample takes its LLM step
-        (phase A of all of them is enqueued before any token is awaited, so the B dependent chains fill each other's bubbles on the GPU),
-        tokens are handled per sample (:517-563), the samples that emitted speech_diffusion are sampled / decoded / re-embedded (:571-670)
-        and their chunks reach the AudioStreamer together, once per step (:644-653).  A sample is the same computation as in a batch of
-        one - bit for bit with injected noise; the random draws follow the reference's order (randn(2 n, latent) per step for the n
-        diffusing samples, rows [:n] used, :699).  `forced_tokens` / `noise` / `sde_noise` may be given per sample (list / leading batch
-        dimension) or once for all."""
-        cfg = self.config
-        B, Lp = input_ids.shape
-        ST, SE, SD, EOS = special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]
-        valid = [ST, SE, SD, EOS] + ([special["bos"]] if special.get("bos") is not None else [])
-        lanes = [self._lane(b) for b in range(B)]
-        for e in lanes[1:]:
-            e.sync_in()
-        keep = attention_mask.bool()
-        L0 = keep.sum(-1).tolist()
-        max_length = cfg.max_pos if max_new_tokens is None else Lp + int(max_new_tokens)            # :370-371 (padded length, as the reference)
-        max_steps = min(max_length - Lp, int(max_length_times * Lp))                                # :420
-        max_step_per_sample = [min(max_length - l, int(max_length_times * l)) for l in L0]          # :421
-        per_list = forced_tokens is not None and len(forced_tokens) > 0 and isinstance(forced_tokens[0], (list, tuple))
-        ftok = [(forced_tokens[b] if per_list else forced_tokens) for b in range(B)]
-        nz = [(noise[b] if (noise is not None and noise.dim() == 3) else noise) for b in range(B)]
-        snz = [(sde_noise[b] if (sde_noise is not None and sde_noise.dim() == 4) else sde_noise) for b in range(B)]
-        x0s, off = [], 0
-        for b in range(B):
-            eng = lanes[b]
-            ids_b = input_ids[b][keep[b]]
-            eng.cfg_scale = float(cfg_scale)
-            eng.begin_sequence(L0[b] + max(max_steps, 1) + 8, valid)
-            with torch.cuda.stream(eng.stream):
-                x0 = eng.embed_ids(ids_b)
-                if speech_input_mask is not None and conn_all is not None:
-                    sp_b = speech_input_mask[b][keep[b]].bool()
-                    n_b = int(sp_b.sum())
-                    if n_b:
-                        eng.stream.wait_stream(self.engine.stream)                                   # conn_all was produced on lane 0's stream
-                        x0[sp_b.to(self.device)] = conn_all[off: off + n_b]                         # :221-224
-                        off += n_b
-            x0s.append(x0)
-        seq = [input_ids[b][keep[b]].tolist() for b in range(B)]
-        chunks = [[] for _ in range(B)]
-        frame = [0] * B
-        finished = [False] * B
-        reach = [False] * B
-        prev_tok = [None] * B
-        pending = []                      # (sample, ring slot) of chunks not yet handed to the streamer
-        ours = [False] * max(B, getattr(audio_streamer, "batch_size", B) if audio_streamer is not None else B)   # streams ended by this loop
-        speculate = self.speculative_frames and sample_fn is None and self._use_graphs
-        sde = lanes[0].sde
-
-        def deliver():
-            if audio_streamer is None or not pending:
-                pending.clear()
-                return
-            idx = [b for b, _ in pending]
-            audio_streamer.put(torch.stack([lanes[b].take_chunk(k)[None] for b, k in pending]), torch.tensor(idx))   # one put per step, all samples (:644-653)
-            pending.clear()
-
-        def draw(n):
-            """the reference's draws for a step with n diffusing samples: randn(2 n, latent), rows [:n]; SDE: n_steps more of the same"""
-            a = torch.randn(2 * n, cfg.latent)[:n]
-            s_ = torch.stack([torch.randn(2 * n, cfg.latent)[:n] for _ in range(lanes[0].n_steps)], dim=1) if sde else None
-            return a, s_
-
-        coupling = _BatchCoupling(B, ST, SD)
-        pool = None
-        if B > 1 and os.environ.get("VV_LANE_THREADS", "1") != "0":
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=min(B, LANES_IN_FLIGHT))
-        for step in range(max_steps):
-            if stop_check_fn is not None and stop_check_fn():                                       # :432-438
-                if verbose:
-                    print(f"Generation stopped externally at step {step + 1}")
-                deliver()
-                if audio_streamer is not None:
-                    audio_streamer.end()
-                break
-            if audio_streamer is not None and hasattr(audio_streamer, "finished_flags") and \
-                    any(f and not ours[i] for i, f in enumerate(audio_streamer.finished_flags)):
-                break       # :441-445 "stopped externally".  Deviation, on purpose: the reference tests any(finished_flags), which its own
-                            # end(new_eos_indices) at :526 also sets - a batch with a streamer then stops at the FIRST sample's EOS; here
-                            # only streams ended by someone else stop the batch, streams this loop ended itself (EOS / max length) do not
-            if all(finished):
-                break
-            if Lp + step >= max_length:                                                             # :452-457
-                for b in range(B):
-                    reach[b] = reach[b] or not finished[b]
-                break
-            live = [b for b in range(B) if not finished[b]]
-            forced = {b: (ftok[b][step] if (ftok[b] is not None and step < len(ftok[b])) else None) for b in live}
-            toks = {}
-            speculated = set()
-            if step == 0:
-                for b in live:
-                    lanes[b].prefill(x0s[b], row=0, pos0=0, chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([ST])))
-                for b in live:
-                    toks[b] = lanes[b].first_token(ST, SD, forced[b], sample_fn)
-                    if toks[b] == SD:
-                        lanes[b].commit_negative_prompt()
-            elif sample_fn is not None:
-                for b in live:
-                    toks[b] = lanes[b].step_decode(ST, SD, forced[b], sample_fn)
-            else:
-                # phase A of every live sample goes out before any token is awaited; a sample in the steady state of a dialogue gets its
-                # diffusion tail enqueued speculatively behind it when its noise is injected (drawn noise depends on how many samples
-                # diffuse in this step, which is only known once the tokens are)
-                specs = {}
-                for b in live:
-                    specs[b] = None
-                    if speculate and prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and (not sde or (snz[b] is not None and frame[b] < len(snz[b]))):
-                        specs[b] = (nz[b][frame[b]], snz[b][frame[b]] if sde else None)
-                        speculated.add(b)
-                # a frame is ~600 graph nodes and the runtime enqueues them node by node: the lanes' launches go out from one host
-                # thread each (the HIP calls release the GIL), or the host becomes the bottleneck at batch > 2
-                # at most LANES_IN_FLIGHT lanes run at once: more streams than that serialise badly on MI355X (8 streams in flight are
-                # slower than 4), so lane b of a larger batch shares the HIP stream of lane b % LANES_IN_FLIGHT and stream order queues
-                # it behind that lane's frame.  One host thread per stream (never two threads on one stream: first use captures graphs).
-                def begin(s_):
-                    for b in live:
-                        if b % LANES_IN_FLIGHT == s_:
-                            lanes[b].decode_begin(ST, SD, forced[b], specs[b])
-                slots = sorted({b % LANES_IN_FLIGHT for b in live})
-                if pool is not None and len(slots) > 1:
-                    list(pool.map(begin, slots))
-                else:
-                    for s_ in slots:
-                        begin(s_)
-                deliver()                  # the previous step's chunks: their copies completed long before this step's tokens
-                for b in live:
-                    toks[b] = lanes[b].decode_end()
-            going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
-            replace, restart = coupling.step(toks, going)
-            for b in replace:
-                e = lanes[b]
-                with torch.cuda.stream(e.stream):
-                    _copy_kv_slot(e._kv_t[0], e._kv_t[1], e._kv_vt if e.kv.vt else None, 1, coupling.vis[b], coupling.vis[b] - 1)
-            diffusing = []
-            for b in live:
-                tok = toks[b]
-                if b in speculated and (tok != SD or b in restart):
-                    lanes[b].rollback_speech_state()
-                    speculated.discard(b)
-                prev_tok[b] = tok
-                seq[b].append(tok)
-                if tok == EOS:                                                                      # :517-526
-                    finished[b] = True
-                    if verbose:
-                        print(f"Samples [{b}] reached EOS token at step {step + 1}.", flush=True)
-                    if audio_streamer is not None:
-                        deliver()
-                        ours[b] = True
-                        audio_streamer.end(torch.tensor([b]))
-                    continue
-                if step >= max_step_per_sample[b]:                                                  # :528-537
-                    finished[b] = True
-                    reach[b] = True
-                    if audio_streamer is not None:
-                        deliver()
-                        ours[b] = True
-                        audio_streamer.end(torch.tensor([b]))
-                    continue
-                if tok == SE:                                                                       # :540-544
-                    with torch.cuda.stream(lanes[b].stream):
-                        lanes[b].reset_speech_caches()
-                if tok == SD:
-                    diffusing.append(b)
-                    if b in restart:
-                        with torch.cuda.stream(lanes[b].stream):
-                            lanes[b].reset_speech_caches()
-                else:
-                    lanes[b].step_embed()                                                           # :567
-            need = [b for b in diffusing if b not in speculated and (nz[b] is None or frame[b] >= len(nz[b]))]
-            drawn = draw(len(need)) if need else None
-            for b in diffusing:                                                                     # :571-670
-                if b not in speculated:
-                    if b in need:
-                        i = need.index(b)
-                        n_row, s_row = drawn[0][i], (drawn[1][i] if sde else None)
-                    else:
-                        n_row, s_row = nz[b][frame[b]], (snz[b][frame[b]] if sde else None)
-                    lanes[b].step_speech(n_row, s_row)
-                with torch.cuda.stream(lanes[b].stream):
-                    chunks[b].append(lanes[b].wav.clone())
-                if audio_streamer is not None:
-                    pending.append((b, lanes[b].stage_chunk()))
-                frame[b] += 1
-        deliver()
-        if pool is not None:
-            pool.shutdown()
-        for e in lanes[:B]:
-            e.stream.synchronize()
-        if audio_streamer is not None:
-            audio_streamer.end()
-        pad_id = getattr(tokenizer, "pad_id", None)
-        if pad_id is None:
-            pad_id = special["eos"]
-        rows = []
-        for b in range(B):
-            rows.append(torch.cat([input_ids[b][~keep[b]], torch.tensor(seq[b], dtype=torch.long)]))
-        mx = max(r.shape[0] for r in rows)
-        seq_t = torch.full((B, mx), int(pad_id), dtype=torch.long)
-        for b, r in enumerate(rows):
-            seq_t[b, : r.shape[0]] = r
-        audios = [(torch.cat(c)[None] if c else None) for c in chunks]
-        return VibeVoiceGenerationOutput(sequences=seq_t.to(in_dev), speech_outputs=audios if return_speech else None,
-                                         reach_max_step_sample=torch.tensor(reach, dtype=torch.bool))
-
-    def _generate_rowbatch(self, input_ids, attention_mask, speech_input_mask, conn_all, special, cfg_scale, max_new_tokens, max_length_times,
-                           forced_tokens, noise, sde_noise, audio_streamer, stop_check_fn, verbose, sample_fn, tokenizer, return_speech, in_dev):
-        """The lock-step loop of `_generate_lockstep` with the B dialogues batched into the ROW dimension of the weight-heavy half of a frame
-        (rowbatch.RowBatch: one Qwen2 decode step with 2 B rows, one diffusion sampling with 2 B rows; the conv tokenizers stay per dialogue on
-        their lanes' streams).  5..16 dialogues run as ceil(B / 4) row batches inside the same loop, all on the main stream: each step enqueues A and
-        H of every batch, then the conv tails - a batch's tails overlap the other batches' A and H.  Token handling, the draws' order, speculation and rollback
-        are those of the lock-step loop: with do_sample every row batch's logits are read back once per step and the tokens drawn in ascending
-        dialogue order, then the noise rows (SDE solver: n_steps more per step), so a seeded call draws what the lanes draw; results agree with the
-        lanes to the rounding of the matrix-core GEMV (activations as bf16 hi + lo, ~2e-6 relative per product)."""
-        from .rowbatch import RowBatch
-        cfg = self.config
-        B, Lp = input_ids.shape
-        ST, SE, SD, EOS = special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]
-        valid = [ST, SE, SD, EOS] + ([special["bos"]] if special.get("bos") is not None else [])
-        if B > 4:
-            # two row batches: no dialogue's conv tail on the main stream (lanes 0, 4, 8, ... live there) - the main stream then runs A and H of
-            # the two batches back to back while all tails run beside it on the three side streams (8 dialogues: 108 -> 119 audio-sec/s, 6: 88 -> 99)
-            idx = [i for i in range(3 * B) if i % LANES_IN_FLIGHT][:B]
-            lanes = [self._lane(i) for i in idx]
-        else:
-            lanes = [self._lane(b) for b in range(B)]
-        keep = attention_mask.bool()
-        L0 = keep.sum(-1).tolist()
-        max_length = cfg.max_pos if max_new_tokens is None else Lp + int(max_new_tokens)            # :370-371 (padded length, as the reference)
-        max_steps = min(max_length - Lp, int(max_length_times * Lp))                                # :420
-        max_step_per_sample = [min(max_length - l, int(max_length_times * l)) for l in L0]          # :421
-        groups, rb_of, loc, off = [], {}, {}, 0
-        n_groups = -(-B // 4)                                                                       # row batches of <= 4 dialogues, sizes balanced
-        for n in [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]:
-            idxs = list(range(off, off + n))
-            key = (n, off) if lanes[0] is self._lanes[0] else (n, off, "side")
-            rb = self._rowbatch.get(key)
-            if rb is None:
-                rb = self._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.engine.stream)
-            rb.begin(max(L0[b] for b in idxs) + max(max_steps, 1) + 8, valid, cfg_scale)
-            groups.append((rb, idxs))
-            for b in idxs:
-                rb_of[b], loc[b] = rb, b - off
-            off += n
-        per_list = forced_tokens is not None and len(forced_tokens) > 0 and isinstance(forced_tokens[0], (list, tuple))
-        ftok = [(forced_tokens[b] if per_list else forced_tokens) for b in range(B)]
-        nz = [(noise[b] if (noise is not None and noise.dim() == 3) else noise) for b in range(B)]
-        snz = [(sde_noise[b] if (sde_noise is not None and sde_noise.dim() == 4) else sde_noise) for b in range(B)]
-        sde = lanes[0].sde
-        x0s, off = [], 0
-        with torch.cuda.stream(self.engine.stream):
-            for b in range(B):
-                x0 = self.engine.embed_ids(input_ids[b][keep[b]])
-                if speech_input_mask is not None and conn_all is not None:
-                    sp_b = speech_input_mask[b][keep[b]].bool()
-                    n_b = int(sp_b.sum())
-                    if n_b:
-                        x0[sp_b.to(self.device)] = conn_all[off: off + n_b]                         # :221-224
-                        off += n_b
-                x0s.append(x0)
-        seq = [input_ids[b][keep[b]].tolist() for b in range(B)]
-        chunks = [[] for _ in range(B)]
-        frame = [0] * B
-        finished = [False] * B
-        reach = [False] * B
-        prev_tok = [None] * B
-        pending = []
-        ours = [False] * max(B, getattr(audio_streamer, "batch_size", B) if audio_streamer is not None else B)
-        speculate = self.speculative_frames and sample_fn is None and self._use_graphs
-
-        def deliver():
-            if audio_streamer is None or not pending:
-                pending.clear()
-                return
-            idx = [b for b, _ in pending]
-            audio_streamer.put(torch.stack([lanes[b].take_chunk(k)[None] for b, k in pending]), torch.tensor(idx))   # one put per step, all samples (:644-653)
-            pending.clear()
-
-        coupling = _BatchCoupling(B, ST, SD)
-
-        def finish(b):
-            finished[b] = True
-            rb_of[b].set_active(loc[b], False)
-            if audio_streamer is not None:
-                deliver()
-                ours[b] = True
-                audio_streamer.end(torch.tensor([b]))
-
-        for step in range(max_steps):
-            if stop_check_fn is not None and stop_check_fn():                                       # :432-438
-                if verbose:
-                    print(f"Generation stopped externally at step {step + 1}")
-                deliver()
-                if audio_streamer is not None:
-                    audio_streamer.end()
-                break
-            if audio_streamer is not None and hasattr(audio_streamer, "finished_flags") and \
-                    any(f and not ours[i] for i, f in enumerate(audio_streamer.finished_flags)):
-                break                                                                               # :441-445, see _generate_lockstep
-            if all(finished):
-                break
-            if Lp + step >= max_length:                                                             # :452-457
-                for b in range(B):
-                    reach[b] = reach[b] or not finished[b]
-                break
-            live = [b for b in range(B) if not finished[b]]
-            forced = {b: (ftok[b][step] if (ftok[b] is not None and step < len(ftok[b])) else None) for b in live}
-            toks = {}
-            speculated = set()
-            if step == 0:
-                st_embed = self.engine.embed_ids(torch.tensor([ST]))
-                for b in live:
-                    rb_of[b].prefill(loc[b], x0s[b], chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=st_embed)
-                for b in live:
-                    toks[b] = rb_of[b].first_token(loc[b], forced[b], sample_fn)
-                    if toks[b] == SD:
-                        rb_of[b].commit_negative(loc[b])
-            elif sample_fn is not None:
-                # do_sample: A1 of every row batch, ONE wait for all their logits, the tokens drawn in ascending dialogue order (the lanes' order),
-                # then A2 with them as forced tokens.  No speculation (the token is known only once the host has drawn it), as on the lanes
-                plan = []
-                for rb, idxs in groups:
-                    lv = [b for b in idxs if b in forced]
-                    if lv:
-                        rb.decode_logits()
-                        plan.append((rb, lv))
-                deliver()
-                lg = {}
-                for rb, lv in plan:
-                    lh = rb.logits_end()
-                    lg.update({b: lh[loc[b]] for b in lv})
-                for b in live:
-                    rb = rb_of[b]
-                    toks[b] = forced[b] if forced[b] is not None else int(sample_fn(lg[b][: len(rb.valid_ids)].clone(), rb.valid_ids))
-                for rb, lv in plan:
-                    rb.decode_commit(ST, SD, {loc[b]: toks[b] for b in lv})
-            else:
-                # graph A of every row batch; a batch in its steady state (every live dialogue diffusing, noise injected) gets its diffusion
-                # sampling enqueued speculatively behind it.  The conv tails follow once all A / H are queued: each batch's tails are enqueued
-                # when ITS sampler has finished (RowBatch.speech_tails) and run while the main stream works on the next batch
-                plan = []
-                for rb, idxs in groups:
-                    lv = [b for b in idxs if b in forced]
-                    if not lv:
-                        continue
-                    spec = speculate and all(prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
-                                             (not sde or (snz[b] is not None and frame[b] < len(snz[b]))) for b in lv)
-                    rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv})
-                    if spec:
-                        rb.speech_begin([loc[b] for b in lv], {loc[b]: nz[b][frame[b]] for b in lv},
-                                        {loc[b]: snz[b][frame[b]] for b in lv} if sde else None)
-                    plan.append((rb, lv, spec))
-                deliver()                  # the previous step's chunks (their copies completed long ago), before the host waits for a sampler
-                for rb, lv, spec in plan:
-                    if spec:
-                        rb.speech_tails([loc[b] for b in lv])
-                        speculated.update(lv)
-                for rb, lv, spec in plan:
-                    tk = rb.decode_end()
-                    toks.update({b: tk[loc[b]] for b in lv})
-            going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
-            replace, restart = coupling.step(toks, going)
-            for b in replace:
-                rb = rb_of[b]
-                with torch.cuda.stream(rb.stream):
-                    _copy_kv_slot(rb._kv_t[0], rb._kv_t[1], rb._kv_vt if rb.kv.vt else None, 2 * loc[b] + 1, coupling.vis[b], coupling.vis[b] - 1)
-            diffusing = []
-            for b in live:
-                tok = toks[b]
-                rb = rb_of[b]
-                if b in speculated and (tok != SD or b in restart):
-                    rb.rollback(loc[b])
-                    speculated.discard(b)
-                prev_tok[b] = tok
-                seq[b].append(tok)
-                if tok == EOS:                                                                      # :517-526
-                    if verbose:
-                        print(f"Samples [{b}] reached EOS token at step {step + 1}.", flush=True)
-                    finish(b)
-                    continue
-                if step >= max_step_per_sample[b]:                                                  # :528-537
-                    reach[b] = True
-                    finish(b)
-                    continue
-                if tok == SE:                                                                       # :540-544
-                    rb.reset_speech(loc[b])
-                if tok == SD:
-                    diffusing.append(b)
-                    if b in restart:
-                        rb.reset_speech(loc[b])
-                else:
-                    rb.embed(loc[b])                                                                # :567
-            todo = [b for b in diffusing if b not in speculated]
-            if todo:
-                need = [b for b in todo if nz[b] is None or frame[b] >= len(nz[b])]
-                drawn, sdrawn = None, None
-                if need:       # the reference's draws for n diffusing samples (:699; SDE: n_steps more, dpm_solver.py:993-998), as _generate_lockstep's draw()
-                    n = len(need)
-                    drawn = torch.randn(2 * n, cfg.latent)[:n]
-                    if sde:
-                        sdrawn = torch.stack([torch.randn(2 * n, cfg.latent)[:n] for _ in range(lanes[0].n_steps)], dim=1)
-                rows = {b: (drawn[need.index(b)] if b in need else nz[b][frame[b]]) for b in todo}
-                srows = {b: (sdrawn[need.index(b)] if b in need else snz[b][frame[b]]) for b in todo} if sde else None
-                for rb, idxs in groups:
-                    mine = [b for b in todo if rb_of[b] is rb]
-                    if mine:
-                        rb.speech([loc[b] for b in mine], {loc[b]: rows[b] for b in mine}, {loc[b]: srows[b] for b in mine} if sde else None)
-            for rb, _ in groups:
-                rb.flush()                 # the conv tails are enqueued from worker threads: the chunk copies below must queue behind them
-            for b in diffusing:                                                                     # :571-670
-                with torch.cuda.stream(lanes[b].stream):
-                    chunks[b].append(lanes[b].wav.clone())
-                if audio_streamer is not None:
-                    pending.append((b, lanes[b].stage_chunk()))
-                frame[b] += 1
-        deliver()
-        for rb, _ in groups:
-            rb.synchronize()
-        if audio_streamer is not None:
-            audio_streamer.end()
-        pad_id = getattr(tokenizer, "pad_id", None)
-        if pad_id is None:
-            pad_id = special["eos"]
-        rows = []
-        for b in range(B):
-            rows.append(torch.cat([input_ids[b][~keep[b]], torch.tensor(seq[b], dtype=torch.long)]))
-        mx = max(r.shape[0] for r in rows)
-        seq_t = torch.full((B, mx), int(pad_id), dtype=torch.long)
-        for b, r in enumerate(rows):
-            seq_t[b, : r.shape[0]] = r
-        audios = [(torch.cat(c)[None] if c else None) for c in chunks]
-        return VibeVoiceGenerationOutput(sequences=seq_t.to(in_dev), speech_outputs=audios if return_speech else None,
-                                         reach_max_step_sample=torch.tensor(reach, dtype=torch.bool))
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
                       noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True):
@@ -933,19 +678,14 @@ class VibeVoiceForConditionalGenerationInference:
             return nz, sz
 
         ST, SE, SD, EOS = special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]
-        valid = [ST, SE, SD, EOS] + ([special["bos"]] if special.get("bos") is not None else [])
         # device-side position bookkeeping (vv_advance_lens): a negative "speech_start" id selects refresh_negative=False - the negative
         # row consumes every step's embedding and is never reset (:501-515); the batch-2 step computes that row anyway
         ST_dev = ST if refresh_negative else -1
         L0 = int(ids.shape[0])
-        max_length = cfg.max_pos if max_new_tokens is None else L0 + int(max_new_tokens)          # :370-371
-        max_steps = min(max_length - L0, int(max_length_times * L0))                            # :420
+        max_length, max_steps = batchloop.limits(cfg.max_pos, L0, max_new_tokens, max_length_times)
         eng.cfg_scale = float(cfg_scale)
-        eng.begin_sequence(L0 + max(max_steps, 1) + 8, valid)
-        x0 = eng.embed_ids(ids)
-        if conn is not None:
-            with torch.cuda.stream(eng.stream):
-                x0[sp_mask.to(self.device)] = conn                                              # :221-224
+        eng.begin_sequence(L0 + max(max_steps, 1) + 8, batchloop.valid_token_ids(special))
+        x0 = _embed_prompt(eng, ids, None if conn is None else (sp_mask, conn))
         seq = ids.tolist()
         chunks: List[torch.Tensor] = []
         reach_max = False

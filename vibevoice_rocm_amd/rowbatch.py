@@ -15,7 +15,8 @@ B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in on
 The conv tokenizers (acoustic decode, semantic encode) and the connectors stay per dialogue - each has its own streaming state - and run as
 B concurrent hipGraphs on the lanes' streams between H and the next A (events fork / join them), exactly the launch sequences the lanes use.
 They are enqueued only once H has finished: a lane queue that sits on a cross-stream wait while the main queue runs A and H slows every dependent
-launch there.  The host loop, token state machine, speculation and rollback are those of the lock-step loop (modeling.py)."""
+launch there.  The host loop, token state machine, speculation and rollback are the one batched loop's (batchloop.run), which drives row batches through
+modeling._RowDriver."""
 from __future__ import annotations
 
 import ctypes as C
