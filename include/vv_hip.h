@@ -13,7 +13,8 @@
  *     with the matching *_ws_bytes() query.  No hidden synchronisation: everything is enqueued on `stream`
  *     and is capturable into a hipGraph (vv_graph_*).
  *   - activations are fp32.  Matrix weights are fp32 or bf16 (`wdt`), vectors (norms, biases, layer scales,
- *     depthwise taps) are always fp32.  KV cache is fp32 or bf16 (`kvdt`).
+ *     depthwise taps) are always fp32.  KV cache is fp32 or bf16 (`kvdt`), or - decode steps only - e4m3fn bytes with one power-of-two
+ *     scale per (layer, KV head) (`kvdt == VV_FP8`, vv_kv.kscale / vscale, filled by vv_kv_quantize).
  *   - convolutional activations are channels-last [T, C] (the reference uses [B, C, T]).
  */
 #ifndef VV_HIP_H
@@ -121,6 +122,13 @@ typedef struct vv_kv {
                  the A-operand fragments of the matrix-core P.V product.  vv_rope_store and vv_attn_decode keep it in step with v; with it (bf16,
                  head_dim 128, s_max % 32 == 0) prompt-sized vv_attn calls and split-key decode steps run both attention products on the matrix
                  cores without a transpose; NULL: the VALU kernels.  Need not be zero-initialised. */
+  /* kvdt == VV_FP8 (head_dim 128, s_max % 32 == 0, s_max >= 64, vt != NULL): k, v and vt keep the layouts above with ONE e4m3fn byte per element, and
+     kscale / vscale are fp32 [layers][kv_heads] powers of two shared by all cache rows: the effective value of a code is fp32(code) * scale.
+     Only vv_kv_quantize writes such a cache from a prompt and only vv_attn_decode (the grouped-query matrix-core kernel, at every context
+     length and key-split count) reads and appends to it; vv_rope_store, vv_attn and the per-head decode kernel return VV_E_UNSUPPORTED.
+     kscale / vscale are NULL and ignored for fp32 / bf16 caches. */
+  float* kscale;
+  float* vscale;
 } vv_kv;
 
 /* rope_table[R][head_dim/2][2] = {cos, sin}(lens[r] * inv_freq[i]): computed once per step, shared by all layers */
@@ -133,6 +141,21 @@ int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv,
  * projection (pre-RoPE); q and the new k are rotated in registers, k/v appended at slot lens[r], attention over 0..lens[r]. */
 int vv_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table,
                    const int* lens, float* out, int64_t ldo, vv_stream_t stream);
+/* The same step with the cached keys of every row split over `nsplit` workgroups per (row, head), as vv_llm_forward runs it on long contexts:
+ * part = vv_attn_decode_part_floats(R, heads, part_cap) floats of scratch, tickets = R * heads ints, zero on entry and left zero.  The grouped
+ * kernel may use up to part_cap >= nsplit splits (vv_tune "attn_gqa_keys").  An fp8 cache (kvdt == VV_FP8) always runs the grouped kernel: the
+ * new token's k (after RoPE) and v take part in the step at fp32, and are appended to k, v and vt as codes saturated to +-448 under the head's
+ * scale. */
+size_t vv_attn_decode_part_floats(int R, int heads, int part_cap);
+int vv_attn_decode_split(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table,
+                         const int* lens, float* out, int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, vv_stream_t stream);
+/* vv_kv_quantize - slots [0, len) of row src_row of a bf16 cache (head_dim 128) into row dst_row of an fp8 cache of the same layers / kv_heads
+ * (s_max may differ; len <= both): k, v and the tile-major vt of dst, codes = e4m3fn(round-to-nearest-even(clamp(x / scale, -448, 448))) - saturating,
+ * never the NaN code.  Slots >= len and every other row are left as they are.  flags & VV_KVQ_DERIVE_SCALES: first sets dst->kscale / vscale of every
+ * (layer, KV head) from the absmax of src K / V over those slots, scale = 2^ceil(log2(absmax / 224)) (2x headroom under e4m3's 448; an all-zero
+ * head gets 1); without it the scales dst already holds are used.  One launch sequence, no allocation, no synchronisation. */
+enum { VV_KVQ_DERIVE_SCALES = 1 };
+int vv_kv_quantize(const vv_kv* src_bf16, const vv_kv* dst_fp8, int src_row, int dst_row, int len, int flags, vv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Block1D first half on channels-last data (modular_vibevoice_tokenizer.py:924-932 with the streaming

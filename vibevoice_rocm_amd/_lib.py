@@ -18,6 +18,7 @@ PRO_NONE, PRO_RMSNORM, PRO_SILU = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SWIGLU = 0, 1, 2
 LIN_X_BF16, LIN_OUT_BF16, LIN_W_REUSED, LIN_W_FRAG = 1, 2, 4, 8
 VV_MAX_STAGES = 8
+KVQ_DERIVE_SCALES = 1  # vv_kv_quantize flags
 
 vp = C.c_void_p
 i64 = C.c_int64
@@ -36,7 +37,19 @@ class LinArgs(C.Structure):
 
 class KV(C.Structure):
     _fields_ = [("k", vp), ("v", vp), ("kvdt", C.c_int), ("layers", C.c_int), ("rows", C.c_int),
-                ("kv_heads", C.c_int), ("s_max", C.c_int), ("head_dim", C.c_int), ("vt", vp)]
+                ("kv_heads", C.c_int), ("s_max", C.c_int), ("head_dim", C.c_int), ("vt", vp),
+                ("kscale", vp), ("vscale", vp)]      # kvdt == VV_FP8: fp32 [layers][kv_heads] powers of two; NULL otherwise
+
+
+def kv_fp8_scale(absmax: float) -> float:
+    """The fp8 KV cache's scale of one (layer, KV head), as vv_kv_quantize derives it: 2^ceil(log2(absmax / 224)) - 2x headroom under e4m3's
+    448 - and 1 for an all-zero head.  Exact: absmax = m 2^e with m in [0.5, 1), 224 = 0.875 x 2^8."""
+    import math
+    a = abs(float(absmax))
+    if a == 0.0:
+        return 1.0
+    m, e = math.frexp(a)
+    return math.ldexp(1.0, e - 8 if m <= 0.875 else e - 7)
 
 
 class LlmLayer(C.Structure):
@@ -111,6 +124,9 @@ PROTOTYPES = {
     "vv_rope_store": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, vp]),
     "vv_attn": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp]),
     "vv_attn_decode": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp]),
+    "vv_attn_decode_part_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vv_attn_decode_split": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp, vp, C.c_int, C.c_int, vp]),
+    "vv_kv_quantize": (C.c_int, [C.POINTER(KV), C.POINTER(KV), C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vv_block_mixer": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_float, vp, vp, vp, vp, vp]),
     "vv_block1d": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "vv_block_mid_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -51,7 +51,7 @@ __device__ unsigned long long g_at_t[8];
 #endif
 #define ATT_UNR 4
 template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* qkv, int64_t ld, int heads, vv_kv kv, int layer, const float2* rope, const int* lens,
+__global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer, const float2* rope, const int* lens,
                                                              float* out, int64_t ldo, float* part, int* tickets) {
   constexpr int d = 128, half = 64, NG = NW * 4, EPL = 8;
   __shared__ __attribute__((aligned(16))) float sacc[NG][d];
@@ -281,6 +281,14 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* qkv, 
 //                                                  (key slot 8 g + j of the 32-deep step = the lane's own eight scores), again as bf16 hi + lo
 // Each of the NW waves walks 32-key tiles wave, wave + NW, ...; the waves' (m, l, O) meet in LDS once.  The new token's score and value come
 // from the projection registers; the workgroup of split 0 appends k (rotated), v and the transposed v at slot pos.
+//
+// fp8 cache (KVA = vv_kv_args8, vv_kv.kvdt == VV_FP8): the same kernel on e4m3fn bytes.  The layouts are the bf16 cache's with one byte per element,
+// so a lane's K fragment (8 d of one key) and V^T fragment (8 keys of one d row) are 8 contiguous bytes: one 8-byte load each, the same
+// number of requests per tile as the bf16 form at half the bytes (a 16-byte load would need the neighbouring k step or key tile next to it,
+// which both layouts keep 32 bytes / 4 KB away).  The codes are widened to bf16 in registers with the (layer, KV head)'s power-of-two scale
+// folded in (v_cvt_scalef32_pk_bf16_fp8: code * 2^p is exact in bf16) and feed the unchanged MFMA sequence: scores, softmax, merge and output
+// are those of the bf16 kernel on the dequantised cache, bit for bit.  The new token takes part in its own step at fp32 as before and is
+// appended as codes saturated to +-448 under the head's scale.
 // ---------------------------------------------------------------------------------------------------------------------------------------
 typedef __bf16 gq_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float gq_f32x4 __attribute__((ext_vector_type(4)));
@@ -298,13 +306,32 @@ __device__ __forceinline__ void gq_split(const float (&x)[8], att_raw& hi, att_r
   lo.x = gq_pk(l[0], l[1]); lo.y = gq_pk(l[2], l[3]); lo.z = gq_pk(l[4], l[5]); lo.w = gq_pk(l[6], l[7]);
 }
 
+typedef __bf16 gq_bf16x2 __attribute__((ext_vector_type(2)));
+// cache bits of one fragment -> the MFMA operand bits: bf16 as they are; e4m3fn codes widened with the head's scale
+__device__ __forceinline__ att_raw gq_widen(att_raw v, float) { return v; }
+__device__ __forceinline__ att_raw gq_widen(gq_u32x2 v, float sc) {
+  const gq_bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, true);
+  const gq_bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, true);
+  return __builtin_bit_cast(att_raw, gq_bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]});
+}
+__device__ __forceinline__ float gq_pow2_inv(float sc) { return __uint_as_float(0x7f000000u - __float_as_uint(sc)); }     // 1 / 2^p, exact
+__device__ __forceinline__ gq_u32x2 gq_codes8(const float (&x)[8], float inv) {
+  gq_u32x2 o;
+  o.x = vv_e4m3_sat(x[0] * inv) | (vv_e4m3_sat(x[1] * inv) << 8) | (vv_e4m3_sat(x[2] * inv) << 16) | (vv_e4m3_sat(x[3] * inv) << 24);
+  o.y = vv_e4m3_sat(x[4] * inv) | (vv_e4m3_sat(x[5] * inv) << 8) | (vv_e4m3_sat(x[6] * inv) << 16) | (vv_e4m3_sat(x[7] * inv) << 24);
+  return o;
+}
+
 constexpr int GQ_MAXG = 8;      // q heads per KV head covered (1.5B: 6, 7B: 7)
 constexpr int GQ_PITCH = 132;   // floats per (wave, query) row of the merge buffer
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* qkv, int64_t ld, int heads, vv_kv kv, int layer, const float2* rope, const int* lens,
+template <int NW, typename KVA>
+__global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* qkv, int64_t ld, int heads, KVA kv, int layer, const float2* rope, const int* lens,
                                                                  float* out, int64_t ldo, float* part, int* tickets) {
   constexpr int d = 128;
+  constexpr bool F8 = std::is_same<KVA, vv_kv_args8>::value;
+  using elem_t = typename std::conditional<F8, uint8_t, bf16_t>::type;      // one cache element
+  using raw_t = typename std::conditional<F8, gq_u32x2, att_raw>::type;     // one fragment of 8 elements as it is loaded
   __shared__ __attribute__((aligned(16))) float so[NW][GQ_MAXG][GQ_PITCH];     // per wave and query: O[128], then m, l
   __shared__ float s_new[GQ_MAXG];
   __shared__ int s_last;
@@ -318,9 +345,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
   const int nq = n < G ? n : G - 1;                      // lanes of the unused query columns read head G - 1 (zeroed below)
   const float* row = qkv + (int64_t)r * ld;
   const int64_t base = ((((int64_t)layer * kv.rows + r) * kv.kv_heads + kvh) * kv.s_max) * d;
-  bf16_t* kc = reinterpret_cast<bf16_t*>(kv.k) + base;
-  bf16_t* vc = reinterpret_cast<bf16_t*>(kv.v) + base;
-  bf16_t* vt = reinterpret_cast<bf16_t*>(kv.vt) + base;   // [s_max / 32][d][32]
+  elem_t* kc = reinterpret_cast<elem_t*>(kv.k) + base;
+  elem_t* vc = reinterpret_cast<elem_t*>(kv.v) + base;
+  elem_t* vt = reinterpret_cast<elem_t*>(kv.vt) + base;   // [s_max / 32][d][32]
+  float ksc = 1.f, vsc = 1.f;                             // fp8: the (layer, KV head)'s power-of-two scales
+  if constexpr (F8) { ksc = kv.kscale[layer * kv.kv_heads + kvh]; vsc = kv.vscale[layer * kv.kv_heads + kvh]; }
   // ---- requests: q chunks of this lane's head, the new k chunks, RoPE table, and (unsplit contexts) the first two key tiles -------------
   const float* qp = row + (int64_t)(kvh * G + nq) * d + 8 * g;
   const float* kp = row + (int64_t)(heads + kvh) * d + 8 * g;
@@ -335,8 +364,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int i = 0; i < 4; ++i) rr[s][i] = *reinterpret_cast<const float4*>(rp + 32 * s + 2 * i);     // {cos, sin} x 2 per float4
-  att_raw kraw[2][2][4];            // [buffer][16-row score tile][k-step]
-  att_raw vraw[2][8];               // [buffer][d tile]: keys 8 g .. 8 g + 7 of the 32-key tile for d row 16 dt + n
+  raw_t kraw[2][2][4];              // [buffer][16-row score tile][k-step]
+  raw_t vraw[2][8];                 // [buffer][d tile]: keys 8 g .. 8 g + 7 of the 32-key tile for d row 16 dt + n
   // Row i of score tile t holds key 8 (i >> 2) + 4 t + (i & 3) of the 32-key tile: lane (n, g)'s eight scores are then keys 8 g .. 8 g + 7 in
   // order - the k slots 8 g + j of the P.V step - and its V^T fragment is ONE 16-byte load from the tile-major transposed cache.
   const int krow = 8 * (n >> 2) + (n & 3);
@@ -345,11 +374,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
     for (int t = 0; t < 2; ++t) {
       const int key = min(key0 + krow + 4 * t, kmax_valid);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) kraw[buf][t][s] = *reinterpret_cast<const att_raw*>(kc + (int64_t)key * d + 32 * s + 8 * g);
+      for (int s = 0; s < 4; ++s) kraw[buf][t][s] = *reinterpret_cast<const raw_t*>(kc + (int64_t)key * d + 32 * s + 8 * g);
     }
-    const bf16_t* vp = vt + (int64_t)(min(key0, kv.s_max - 32) >> 5) * (32 * d) + n * 32 + 8 * g;
+    const elem_t* vp = vt + (int64_t)(min(key0, kv.s_max - 32) >> 5) * (32 * d) + n * 32 + 8 * g;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) vraw[buf][dt] = *reinterpret_cast<const att_raw*>(vp + dt * 16 * 32);
+    for (int dt = 0; dt < 8; ++dt) vraw[buf][dt] = *reinterpret_cast<const raw_t*>(vp + dt * 16 * 32);
   };
   const bool spec = nsplit == 1;     // unsplit: the first tiles are requested before the position is known (masked / scrubbed when consumed)
   if (spec) issue(0, 32 * wave, kv.s_max - 1);
@@ -401,9 +430,13 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
   if (split == 0 && wave == 0 && n == 0) {          // one writer per (row, kv head): append the rotated key at slot pos
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      att_raw pk;
-      pk.x = gq_pk(kn[s][0], kn[s][1]); pk.y = gq_pk(kn[s][2], kn[s][3]); pk.z = gq_pk(kn[s][4], kn[s][5]); pk.w = gq_pk(kn[s][6], kn[s][7]);
-      *reinterpret_cast<att_raw*>(kc + (int64_t)pos * d + 32 * s + 8 * g) = pk;
+      if constexpr (F8) {
+        *reinterpret_cast<gq_u32x2*>(kc + (int64_t)pos * d + 32 * s + 8 * g) = gq_codes8(kn[s], gq_pow2_inv(ksc));
+      } else {
+        att_raw pk;
+        pk.x = gq_pk(kn[s][0], kn[s][1]); pk.y = gq_pk(kn[s][2], kn[s][3]); pk.z = gq_pk(kn[s][4], kn[s][5]); pk.w = gq_pk(kn[s][6], kn[s][7]);
+        *reinterpret_cast<att_raw*>(kc + (int64_t)pos * d + 32 * s + 8 * g) = pk;
+      }
     }
   }
   ASTAMP(1);                                       // q / k / rope landed, RoPE, split, new token
@@ -420,8 +453,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
       sc[t] = gq_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(kraw[buf][t][s]), gq_frag(qhi[s]), sc[t], 0, 0, 0);
-        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(kraw[buf][t][s]), gq_frag(qlo[s]), sc[t], 0, 0, 0);
+        const att_raw kf = gq_widen(kraw[buf][t][s], ksc);
+        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(kf), gq_frag(qhi[s]), sc[t], 0, 0, 0);
+        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(kf), gq_frag(qlo[s]), sc[t], 0, 0, 0);
       }
     }
     float p[8];
@@ -451,8 +485,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
     const unsigned a0 = keep(0), a1 = keep(2), a2 = keep(4), a3 = keep(6);
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
+      const att_raw vf = gq_widen(vraw[buf][dt], vsc);
       att_raw a;
-      a.x = vraw[buf][dt].x & a0; a.y = vraw[buf][dt].y & a1; a.z = vraw[buf][dt].z & a2; a.w = vraw[buf][dt].w & a3;
+      a.x = vf.x & a0; a.y = vf.y & a1; a.z = vf.z & a2; a.w = vf.w & a3;
       gq_f32x4 o = oacc[dt];
       o[0] *= corr; o[1] *= corr; o[2] *= corr; o[3] *= corr;
       o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(a), gq_frag(phi), o, 0, 0, 0);
@@ -507,7 +542,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
       if (dd == 0) { pp[0] = M; pp[1] = den; }
     }
     if (split == 0 && qh == 0) {                       // append v (key-major and transposed copies) at slot pos
-      const bf16_t vb = (bf16_t)bf16_bits(vn);
+      const elem_t vb = F8 ? (elem_t)vv_e4m3_sat(vn * gq_pow2_inv(vsc)) : (elem_t)bf16_bits(vn);
       vc[(int64_t)pos * d + dd] = vb;
       vt[(int64_t)(pos >> 5) * (32 * d) + dd * 32 + (pos & 31)] = vb;
     }
@@ -601,7 +636,15 @@ int g_gqa = 1;     // tuning hook "attn_gqa"
 // 1 launched, 0 not covered (caller falls back to the generic kernel), < 0 error.  part / tickets: split-key workspace or null (nsplit = 1)
 int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float2* rope, const int* lens, float* out,
                           int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, hipStream_t s) {
-  if (kv->kvdt != VV_BF16 || kv->head_dim != 128) return 0;
+  if (kv->kvdt == VV_FP8) {
+    // an fp8 cache has this one kernel: every shape it does not cover is an error, never another kernel
+    if (kv->head_dim != 128 || kv->s_max % 32 || kv->s_max < 64 || !kv->vt || !kv->kscale || !kv->vscale)
+      return vv_set_error(VV_E_UNSUPPORTED, "vv_attn_decode: an fp8 KV cache needs head_dim 128, s_max %% 32 == 0, s_max >= 64, vt, kscale and vscale");
+    if (heads / kv->kv_heads > GQ_MAXG) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn_decode: fp8 KV cache with %d q heads per KV head (at most %d)", heads / kv->kv_heads, GQ_MAXG);
+    if (!g_gqa) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn_decode: the per-head decode kernel has no fp8 form (fp8 KV caches run the grouped-query kernel only)");
+    if (((uintptr_t)qkv % 16) || (ld_qkv % 4) || ((uintptr_t)rope % 16) || ((uintptr_t)kv->k % 16) || ((uintptr_t)kv->v % 16) || ((uintptr_t)kv->vt % 16))
+      return vv_set_error(VV_E_ARG, "vv_attn_decode: fp8 KV cache: qkv, rope_table, k, v and vt must be 16-byte aligned (ld_qkv %% 4 == 0)");
+  } else if (kv->kvdt != VV_BF16 || kv->head_dim != 128) return 0;
   if (((uintptr_t)qkv % 16) || (ld_qkv % 4) || ((uintptr_t)rope % 16) || ((uintptr_t)kv->k % 16) || ((uintptr_t)kv->v % 16)) return 0;
   if (!part || !tickets || nsplit < 1) nsplit = 1;
   if (nsplit > 16) nsplit = 16;
@@ -614,7 +657,8 @@ int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, co
   // 7.4 us for the per-head kernel's 24 workgroups; phase timing: tools/convffn_phase.py attn 2 / attn_split), so short contexts keep the
   // per-head kernel.  g_gqa (tuning hook "attn_gqa"): 1 = by that rule, 2 = always, 0 = never.
   const long gqa_min = 12288;                              // cached key rows per (layer, cache row): kv_heads x s_max
-  if (g_gqa && ((nsplit > 1 && (long)kv->kv_heads * kv->s_max >= gqa_min) || g_gqa == 2) && kv->vt && G <= GQ_MAXG && kv->s_max % 32 == 0 && kv->s_max >= 64 && ((uintptr_t)kv->vt % 8) == 0) {
+  const bool f8 = kv->kvdt == VV_FP8;                      // checked above: always the grouped kernel
+  if (f8 || (g_gqa && ((nsplit > 1 && (long)kv->kv_heads * kv->s_max >= gqa_min) || g_gqa == 2) && kv->vt && G <= GQ_MAXG && kv->s_max % 32 == 0 && kv->s_max >= 64 && ((uintptr_t)kv->vt % 8) == 0)) {
     // very long contexts: more splits than the per-head kernel's 16, so that a workgroup pulls ~0.5 MB through its CU instead of megabytes
     // (4 - 8 (row, KV head) pairs x 16 splits leave three quarters of the chip idle: 68 us per layer at S = 64 000)
     int ng = nsplit;
@@ -623,7 +667,8 @@ int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, co
       if (ng > part_cap) ng = part_cap;
       if (ng > 64) ng = 64;                             // the last workgroup folds <= 16 splits per thread quarter with all loads in flight
     }
-    hipLaunchKernelGGL((attn_decode_gqa_kernel<8>), dim3(kv->kv_heads, R, ng), dim3(512), 0, s, qkv, ld_qkv, heads, *kv, layer, rope, lens, out, ldo, part, tickets);
+    if (f8) hipLaunchKernelGGL((attn_decode_gqa_kernel<8, vv_kv_args8>), dim3(kv->kv_heads, R, ng), dim3(512), 0, s, qkv, ld_qkv, heads, vv_kv_args8(*kv), layer, rope, lens, out, ldo, part, tickets);
+    else hipLaunchKernelGGL((attn_decode_gqa_kernel<8, vv_kv_args>), dim3(kv->kv_heads, R, ng), dim3(512), 0, s, qkv, ld_qkv, heads, vv_kv_args(*kv), layer, rope, lens, out, ldo, part, tickets);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_attn_decode (gqa): %s", hipGetErrorString(e));
     return 1;
@@ -632,6 +677,116 @@ int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, co
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_attn_decode: %s", hipGetErrorString(e));
   return 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// vv_kv_quantize: a prompt's rows of a bf16 cache into an fp8 cache (vv_hip.h).  Two launches: the scales of every (layer, KV head) from the
+// absmax of the source slots (optional), then the codes of k, v and the tile-major v^T.  Load-time work (once per prompt): plain kernels.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// scale = 2^ceil(log2(absmax / 224)) without a logarithm: absmax = m 2^e with m in [0.5, 1) and 224 = 0.875 x 2^8, so the smallest p with
+// absmax <= 224 x 2^p is e - 8 when m <= 0.875 and e - 7 otherwise.  Zero gives 1.
+__device__ __forceinline__ float kvq_scale(unsigned absmax_bf16) {
+  if (absmax_bf16 == 0) return 1.f;
+  int p = 100;
+  if (absmax_bf16 < 0x7f80u) {
+    int e;
+    const float m = frexpf(__uint_as_float(absmax_bf16 << 16), &e);
+    p = m <= 0.875f ? e - 8 : e - 7;
+    p = max(-100, min(100, p));
+  }
+  return ldexpf(1.f, p);
+}
+
+// grid (kv_heads, layers, 2 = {k, v}), 256 threads: one (layer, KV head) of one array per workgroup, its len x 128 bf16 are contiguous
+__global__ __launch_bounds__(256) void kvq_absmax_kernel(vv_kv_args src, vv_kv_args8 dst, int src_row, int len) {
+  __shared__ unsigned s_m[4];
+  const int kvh = blockIdx.x, layer = blockIdx.y, tid = threadIdx.x;
+  const int64_t base = ((((int64_t)layer * src.rows + src_row) * src.kv_heads + kvh) * src.s_max) * 128;
+  const att_raw* p = reinterpret_cast<const att_raw*>(reinterpret_cast<const bf16_t*>(blockIdx.z ? src.v : src.k) + base);
+  unsigned m = 0;
+  for (int i = tid; i < len * 16; i += 256) {
+    const att_raw w = p[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { m = max(m, w[j] & 0x7fffu); m = max(m, (w[j] >> 16) & 0x7fffu); }     // |bf16| orders as its bits
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+  if ((tid & 63) == 0) s_m[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+    float* out = const_cast<float*>(blockIdx.z ? dst.vscale : dst.kscale);
+    out[layer * src.kv_heads + kvh] = kvq_scale(m);
+  }
+}
+
+__device__ __forceinline__ att_raw kvq_codes16(const att_raw a, const att_raw b, float inv) {
+  float x[8], y[8];
+  unpack8(a, x); unpack8(b, y);
+  const gq_u32x2 lo = gq_codes8(x, inv), hi = gq_codes8(y, inv);
+  return att_raw{lo.x, lo.y, hi.x, hi.y};
+}
+
+// grid (ceil(len / 32), kv_heads, layers), 256 threads: one 32-key tile of one (layer, KV head).  Thread (key = tid >> 3, c = tid & 7) converts
+// d = 16 c .. 16 c + 15 of its key for k and v (one 16-byte store each); the v codes also go through LDS and leave transposed, thread
+// (d = tid >> 1, half = tid & 1) storing keys 16 half .. + 15 of row d of the v^T tile - 16 bytes at once in a full tile, byte by byte in
+// the last, partial one (slots >= len stay as they are).
+__global__ __launch_bounds__(256) void kvq_codes_kernel(vv_kv_args src, vv_kv_args8 dst, int src_row, int dst_row, int len) {
+  __shared__ __attribute__((aligned(16))) uint8_t sv[32][128 + 16];
+  const int tile = blockIdx.x, kvh = blockIdx.y, layer = blockIdx.z, tid = threadIdx.x;
+  const int64_t sb = ((((int64_t)layer * src.rows + src_row) * src.kv_heads + kvh) * src.s_max) * 128;
+  const int64_t db = ((((int64_t)layer * dst.rows + dst_row) * dst.kv_heads + kvh) * dst.s_max) * 128;
+  const float kinv = gq_pow2_inv(dst.kscale[layer * dst.kv_heads + kvh]), vinv = gq_pow2_inv(dst.vscale[layer * dst.kv_heads + kvh]);
+  const int key = tid >> 3, c = tid & 7, slot = tile * 32 + key;
+  if (slot < len) {
+    const int64_t so = sb + (int64_t)slot * 128 + 16 * c, dof = db + (int64_t)slot * 128 + 16 * c;
+    const att_raw* kp = reinterpret_cast<const att_raw*>(reinterpret_cast<const bf16_t*>(src.k) + so);
+    const att_raw* vp = reinterpret_cast<const att_raw*>(reinterpret_cast<const bf16_t*>(src.v) + so);
+    const att_raw kq = kvq_codes16(kp[0], kp[1], kinv), vq = kvq_codes16(vp[0], vp[1], vinv);
+    *reinterpret_cast<att_raw*>(reinterpret_cast<uint8_t*>(dst.k) + dof) = kq;
+    *reinterpret_cast<att_raw*>(reinterpret_cast<uint8_t*>(dst.v) + dof) = vq;
+    *reinterpret_cast<att_raw*>(&sv[key][16 * c]) = vq;
+  }
+  __syncthreads();
+  const int dr = tid >> 1, half = tid & 1, nk = min(32, len - tile * 32);       // keys of this tile that exist
+  uint8_t* vt = reinterpret_cast<uint8_t*>(dst.vt) + db + (int64_t)tile * (32 * 128) + dr * 32 + 16 * half;
+  if (nk == 32) {
+    unsigned w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      w[j] = (unsigned)sv[16 * half + 4 * j][dr] | ((unsigned)sv[16 * half + 4 * j + 1][dr] << 8) | ((unsigned)sv[16 * half + 4 * j + 2][dr] << 16) |
+             ((unsigned)sv[16 * half + 4 * j + 3][dr] << 24);
+    *reinterpret_cast<att_raw*>(vt) = att_raw{w[0], w[1], w[2], w[3]};
+  } else {
+    for (int j = 0; j < 16; ++j)
+      if (16 * half + j < nk) vt[j] = sv[16 * half + j][dr];
+  }
+}
+
+}  // namespace
+
+int vv_launch_kv_quantize(const vv_kv* src, const vv_kv* dst, int src_row, int dst_row, int len, int flags, hipStream_t s) {
+  if (!src || !dst) return vv_set_error(VV_E_ARG, "vv_kv_quantize: null pointer");
+  if (src->kvdt != VV_BF16 || dst->kvdt != VV_FP8) return vv_set_error(VV_E_ARG, "vv_kv_quantize: src must be a bf16 cache and dst an fp8 cache");
+  if (src->head_dim != 128 || dst->head_dim != 128 || dst->s_max % 32 || !dst->vt || !dst->kscale || !dst->vscale || !src->k || !src->v || !dst->k || !dst->v)
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_kv_quantize: head_dim 128 on both sides; dst needs s_max %% 32 == 0, vt, kscale and vscale");
+  if (src->layers != dst->layers || src->kv_heads != dst->kv_heads) return vv_set_error(VV_E_ARG, "vv_kv_quantize: layers / kv_heads differ");
+  if (src_row < 0 || src_row >= src->rows || dst_row < 0 || dst_row >= dst->rows || len < 0 || len > src->s_max || len > dst->s_max)
+    return vv_set_error(VV_E_ARG, "vv_kv_quantize: row or len out of range");
+  if (((uintptr_t)src->k % 16) || ((uintptr_t)src->v % 16) || ((uintptr_t)dst->k % 16) || ((uintptr_t)dst->v % 16) || ((uintptr_t)dst->vt % 16))
+    return vv_set_error(VV_E_ARG, "vv_kv_quantize: cache pointers must be 16-byte aligned");
+  if (flags & VV_KVQ_DERIVE_SCALES) {
+    hipLaunchKernelGGL(kvq_absmax_kernel, dim3(src->kv_heads, src->layers, 2), dim3(256), 0, s, vv_kv_args(*src), vv_kv_args8(*dst), src_row, len);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_kv_quantize (scales): %s", hipGetErrorString(e));
+  }
+  if (len == 0) return 0;
+  hipLaunchKernelGGL(kvq_codes_kernel, dim3((len + 31) / 32, src->kv_heads, src->layers), dim3(256), 0, s, vv_kv_args(*src), vv_kv_args8(*dst), src_row, dst_row, len);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_kv_quantize: %s", hipGetErrorString(e));
+  return 0;
 }
 
 void vv_attn_decode_set_gqa(int on) { g_gqa = on; }

@@ -36,7 +36,7 @@ __device__ __forceinline__ unsigned pk2(float a, float b) {      // two floats -
 }
 __device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
-__global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int64_t ld, int heads, vv_kv kv, int layer, const int* lens, const int* cache_rows,
+__global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer, const int* lens, const int* cache_rows,
                                                           int R, float* out, int64_t ldo) {
   constexpr int d = 128;
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;

@@ -20,6 +20,19 @@ int vv_set_error(int code, const char* fmt, ...);
     if (rc_) return rc_;        \
   } while (0)
 
+// What the attention kernels take by value: vv_kv without the fp8 scale pointers (they travel in vv_kv_args8, to the one kernel that reads
+// them), so that growing vv_kv moves no kernel argument of the fp32 / bf16 kernels.
+struct vv_kv_args {
+  void* k; void* v;
+  int kvdt, layers, rows, kv_heads, s_max, head_dim;
+  void* vt;
+  vv_kv_args(const vv_kv& a) : k(a.k), v(a.v), kvdt(a.kvdt), layers(a.layers), rows(a.rows), kv_heads(a.kv_heads), s_max(a.s_max), head_dim(a.head_dim), vt(a.vt) {}
+};
+struct vv_kv_args8 : vv_kv_args {
+  const float* kscale; const float* vscale;
+  vv_kv_args8(const vv_kv& a) : vv_kv_args(a), kscale(a.kscale), vscale(a.vscale) {}
+};
+
 int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s);   // vv_gemv_stream.hip: 1 = launched, 0 = not covered
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
@@ -51,6 +64,7 @@ int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, co
                           int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, hipStream_t s);
 int vv_attn_decode_ws(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table, const int* lens, float* out,
                       int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, vv_stream_t stream);
+int vv_launch_kv_quantize(const vv_kv* src, const vv_kv* dst, int src_row, int dst_row, int len, int flags, hipStream_t s);   // vv_attn_decode.hip
 // vv_attn_prefill.hip: matrix-core prompt attention (bf16 cache + kv->vt, head_dim 128); 1 launched, 0 not covered, < 0 error
 int vv_launch_attn_prefill(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const int* lens, const int* cache_rows,
                            float* out, int64_t ldo, hipStream_t s);
@@ -92,6 +106,20 @@ void vv_skinny_set(int on, int min_m, int max_m);
 int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s);
 
 #ifdef __HIPCC__
+// fp32 -> e4m3fn code, round to nearest even, saturating at +-448 (never the NaN code 0x7f; a NaN input gives +-448): the KV cache's codes
+__host__ __device__ __forceinline__ unsigned vv_e4m3_sat(float x) {
+  union { float f; unsigned u; } a, t;
+  a.f = x;
+  const unsigned sign = (a.u >> 24) & 0x80u;
+  a.u &= 0x7fffffffu;
+  if (!(a.f < 448.f)) a.f = 448.f;
+  if (a.u < 0x3c800000u) {             // below 2^-6: subnormal codes, quantum 2^-9 (8 = the smallest normal)
+    t.f = a.f * 512.f + 8388608.f;
+    return sign | (t.u & 0xffu);
+  }
+  const unsigned r = (a.u + 0x7ffffu + ((a.u >> 20) & 1u)) >> 20;     // 3 mantissa bits
+  return sign | (r - ((127u - 7u) << 3));
+}
 // GELU (exact-erf form) with erf from Abramowitz & Stegun 7.1.26: |erf error| <= 1.5e-7, one v_exp + one v_rcp + 6 FMA instead
 // of libm's erff (~4x the instructions).  The reciprocal is the hardware's v_rcp_f32 (1 ulp): __frcp_rn expands to the IEEE division
 // sequence (v_div_scale / v_div_fmas / v_div_fixup + Newton steps, ~10 more instructions per GELU), and these kernels are bound by

@@ -29,7 +29,7 @@ int vv_set_error(int code, const char* fmt, ...) {
 }
 
 extern "C" const char* vv_last_error(void) { return g_err; }
-extern "C" int vv_abi_version(void) { return 6; }   // 6: fragment-major weight copies (vv_llm_layer.f_*, vv_head_layer.f_*, VV_LIN_W_FRAG), vv_llm_tail_batch, vv_head_sample_batch; 5: vv_kv.vt in 32-key tiles, vv_attn_decode maintains it, vv_advance_lens tok_start < 0; 2: vv_w8 fp8 companions, vv_dpm_coef.cn + variance-noise arguments; 3: vv_head.fused_g, vv_llm_tail, vv_llm_forward(out = NULL); 4: vv_block.dw_last / hs, vv_block_mid
+extern "C" int vv_abi_version(void) { return 6; }   // 6 (still: vv_sizeof catches a stale vv_kv mirror): vv_kv.kscale / vscale (fp8 KV cache for decode), vv_kv_quantize, vv_attn_decode_split; 6: fragment-major weight copies (vv_llm_layer.f_*, vv_head_layer.f_*, VV_LIN_W_FRAG), vv_llm_tail_batch, vv_head_sample_batch; 5: vv_kv.vt in 32-key tiles, vv_attn_decode maintains it, vv_advance_lens tok_start < 0; 2: vv_w8 fp8 companions, vv_dpm_coef.cn + variance-noise arguments; 3: vv_head.fused_g, vv_llm_tail, vv_llm_forward(out = NULL); 4: vv_block.dw_last / hs, vv_block_mid
 int vv_mixer_init();
 extern "C" int vv_init(void) {
   VV_TRY(vv_mixer_init());
@@ -734,7 +734,7 @@ extern "C" int vv_rope_table(const int* lens, const float* inv_freq, int R, int 
 }
 
 template <typename KT>
-__global__ __launch_bounds__(256) void rope_store_kernel(float* qkv, int64_t ld, int heads, vv_kv kv, int layer,
+__global__ __launch_bounds__(256) void rope_store_kernel(float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer,
                                                          const float2* rope, const int* lens, const int* cache_rows) {
   const int r = blockIdx.x;
   const int d = kv.head_dim, half = d >> 1;
@@ -777,6 +777,7 @@ extern "C" int vv_rope_store(float* qkv, int64_t ld_qkv, int R, int heads, const
   if (!qkv || !kv || !inv_freq || !lens) return vv_set_error(VV_E_ARG, "vv_rope_store: null pointer");
   if (layer < 0 || layer >= kv->layers || R <= 0) return vv_set_error(VV_E_ARG, "vv_rope_store: bad layer/R");
   if (kv->head_dim % 2) return vv_set_error(VV_E_ARG, "vv_rope_store: odd head_dim");
+  if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "vv_rope_store: an fp8 KV cache is written by vv_kv_quantize and vv_attn_decode only (kv dtype %d)", kv->kvdt);
   hipStream_t s = (hipStream_t)stream;
   if (kv->kvdt == VV_F32) hipLaunchKernelGGL((rope_store_kernel<float>), dim3(R), dim3(256), 0, s, qkv, ld_qkv, heads, *kv, layer, inv_freq, lens, cache_rows);
   else hipLaunchKernelGGL((rope_store_kernel<bf16_t>), dim3(R), dim3(256), 0, s, qkv, ld_qkv, heads, *kv, layer, inv_freq, lens, cache_rows);
@@ -818,7 +819,7 @@ __device__ __forceinline__ float group_dot_sum(float v, int G) {
 // so a wave covers 64/G keys per step with fully coalesced 16-byte loads; online softmax per lane group,
 // groups merged through LDS at the end.
 template <typename KT, int EPL>
-__global__ __launch_bounds__(256) void attn_kernel(const float* qkv, int64_t ld, int heads, vv_kv kv, int layer,
+__global__ __launch_bounds__(256) void attn_kernel(const float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer,
                                                    const int* lens, const int* cache_rows, float* out, int64_t ldo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int r = blockIdx.y, h = blockIdx.x;
@@ -888,7 +889,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* qkv, int64_t ld,
 // per-head kernel above re-reads the cache once per q head: at 330 rows x 12 heads that is ~340 MB of L2 traffic per layer and
 // the whole cost of the kernel); loads run one batch of keys ahead of the arithmetic.
 template <typename KT, int EPL, int NQ, int GT>      // GT: lanes per key when known at compile time (head_dim 128), 0 = from kv.head_dim
-__global__ __launch_bounds__(256) void attn_group_kernel(const float* qkv, int64_t ld, vv_kv kv, int layer,
+__global__ __launch_bounds__(256) void attn_group_kernel(const float* qkv, int64_t ld, vv_kv_args kv, int layer,
                                                          const int* lens, const int* cache_rows, float* out, int64_t ldo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int U = 2;
@@ -1013,6 +1014,7 @@ extern "C" int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const
                        const int* cache_rows, float* out, int64_t ldo, vv_stream_t stream) {
   if (!qkv || !kv || !lens || !out) return vv_set_error(VV_E_ARG, "vv_attn: null pointer");
   if (layer < 0 || layer >= kv->layers || R <= 0 || heads % kv->kv_heads) return vv_set_error(VV_E_ARG, "vv_attn: bad layer/R/heads");
+  if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn: an fp8 KV cache is read by vv_attn_decode only (kv dtype %d): prompt attention runs on a bf16 cache", kv->kvdt);
   const int d = kv->head_dim;
   const int epl = kv->kvdt == VV_F32 ? 4 : 8;
   if (d % epl || 64 % (d / epl) || d / epl > 64) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn: head_dim %d unsupported for kv dtype %d", d, kv->kvdt);
@@ -1047,7 +1049,7 @@ extern "C" int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const
 // ---------------------------------------------------------------------------------------------------------------
 #define ATT_UNR 4
 template <typename KT, int EPL, int GT>      // GT: lanes per key when known at compile time (head_dim 128), 0 = from kv.head_dim
-__global__ __launch_bounds__(1024) void attn_fused_kernel(const float* qkv, int64_t ld, int heads, vv_kv kv, int layer,
+__global__ __launch_bounds__(1024) void attn_fused_kernel(const float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer,
                                                          const float2* rope, const int* lens, float* out, int64_t ldo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int r = blockIdx.y, h = blockIdx.x;
@@ -1186,6 +1188,21 @@ extern "C" int vv_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads
   return vv_attn_decode_ws(qkv, ld_qkv, R, heads, kv, layer, rope_table, lens, out, ldo, nullptr, nullptr, 1, 1, stream);
 }
 
+extern "C" size_t vv_attn_decode_part_floats(int R, int heads, int part_cap) {
+  return (R <= 0 || heads <= 0 || part_cap <= 0) ? 0 : (size_t)R * heads * part_cap * 130;     // (m, l, O[128]) per (row, head, split), head_dim 128
+}
+
+extern "C" int vv_attn_decode_split(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table,
+                                    const int* lens, float* out, int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, vv_stream_t stream) {
+  if (!part || !tickets || nsplit < 1 || part_cap < nsplit) return vv_set_error(VV_E_ARG, "vv_attn_decode_split: part / tickets missing or part_cap < nsplit");
+  if (!kv || kv->head_dim != 128 || (kv->kvdt != VV_BF16 && kv->kvdt != VV_FP8)) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn_decode_split: bf16 or fp8 cache with head_dim 128 only");
+  return vv_attn_decode_ws(qkv, ld_qkv, R, heads, kv, layer, rope_table, lens, out, ldo, part, tickets, nsplit, part_cap, stream);
+}
+
+extern "C" int vv_kv_quantize(const vv_kv* src_bf16, const vv_kv* dst_fp8, int src_row, int dst_row, int len, int flags, vv_stream_t stream) {
+  return vv_launch_kv_quantize(src_bf16, dst_fp8, src_row, dst_row, len, flags, (hipStream_t)stream);
+}
+
 int vv_attn_decode_ws(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table, const int* lens, float* out,
                       int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, vv_stream_t stream) {
   const float2* inv_freq = reinterpret_cast<const float2*>(rope_table);
@@ -1201,6 +1218,7 @@ int vv_attn_decode_ws(const float* qkv, int64_t ld_qkv, int R, int heads, const 
     const int rc = vv_launch_attn_decode(qkv, ld_qkv, R, heads, kv, layer, inv_freq, lens, out, ldo, part, tickets, nsplit, part_cap, s);
     if (rc) return rc < 0 ? rc : 0;
   }
+  if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn_decode: kv dtype %d has no generic kernel", kv->kvdt);
   dim3 grid(heads, R);
   if (kv->kvdt == VV_F32) {
     if (d == 128) hipLaunchKernelGGL((attn_fused_kernel<float, 4, 32>), grid, dim3(1024), lds, s, qkv, ld_qkv, heads, *kv, layer, inv_freq, lens, out, ldo);

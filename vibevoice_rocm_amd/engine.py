@@ -32,18 +32,35 @@ from .weights import DeviceWeights
 _IDLE_STREAMS: Dict[str, list] = {}
 
 
+def check_kv_cache_dtype(kv_cache_dtype: Optional[str], dtype: torch.dtype, head_dim: int) -> bool:
+    """Validate the `kv_cache_dtype` option (None / "bf16": no effect at all - the cache stays in the compute dtype, fp32 arithmetic included; "fp8": e4m3 bytes with one power-of-two scale per
+    (layer, KV head), decode steps only).  Returns True for the fp8 cache.  Pure host logic: raises ValueError before anything touches a GPU."""
+    if kv_cache_dtype is None or kv_cache_dtype == "bf16":
+        return False
+    if kv_cache_dtype != "fp8":
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None, 'bf16' or 'fp8'")
+    if dtype != torch.bfloat16:
+        raise ValueError(f"kv_cache_dtype='fp8' needs torch_dtype=torch.bfloat16 (the fp8 decode attention widens codes to bf16), not {dtype}")
+    if head_dim != 128:
+        raise ValueError(f"kv_cache_dtype='fp8' needs head_dim 128 (the grouped-query matrix-core decode kernel), not {head_dim}")
+    return True
+
+
 class Engine:
     def __init__(self, cfg: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", dtype=torch.bfloat16,
                  kv_dtype: Optional[torch.dtype] = None, use_graphs: bool = True, bf16_timestep_quirk: Optional[bool] = None,
                  weight_quant: Optional[str] = None, stream: Optional[torch.cuda.Stream] = None, weights_from: Optional["Engine"] = None,
-                 prequant: Optional[dict] = None):
+                 prequant: Optional[dict] = None, kv_cache_dtype: Optional[str] = None):
+        self.kv_fp8 = check_kv_cache_dtype(kv_cache_dtype, dtype, cfg.head_dim)
         self.lib = L.load()
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.VVError("the VibeVoice MI355X engine needs a GPU device (there is no CPU path)")
         self.dtype = dtype
-        self.kv_dtype = kv_dtype or dtype
+        self.kv_dtype = kv_dtype or dtype     # kv_cache_dtype None / "bf16": exactly as without the option; "fp8": the dtype of the prompt's staging cache
+        if self.kv_fp8 and self.kv_dtype != torch.bfloat16:
+            raise ValueError("kv_cache_dtype='fp8' stages the prompt in a bf16 cache: kv_dtype must be bfloat16")
         self.use_graphs = use_graphs
         self.bf16_t_quirk = (dtype == torch.bfloat16) if bf16_timestep_quirk is None else bf16_timestep_quirk
         torch.cuda.set_device(self.device)
@@ -186,16 +203,22 @@ class Engine:
         with torch.cuda.stream(self.stream):
             if self.kv is None or self.kv.s_max < s_max:
                 shape = (cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim)
-                self._kv_t = (torch.zeros(shape, dtype=self.kv_dtype, device=self.device),
-                              torch.zeros(shape, dtype=self.kv_dtype, device=self.device))
+                cdt = torch.uint8 if self.kv_fp8 else self.kv_dtype        # fp8: e4m3fn codes, one byte per element, same shapes
+                self._kv_t = (torch.zeros(shape, dtype=cdt, device=self.device),
+                              torch.zeros(shape, dtype=cdt, device=self.device))
                 kv = L.KV()
                 kv.k, kv.v = self._kv_t[0].data_ptr(), self._kv_t[1].data_ptr()
-                if self.kv_dtype == torch.bfloat16 and cfg.head_dim == 128:
+                if self.kv_fp8:
+                    self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=cdt, device=self.device)
+                    self._kv_scale = torch.ones(2, cfg.layers, cfg.kv_heads, dtype=torch.float32, device=self.device)     # {k, v}: set by prefill
+                    kv.vt = self._kv_vt.data_ptr()
+                    kv.kscale, kv.vscale = self._kv_scale[0].data_ptr(), self._kv_scale[1].data_ptr()
+                elif self.kv_dtype == torch.bfloat16 and cfg.head_dim == 128:
                     # transposed value cache in 32-key tiles [.., s_max / 32, head_dim, 32] for the matrix-core attention kernels (kept in step
                     # with v by vv_rope_store for prompt rows and by vv_attn_decode for decode steps)
                     self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=self.kv_dtype, device=self.device)
                     kv.vt = self._kv_vt.data_ptr()
-                kv.kvdt = L.VV_F32 if self.kv_dtype == torch.float32 else L.VV_BF16
+                kv.kvdt = L.VV_FP8 if self.kv_fp8 else (L.VV_F32 if self.kv_dtype == torch.float32 else L.VV_BF16)
                 kv.layers, kv.rows, kv.kv_heads, kv.s_max, kv.head_dim = cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim
                 self.kv = kv
                 self._drop_graphs()
@@ -220,10 +243,10 @@ class Engine:
     # ---------------------------------------------------------------------------------------------------------
     # component launch sequences (all asynchronous on self.stream)
     # ---------------------------------------------------------------------------------------------------------
-    def llm_forward(self, x: torch.Tensor, lens: torch.Tensor, cache_rows: Optional[torch.Tensor], out: torch.Tensor):
+    def llm_forward(self, x: torch.Tensor, lens: torch.Tensor, cache_rows: Optional[torch.Tensor], out: torch.Tensor, kv=None):
         R = x.shape[0]
         self._ensure_llm_ws(R)
-        self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(self.kv), x.data_ptr(), x.stride(0), R, lens.data_ptr(),
+        self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(kv or self.kv), x.data_ptr(), x.stride(0), R, lens.data_ptr(),
                                          L.ptr(cache_rows), out.data_ptr(), out.stride(0), self._llm_ws.data_ptr(), self.sp),
                  "vv_llm_forward")
 
@@ -235,6 +258,14 @@ class Engine:
         one more row of the last chunk - cache row 1, position 0 - instead of a weight pass of its own (1.1 ms of the first chunk's latency);
         hidden2[1] then holds its state and the CALLER sets lens[1] = 1 if the branch is in use (`commit_negative_prompt`)."""
         L0 = embeds.shape[0]
+        kv, stage = None, None
+        if self.kv_fp8:
+            # fp8 KV cache: the prompt runs exactly as on a bf16 cache, on a bf16 staging cache sized to the prompt (rows 0 and 1: the negative
+            # branch's one-token prompt is a row of this prefill); its rows are then converted into the byte cache and the staging cache freed
+            if pos0 != 0 or row != 0:
+                raise L.VVError("kv_cache_dtype='fp8': the prompt is prefilled once, at position 0 of cache row 0 (prompt attention has no fp8-KV form)")
+            with torch.cuda.stream(self.stream):     # allocated, zeroed, used and freed on the engine's stream: the allocator reuses it in that stream's order
+                kv, stage = self._staging_kv(L0)
         n_chunks = max(1, -(-L0 // max(1, chunk)))
         size = -(-L0 // n_chunks)
         size = min(chunk, (size + 31) // 32 * 32) if n_chunks > 1 else L0
@@ -251,13 +282,32 @@ class Engine:
                     rows[-1] = 1
                     x = torch.cat([x, neg_embed.to(x.dtype).reshape(1, -1)])
                 out = torch.empty(x.shape[0], self.cfg.hidden, dtype=torch.float32, device=self.device)
-                self.llm_forward(x, lens, rows, out)
+                self.llm_forward(x, lens, rows, out, kv=kv)
+            if stage is not None:
+                # row 0 sets the scales of every (layer, KV head) from the prompt's K / V absmax; row 1 (the negative prompt) reuses them
+                self._ck(self.lib.vv_kv_quantize(C.byref(kv), C.byref(self.kv), 0, 0, L0, L.KVQ_DERIVE_SCALES, self.sp), "vv_kv_quantize")
+                self._ck(self.lib.vv_kv_quantize(C.byref(kv), C.byref(self.kv), 1, 1, 1 if neg_embed is not None else 0, 0, self.sp), "vv_kv_quantize")
+                del stage, kv         # back to the pool of the engine's stream, on which it was allocated (see above)
             if neg_embed is not None:
                 self.hidden2[row].copy_(out[-2])
                 self.hidden2[1].copy_(out[-1])
             else:
                 self.hidden2[row].copy_(out[-1])
             self.lens[row] = pos0 + L0
+
+    def _staging_kv(self, n_tokens: int):
+        """bf16 cache for a prompt of n_tokens (rounded up to the caches' 64-slot granule), rows {positive, negative}: (vv_kv, its tensors).
+        Call it under `torch.cuda.stream(self.stream)`: the tensors must belong to the stream that uses them."""
+        cfg = self.cfg
+        s_max = max(64, (int(n_tokens) + 63) // 64 * 64)
+        shape = (cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim)
+        t = (torch.zeros(shape, dtype=torch.bfloat16, device=self.device), torch.zeros(shape, dtype=torch.bfloat16, device=self.device),
+             torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=torch.bfloat16, device=self.device))
+        kv = L.KV()
+        kv.k, kv.v, kv.vt = t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr()
+        kv.kvdt = L.VV_BF16
+        kv.layers, kv.rows, kv.kv_heads, kv.s_max, kv.head_dim = cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim
+        return kv, t
 
     def commit_negative_prompt(self):
         """the negative branch consumed its one-token prompt (see prefill, neg_embed)"""

@@ -24,7 +24,7 @@ from . import _lib as L
 from . import batchloop
 from .batchloop import VibeVoiceGenerationOutput, _BatchCoupling      # noqa: F401  (public names of this module)
 from .config import VVConfig
-from .engine import Engine
+from .engine import Engine, check_kv_cache_dtype
 from .synth import state_dict_shapes
 
 LANES_IN_FLIGHT = 4       # lock-step batches: lanes (one HIP stream each) enqueued concurrently; see _LaneDriver
@@ -418,7 +418,13 @@ class _RowDriver:
 
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
-                 attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None):
+                 attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
+                 kv_cache_dtype: Optional[str] = None):
+        # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
+        # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
+        # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
+        check_kv_cache_dtype(kv_cache_dtype, torch.bfloat16 if prequant else torch_dtype, config.head_dim)
+        self.kv_cache_dtype = kv_cache_dtype
         # prequant: the NF4 matrices of a pre-quantized bitsandbytes checkpoint ({weight key: bnb.BnbNF4}, load_prequantized_dir); they run as
         # weight_quant="nf4" with bf16 compute, codes and scales taken as the file holds them
         shapes = state_dict_shapes(config)
@@ -444,7 +450,7 @@ class VibeVoiceForConditionalGenerationInference:
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
-                             prequant=prequant)
+                             prequant=prequant, kv_cache_dtype=kv_cache_dtype)
         self.device = self.engine.device
         # batches run in lock step on one Engine per sample (own HIP stream, KV cache and conv state; matrices already in the streamed
         # dtype on the device are shared, not copied): lanes beyond the first are built on first use from this state dict
@@ -491,7 +497,7 @@ class VibeVoiceForConditionalGenerationInference:
         if str(device) == "cuda":
             device = "cuda:0"
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
-                   use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None)
+                   use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -615,7 +621,7 @@ class VibeVoiceForConditionalGenerationInference:
                 raise NotImplementedError("refresh_negative=False is built for batch size 1 only")
             # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py), or one engine lane each
             rows = kwargs.get("row_batch", self.row_batch) and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and \
-                self.weight_quant in (None, "fp8")
+                self.weight_quant in (None, "fp8") and self.kv_cache_dtype != "fp8"      # fp8 KV: on the lanes (RowBatch needs a bf16 cache)
             driver = (_RowDriver if rows else _LaneDriver)(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"])
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
@@ -653,7 +659,7 @@ class VibeVoiceForConditionalGenerationInference:
     def _lane(self, b: int) -> Engine:
         while len(self._lanes) <= b:
             n = len(self._lanes)             # lanes past LANES_IN_FLIGHT share the stream of lane n % LANES_IN_FLIGHT: see _LaneDriver
-            eng = Engine(self.config, None, device=self.device, dtype=self.dtype, use_graphs=self._use_graphs, weight_quant=self.weight_quant,
+            eng = Engine(self.config, None, device=self.device, dtype=self.dtype, use_graphs=self._use_graphs, weight_quant=self.weight_quant, kv_cache_dtype=self.kv_cache_dtype,
                          stream=self._lanes[n % LANES_IN_FLIGHT].stream if n >= LANES_IN_FLIGHT else None, weights_from=self.engine)
             self._lanes.append(eng)
         eng = self._lanes[b]

@@ -61,8 +61,9 @@ class RowBatch:
         eng = self.main = lanes[0]
         self.lib, self.cfg, self.device, self.stream = eng.lib, eng.cfg, eng.device, (stream or eng.stream)
         self._on_main = [e.stream.cuda_stream == self.stream.cuda_stream for e in lanes]
-        if eng.dtype != torch.bfloat16 or eng.kv_dtype != torch.bfloat16 or eng.w.quant not in (None, "fp8"):
-            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions) and a bf16 KV cache")
+        if eng.dtype != torch.bfloat16 or eng.kv_dtype != torch.bfloat16 or getattr(eng, "kv_fp8", False) or eng.w.quant not in (None, "fp8"):
+            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions) and a bf16 KV cache "
+                            "(kv_cache_dtype='fp8' batches run on the lanes: the row-batched decode step has no fp8-KV form)")
         self.uid = next(_UID)
         cfg, H = self.cfg, self.cfg.hidden
         f32 = dict(dtype=torch.float32, device=self.device)
