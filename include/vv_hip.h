@@ -142,8 +142,12 @@ int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv,
 int vv_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table,
                    const int* lens, float* out, int64_t ldo, vv_stream_t stream);
 /* The same step with the cached keys of every row split over `nsplit` workgroups per (row, head), as vv_llm_forward runs it on long contexts:
- * part = vv_attn_decode_part_floats(R, heads, part_cap) floats of scratch, tickets = R * heads ints, zero on entry and left zero.  The grouped
- * kernel may use up to part_cap >= nsplit splits (vv_tune "attn_gqa_keys").  An fp8 cache (kvdt == VV_FP8) always runs the grouped kernel: the
+ * part = vv_attn_decode_part_floats(R, heads, part_cap) floats of scratch, tickets = R * heads ints, zero on entry and left zero.  The per-head
+ * kernel clamps nsplit to 16 splits of ceil(lens[r] / nsplit) keys.  The grouped kernel launches
+ * min(max(min(nsplit, 16), s_max / attn_gqa_keys), part_cap, 64) splits of whole 32-key tiles (vv_tune "attn_gqa_keys": cached keys per split, 1024
+ * unless tuned, at least 32), so it may use more than nsplit splits but never more than part_cap >= nsplit nor more than 64: its last workgroup
+ * folds at most 16 splits per thread quarter.  Either kernel writes one (m, l, O[128]) record per (row, head, launched split), empty splits
+ * included, and nothing else of part.  An fp8 cache (kvdt == VV_FP8) always runs the grouped kernel: the
  * new token's k (after RoPE) and v take part in the step at fp32, and are appended to k, v and vt as codes saturated to +-448 under the head's
  * scale. */
 size_t vv_attn_decode_part_floats(int R, int heads, int part_cap);

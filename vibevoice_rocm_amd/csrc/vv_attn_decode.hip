@@ -790,7 +790,7 @@ int vv_launch_kv_quantize(const vv_kv* src, const vv_kv* dst, int src_row, int d
 }
 
 void vv_attn_decode_set_gqa(int on) { g_gqa = on; }
-void vv_attn_decode_set_gqa_keys(int k) { if (k >= 256) g_gqa_keys = k; }
+void vv_attn_decode_set_gqa_keys(int k) { if (k >= 32) g_gqa_keys = k; }     // one 32-key tile is the kernel's split granularity
 
 #ifdef VV_CF_TIMING
 extern "C" int vv_attn_debug_times(unsigned long long* out8, int reset) {
