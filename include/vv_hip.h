@@ -259,6 +259,32 @@ int vv_llm_tail_batch(const vv_llm* m, const float* h, int64_t ldh, int B, float
                       float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
                       const int* active, vv_stream_t stream);
 
+/* do_sample on the device.  The reference draws the token with torch.multinomial(softmax(warped logits), 1) on the host
+ * (modeling_vibevoice_inference.py:491-494); on the CPU that is argmax_i(p_i / q_i) with q = empty_like(p).exponential_(1) from the same
+ * generator, and the draws q do not depend on the logits - so the host draws q BEFORE it enqueues the step and the device finishes the choice.
+ * For nv <= 8 constrained ids, in this order (the HF warpers' order):
+ *   1. z_i = double(logit_i) / temperature
+ *   2. top-k (0 < top_k < nv): every z_i below the k-th largest becomes -inf
+ *   3. top-p (top_p < 1): ascending stable sort, cum = cumsum(softmax(z)) in that order, entries with cum <= 1 - top_p become -inf; the
+ *      largest is never removed
+ *   4. p_i = float(softmax(z)_i), fp64 up to the cast (a masked id has p = 0)
+ *   5. token = ids[argmax_i(p_i / q_i)], the division and the comparison in fp32, first maximum in index order
+ * temperature > 0, 0 < top_p <= 1, top_k <= 0: no top-k.  q: nv fp32 values in device memory (exponential draws, > 0). */
+typedef struct vv_sampler { float temperature; int top_k; float top_p; } vv_sampler;
+/* vv_llm_tail with step 1-5 in place of the argmax.  *forced_token >= 0 still wins (q is then not read for the choice); out, logits_out and
+ * the position bookkeeping are those of vv_llm_tail called with the sampled token forced.  VV_E_ARG: temperature <= 0, top_p outside
+ * (0, 1], nv > 8, NULL sampler or q. */
+int vv_llm_tail_sample(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                       float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
+                       const vv_sampler* sampler, const float* q, vv_stream_t stream);
+/* vv_llm_tail_batch likewise: q[B][8], dialogue b reads q[b][0 .. nv). */
+int vv_llm_tail_batch_sample(const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                             float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                             int* frame_counter, const int* active, const vv_sampler* sampler, const float* q, vv_stream_t stream);
+/* vv_argmax_ids likewise (the first token after the prompt prefill): logits[n], n <= 8. */
+int vv_sample_ids(const float* logits, int n, const int* ids, const vv_sampler* sampler, const float* q, int* token_out, const int* forced_token,
+                  vv_stream_t stream);
+
 typedef struct vv_head_layer {
   const float* norm_w;
   const void* wgate;  /* [ffn, D] */

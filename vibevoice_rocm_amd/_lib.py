@@ -105,13 +105,17 @@ class Nf4Src(C.Structure):     # vv_nf4_src: one matrix of a pre-quantized bitsa
                 ("nested_blocksize", C.c_int), ("n", C.c_int), ("k", C.c_int), ("blocksize", C.c_int)]
 
 
+class Sampler(C.Structure):    # vv_sampler: the do_sample warpers of the device-side token draw (vv_llm_tail_sample, vv_sample_ids)
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("m", C.c_int), ("n", C.c_int), ("k", C.c_int), ("dual", C.c_int), ("wdt", C.c_int), ("count", C.c_int),
                 ("total_ms", C.c_double)]
 
 
 _STRUCTS = dict(vv_w8=W8, vv_prof_entry=ProfEntry, vv_lin_args=LinArgs, vv_kv=KV, vv_llm_layer=LlmLayer, vv_llm=Llm, vv_head_layer=HeadLayer, vv_head=Head,
-                vv_dpm_coef=DpmCoef, vv_block=Block, vv_conv=Conv, vv_convnet=ConvNet, vv_connector=Connector, vv_nf4_src=Nf4Src)
+                vv_dpm_coef=DpmCoef, vv_block=Block, vv_conv=Conv, vv_convnet=ConvNet, vv_connector=Connector, vv_nf4_src=Nf4Src, vv_sampler=Sampler)
 
 # name -> (restype, argtypes); every symbol include/vv_hip.h declares
 PROTOTYPES = {
@@ -149,6 +153,9 @@ PROTOTYPES = {
     "vv_llm_forward": (C.c_int, [C.POINTER(Llm), C.POINTER(KV), vp, i64, C.c_int, vp, vp, vp, i64, vp, vp]),
     "vv_llm_tail": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "vv_llm_tail_batch": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "vv_llm_tail_sample": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(Sampler), vp, vp]),
+    "vv_llm_tail_batch_sample": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(Sampler), vp, vp]),
+    "vv_sample_ids": (C.c_int, [vp, C.c_int, vp, C.POINTER(Sampler), vp, vp, vp, vp]),
     "vv_head_ws_bytes": (C.c_size_t, [C.POINTER(Head), C.c_int]),
     "vv_head_ws_bytes_batch": (C.c_size_t, [C.POINTER(Head), C.c_int, C.c_int]),
     "vv_head_sample_batch": (C.c_int, [C.POINTER(Head), vp, i64, vp, i64, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, i64, C.c_int, vp, vp]),

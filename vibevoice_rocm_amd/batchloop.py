@@ -16,7 +16,11 @@ a recording fake on a machine without a GPU (tests/test_host_cpu.py).  A driver 
   finished(b)                                the dialogue takes no more steps
   speech(rows)                               the frame of every dialogue in {dialogue: (noise row, SDE rows)}; all launches enqueued on return
   chunk(b) / stage_chunk(b) / take_chunk(b, slot)     the frame's samples (device), its copy to the host ring, the host samples
-  synchronize()"""
+  synchronize()
+
+do_sample on the device (BatchCall.sampler): the driver is told the warpers once (`set_sampler(temperature, top_k, top_p)`), sample_fn is None and
+first_tokens / decode get `q=` {dialogue: its exponential draws [nv]} for the live dialogues without a forced token; the token comes back
+like a greedy one."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -49,6 +53,7 @@ class BatchCall:
     stop_check_fn: Optional[Callable[[], bool]] = None
     verbose: bool = False
     sample_fn: Optional[Callable] = None
+    sampler: Optional[tuple] = None       # do_sample on the device: the warpers (temperature, top_k, top_p); sample_fn is None then
     speculate: bool = True                # frames may be launched before their token is known (never with sample_fn)
     return_speech: bool = True
     in_dev: object = "cpu"
@@ -58,6 +63,17 @@ def valid_token_ids(special: dict) -> List[int]:
     """the ids generation is constrained to (modeling_vibevoice_inference.py:53-66)"""
     return [special["speech_start"], special["speech_end"], special["speech_diffusion"], special["eos"]] + \
         ([special["bos"]] if special.get("bos") is not None else [])
+
+
+def sampler_params(gen_cfg: dict) -> tuple:
+    """(temperature, top_k, top_p) as modeling._make_sampler reads them from a generation_config dict"""
+    return (float(gen_cfg.get("temperature", 1.0) or 1.0), int(gen_cfg.get("top_k", 0) or 0), float(gen_cfg.get("top_p", 1.0) or 1.0))
+
+
+def draw_q(nv: int) -> torch.Tensor:
+    """The draws torch.multinomial(p, 1) makes on the CPU for nv probabilities - q = empty_like(p).exponential_(1), token = argmax(p / q) - from
+    the default generator, which is left where multinomial leaves it.  They do not depend on p: the device finishes the choice (vv_sampler)."""
+    return torch.empty(nv, dtype=torch.float32).exponential_(1)
 
 
 def limits(max_pos: int, prompt_len: int, max_new_tokens: Optional[int], max_length_times: float):
@@ -156,6 +172,11 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
     pending = []                      # (sample, ring slot) of chunks not yet handed to the streamer
     ours = [False] * max(B, getattr(streamer, "batch_size", B) if streamer is not None else B)   # streams ended by this loop
     speculate = call.speculate and sample_fn is None
+    nv = len(set(valid_token_ids(special)))
+    if call.sampler is not None:
+        if sample_fn is not None:
+            raise ValueError("BatchCall: sampler (device) and sample_fn (host) exclude each other")
+        driver.set_sampler(*call.sampler)
     coupling = _BatchCoupling(B, ST, SD)
 
     def deliver():
@@ -191,15 +212,18 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
             break
         live = [b for b in range(B) if not finished[b]]
         forced = {b: (ftok[b][step] if (ftok[b] is not None and step < len(ftok[b])) else None) for b in live}
+        # device-side do_sample: one exponential_ per live dialogue without a forced token, in ascending order - where the host sampler's
+        # multinomial draws them.  Batches speculate with injected noise only, so no other draw can come between these and the token
+        kw = {} if call.sampler is None else dict(q={b: draw_q(nv) for b in live if forced[b] is None})
         if step == 0:
-            toks, speculated = driver.first_tokens(live, forced, sample_fn), set()
+            toks, speculated = driver.first_tokens(live, forced, sample_fn, **kw), set()
         else:
             # a dialogue in its steady state may get its diffusion tail enqueued speculatively behind its LLM step when its noise is injected
             # (drawn noise depends on how many samples diffuse in this step, which is only known once the tokens are)
             eligible = {b: (nz[b][frame[b]], snz[b][frame[b]] if sde else None) for b in live
                         if speculate and prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
                         (not sde or (snz[b] is not None and frame[b] < len(snz[b])))}
-            toks, speculated = driver.decode(live, forced, eligible, sample_fn, deliver)
+            toks, speculated = driver.decode(live, forced, eligible, sample_fn, deliver, **kw)
         going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
         replace, restart = coupling.step(toks, going)
         for b in replace:

@@ -134,6 +134,72 @@ __device__ __forceinline__ float vv_gelu_as(float v) {
   return 0.5f * v * (1.0f + copysignf(erf_abs, x));
 }
 
+// do_sample token choice over nv <= 8 constrained logits (vv_hip.h, vv_sampler: the arithmetic and its order): index of the chosen id.
+// One thread; every array index is a compile-time constant after unrolling, so the eight values stay in registers (no scratch): ranks by
+// counting instead of a sort - rank_i = #{j : z_j < z_i, or z_j == z_i and j < i} is i's place in the ascending stable sort - and the walk
+// over the sorted order as a select per place.  Entries i >= nv ride along as masked ones at the bottom of the order.
+__device__ __forceinline__ int vv_sample_choice(const float (&l)[8], int nv, const vv_sampler sp, const float (&q)[8]) {
+  constexpr int NV = 8;
+  const double ninf = -__builtin_huge_val();
+  const double T = (double)sp.temperature;
+  double z[NV], e[NV];
+  bool keep[NV];
+  int rank[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) { keep[i] = i < nv; z[i] = keep[i] ? (double)l[i] / T : ninf; }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    int r = 0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) r += (j != i && (z[j] < z[i] || (z[j] == z[i] && j < i))) ? 1 : 0;
+    rank[i] = r;
+  }
+  double zmax = ninf;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) if (rank[i] == NV - 1) zmax = z[i];
+  if (sp.top_k > 0 && sp.top_k < nv) {
+    double kth = ninf;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) if (rank[i] == NV - sp.top_k) kth = z[i];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) keep[i] = keep[i] && !(z[i] < kth);
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) e[i] = keep[i] ? exp(z[i] - zmax) : 0.0;
+  if (sp.top_p < 1.f) {
+    const double thr = 1.0 - (double)sp.top_p;
+    double S = 0.0, cum = 0.0;
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) if (rank[i] == r) S += e[i];
+    }
+#pragma unroll
+    for (int r = 0; r < NV - 1; ++r) {               // place NV - 1 holds the largest: never removed
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        if (rank[i] == r) {
+          cum += e[i] / S;
+          if (cum <= thr) keep[i] = false;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) if (!keep[i]) e[i] = 0.0;
+  }
+  double S = 0.0;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) S += e[i];
+  int best = 0;
+  float vbest = (float)(e[0] / S) / q[0];
+#pragma unroll
+  for (int i = 1; i < NV; ++i) {
+    const float v = (float)(e[i] / S) / q[i];
+    if (i < nv && v > vbest) { vbest = v; best = i; }
+  }
+  return best;
+}
+
 // Wave-wide (64 lanes) sum, result in every lane.  DPP row operations reduce each 16-lane row at VALU speed (4 dependent
 // v_add with a DPP operand), the four row sums are combined through readlane.  The usual __shfl_xor butterfly is six
 // dependent ds_bpermute round trips (~100+ cycles each): with one or two waves per SIMD, as in the weight-streaming

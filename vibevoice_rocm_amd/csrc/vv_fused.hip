@@ -230,10 +230,12 @@ template <int KU> void launch_boundary(const BoundaryArgs& a, int B, hipStream_t
 // ---------------------------------------------------------------------------------------------------------------
 // LLM step tail
 // ---------------------------------------------------------------------------------------------------------------
-template <typename WT>
+// SAMPLE: the token is drawn (vv_sampler, vv_hip.h: warpers + argmax p / q over the host's exponential draws q) instead of the argmax; the
+// argmax instantiation is the code it was.
+template <typename WT, bool SAMPLE>
 __global__ __launch_bounds__(256) void llm_tail_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out, int64_t ldo,
                                                        const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out, const int* forced,
-                                                       int* lens, int tok_start, int tok_diff, int* frame_ctr) {
+                                                       int* lens, int tok_start, int tok_diff, int* frame_ctr, const vv_sampler smp, const float* q) {
   extern __shared__ float hn0[];          // [H] normalised row 0 (the positive branch: the only row logits are taken from)
   __shared__ float red[4];
   __shared__ float lg[16];
@@ -264,8 +266,15 @@ __global__ __launch_bounds__(256) void llm_tail_kernel(const float* h, int64_t l
   __syncthreads();
   if (tid == 0) {
     int best = 0;
+    if constexpr (SAMPLE) {
+      float l8[8], q8[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { l8[i] = i < nv ? lg[i] : 0.f; q8[i] = i < nv ? q[i] : 1.f; }
+      best = vv_sample_choice(l8, nv, smp, q8);
+    } else {
     for (int i = 1; i < nv; ++i)
       if (lg[i] > lg[best] || (lg[i] == lg[best] && ids[i] < ids[best])) best = i;     // first maximum in ascending id order, as torch.argmax over the masked vocabulary
+    }
     const int f = forced ? *forced : -1;
     const int t = f >= 0 ? f : ids[best];
     *token_out = t;
@@ -281,10 +290,13 @@ __global__ __launch_bounds__(256) void llm_tail_kernel(const float* h, int64_t l
 // The decode shape (R <= 2 rows, <= 8 constrained ids, H <= 4096): every operand - the rows, the norm weight, this thread's 4-column
 // slices of the constrained vocabulary rows, ids, forced token - is requested in one burst, then two barriers: row statistics,
 // logit partials.  The general kernel above walks rows and vocabulary rows one after the other (5-6 dependent trips, 21 us).
-template <typename WT>
+// SAMPLE as above; the draws q ([8] per block) are requested by thread 0 with the other operands, the choice runs in thread 0 alone behind the
+// last barrier, where the argmax ran.
+template <typename WT, bool SAMPLE>
 __global__ __launch_bounds__(256) void llm_tail_fast_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out, int64_t ldo,
                                                             const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out, const int* forced,
-                                                            int* lens, int tok_start, int tok_diff, int* frame_ctr, const int* active) {
+                                                            int* lens, int tok_start, int tok_diff, int* frame_ctr, const int* active,
+                                                            const vv_sampler smp, const float* q) {
   {   // dialogues of a row-batched step: block b owns rows 2 b, 2 b + 1 and the b-th token / forced token / counters
     const int b = blockIdx.x;
     h += (int64_t)2 * b * ldh; out += (int64_t)2 * b * ldo; logits_out += 8 * b; token_out += b;
@@ -292,6 +304,7 @@ __global__ __launch_bounds__(256) void llm_tail_fast_kernel(const float* h, int6
     if (lens) lens += 2 * b;
     if (frame_ctr) frame_ctr += b;
     if (active) active += b;
+    if constexpr (SAMPLE) q += 8 * b;
   }
   constexpr int NC = 4, NV = 8;                    // column chunks (of 4) per thread per row, constrained ids
   __shared__ float red[4][2];
@@ -322,6 +335,11 @@ __global__ __launch_bounds__(256) void llm_tail_fast_kernel(const float* h, int6
   for (int i = 0; i < NV; ++i) idv[i] = ids[i < nv ? i : 0];
   const int fv = forced ? *forced : -1;
   const int live = active ? *active : 1;
+  float qv[NV];
+  if constexpr (SAMPLE) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) qv[i] = (tid == 0 && i < nv) ? q[i] : 1.f;
+  }
   const int l0 = lens ? lens[0] : 0, l1 = lens ? lens[1] : 0, fc = frame_ctr ? *frame_ctr : 0;
   float ss[2] = {0.f, 0.f};
 #pragma unroll
@@ -367,7 +385,14 @@ __global__ __launch_bounds__(256) void llm_tail_fast_kernel(const float* h, int6
     for (int i = 0; i < nv; ++i) {
       l[i] = (lgp[0][i] + lgp[1][i]) + (lgp[2][i] + lgp[3][i]);
       logits_out[i] = l[i];
-      if (i && (l[i] > l[best] || (l[i] == l[best] && idv[i] < idv[best]))) best = i;
+      if (!SAMPLE && i && (l[i] > l[best] || (l[i] == l[best] && idv[i] < idv[best]))) best = i;
+    }
+    if constexpr (SAMPLE) {
+      if (fv < 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) if (i >= nv) l[i] = 0.f;
+        best = vv_sample_choice(l, nv, smp, qv);
+      }
     }
     const int t = fv >= 0 ? fv : idv[best];
     *token_out = t;
@@ -861,33 +886,73 @@ int vv_head_boundary_batch(const vv_head* h, const float* hrows, int64_t ldh, co
   return 0;
 }
 
+// The argmax (smp == nullptr) and the sampling form of the step tail share the argument checks and the kernel choice.
+static int check_sampler(const char* name, const vv_sampler* smp, const float* q, int nv) {
+  if (!smp || !q) return vv_set_error(VV_E_ARG, "%s: null sampler / q", name);
+  if (!(smp->temperature > 0.f) || !(smp->top_p > 0.f && smp->top_p <= 1.f)) return vv_set_error(VV_E_ARG, "%s: temperature=%g (> 0) top_p=%g (0 < top_p <= 1)", name, (double)smp->temperature, (double)smp->top_p);
+  if (nv > 8) return vv_set_error(VV_E_ARG, "%s: nv=%d (<= 8)", name, nv);
+  return 0;
+}
+
+#define VV_TAIL_FAST(WT, SAMPLE, grid, R_, act)                                                                                                          \
+  hipLaunchKernelGGL((llm_tail_fast_kernel<WT, SAMPLE>), dim3(grid), dim3(256), 0, s, h, ldh, R_, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const WT*)w_valid, nv, \
+                     ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, act, sv, q)
+#define VV_TAIL_GEN(WT, SAMPLE)                                                                                                                         \
+  hipLaunchKernelGGL((llm_tail_kernel<WT, SAMPLE>), dim3(1), dim3(256), lds, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const WT*)w_valid, nv, ids, \
+                     logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, sv, q)
+
+static int llm_tail_launch(const char* name, const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                           float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
+                           const vv_sampler* smp, const float* q, hipStream_t s) {
+  const vv_sampler sv = smp ? *smp : vv_sampler{1.f, 0, 1.f};
+  const size_t lds = (size_t)m->hidden * sizeof(float);
+  auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
+  if (R <= 2 && nv <= 8 && m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
+      ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0 && (m->wdt == VV_F32 || m->hidden % 4 == 0)) {
+    if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, 1, R, (const int*)nullptr); else VV_TAIL_FAST(float, false, 1, R, (const int*)nullptr); }
+    else { if (smp) VV_TAIL_FAST(bf16_t, true, 1, R, (const int*)nullptr); else VV_TAIL_FAST(bf16_t, false, 1, R, (const int*)nullptr); }
+    VV_CHECK_LAUNCH(name);
+    return 0;
+  }
+  if (m->wdt == VV_F32) { if (smp) VV_TAIL_GEN(float, true); else VV_TAIL_GEN(float, false); }
+  else { if (smp) VV_TAIL_GEN(bf16_t, true); else VV_TAIL_GEN(bf16_t, false); }
+  VV_CHECK_LAUNCH(name);
+  return 0;
+}
+
+static int llm_tail_batch_launch(const char* name, const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv,
+                                 const int* ids, float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                                 int* frame_counter, const int* active, const vv_sampler* smp, const float* q, hipStream_t s) {
+  const vv_sampler sv = smp ? *smp : vv_sampler{1.f, 0, 1.f};
+  auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
+  if (!(m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
+        ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0))
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: hidden=%d / alignment not covered", name, m->hidden);
+  if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, B, 2, active); else VV_TAIL_FAST(float, false, B, 2, active); }
+  else { if (smp) VV_TAIL_FAST(bf16_t, true, B, 2, active); else VV_TAIL_FAST(bf16_t, false, B, 2, active); }
+  VV_CHECK_LAUNCH(name);
+  return 0;
+}
+#undef VV_TAIL_FAST
+#undef VV_TAIL_GEN
+
 extern "C" int vv_llm_tail(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
                            float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
                            int* frame_counter, vv_stream_t stream) {
   if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail: null pointer");
   if (R <= 0 || nv <= 0 || nv > 16) return vv_set_error(VV_E_ARG, "vv_llm_tail: R=%d nv=%d (nv <= 16)", R, nv);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = (size_t)m->hidden * sizeof(float);
-  auto a16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-  if (R <= 2 && nv <= 8 && m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
-      ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0 && (m->wdt == VV_F32 || m->hidden % 4 == 0)) {
-    if (m->wdt == VV_F32)
-      hipLaunchKernelGGL((llm_tail_fast_kernel<float>), dim3(1), dim3(256), 0, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const float*)w_valid, nv,
-                         ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, (const int*)nullptr);
-    else
-      hipLaunchKernelGGL((llm_tail_fast_kernel<bf16_t>), dim3(1), dim3(256), 0, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const bf16_t*)w_valid,
-                         nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, (const int*)nullptr);
-    VV_CHECK_LAUNCH("vv_llm_tail");
-    return 0;
-  }
-  if (m->wdt == VV_F32)
-    hipLaunchKernelGGL((llm_tail_kernel<float>), dim3(1), dim3(256), lds, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const float*)w_valid, nv, ids,
-                       logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter);
-  else
-    hipLaunchKernelGGL((llm_tail_kernel<bf16_t>), dim3(1), dim3(256), lds, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const bf16_t*)w_valid, nv, ids,
-                       logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter);
-  VV_CHECK_LAUNCH("vv_llm_tail");
-  return 0;
+  return llm_tail_launch("vv_llm_tail", m, h, ldh, R, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter,
+                         nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vv_llm_tail_sample(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                                  float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                                  int* frame_counter, const vv_sampler* sampler, const float* q, vv_stream_t stream) {
+  if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_sample: null pointer");
+  if (R <= 0 || nv <= 0) return vv_set_error(VV_E_ARG, "vv_llm_tail_sample: R=%d nv=%d", R, nv);
+  VV_TRY(check_sampler("vv_llm_tail_sample", sampler, q, nv));
+  return llm_tail_launch("vv_llm_tail_sample", m, h, ldh, R, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion,
+                         frame_counter, sampler, q, (hipStream_t)stream);
 }
 
 // The tail of a row-batched decode step (B dialogues, rows {positive, negative} x B): block b does what vv_llm_tail does for dialogue b.
@@ -896,19 +961,18 @@ extern "C" int vv_llm_tail_batch(const vv_llm* m, const float* h, int64_t ldh, i
                                  int* frame_counter, const int* active, vv_stream_t stream) {
   if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch: null pointer");
   if (B <= 0 || B > 4 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch: B=%d (1..4) nv=%d (<= 8)", B, nv);
-  auto a16 = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-  if (!(m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
-        ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0))
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_llm_tail_batch: hidden=%d / alignment not covered", m->hidden);
-  hipStream_t s = (hipStream_t)stream;
-  if (m->wdt == VV_F32)
-    hipLaunchKernelGGL((llm_tail_fast_kernel<float>), dim3(B), dim3(256), 0, s, h, ldh, 2, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const float*)w_valid, nv,
-                       ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, active);
-  else
-    hipLaunchKernelGGL((llm_tail_fast_kernel<bf16_t>), dim3(B), dim3(256), 0, s, h, ldh, 2, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const bf16_t*)w_valid,
-                       nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, active);
-  VV_CHECK_LAUNCH("vv_llm_tail_batch");
-  return 0;
+  return llm_tail_batch_launch("vv_llm_tail_batch", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion,
+                               frame_counter, active, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vv_llm_tail_batch_sample(const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                                        float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                                        int* frame_counter, const int* active, const vv_sampler* sampler, const float* q, vv_stream_t stream) {
+  if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample: null pointer");
+  if (B <= 0 || B > 4 || nv <= 0) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample: B=%d (1..4) nv=%d", B, nv);
+  VV_TRY(check_sampler("vv_llm_tail_batch_sample", sampler, q, nv));
+  return llm_tail_batch_launch("vv_llm_tail_batch_sample", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start,
+                               tok_diffusion, frame_counter, active, sampler, q, (hipStream_t)stream);
 }
 
 int vv_conv_ctx_batch(const vv_conv_ctx_item* items, int n, int scatter, hipStream_t s) {

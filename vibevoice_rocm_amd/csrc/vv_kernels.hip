@@ -1633,6 +1633,27 @@ extern "C" int vv_argmax_ids(const float* logits, int n, const int* ids, int* to
   return 0;
 }
 
+// the sampling sibling of argmax_ids_kernel (vv_sampler, vv_hip.h): the first token after the prompt prefill under do_sample
+__global__ void sample_ids_kernel(const float* logits, int n, const int* ids, const vv_sampler smp, const float* q, int* token_out, const int* forced) {
+  if (threadIdx.x == 0) {
+    const int f = forced ? *forced : -1;
+    if (f >= 0) { *token_out = f; return; }
+    float l8[8], q8[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { l8[i] = i < n ? logits[i] : 0.f; q8[i] = i < n ? q[i] : 1.f; }
+    *token_out = ids[vv_sample_choice(l8, n, smp, q8)];
+  }
+}
+extern "C" int vv_sample_ids(const float* logits, int n, const int* ids, const vv_sampler* sampler, const float* q, int* token_out, const int* forced_token,
+                             vv_stream_t stream) {
+  if (!logits || !ids || !token_out || n <= 0) return vv_set_error(VV_E_ARG, "vv_sample_ids: bad args");
+  if (!sampler || !q || n > 8 || !(sampler->temperature > 0.f) || !(sampler->top_p > 0.f && sampler->top_p <= 1.f))
+    return vv_set_error(VV_E_ARG, "vv_sample_ids: sampler / q / n=%d (<= 8), temperature > 0, 0 < top_p <= 1", n);
+  hipLaunchKernelGGL(sample_ids_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, logits, n, ids, *sampler, q, token_out, forced_token);
+  VV_CHECK_LAUNCH("vv_sample_ids");
+  return 0;
+}
+
 __global__ void dpm_step_kernel(const float* v, int64_t ldv, int ns, int latent, float cfg, float alpha_s, float sigma_s, float cx,
                                 float cd, float rinv, int order, float* x, float* m_prev) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

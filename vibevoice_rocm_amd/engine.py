@@ -94,12 +94,16 @@ class Engine:
             self.sem = torch.zeros(cfg.sem_dim, **f32)
             self.conn_ws = torch.zeros(8 * H, **f32)
             self.logits = torch.zeros(8, **f32)
+            self.q_dev = torch.ones(8, **f32)             # device-side do_sample: the step's exponential draws, one per constrained id
         self.token_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.logits_host = torch.zeros(8, dtype=torch.float32).pin_memory()
         self.forced_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
         self._forced_dev_val = -1                         # what forced_dev holds (see _set_forced)
         self.noise_host = torch.zeros(2, cfg.latent, dtype=torch.float32).pin_memory()   # double-buffered: the host runs a frame ahead
         self._noise_k = 0
+        self.q_host = torch.ones(2, 8, dtype=torch.float32).pin_memory()                 # double-buffered like the noise rows
+        self._q_k = 0
+        self._sampler, self._sampler_key = None, None     # set_sampler
         self._tok_event = torch.cuda.Event()
         # streaming delivery: a frame's 3200 samples go device -> pinned ring asynchronously, an event per
         # slot says when the host may hand them to the AudioStreamer; generate() never blocks the launch queue on a D2H copy
@@ -343,6 +347,19 @@ class Engine:
                                       self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.sp),
                  "vv_llm_tail")
 
+    def _seq_AS(self, tok_start, tok_diff, temperature, top_k, top_p):
+        """_seq_A with the sampling tail: the token is drawn on the device from the warped constrained logits and the host's exponential
+        draws in q_dev (vv_llm_tail_sample).  The warpers are kernel arguments, i.e. part of the captured graph: they are part of its key
+        (_run), a call with other warpers captures a graph of its own."""
+        nv = len(self.valid_ids)
+        smp = L.Sampler(temperature, top_k, top_p)
+        self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(self.kv), self.x2.data_ptr(), self.cfg.hidden, 2,
+                                         self.lens.data_ptr(), None, None, 0, self._llm_ws.data_ptr(), self.sp), "vv_llm_forward")
+        self._ck(self.lib.vv_llm_tail_sample(C.byref(self.w.llm), self._llm_ws.data_ptr(), self.cfg.hidden, 2, self.hidden2.data_ptr(), self.cfg.hidden,
+                                             self._w_valid.data_ptr(), nv, self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(),
+                                             self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(),
+                                             C.byref(smp), self.q_dev.data_ptr(), self.sp), "vv_llm_tail_sample")
+
     def _seq_A1(self):
         self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(self.kv), self.x2.data_ptr(), self.cfg.hidden, 2,
                                          self.lens.data_ptr(), None, self.hidden2.data_ptr(), self.cfg.hidden,
@@ -444,15 +461,38 @@ class Engine:
         self.forced_dev.copy_(self.forced_host, non_blocking=True)
         self._forced_dev_val = v
 
+    def set_sampler(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        """The warpers of the device-side token draw (steps given `q`), fixed per generate() call."""
+        self._sampler_key = (float(temperature), int(top_k), float(top_p))
+        self._sampler = L.Sampler(*self._sampler_key)
+
+    def _upload_q(self, q: torch.Tensor):
+        """The step's exponential draws (CPU fp32 [nv]): pinned staging row + async copy on the engine stream, like _upload_noise."""
+        if self._sampler is None:
+            raise L.VVError("device-side sampling needs set_sampler() first")
+        self._q_k ^= 1
+        qh = self.q_host[self._q_k]
+        qh[: q.numel()].copy_(q.reshape(-1))
+        self.q_dev.copy_(qh, non_blocking=True)
+
+    def _phase_A(self, tok_start: int, tok_diff: int, q: Optional[torch.Tensor]):
+        """graph A; with draws `q` its sampling variant"""
+        if q is None:
+            self._run("A", self._seq_A, int(tok_start), int(tok_diff))
+        else:
+            self._upload_q(q)
+            self._run("AS", self._seq_AS, int(tok_start), int(tok_diff), *self._sampler_key)
+
     def _host_logits(self) -> torch.Tensor:
         with torch.cuda.stream(self.stream):
             self.logits_host.copy_(self.logits, non_blocking=True)
         self.stream.synchronize()
         return self.logits_host[: len(self.valid_ids)].clone()
 
-    def step_decode(self, tok_start: int, tok_diff: int, forced: Optional[int] = None, sample_fn=None, on_enqueued=None) -> int:
-        """Phase A + the frame's only host sync: returns the chosen token.  With `sample_fn(logits, ids) -> token` (do_sample)
-        the constrained logits are read back first and the sampled token is fed to the device-side bookkeeping."""
+    def step_decode(self, tok_start: int, tok_diff: int, forced: Optional[int] = None, sample_fn=None, on_enqueued=None, q=None) -> int:
+        """Phase A + the frame's only host sync: returns the chosen token.  With `sample_fn(logits, ids) -> token` (do_sample, host sampler)
+        the constrained logits are read back first and the sampled token is fed to the device-side bookkeeping.  With `q` (do_sample,
+        device sampler: the step's exponential draws [nv], set_sampler) the token is drawn inside graph A: one graph, one 4-byte read-back."""
         if sample_fn is not None and forced is None:
             with torch.cuda.stream(self.stream):
                 self._run("A1", self._seq_A1)
@@ -464,15 +504,25 @@ class Engine:
             return tok
         with torch.cuda.stream(self.stream):
             self._set_forced(forced)
-            self._run("A", self._seq_A, int(tok_start), int(tok_diff))
+            self._phase_A(tok_start, tok_diff, q)
             self.token_host.copy_(self.token_dev, non_blocking=True)
         if on_enqueued is not None:
             on_enqueued()
         self.stream.synchronize()
         return int(self.token_host[0])
 
-    def first_token(self, tok_start: int, tok_diff: int, forced: Optional[int] = None, sample_fn=None) -> int:
-        """Token selection right after prefill (hidden2[0] already holds the last prompt state)."""
+    def first_token(self, tok_start: int, tok_diff: int, forced: Optional[int] = None, sample_fn=None, q=None) -> int:
+        """Token selection right after prefill (hidden2[0] already holds the last prompt state); `q`: drawn on the device (step_decode)."""
+        if q is not None and forced is None:
+            with torch.cuda.stream(self.stream):
+                self._set_forced(None)
+                self._upload_q(q)
+                self._logits()
+                self._ck(self.lib.vv_sample_ids(self.logits.data_ptr(), len(self.valid_ids), self._ids_dev.data_ptr(), C.byref(self._sampler),
+                                                self.q_dev.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(), self.sp), "vv_sample_ids")
+                self.token_host.copy_(self.token_dev, non_blocking=True)
+            self.stream.synchronize()
+            return int(self.token_host[0])
         if sample_fn is not None and forced is None:
             with torch.cuda.stream(self.stream):
                 self._logits()
@@ -506,14 +556,14 @@ class Engine:
             return self._speech(float(self.cfg_scale), stage)
 
     def step_decode_speculative(self, tok_start: int, tok_diff: int, forced: Optional[int], noise: torch.Tensor,
-                                sde_noise: Optional[torch.Tensor] = None, on_enqueued=None, stage: bool = False) -> int:
+                                sde_noise: Optional[torch.Tensor] = None, on_enqueued=None, stage: bool = False, q=None) -> int:
         """Phase A, then phase B enqueued right behind it ON THE ASSUMPTION that the token is speech_diffusion (the steady state
         of a dialogue), then one host wait on the token alone.  The GPU therefore never idles between A and B while the host
         wakes up and decides; if the token turns out to be something else the caller rolls the speech state back
         (`rollback_speech_state`) - phase B touches nothing else that survives (x2 is rewritten by the embed phase)."""
         with torch.cuda.stream(self.stream):
             self._set_forced(forced)
-            self._run("A", self._seq_A, int(tok_start), int(tok_diff))
+            self._phase_A(tok_start, tok_diff, q)
             self.token_host.copy_(self.token_dev, non_blocking=True)
             self._tok_event.record(self.stream)
             self._upload_noise(noise, sde_noise)
@@ -531,12 +581,12 @@ class Engine:
         except Exception:      # noqa: BLE001  (interpreter shutdown)
             pass
 
-    def decode_begin(self, tok_start: int, tok_diff: int, forced: Optional[int], spec_noise=None):
+    def decode_begin(self, tok_start: int, tok_diff: int, forced: Optional[int], spec_noise=None, q=None):
         """Lock-step batches (one Engine per sample, one host loop): enqueue phase A - and, with `spec_noise` = (noise, sde_noise), the
-        speculative phase B behind it - without waiting; `decode_end` returns the token."""
+        speculative phase B behind it - without waiting; `decode_end` returns the token.  `q`: the token is drawn on the device (step_decode)."""
         with torch.cuda.stream(self.stream):
             self._set_forced(forced)
-            self._run("A", self._seq_A, int(tok_start), int(tok_diff))
+            self._phase_A(tok_start, tok_diff, q)
             self.token_host.copy_(self.token_dev, non_blocking=True)
             self._tok_event.record(self.stream)
             if spec_noise is not None:

@@ -152,15 +152,13 @@ def _copy_kv_slot(k: torch.Tensor, v: torch.Tensor, vt: Optional[torch.Tensor], 
         vt[:, row, :, dst // 32, :, dst % 32].copy_(vt[:, row, :, src // 32, :, src % 32])
 
 
-def _make_sampler(gen_cfg: dict):
-    """do_sample path (modeling_vibevoice_inference.py:491-494): softmax over the constrained logits + multinomial, with the
-    HF warpers the reference's callers configure (temperature, top_k, top_p; main.py:1187-1196) applied in HF order.
-    Runs on the host over the 4-5 valid logits; draws from torch's CPU generator."""
-    temperature = float(gen_cfg.get("temperature", 1.0) or 1.0)
-    top_k = int(gen_cfg.get("top_k", 0) or 0)
-    top_p = float(gen_cfg.get("top_p", 1.0) or 1.0)
+def _warped_probs(gen_cfg: dict):
+    """logits -> fp32 probabilities of the do_sample path (modeling_vibevoice_inference.py:491-494): the HF warpers the reference's callers
+    configure (temperature, top_k, top_p; main.py:1187-1196) in HF order, softmax in fp64.  The device-side sampler (vv_sampler in
+    include/vv_hip.h) restates exactly this arithmetic."""
+    temperature, top_k, top_p = batchloop.sampler_params(gen_cfg)
 
-    def sample(logits: torch.Tensor, ids):
+    def probs(logits: torch.Tensor) -> torch.Tensor:
         z = logits.double() / temperature
         if 0 < top_k < z.numel():
             kth = torch.topk(z, top_k).values[-1]
@@ -171,8 +169,16 @@ def _make_sampler(gen_cfg: dict):
             remove = cum <= (1 - top_p)
             remove[-1] = False
             z[order[remove]] = float("-inf")
-        p = torch.softmax(z, -1)
-        return ids[int(torch.multinomial(p.float(), 1))]
+        return torch.softmax(z, -1).float()
+    return probs
+
+
+def _make_sampler(gen_cfg: dict):
+    """do_sample path on the host: the warped probabilities of the 4-5 valid logits (_warped_probs) + multinomial from torch's CPU generator."""
+    probs = _warped_probs(gen_cfg)
+
+    def sample(logits: torch.Tensor, ids):
+        return ids[int(torch.multinomial(probs(logits), 1))]
     return sample
 
 
@@ -211,18 +217,22 @@ class _LaneDriver:
             eng.begin_sequence(len(ids) + max(max_steps, 1) + 8, valid)
             self.x0.append(_embed_prompt(eng, ids, voice, after=self.model.engine.stream))     # conn_all was produced on lane 0's stream
 
-    def first_tokens(self, live, forced, sample_fn):
+    def set_sampler(self, temperature, top_k, top_p):
+        for e in self.lanes:
+            e.set_sampler(temperature, top_k, top_p)
+
+    def first_tokens(self, live, forced, sample_fn, q=None):
         lanes, toks = self.lanes, {}
         for b in live:
             lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])))
         for b in live:
-            toks[b] = lanes[b].first_token(self.ST, self.SD, forced[b], sample_fn)
+            toks[b] = lanes[b].first_token(self.ST, self.SD, forced[b], sample_fn, q=(q or {}).get(b))
             if toks[b] == self.SD:
                 lanes[b].commit_negative_prompt()
         return toks
 
-    def decode(self, live, forced, eligible, sample_fn, deliver):
-        lanes = self.lanes
+    def decode(self, live, forced, eligible, sample_fn, deliver, q=None):
+        lanes, q = self.lanes, q or {}
         if sample_fn is not None:
             deliver()                  # step_decode waits inside: the previous step's chunks go out ahead of it
             return {b: lanes[b].step_decode(self.ST, self.SD, forced[b], sample_fn) for b in live}, set()
@@ -234,7 +244,7 @@ class _LaneDriver:
         def begin(s_):
             for b in live:
                 if b % LANES_IN_FLIGHT == s_:
-                    lanes[b].decode_begin(self.ST, self.SD, forced[b], eligible.get(b))
+                    lanes[b].decode_begin(self.ST, self.SD, forced[b], eligible.get(b), q=q.get(b))
         slots = sorted({b % LANES_IN_FLIGHT for b in live})
         if self.pool is not None and len(slots) > 1:
             list(self.pool.map(begin, slots))
@@ -321,20 +331,24 @@ class _RowDriver:
             off += n
         self.x0 = [_embed_prompt(self.main, ids, voice) for ids, voice in zip(prompts, voices)]
 
-    def first_tokens(self, live, forced, sample_fn):
+    def set_sampler(self, temperature, top_k, top_p):
+        for rb, _ in self.groups:
+            rb.set_sampler(temperature, top_k, top_p)
+
+    def first_tokens(self, live, forced, sample_fn, q=None):
         at, toks = self.at, {}
         st_embed = self.main.embed_ids(torch.tensor([self.ST]))
         for b in live:
             at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed)
         for b in live:
             rb, loc = at[b]
-            toks[b] = rb.first_token(loc, forced[b], sample_fn)
+            toks[b] = rb.first_token(loc, forced[b], sample_fn, q=(q or {}).get(b))
             if toks[b] == self.SD:
                 rb.commit_negative(loc)
         return toks
 
-    def decode(self, live, forced, eligible, sample_fn, deliver):
-        at, ST, SD = self.at, self.ST, self.SD
+    def decode(self, live, forced, eligible, sample_fn, deliver, q=None):
+        at, ST, SD, q = self.at, self.ST, self.SD, q or {}
         loc = {b: at[b][1] for b in live}
         plan = [(rb, [b for b in idxs if b in forced]) for rb, idxs in self.groups]
         plan = [(rb, lv) for rb, lv in plan if lv]
@@ -359,7 +373,7 @@ class _RowDriver:
         # sampling enqueued speculatively behind it.  The conv tails follow once all A / H are queued: each batch's tails are enqueued
         # when ITS sampler has finished (RowBatch.speech_tails) and run while the main stream works on the next batch
         for rb, lv in plan:
-            rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv})
+            rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv}, q={loc[b]: q[b] for b in lv if b in q})
             if all(b in eligible for b in lv):
                 rb.speech_begin([loc[b] for b in lv], {loc[b]: eligible[b][0] for b in lv}, {loc[b]: eligible[b][1] for b in lv} if self.sde else None)
                 speculated.update(lv)
@@ -419,7 +433,7 @@ class _RowDriver:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
-                 kv_cache_dtype: Optional[str] = None):
+                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False):
         # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
         # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
         # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
@@ -446,6 +460,11 @@ class VibeVoiceForConditionalGenerationInference:
         self.row_batch = os.environ.get("VV_ROW_BATCH", "1") != "0"
         self.row_batch_min = int(os.environ.get("VV_ROW_BATCH_MIN", "2"))      # 2 dialogues: 64 vs 58 audio-sec/s on the lanes
         self._rowbatch = {}
+        # do_sample: draw the token inside the LLM step's tail launch from exponential draws the host makes before it enqueues the step
+        # (vv_sampler), instead of reading the logits back for a host softmax / multinomial: one graph and one 4-byte read-back per token, and
+        # speculative frame launch as for greedy decoding.  Seeded calls keep their tokens and the generator its state.  Off by default;
+        # generate(..., device_sampling=...) overrides it per call
+        self.device_sampling = bool(device_sampling)
         # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         self.weight_quant = weight_quant
@@ -497,7 +516,8 @@ class VibeVoiceForConditionalGenerationInference:
         if str(device) == "cuda":
             device = "cuda:0"
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
-                   use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"))
+                   use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
+                   device_sampling=kw.get("device_sampling", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -584,7 +604,9 @@ class VibeVoiceForConditionalGenerationInference:
         if tokenizer is None:
             raise ValueError("generate() needs tokenizer= (for the speech_start/end/diffusion and eos ids)")
         gen_cfg = dict(generation_config or {})
-        sample_fn = _make_sampler(gen_cfg) if gen_cfg.get("do_sample", False) else None
+        do_sample = bool(gen_cfg.get("do_sample", False))
+        sampler = batchloop.sampler_params(gen_cfg) if do_sample and kwargs.get("device_sampling", self.device_sampling) else None
+        sample_fn = _make_sampler(gen_cfg) if do_sample and sampler is None else None
         verbose = kwargs.get("verbose", False)
         max_length_times = kwargs.get("max_length_times", 2)
         refresh_negative = bool(kwargs.get("refresh_negative", True))     # False: reference :501-515 (no caller of the reference uses it)
@@ -626,7 +648,7 @@ class VibeVoiceForConditionalGenerationInference:
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
-                                       sample_fn=sample_fn, speculate=self.speculative_frames and self._use_graphs, return_speech=return_speech,
+                                       sample_fn=sample_fn, sampler=sampler, speculate=self.speculative_frames and self._use_graphs, return_speech=return_speech,
                                        in_dev=in_dev)
             try:
                 return batchloop.run(driver, input_ids, attention_mask, speech_input_mask, conn_all, call)
@@ -640,7 +662,7 @@ class VibeVoiceForConditionalGenerationInference:
             if int(sp.sum()) and conn_all is not None:
                 conn = conn_all[: int(sp.sum())]
         r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
-                               stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative)
+                               stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler)
         if audio_streamer is not None:
             audio_streamer.end()
         return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
@@ -671,8 +693,15 @@ class VibeVoiceForConditionalGenerationInference:
         return eng
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
-                      noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True):
+                      noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None):
         eng, cfg = self.engine, self.config
+        nv = len(set(batchloop.valid_token_ids(special)))
+        if sampler is not None:
+            eng.set_sampler(*sampler)
+        # device-side do_sample with drawn noise: a speculated frame's noise is drawn BEFORE its token is known.  Kept for the next frame after
+        # a mis-speculation (the greedy rule) it would sit in front of the token draws in between and reorder the generator's sequence, so the
+        # generator is put back to where it stood before the noise draw and the rows are dropped
+        rewind = sampler is not None and (noise is None or (eng.sde and sde_noise is None))
 
         def draw(frame):
             """The frame's random draws, in the reference's order: randn(2, latent) for the initial latent (:699), then - SDE solver
@@ -697,7 +726,8 @@ class VibeVoiceForConditionalGenerationInference:
         reach_max = False
         frame = 0
         stream_idx = torch.tensor([sample_idx])
-        # speculative frame launch needs the greedy / forced token path (a sampled token needs the logits on the host first)
+        # speculative frame launch needs the token chosen on the device: greedy, forced, or sampled there (`sampler`); the host sampler
+        # (sample_fn) needs the logits on the host first
         speculate = self.speculative_frames and sample_fn is None and eng.use_graphs
         prev_tok, pending_nz = None, None
         staged: List[int] = []          # ring slots whose audio has not been handed to the streamer yet (at most 2)
@@ -724,10 +754,11 @@ class VibeVoiceForConditionalGenerationInference:
                 break
             forced = forced_tokens[step] if (forced_tokens is not None and step < len(forced_tokens)) else None
             speculated = False
+            q = batchloop.draw_q(nv) if (sampler is not None and forced is None) else None     # where the host sampler's multinomial draws
             if step == 0:
                 # the negative branch's prompt, a single speech_start (:377-381), is one more row of the prompt prefill (cache row 1, position 0)
                 eng.prefill(x0, row=0, pos0=0, chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=eng.embed_ids(torch.tensor([ST])))
-                tok = eng.first_token(ST_dev, SD, forced, sample_fn)
+                tok = eng.first_token(ST_dev, SD, forced, sample_fn, q=q)
                 if tok == SD or not refresh_negative:
                     eng.commit_negative_prompt()         # the branch is in use from step 0 on (otherwise the row is overwritten by the next speech_start)
             elif speculate and prev_tok == SD and (pending_nz is not None or ((noise is None or frame < len(noise)) and
@@ -736,13 +767,17 @@ class VibeVoiceForConditionalGenerationInference:
                 # for the token only.  The noise row is the draw the reference makes when the token IS speech_diffusion; a draw
                 # made for a mis-speculated frame is kept for the next real one (same RNG sequence).
                 if pending_nz is None:
+                    rng = torch.get_rng_state() if rewind else None
                     pending_nz = draw(frame)
-                tok = eng.step_decode_speculative(ST_dev, SD, forced, *pending_nz, on_enqueued=hook, stage=audio_streamer is not None)
+                tok = eng.step_decode_speculative(ST_dev, SD, forced, *pending_nz, on_enqueued=hook, stage=audio_streamer is not None, q=q)
                 speculated = True
                 if tok != SD:
                     eng.rollback_speech_state()
+                    if rewind:
+                        torch.set_rng_state(rng)
+                        pending_nz = None
             else:
-                tok = eng.step_decode(ST_dev, SD, forced, sample_fn, on_enqueued=hook)          # :478-496 (+ speculative :581-583)
+                tok = eng.step_decode(ST_dev, SD, forced, sample_fn, on_enqueued=hook, q=q)          # :478-496 (+ speculative :581-583)
             prev_tok = tok
             seq.append(tok)
             if tok == EOS:                                                                      # :517-526

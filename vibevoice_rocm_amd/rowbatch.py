@@ -79,6 +79,7 @@ class RowBatch:
             self.active_dev = torch.ones(B, **i32)
             self.logits = torch.zeros(B, 8, **f32)
             self.logits_host = torch.zeros(B, 8, dtype=torch.float32).pin_memory()
+            self.q_dev = torch.ones(B, 8, **f32)          # device-side do_sample: every dialogue's exponential draws of the step
             self.noise_dev = torch.zeros(B, cfg.latent, **f32)
             self.latent = torch.zeros(B, cfg.latent, **f32)
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
@@ -89,6 +90,9 @@ class RowBatch:
         self.active_host = torch.ones(B, dtype=torch.int32).pin_memory()
         self.noise_host = torch.zeros(2, B, cfg.latent, dtype=torch.float32).pin_memory()
         self._noise_k = 0
+        self.q_host = torch.ones(2, B, 8, dtype=torch.float32).pin_memory()
+        self._q_k = 0
+        self._sampler, self._sampler_key = None, None
         self._forced_val = [-1] * B
         self._active_val = [1] * B
         self._tok_event = torch.cuda.Event()
@@ -252,9 +256,26 @@ class RowBatch:
         with torch.cuda.stream(self.stream):
             self.lens[2 * b + 1] = 1
 
-    def first_token(self, b: int, forced: Optional[int], sample_fn=None) -> int:
+    def set_sampler(self, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+        """The warpers of the device-side token draw (Engine.set_sampler)."""
+        self._sampler_key = (float(temperature), int(top_k), float(top_p))
+        self._sampler = L.Sampler(*self._sampler_key)
+
+    def _upload_q(self, q: Dict[int, torch.Tensor]):
+        """{dialogue: its exponential draws [nv]} -> q_dev through a pinned double-buffered [B][8] row (the other dialogues' rows are not read
+        for a choice that counts: they are forced or finished)"""
+        if self._sampler is None:
+            raise L.VVError("device-side sampling needs set_sampler() first")
+        self._q_k ^= 1
+        qh = self.q_host[self._q_k]
+        for b, row in q.items():
+            qh[b, : row.numel()].copy_(row.reshape(-1))
+        self.q_dev.copy_(qh, non_blocking=True)
+
+    def first_token(self, b: int, forced: Optional[int], sample_fn=None, q=None) -> int:
         """Token selection right after the prefill of dialogue b (hidden[2 b] holds its last prompt state).  With `sample_fn(logits, ids) -> token`
-        (do_sample) the constrained logits are read back and the drawn token is selected as a forced one (Engine.first_token)."""
+        (do_sample) the constrained logits are read back and the drawn token is selected as a forced one (Engine.first_token); with `q` (the
+        dialogue's exponential draws [nv]) the token is drawn on the device (vv_sample_ids)."""
         nv = len(self.valid_ids)
         with torch.cuda.stream(self.stream):
             a = L.LinArgs()
@@ -264,6 +285,15 @@ class RowBatch:
             self._ck(self.lib.vv_linear(C.byref(a), self.sp), "lm_head")
         if sample_fn is not None and forced is None:
             forced = int(sample_fn(self.read_logits()[b, :nv].clone(), self.valid_ids))
+        if q is not None and forced is None:
+            with torch.cuda.stream(self.stream):
+                self._set_forced({b: None})
+                self._upload_q({b: q})
+                self._ck(self.lib.vv_sample_ids(self.logits[b].data_ptr(), nv, self._ids_dev.data_ptr(), C.byref(self._sampler), self.q_dev[b].data_ptr(),
+                                                self.token_dev[b:].data_ptr(), self.forced_dev[b:].data_ptr(), self.sp), "vv_sample_ids")
+                self.token_host.copy_(self.token_dev, non_blocking=True)
+            self.stream.synchronize()
+            return int(self.token_host[b])
         with torch.cuda.stream(self.stream):
             self._set_forced({b: forced})
             self._ck(self.lib.vv_argmax_ids(self.logits[b].data_ptr(), nv, self._ids_dev.data_ptr(), self.token_dev[b:].data_ptr(),
@@ -303,6 +333,18 @@ class RowBatch:
                                             self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(),
                                             self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.active_dev.data_ptr(), self.sp),
                  "vv_llm_tail_batch")
+
+    def _seq_AS(self, tok_start, tok_diff, temperature, top_k, top_p):
+        """_seq_A with the sampling tail (vv_llm_tail_batch_sample); the warpers are part of the graph's key (Engine._seq_AS)"""
+        eng, B, H = self.main, self.B, self.cfg.hidden
+        nv = len(self.valid_ids)
+        smp = L.Sampler(temperature, top_k, top_p)
+        self._ck(self.lib.vv_llm_forward(C.byref(eng.w.llm), C.byref(self.kv), self.x.data_ptr(), H, 2 * B, self.lens.data_ptr(), None, None, 0,
+                                         self._llm_ws.data_ptr(), self.sp), "vv_llm_forward")
+        self._ck(self.lib.vv_llm_tail_batch_sample(C.byref(eng.w.llm), self._llm_ws.data_ptr(), H, B, self.hidden.data_ptr(), H, self._w_valid.data_ptr(), nv,
+                                                   self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(),
+                                                   self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.active_dev.data_ptr(),
+                                                   C.byref(smp), self.q_dev.data_ptr(), self.sp), "vv_llm_tail_batch_sample")
 
     def _seq_A1(self):
         """the decode step and the constrained logits of every dialogue; positions stay (lens / frame_counter NULL)"""
@@ -365,8 +407,9 @@ class RowBatch:
             self._lane_event[b].record(self.lanes[b].stream)
             self._lane_dirty[b] = True
 
-    def decode_begin(self, tok_start: int, tok_diff: int, forced: Dict[int, Optional[int]]):
-        """graph A for all dialogues + the asynchronous token read-back; `decode_end` returns the tokens."""
+    def decode_begin(self, tok_start: int, tok_diff: int, forced: Dict[int, Optional[int]], q: Optional[Dict[int, torch.Tensor]] = None):
+        """graph A for all dialogues + the asynchronous token read-back; `decode_end` returns the tokens.  `q` = {dialogue: exponential draws
+        [nv]} (do_sample on the device): the sampling variant of graph A - a dialogue with a forced token keeps it, the others draw theirs."""
         with torch.cuda.stream(self.stream):
             self._join_lanes()
             self._set_forced(forced)
@@ -374,7 +417,11 @@ class RowBatch:
                 self._tcur = dict(a0=torch.cuda.Event(enable_timing=True), a1=torch.cuda.Event(enable_timing=True), h1=None, t=[])
                 self._timing.append(self._tcur)
                 self._tcur["a0"].record(self.stream)
-            self._run("A", self._seq_A, int(tok_start), int(tok_diff))
+            if q:
+                self._upload_q(q)
+                self._run("AS", self._seq_AS, int(tok_start), int(tok_diff), *self._sampler_key)
+            else:
+                self._run("A", self._seq_A, int(tok_start), int(tok_diff))
             if self._timing is not None:
                 self._tcur["a1"].record(self.stream)
             self.token_host.copy_(self.token_dev, non_blocking=True)
