@@ -160,6 +160,15 @@ int vv_attn_decode_split(const float* qkv, int64_t ld_qkv, int R, int heads, con
  * head gets 1); without it the scales dst already holds are used.  One launch sequence, no allocation, no synchronisation. */
 enum { VV_KVQ_DERIVE_SCALES = 1 };
 int vv_kv_quantize(const vv_kv* src_bf16, const vv_kv* dst_fp8, int src_row, int dst_row, int len, int flags, vv_stream_t stream);
+/* vv_kv_copy - slots [0, len) of cache row src_row of src -> cache row dst_row of dst, every layer and KV head: k, v, and dst->vt if dst has one.
+ * Same kvdt (VV_F32 or VV_BF16), layers, kv_heads, head_dim; rows and s_max may differ (len <= both s_max).  dst->vt is always built from src->v
+ * (bf16, head_dim 128, dst s_max % 32 == 0; anything else with dst->vt: VV_E_UNSUPPORTED), so src->vt may be NULL and is never read.  Slots >= len
+ * of the destination row (in k, v AND in the last, partial 32-key tile of vt) and every other row are left exactly as they are.  A prefix store -
+ * the K / V of a prompt prefix kept for reuse - is an ordinary vv_kv with rows = 1, its own small s_max and vt = NULL: saving a cache row into it
+ * and restoring it into a cache are this one call.  src and dst may be the same cache when the rows differ.  VV_FP8 on either side:
+ * VV_E_UNSUPPORTED (an fp8 cache is filled through a bf16 staging cache and vv_kv_quantize, as the prompt is).  One launch, no allocation, no
+ * synchronisation. */
+int vv_kv_copy(const vv_kv* src, int src_row, const vv_kv* dst, int dst_row, int len, vv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Block1D first half on channels-last data (modular_vibevoice_tokenizer.py:924-932 with the streaming

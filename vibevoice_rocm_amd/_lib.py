@@ -131,6 +131,7 @@ PROTOTYPES = {
     "vv_attn_decode_part_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vv_attn_decode_split": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp, vp, C.c_int, C.c_int, vp]),
     "vv_kv_quantize": (C.c_int, [C.POINTER(KV), C.POINTER(KV), C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "vv_kv_copy": (C.c_int, [C.POINTER(KV), C.c_int, C.POINTER(KV), C.c_int, C.c_int, vp]),
     "vv_block_mixer": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_float, vp, vp, vp, vp, vp]),
     "vv_block1d": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
     "vv_block_mid_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),

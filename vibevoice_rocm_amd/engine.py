@@ -203,29 +203,8 @@ class Engine:
     def begin_sequence(self, s_max: int, valid_ids: List[int]):
         """Fresh utterance: KV cache sized for s_max tokens, conv states zeroed, constrained-vocabulary rows gathered."""
         cfg = self.cfg
-        s_max = (int(s_max) + 63) // 64 * 64
         with torch.cuda.stream(self.stream):
-            if self.kv is None or self.kv.s_max < s_max:
-                shape = (cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim)
-                cdt = torch.uint8 if self.kv_fp8 else self.kv_dtype        # fp8: e4m3fn codes, one byte per element, same shapes
-                self._kv_t = (torch.zeros(shape, dtype=cdt, device=self.device),
-                              torch.zeros(shape, dtype=cdt, device=self.device))
-                kv = L.KV()
-                kv.k, kv.v = self._kv_t[0].data_ptr(), self._kv_t[1].data_ptr()
-                if self.kv_fp8:
-                    self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=cdt, device=self.device)
-                    self._kv_scale = torch.ones(2, cfg.layers, cfg.kv_heads, dtype=torch.float32, device=self.device)     # {k, v}: set by prefill
-                    kv.vt = self._kv_vt.data_ptr()
-                    kv.kscale, kv.vscale = self._kv_scale[0].data_ptr(), self._kv_scale[1].data_ptr()
-                elif self.kv_dtype == torch.bfloat16 and cfg.head_dim == 128:
-                    # transposed value cache in 32-key tiles [.., s_max / 32, head_dim, 32] for the matrix-core attention kernels (kept in step
-                    # with v by vv_rope_store for prompt rows and by vv_attn_decode for decode steps)
-                    self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=self.kv_dtype, device=self.device)
-                    kv.vt = self._kv_vt.data_ptr()
-                kv.kvdt = L.VV_FP8 if self.kv_fp8 else (L.VV_F32 if self.kv_dtype == torch.float32 else L.VV_BF16)
-                kv.layers, kv.rows, kv.kv_heads, kv.s_max, kv.head_dim = cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim
-                self.kv = kv
-                self._drop_graphs()
+            self._ensure_kv(s_max)
             ids = sorted(set(int(i) for i in valid_ids))
             if ids != self.valid_ids:
                 self.valid_ids = ids
@@ -238,6 +217,32 @@ class Engine:
             self.lens.zero_()
             self.frame_ctr.zero_()
             self.reset_speech_caches()
+
+    def _ensure_kv(self, s_max: int):
+        """The KV cache (rows {positive, negative}) with room for s_max tokens; call it under `torch.cuda.stream(self.stream)`."""
+        cfg = self.cfg
+        s_max = (int(s_max) + 63) // 64 * 64
+        if self.kv is None or self.kv.s_max < s_max:
+            shape = (cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim)
+            cdt = torch.uint8 if self.kv_fp8 else self.kv_dtype        # fp8: e4m3fn codes, one byte per element, same shapes
+            self._kv_t = (torch.zeros(shape, dtype=cdt, device=self.device),
+                          torch.zeros(shape, dtype=cdt, device=self.device))
+            kv = L.KV()
+            kv.k, kv.v = self._kv_t[0].data_ptr(), self._kv_t[1].data_ptr()
+            if self.kv_fp8:
+                self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=cdt, device=self.device)
+                self._kv_scale = torch.ones(2, cfg.layers, cfg.kv_heads, dtype=torch.float32, device=self.device)     # {k, v}: set by prefill
+                kv.vt = self._kv_vt.data_ptr()
+                kv.kscale, kv.vscale = self._kv_scale[0].data_ptr(), self._kv_scale[1].data_ptr()
+            elif self.kv_dtype == torch.bfloat16 and cfg.head_dim == 128:
+                # transposed value cache in 32-key tiles [.., s_max / 32, head_dim, 32] for the matrix-core attention kernels (kept in step
+                # with v by vv_rope_store for prompt rows and by vv_attn_decode for decode steps)
+                self._kv_vt = torch.empty((cfg.layers, 2, cfg.kv_heads, s_max // 32, cfg.head_dim, 32), dtype=self.kv_dtype, device=self.device)
+                kv.vt = self._kv_vt.data_ptr()
+            kv.kvdt = L.VV_FP8 if self.kv_fp8 else (L.VV_F32 if self.kv_dtype == torch.float32 else L.VV_BF16)
+            kv.layers, kv.rows, kv.kv_heads, kv.s_max, kv.head_dim = cfg.layers, 2, cfg.kv_heads, s_max, cfg.head_dim
+            self.kv = kv
+            self._drop_graphs()
 
     def reset_speech_caches(self):
         """acoustic_cache.set_to_zero / semantic_cache.set_to_zero (modeling_vibevoice_inference.py:540-544)."""
@@ -254,14 +259,25 @@ class Engine:
                                          L.ptr(cache_rows), out.data_ptr(), out.stride(0), self._llm_ws.data_ptr(), self.sp),
                  "vv_llm_forward")
 
-    def prefill(self, embeds: torch.Tensor, row: int = 0, pos0: int = 0, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None) -> None:
+    def prefill(self, embeds: torch.Tensor, row: int = 0, pos0: int = 0, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None,
+                prefix=None, keep_staging: bool = False):
         """Prompt prefill on cache row `row`: embeds [L0, H] fp32 -> self.hidden2[row] = last hidden state; lens[row] = pos0+L0.
         Prompts longer than `chunk` rows run as ceil(L0 / chunk) EQUAL chunks (rounded up to 32 rows): a short trailing chunk would stream
         every weight matrix once more for a handful of rows (1 040 tokens as 1 024 + 16 cost 18.5 ms, as 2 x 520 they cost 12).
         neg_embed [1, H]: the negative branch's one-token prompt (a single speech_start, modeling_vibevoice_inference.py:377-381) rides along as
         one more row of the last chunk - cache row 1, position 0 - instead of a weight pass of its own (1.1 ms of the first chunk's latency);
-        hidden2[1] then holds its state and the CALLER sets lens[1] = 1 if the branch is in use (`commit_negative_prompt`)."""
+        hidden2[1] then holds its state and the CALLER sets lens[1] = 1 if the branch is in use (`commit_negative_prompt`).
+        prefix (a VoicePrefix, voice_prefix.py): its P slots are restored into slots [0, P) of the row with one vv_kv_copy and `embeds` - the rows
+        after the prefix only - are prefilled at position P (pos0 must be 0: the prefix implies it).  On an fp8 KV cache the restore goes into the
+        staging cache, sized for P + L0, and the scales are derived from all P + L0 slots, as without a prefix.
+        keep_staging (fp8 KV cache): skip the conversion and return the staging cache (vv_kv, its tensors) - how save_prefix gets at the prompt's
+        bf16 K / V; the byte cache is left alone and the engine is not ready to decode."""
         L0 = embeds.shape[0]
+        P = 0
+        if prefix is not None:
+            if pos0 != 0:
+                raise L.VVError("prefill: a prefix fixes the position of the rows after it (pos0 must be 0)")
+            P = int(prefix.P)
         kv, stage = None, None
         if self.kv_fp8:
             # fp8 KV cache: the prompt runs exactly as on a bf16 cache, on a bf16 staging cache sized to the prompt (rows 0 and 1: the negative
@@ -269,11 +285,16 @@ class Engine:
             if pos0 != 0 or row != 0:
                 raise L.VVError("kv_cache_dtype='fp8': the prompt is prefilled once, at position 0 of cache row 0 (prompt attention has no fp8-KV form)")
             with torch.cuda.stream(self.stream):     # allocated, zeroed, used and freed on the engine's stream: the allocator reuses it in that stream's order
-                kv, stage = self._staging_kv(L0)
+                kv, stage = self._staging_kv(P + L0)
+        elif keep_staging:
+            raise L.VVError("prefill(keep_staging=True) is for an fp8 KV cache (any other cache holds the prompt's K / V itself)")
+        pos0 += P
         n_chunks = max(1, -(-L0 // max(1, chunk)))
         size = -(-L0 // n_chunks)
         size = min(chunk, (size + 31) // 32 * 32) if n_chunks > 1 else L0
         with torch.cuda.stream(self.stream):
+            if prefix is not None:
+                self._ck(self.lib.vv_kv_copy(C.byref(prefix.kv), 0, C.byref(kv or self.kv), row, P, self.sp), "vv_kv_copy")
             for c0 in range(0, L0, size):
                 c1 = min(L0, c0 + size)
                 n = c1 - c0
@@ -287,9 +308,9 @@ class Engine:
                     x = torch.cat([x, neg_embed.to(x.dtype).reshape(1, -1)])
                 out = torch.empty(x.shape[0], self.cfg.hidden, dtype=torch.float32, device=self.device)
                 self.llm_forward(x, lens, rows, out, kv=kv)
-            if stage is not None:
+            if stage is not None and not keep_staging:
                 # row 0 sets the scales of every (layer, KV head) from the prompt's K / V absmax; row 1 (the negative prompt) reuses them
-                self._ck(self.lib.vv_kv_quantize(C.byref(kv), C.byref(self.kv), 0, 0, L0, L.KVQ_DERIVE_SCALES, self.sp), "vv_kv_quantize")
+                self._ck(self.lib.vv_kv_quantize(C.byref(kv), C.byref(self.kv), 0, 0, pos0 + L0, L.KVQ_DERIVE_SCALES, self.sp), "vv_kv_quantize")
                 self._ck(self.lib.vv_kv_quantize(C.byref(kv), C.byref(self.kv), 1, 1, 1 if neg_embed is not None else 0, 0, self.sp), "vv_kv_quantize")
                 del stage, kv         # back to the pool of the engine's stream, on which it was allocated (see above)
             if neg_embed is not None:
@@ -298,6 +319,28 @@ class Engine:
             else:
                 self.hidden2[row].copy_(out[-1])
             self.lens[row] = pos0 + L0
+        if keep_staging:
+            return kv, stage
+
+    def save_prefix(self, ids: torch.Tensor, row: int = 0, kv=None):
+        """The first P = len(ids) slots of cache row `row` (of `kv`, default the engine's cache; an fp8 engine passes the staging cache that
+        prefill(keep_staging=True) returned) as a freshly allocated VoicePrefix: one vv_kv_copy.  Synchronises: the store is complete and
+        read-only when this returns."""
+        from . import voice_prefix as VP
+        cfg = self.cfg
+        src = kv or self.kv
+        if src is None or src.kvdt == L.VV_FP8:
+            raise L.VVError("save_prefix: no bf16 / fp32 cache to read (an fp8 KV cache is saved from its staging cache)")
+        ids = torch.as_tensor(ids).reshape(-1).cpu().long().clone()
+        P = int(ids.numel())
+        with torch.cuda.stream(self.stream):
+            shape = VP.store_shape(cfg.layers, cfg.kv_heads, cfg.head_dim, P)
+            k = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
+            v = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
+            skv = VP.describe(k, v)
+            self._ck(self.lib.vv_kv_copy(C.byref(src), row, C.byref(skv), 0, P, self.sp), "vv_kv_copy")
+        self.stream.synchronize()
+        return VP.VoicePrefix(ids=ids, P=P, k=k, v=v, kv=skv, nbytes=k.numel() * k.element_size() + v.numel() * v.element_size())
 
     def _staging_kv(self, n_tokens: int):
         """bf16 cache for a prompt of n_tokens (rounded up to the caches' 64-slot granule), rows {positive, negative}: (vv_kv, its tensors).

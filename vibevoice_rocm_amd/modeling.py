@@ -22,10 +22,12 @@ import torch
 
 from . import _lib as L
 from . import batchloop
+from . import voice_prefix as VP
 from .batchloop import VibeVoiceGenerationOutput, _BatchCoupling      # noqa: F401  (public names of this module)
 from .config import VVConfig
 from .engine import Engine, check_kv_cache_dtype
 from .synth import state_dict_shapes
+from .voice_prefix import VoicePrefix      # noqa: F401  (public name of this module)
 
 LANES_IN_FLIGHT = 4       # lock-step batches: lanes (one HIP stream each) enqueued concurrently; see _LaneDriver
 
@@ -202,6 +204,7 @@ class _LaneDriver:
     def __init__(self, model, B: int, cfg_scale: float, ST: int, SD: int):
         self.model, self.cfg_scale, self.ST, self.SD = model, float(cfg_scale), ST, SD
         self.lanes = [model._lane(b) for b in range(B)]
+        self.prefixes = [None] * B          # generate(voice_prefix=): dialogue -> VoicePrefix or None
         for e in self.lanes[1:]:
             e.sync_in()
         self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
@@ -212,9 +215,11 @@ class _LaneDriver:
 
     def begin(self, prompts, voices, max_steps, valid):
         self.x0 = []
-        for eng, ids, voice in zip(self.lanes, prompts, voices):
+        for eng, ids, voice, vp in zip(self.lanes, prompts, voices, self.prefixes):
             eng.cfg_scale = self.cfg_scale
             eng.begin_sequence(len(ids) + max(max_steps, 1) + 8, valid)
+            if vp is not None:
+                ids, voice = ids[vp.P:], None           # the rows after the prefix; every voice row lies inside it (VP.check)
             self.x0.append(_embed_prompt(eng, ids, voice, after=self.model.engine.stream))     # conn_all was produced on lane 0's stream
 
     def set_sampler(self, temperature, top_k, top_p):
@@ -224,7 +229,8 @@ class _LaneDriver:
     def first_tokens(self, live, forced, sample_fn, q=None):
         lanes, toks = self.lanes, {}
         for b in live:
-            lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])))
+            lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])),
+                             prefix=self.prefixes[b])
         for b in live:
             toks[b] = lanes[b].first_token(self.ST, self.SD, forced[b], sample_fn, q=(q or {}).get(b))
             if toks[b] == self.SD:
@@ -313,6 +319,7 @@ class _RowDriver:
             self.lanes = [model._lane(b) for b in range(B)]
         self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
         self.groups, self.at = [], {}          # (row batch, its dialogues); dialogue -> (row batch, index in it)
+        self.prefixes = [None] * B             # generate(voice_prefix=): dialogue -> VoicePrefix or None
 
     def begin(self, prompts, voices, max_steps, valid):
         from .rowbatch import RowBatch
@@ -329,7 +336,8 @@ class _RowDriver:
             for b in idxs:
                 self.at[b] = (rb, b - off)
             off += n
-        self.x0 = [_embed_prompt(self.main, ids, voice) for ids, voice in zip(prompts, voices)]
+        self.x0 = [_embed_prompt(self.main, ids, voice) if vp is None else _embed_prompt(self.main, ids[vp.P:], None)
+                   for ids, voice, vp in zip(prompts, voices, self.prefixes)]
 
     def set_sampler(self, temperature, top_k, top_p):
         for rb, _ in self.groups:
@@ -339,7 +347,7 @@ class _RowDriver:
         at, toks = self.at, {}
         st_embed = self.main.embed_ids(torch.tensor([self.ST]))
         for b in live:
-            at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed)
+            at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed, prefix=self.prefixes[b])
         for b in live:
             rb, loc = at[b]
             toks[b] = rb.first_token(loc, forced[b], sample_fn, q=(q or {}).get(b))
@@ -585,6 +593,42 @@ class VibeVoiceForConditionalGenerationInference:
         conn = eng.connector("acoustic", sel)
         return feats, conn
 
+    # ---- voice prefix cache (voice_prefix.py) --------------------------------------------------------------------
+    @torch.no_grad()
+    def prepare_voice_prefix(self, input_ids, speech_tensors=None, speech_masks=None, speech_input_mask=None, speech_noise=None,
+                             prefill_chunk: int = 1024) -> VoicePrefix:
+        """The voice-only head of a prompt (`VibeVoiceProcessor.voice_prefix`), done once: the voice encode, the prefill of its P positions on the
+        main engine - chunked as generate() chunks a prompt - and one vv_kv_copy of cache row 0 into a freshly allocated store.  The latents'
+        noise (modeling_vibevoice_inference.py:149-163) is drawn here, once, or injected as `speech_noise` = (std_noise [S], eps_noise [S, F, 64]).
+        Synchronises before it returns; the caller owns the VoicePrefix and hands it to generate(voice_prefix=...)."""
+        eng = self.engine
+        ids = torch.as_tensor(input_ids).cpu().long()
+        if ids.dim() == 2 and ids.shape[0] == 1:
+            ids = ids[0]
+        if ids.dim() != 1 or ids.numel() == 0:
+            raise ValueError(f"prepare_voice_prefix: input_ids must be one prefix ([P] or [1, P]), not shape {tuple(ids.shape)}")
+        sp = None if speech_input_mask is None else torch.as_tensor(speech_input_mask).cpu().bool().reshape(-1)
+        if sp is not None and sp.numel() != ids.numel():
+            raise ValueError(f"prepare_voice_prefix: speech_input_mask has {sp.numel()} positions, input_ids {ids.numel()}")
+        eng.sync_in()
+        with torch.cuda.stream(eng.stream):
+            voice = None
+            if speech_tensors is not None and speech_masks is not None and sp is not None and int(sp.sum()):
+                _, conn = self._process_speech_inputs(torch.as_tensor(speech_tensors).float(), torch.as_tensor(speech_masks).bool(), *(speech_noise or (None, None)))
+                if conn.shape[0] != int(sp.sum()):
+                    raise ValueError(f"prepare_voice_prefix: speech_input_mask marks {int(sp.sum())} positions, the voices have {conn.shape[0]} frames")
+                voice = (sp, conn)
+            x0 = _embed_prompt(eng, ids, voice)
+            if eng.kv_fp8:
+                kv, stage = eng.prefill(x0, chunk=int(prefill_chunk), keep_staging=True)      # the prompt's bf16 K / V, not their codes
+                vp = eng.save_prefix(ids, kv=kv)
+                del stage
+            else:
+                eng._ensure_kv(ids.numel())
+                eng.prefill(x0, chunk=int(prefill_chunk))
+                vp = eng.save_prefix(ids)
+        return vp
+
     # ---- generation --------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
@@ -632,6 +676,10 @@ class VibeVoiceForConditionalGenerationInference:
         pad_id = getattr(tokenizer, "pad_id", None)
         if pad_id is None:
             pad_id = special["eos"]
+        vps = VP.per_dialogue(kwargs.get("voice_prefix"), B)
+        if vps is not None:
+            speech_tensors, speech_masks, speech_noise, speech_input_mask = self._apply_voice_prefixes(
+                vps, input_ids, attention_mask, speech_input_mask, speech_tensors, speech_masks, speech_noise)
         conn_all = None
         if speech_tensors is not None and speech_masks is not None:
             sn = speech_noise or (None, None)
@@ -645,6 +693,8 @@ class VibeVoiceForConditionalGenerationInference:
             rows = kwargs.get("row_batch", self.row_batch) and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and \
                 self.weight_quant in (None, "fp8") and self.kv_cache_dtype != "fp8"      # fp8 KV: on the lanes (RowBatch needs a bf16 cache)
             driver = (_RowDriver if rows else _LaneDriver)(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"])
+            if vps is not None:
+                driver.prefixes = vps
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
@@ -662,10 +712,46 @@ class VibeVoiceForConditionalGenerationInference:
             if int(sp.sum()) and conn_all is not None:
                 conn = conn_all[: int(sp.sum())]
         r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
-                               stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler)
+                               stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler,
+                               prefix=None if vps is None else vps[0])
         if audio_streamer is not None:
             audio_streamer.end()
         return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
+
+    def _apply_voice_prefixes(self, vps, input_ids, attention_mask, speech_input_mask, speech_tensors, speech_masks, speech_noise):
+        """generate(voice_prefix=): every dialogue with a prefix is checked against it (VP.check: ValueError naming what differs) and loses its
+        voice inputs - its voice rows are already in the store's K / V: its speech_input_mask row is cleared and its voices are not encoded.
+        `speech_tensors` / `speech_masks` may be omitted when every dialogue has a prefix; otherwise they hold the voices of ALL dialogues, as the
+        processor returns them for the batch, and the rows of the prefixed dialogues are skipped.  A dialogue's number of voices is the number
+        of placeholder runs in its mask row.  Returns (speech_tensors, speech_masks, speech_noise, speech_input_mask)."""
+        cfg, B = self.config, input_ids.shape[0]
+        keep = attention_mask.bool()
+        n_voices = []
+        for b in range(B):
+            sp_b = None if speech_input_mask is None else speech_input_mask[b][keep[b]].bool()
+            if vps[b] is not None:
+                dv = vps[b].k.device                # an index-less "cuda" is the current device: compare resolved indices
+                if dv.type != self.device.type or dv.index != (torch.cuda.current_device() if self.device.index is None else self.device.index):
+                    raise ValueError(f"voice_prefix: the store lives on {vps[b].k.device}, this model on {self.device}")
+                VP.check(vps[b], input_ids[b][keep[b]], sp_b, cfg.layers, cfg.kv_heads, cfg.head_dim, self.engine.kv_dtype, where=f" (dialogue {b})" if B > 1 else "")
+            n_voices.append(0 if sp_b is None or not sp_b.numel() else int((sp_b[1:] & ~sp_b[:-1]).sum()) + int(sp_b[0]))     # runs of True
+        if speech_input_mask is not None:
+            speech_input_mask = speech_input_mask.clone()
+            for b in range(B):
+                if vps[b] is not None:
+                    speech_input_mask[b] = False
+        full = [b for b in range(B) if vps[b] is None and n_voices[b]]
+        if not full or speech_tensors is None or speech_masks is None:
+            return (None, None, None, speech_input_mask) if not full else (speech_tensors, speech_masks, speech_noise, speech_input_mask)
+        S = int(torch.as_tensor(speech_tensors).shape[0])
+        if S != sum(n_voices):
+            raise ValueError(f"voice_prefix: speech_tensors holds {S} voices, the dialogues' speech_input_mask rows mark {sum(n_voices)}: with a "
+                             "per-dialogue list, give the voices of all dialogues as the processor returns them")
+        first = [sum(n_voices[:b]) for b in range(B)]
+        rows = torch.tensor([first[b] + i for b in full for i in range(n_voices[b])], dtype=torch.long)
+        if speech_noise is not None:
+            speech_noise = tuple(torch.as_tensor(t)[rows] for t in speech_noise)
+        return torch.as_tensor(speech_tensors)[rows], torch.as_tensor(speech_masks)[rows], speech_noise, speech_input_mask
 
     # ---- batches: lock step over samples (batchloop.run through _LaneDriver / _RowDriver) -----------------------------------
     def release_lanes(self) -> None:
@@ -693,7 +779,8 @@ class VibeVoiceForConditionalGenerationInference:
         return eng
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
-                      noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None):
+                      noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None,
+                      prefix: Optional[VoicePrefix] = None):
         eng, cfg = self.engine, self.config
         nv = len(set(batchloop.valid_token_ids(special)))
         if sampler is not None:
@@ -720,7 +807,8 @@ class VibeVoiceForConditionalGenerationInference:
         max_length, max_steps = batchloop.limits(cfg.max_pos, L0, max_new_tokens, max_length_times)
         eng.cfg_scale = float(cfg_scale)
         eng.begin_sequence(L0 + max(max_steps, 1) + 8, batchloop.valid_token_ids(special))
-        x0 = _embed_prompt(eng, ids, None if conn is None else (sp_mask, conn))
+        # prefix: its P positions come out of the store; only the rows after it are embedded and prefilled (every voice row lies inside it)
+        x0 = _embed_prompt(eng, ids, None if conn is None else (sp_mask, conn)) if prefix is None else _embed_prompt(eng, ids[prefix.P:], None)
         seq = ids.tolist()
         chunks: List[torch.Tensor] = []
         reach_max = False
@@ -757,7 +845,7 @@ class VibeVoiceForConditionalGenerationInference:
             q = batchloop.draw_q(nv) if (sampler is not None and forced is None) else None     # where the host sampler's multinomial draws
             if step == 0:
                 # the negative branch's prompt, a single speech_start (:377-381), is one more row of the prompt prefill (cache row 1, position 0)
-                eng.prefill(x0, row=0, pos0=0, chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=eng.embed_ids(torch.tensor([ST])))
+                eng.prefill(x0, row=0, pos0=0, chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=eng.embed_ids(torch.tensor([ST])), prefix=prefix)
                 tok = eng.first_token(ST_dev, SD, forced, sample_fn, q=q)
                 if tok == SD or not refresh_negative:
                     eng.commit_negative_prompt()         # the branch is in use from step 0 on (otherwise the row is overwritten by the next speech_start)

@@ -174,6 +174,36 @@ class VibeVoiceProcessor:
             speech_inputs.append(wav.astype(np.float32))
         return tokens, speech_inputs, masks
 
+    def _prompt_head(self, voice_samples=None):
+        """The part of a prompt that depends on the voices alone (:231-268): system prompt, " Voice input:\n" with every speaker's
+        placeholders, " Text input:\n".  Each piece is tokenised on its own and the lists concatenated, so these ids are a true prefix of
+        every prompt `_process_single` builds for the same voices.  Returns (ids, speech_input_mask, speech_inputs)."""
+        tok = self.tokenizer
+        full = tok.encode(self.system_prompt)
+        mask = [False] * len(full)
+        speech_inputs = []
+        if voice_samples:
+            vt, speech_inputs, vm = self._create_voice_prompt(voice_samples)
+            full += vt
+            mask += vm
+        t = tok.encode(" Text input:\n", add_special_tokens=False)
+        full += t
+        mask += [False] * len(t)
+        return full, mask, speech_inputs
+
+    def voice_prefix(self, voice_samples, return_tensors="pt") -> Dict[str, Any]:
+        """The voice-only prefix of every prompt spoken in `voice_samples` (one sample per speaker of the script, in speaker order; a script
+        with fewer speakers uses fewer samples and therefore another prefix): `input_ids` [1, P], `speech_input_mask` [1, P], `speech_tensors`
+        and `speech_masks` as `__call__` returns them - what `model.prepare_voice_prefix` takes."""
+        if not voice_samples:
+            raise ValueError("voice_prefix needs at least one voice sample")
+        ids, mask, speech_inputs = self._prompt_head(list(voice_samples))
+        sp = self.prepare_speech_inputs(speech_inputs, return_tensors=return_tensors)
+        if return_tensors is not None:
+            return dict(input_ids=torch.tensor([ids], dtype=torch.long), speech_input_mask=torch.tensor([mask], dtype=torch.bool),
+                        speech_tensors=sp["padded_speeches"], speech_masks=sp["speech_masks"])
+        return dict(input_ids=[ids], speech_input_mask=[mask], speech_tensors=sp["padded_speeches"], speech_masks=sp["speech_masks"])
+
     def _process_single(self, text: str, voice_samples=None) -> Dict[str, Any]:
         if not isinstance(text, str):
             raise ValueError(f"Could not process input text: {text}")
@@ -184,16 +214,7 @@ class VibeVoiceProcessor:
         parsed = self._parse_script(text)
         speakers = list(set(s for s, _ in parsed))
         tok = self.tokenizer
-        full = tok.encode(self.system_prompt)
-        mask = [False] * len(full)
-        speech_inputs = []
-        if voice_samples:
-            vt, speech_inputs, vm = self._create_voice_prompt(voice_samples[: len(speakers)])
-            full += vt
-            mask += vm
-        t = tok.encode(" Text input:\n", add_special_tokens=False)
-        full += t
-        mask += [False] * len(t)
+        full, mask, speech_inputs = self._prompt_head(voice_samples[: len(speakers)] if voice_samples else None)
         for sid, stext in parsed:
             t = tok.encode(f" Speaker {sid}:{stext}\n", add_special_tokens=False)
             full += t

@@ -218,12 +218,16 @@ class RowBatch:
                 e.reset_speech_caches()
         self._lane_dirty = [False] * B
 
-    def prefill(self, b: int, embeds: torch.Tensor, neg: bool = False, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None):
+    def prefill(self, b: int, embeds: torch.Tensor, neg: bool = False, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None, prefix=None):
         """Prompt prefill of dialogue b on cache row 2 b (neg: 2 b + 1), on the main stream; hidden[row] = last hidden state.  neg_embed [1, H]:
         the negative branch's one-token prompt rides along as one more row of the last chunk (cache row 2 b + 1, position 0; Engine.prefill);
-        `commit_negative` then puts the branch in use."""
+        `commit_negative` then puts the branch in use.  prefix (a VoicePrefix): restored into slots [0, P) of row 2 b with one vv_kv_copy, `embeds`
+        - the rows after it - prefilled at position P (Engine.prefill)."""
+        if prefix is not None and neg:
+            raise L.VVError("RowBatch.prefill: a prefix belongs to the positive row")
         row = 2 * b + (1 if neg else 0)
         L0 = embeds.shape[0]
+        P = 0 if prefix is None else int(prefix.P)
         n_chunks = max(1, -(-L0 // max(1, chunk)))
         size = -(-L0 // n_chunks)
         size = min(chunk, (size + 31) // 32 * 32) if n_chunks > 1 else L0
@@ -231,11 +235,13 @@ class RowBatch:
             if max(size, 1) + 1 > self._pf_rows:
                 self._pf_rows = max(size + 1, 64)
                 self._pf_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(self.main.w.llm), self._pf_rows), dtype=torch.uint8, device=self.device)
+            if prefix is not None:
+                self._ck(self.lib.vv_kv_copy(C.byref(prefix.kv), 0, C.byref(self.kv), row, P, self.sp), "vv_kv_copy")
             for c0 in range(0, L0, size):
                 c1 = min(L0, c0 + size)
                 last = c1 == L0 and neg_embed is not None
                 n = c1 - c0 + (1 if last else 0)
-                lens = torch.arange(c0, c0 + n, dtype=torch.int32, device=self.device)
+                lens = torch.arange(P + c0, P + c0 + n, dtype=torch.int32, device=self.device)
                 rows = torch.full((n,), row, dtype=torch.int32, device=self.device)
                 xe = embeds[c0:c1].contiguous()
                 if last:
@@ -250,7 +256,7 @@ class RowBatch:
                 self.hidden[2 * b + 1].copy_(out[-1])
             else:
                 self.hidden[row].copy_(out[-1])
-            self.lens[row] = L0
+            self.lens[row] = P + L0
 
     def commit_negative(self, b: int):
         with torch.cuda.stream(self.stream):
