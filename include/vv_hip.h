@@ -359,6 +359,17 @@ size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int B);
 int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
                              const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
                              const float* sde_noise, int64_t ld_sde, vv_stream_t stream);
+/* The samplers' Gaussian noise drawn on the device, one launch for B utterances: noise[b * ld_noise + e], e < n, is the initial latent (kind 0) and,
+ * when sde_noise is given, sde_noise[b * ld_sde + s * n + e] the variance noise of solver step s < n_steps (kind 1 + s) - the buffers
+ * vv_head_sample and vv_head_sample_batch(_sde) read.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85)
+ * with key = (seeds[b] & 0xffffffff, seeds[b] >> 32) and counter = (j, (uint32) frames[b], kind, 0) gives the four values of quad j (elements
+ * 4 j .. 4 j + 3): u_i = (float) x_i * 2^-32 + 2^-33 in (0, 1], z[4 j] = r(u0) cos(2 pi u1), z[4 j + 1] = r(u0) sin(2 pi u1), z[4 j + 2] and
+ * z[4 j + 3] likewise from (u2, u3), r(u) = sqrtf(-2 logf(u)); elements >= n of the last quad are dropped, columns n .. ld are not written.  A
+ * row is a function of (seed, frame, kind) alone: not of B, of the row's place in the call or of anything drawn before.  seeds and frames
+ * are device arrays [B], every other argument a pointer or a shape: the launch can be captured into a graph.  VV_E_ARG, nothing launched:
+ * NULL noise / seeds / frames, B <= 0, n <= 0, n_steps < 0, ld_noise < n, ld_sde < n_steps * n with sde_noise given. */
+int vv_noise_normal(float* noise, int64_t ld_noise, float* sde_noise, int64_t ld_sde, int B, int n, int n_steps, const uint64_t* seeds,
+                    const int* frames, vv_stream_t stream);
 /* VibeVoiceDiffusionHead.forward alone (parity tests): x[R, latent], temb_rows[R, D], cond[R, cond_dim] -> v[R, latent] */
 int vv_head_forward(const vv_head* h, const float* x, const float* temb_rows, const float* cond, int R, float* v,
                     void* ws, vv_stream_t stream);

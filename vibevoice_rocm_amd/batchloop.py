@@ -20,7 +20,11 @@ a recording fake on a machine without a GPU (tests/test_host_cpu.py).  A driver 
 
 do_sample on the device (BatchCall.sampler): the driver is told the warpers once (`set_sampler(temperature, top_k, top_p)`), sample_fn is None and
 first_tokens / decode get `q=` {dialogue: its exponential draws [nv]} for the live dialogues without a forced token; the token comes back
-like a greedy one."""
+like a greedy one.
+
+Diffusion noise on the device (BatchCall.noise_seeds): the driver is told every dialogue's seed once (`set_noise_seeds(seeds)`, after begin) and
+draws a frame's noise itself from (seed, frame index); `eligible` and the rows of `speech` then carry `(frame index, None)` in place of the
+noise rows, every dialogue in its steady state may be speculated, and the loop makes no draw of its own."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -54,6 +58,7 @@ class BatchCall:
     verbose: bool = False
     sample_fn: Optional[Callable] = None
     sampler: Optional[tuple] = None       # do_sample on the device: the warpers (temperature, top_k, top_p); sample_fn is None then
+    noise_seeds: Optional[List[int]] = None   # diffusion noise on the device: one 64-bit seed per dialogue; noise / sde_noise are None then
     speculate: bool = True                # frames may be launched before their token is known (never with sample_fn)
     return_speech: bool = True
     in_dev: object = "cpu"
@@ -177,6 +182,13 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
         if sample_fn is not None:
             raise ValueError("BatchCall: sampler (device) and sample_fn (host) exclude each other")
         driver.set_sampler(*call.sampler)
+    dn = call.noise_seeds is not None
+    if dn:
+        if noise is not None or sde_noise is not None:
+            raise ValueError("BatchCall: noise_seeds (drawn on the device) and injected noise / sde_noise exclude each other")
+        if len(call.noise_seeds) != B:
+            raise ValueError(f"BatchCall: noise_seeds has {len(call.noise_seeds)} entries for {B} dialogues")
+        driver.set_noise_seeds([int(s_) for s_ in call.noise_seeds])
     coupling = _BatchCoupling(B, ST, SD)
 
     def deliver():
@@ -220,9 +232,13 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
         else:
             # a dialogue in its steady state may get its diffusion tail enqueued speculatively behind its LLM step when its noise is injected
             # (drawn noise depends on how many samples diffuse in this step, which is only known once the tokens are)
-            eligible = {b: (nz[b][frame[b]], snz[b][frame[b]] if sde else None) for b in live
-                        if speculate and prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
-                        (not sde or (snz[b] is not None and frame[b] < len(snz[b])))}
+            if dn:
+                # noise drawn on the device: a frame's noise is a function of its index, whoever else diffuses and whether or not it was speculated
+                eligible = {b: (frame[b], None) for b in live if speculate and prev_tok[b] == SD}
+            else:
+                eligible = {b: (nz[b][frame[b]], snz[b][frame[b]] if sde else None) for b in live
+                            if speculate and prev_tok[b] == SD and nz[b] is not None and frame[b] < len(nz[b]) and
+                            (not sde or (snz[b] is not None and frame[b] < len(snz[b])))}
             toks, speculated = driver.decode(live, forced, eligible, sample_fn, deliver, **kw)
         going = [b for b in live if toks[b] != EOS and step < max_step_per_sample[b]]
         replace, restart = coupling.step(toks, going)
@@ -253,7 +269,7 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
                     driver.reset_speech(b)
             else:
                 driver.embed(b)                                                                     # :567
-        need = [b for b in diffusing if b not in speculated and (nz[b] is None or frame[b] >= len(nz[b]))]
+        need = [] if dn else [b for b in diffusing if b not in speculated and (nz[b] is None or frame[b] >= len(nz[b]))]
         if need:
             n = len(need)
             drawn = torch.randn(2 * n, call.latent)[:n]
@@ -264,7 +280,7 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
                 i = need.index(b)
                 rows[b] = (drawn[i], sdrawn[i] if sde else None)
             elif b not in speculated:
-                rows[b] = (nz[b][frame[b]], snz[b][frame[b]] if sde else None)
+                rows[b] = (frame[b], None) if dn else (nz[b][frame[b]], snz[b][frame[b]] if sde else None)
         driver.speech(rows)
         for b in diffusing:
             chunks[b].append(driver.chunk(b))

@@ -95,12 +95,18 @@ class Engine:
             self.conn_ws = torch.zeros(8 * H, **f32)
             self.logits = torch.zeros(8, **f32)
             self.q_dev = torch.ones(8, **f32)             # device-side do_sample: the step's exponential draws, one per constrained id
+            # device-side diffusion noise (vv_noise_normal): the dialogue's 64-bit seed (its bits in an int64) and the index of the frame to draw
+            self.noise_seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.noise_frame_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.token_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.logits_host = torch.zeros(8, dtype=torch.float32).pin_memory()
         self.forced_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
         self._forced_dev_val = -1                         # what forced_dev holds (see _set_forced)
         self.noise_host = torch.zeros(2, cfg.latent, dtype=torch.float32).pin_memory()   # double-buffered: the host runs a frame ahead
         self._noise_k = 0
+        self.noise_seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()            # written once per sequence (set_noise_seed)
+        self.noise_frame_host = torch.zeros(2, 1, dtype=torch.int32).pin_memory()        # double-buffered like the noise rows
+        self._frame_k = 0
         self.q_host = torch.ones(2, 8, dtype=torch.float32).pin_memory()                 # double-buffered like the noise rows
         self._q_k = 0
         self._sampler, self._sampler_key = None, None     # set_sampler
@@ -414,9 +420,20 @@ class Engine:
         self._ck(self.lib.vv_advance_lens(self.lens.data_ptr(), self.token_dev.data_ptr(), tok_start, tok_diff,
                                           self.frame_ctr.data_ptr(), self.sp), "vv_advance_lens")
 
-    def _seq_B(self, cfg_scale):
-        """speech_diffusion tail: sample latent, decode audio, re-encode semantics, build the next embedding."""
+    def _seq_noise(self):
+        """device noise: the frame's initial latent - and the SDE solver's per-step variance noise - drawn into noise_dev / sde_noise_dev from
+        (noise_seed_dev, noise_frame_dev) by one launch at the head of the frame's graph"""
+        cfg = self.cfg
+        self._ck(self.lib.vv_noise_normal(self.noise_dev.data_ptr(), cfg.latent, self.sde_noise_dev.data_ptr() if self.sde else None,
+                                          self.n_steps * cfg.latent, 1, cfg.latent, self.n_steps if self.sde else 0, self.noise_seed_dev.data_ptr(),
+                                          self.noise_frame_dev.data_ptr(), self.sp), "vv_noise_normal")
+
+    def _seq_B(self, cfg_scale, dn=None):
+        """speech_diffusion tail: sample latent, decode audio, re-encode semantics, build the next embedding.  dn == "dn": the noise is drawn
+        on the device first (_seq_noise); the marker is part of the graph's key, so ("B", cfg_scale) stays the graph it was."""
         lib, w, cfg = self.lib, self.w, self.cfg
+        if dn:
+            self._seq_noise()
         # snapshot of the streaming state (one ~1.4 MB copy): lets a frame that was launched speculatively be rolled back
         blob = w.state_blob()
         self._ck(lib.vv_copy_rows(blob.data_ptr(), blob.numel(), self._state_snap.data_ptr(), blob.numel(), 1, blob.numel(), self.sp), "snapshot")
@@ -430,9 +447,11 @@ class Engine:
         self._ck(lib.vv_connector_pair(C.byref(w.ac_conn), C.byref(w.sem_conn), self.latent.data_ptr(), self.sem.data_ptr(), self.x2.data_ptr(), cfg.hidden, 2,
                                        self.conn_ws.data_ptr(), self.sp), "connectors")
 
-    def _seq_B1(self, cfg_scale):
+    def _seq_B1(self, cfg_scale, dn=None):
         """first half of _seq_B, up to the frame's audio (streaming delivery: the chunk's D2H copy goes out between the halves)"""
         lib, w, cfg = self.lib, self.w, self.cfg
+        if dn:
+            self._seq_noise()
         blob = w.state_blob()
         self._ck(lib.vv_copy_rows(blob.data_ptr(), blob.numel(), self._state_snap.data_ptr(), blob.numel(), 1, blob.numel(), self.sp), "snapshot")
         self._ck(lib.vv_head_sample(C.byref(w.head), self.hidden2.data_ptr(), cfg.hidden, self.noise_dev.data_ptr(),
@@ -449,14 +468,15 @@ class Engine:
         self._ck(lib.vv_connector_pair(C.byref(w.ac_conn), C.byref(w.sem_conn), self.latent.data_ptr(), self.sem.data_ptr(), self.x2.data_ptr(), cfg.hidden, 2,
                                        self.conn_ws.data_ptr(), self.sp), "connectors")
 
-    def _speech(self, cfg_scale: float, stage: bool) -> Optional[int]:
+    def _speech(self, cfg_scale: float, stage: bool, dn: bool = False) -> Optional[int]:
         """Phase B on the current stream.  stage: a consumer is waiting for the audio (AudioStreamer) - the frame runs as two graphs and the
         chunk's device -> pinned copy is enqueued BETWEEN them, as soon as the acoustic decoder has produced it: the chunk reaches the host
         ~0.5 ms earlier than behind the semantic encoder and the connectors (which only the NEXT step needs).  Returns the ring slot."""
+        key = (cfg_scale, "dn") if dn else (cfg_scale,)
         if not stage:
-            self._run("B", self._seq_B, cfg_scale)
+            self._run("B", self._seq_B, *key)
             return None
-        self._run("B1", self._seq_B1, cfg_scale)
+        self._run("B1", self._seq_B1, *key)
         k = self._ring_n % len(self._ring)
         self._ring_n += 1
         self._ring[k].copy_(self.wav, non_blocking=True)
@@ -590,16 +610,41 @@ class Engine:
             sh.copy_(sde_noise.reshape(self.n_steps, -1)[:, : self.cfg.latent])
             self.sde_noise_dev.copy_(sh, non_blocking=True)
 
-    def step_speech(self, noise: torch.Tensor, sde_noise: Optional[torch.Tensor] = None, stage: bool = False) -> Optional[int]:
+    def set_noise_seed(self, seed: int):
+        """Device noise: the 64-bit seed of the dialogue this engine runs next, once per sequence (after begin_sequence).  Every frame given a
+        `frame` index then draws its noise on the device as a function of (seed, frame) alone."""
+        s = int(seed) & (2 ** 64 - 1)
+        self.noise_seed_host[0] = s - 2 ** 64 if s >= 2 ** 63 else s      # the seed's 64 bits, held in an int64
+        with torch.cuda.stream(self.stream):
+            self.noise_seed_dev.copy_(self.noise_seed_host, non_blocking=True)
+
+    def _upload_frame(self, frame: int):
+        """Device noise: the index of the frame about to be enqueued - a 4-byte async copy in place of the noise rows (double-buffered pinned
+        word: the host runs up to a frame ahead)"""
+        self._frame_k ^= 1
+        fh = self.noise_frame_host[self._frame_k]
+        fh[0] = int(frame)
+        self.noise_frame_dev.copy_(fh, non_blocking=True)
+
+    def _noise_in(self, noise, sde_noise, frame) -> bool:
+        """what a frame's noise comes from: its index (device noise, True) or the host's rows (False)"""
+        if frame is not None:
+            self._upload_frame(frame)
+            return True
+        self._upload_noise(noise, sde_noise)
+        return False
+
+    def step_speech(self, noise: Optional[torch.Tensor], sde_noise: Optional[torch.Tensor] = None, stage: bool = False, frame: Optional[int] = None) -> Optional[int]:
         """Phase B.  `noise` is the CPU fp32 [latent] row the reference would have drawn (modeling_vibevoice_inference.py:699),
         `sde_noise` [n_steps, latent] the variance noise of the SDE solver's steps (dpm_solver.py:993-998), if that solver is set.
-        stage: also enqueue the chunk's copy to the pinned ring as soon as the decoder is done (see _speech); returns the slot."""
+        stage: also enqueue the chunk's copy to the pinned ring as soon as the decoder is done (see _speech); returns the slot.
+        frame: device noise (set_noise_seed) - the frame's index is uploaded instead and the rows are drawn inside the graph."""
         with torch.cuda.stream(self.stream):
-            self._upload_noise(noise, sde_noise)
-            return self._speech(float(self.cfg_scale), stage)
+            dn = self._noise_in(noise, sde_noise, frame)
+            return self._speech(float(self.cfg_scale), stage, dn)
 
-    def step_decode_speculative(self, tok_start: int, tok_diff: int, forced: Optional[int], noise: torch.Tensor,
-                                sde_noise: Optional[torch.Tensor] = None, on_enqueued=None, stage: bool = False, q=None) -> int:
+    def step_decode_speculative(self, tok_start: int, tok_diff: int, forced: Optional[int], noise: Optional[torch.Tensor],
+                                sde_noise: Optional[torch.Tensor] = None, on_enqueued=None, stage: bool = False, q=None, frame: Optional[int] = None) -> int:
         """Phase A, then phase B enqueued right behind it ON THE ASSUMPTION that the token is speech_diffusion (the steady state
         of a dialogue), then one host wait on the token alone.  The GPU therefore never idles between A and B while the host
         wakes up and decides; if the token turns out to be something else the caller rolls the speech state back
@@ -609,8 +654,8 @@ class Engine:
             self._phase_A(tok_start, tok_diff, q)
             self.token_host.copy_(self.token_dev, non_blocking=True)
             self._tok_event.record(self.stream)
-            self._upload_noise(noise, sde_noise)
-            self.spec_slot = self._speech(float(self.cfg_scale), stage)     # ring slot of the speculative frame's chunk (stage), or None
+            dn = self._noise_in(noise, sde_noise, frame)      # frame: device noise, as in step_speech
+            self.spec_slot = self._speech(float(self.cfg_scale), stage, dn)     # ring slot of the speculative frame's chunk (stage), or None
         if on_enqueued is not None:
             on_enqueued()          # e.g. hand the previous frame's audio to the streamer: it completes before this step's token
         self._tok_event.synchronize()
@@ -624,15 +669,19 @@ class Engine:
         except Exception:      # noqa: BLE001  (interpreter shutdown)
             pass
 
-    def decode_begin(self, tok_start: int, tok_diff: int, forced: Optional[int], spec_noise=None, q=None):
+    def decode_begin(self, tok_start: int, tok_diff: int, forced: Optional[int], spec_noise=None, q=None, spec_frame: Optional[int] = None):
         """Lock-step batches (one Engine per sample, one host loop): enqueue phase A - and, with `spec_noise` = (noise, sde_noise), the
-        speculative phase B behind it - without waiting; `decode_end` returns the token.  `q`: the token is drawn on the device (step_decode)."""
+        speculative phase B behind it - without waiting; `decode_end` returns the token.  `q`: the token is drawn on the device (step_decode).
+        spec_frame: the speculative phase B with device noise, drawn for that frame index."""
         with torch.cuda.stream(self.stream):
             self._set_forced(forced)
             self._phase_A(tok_start, tok_diff, q)
             self.token_host.copy_(self.token_dev, non_blocking=True)
             self._tok_event.record(self.stream)
-            if spec_noise is not None:
+            if spec_frame is not None:
+                self._upload_frame(spec_frame)
+                self._run("B", self._seq_B, float(self.cfg_scale), "dn")
+            elif spec_noise is not None:
                 self._upload_noise(*spec_noise)
                 self._run("B", self._seq_B, float(self.cfg_scale))
 

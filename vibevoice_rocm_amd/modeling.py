@@ -208,6 +208,7 @@ class _LaneDriver:
         for e in self.lanes[1:]:
             e.sync_in()
         self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
+        self.dn = False                     # set_noise_seeds: `eligible` / `speech` rows are (frame index, None), the lanes draw the noise
         self.pool = None
         if os.environ.get("VV_LANE_THREADS", "1") != "0":
             from concurrent.futures import ThreadPoolExecutor
@@ -225,6 +226,11 @@ class _LaneDriver:
     def set_sampler(self, temperature, top_k, top_p):
         for e in self.lanes:
             e.set_sampler(temperature, top_k, top_p)
+
+    def set_noise_seeds(self, seeds):
+        self.dn = True
+        for e, sd in zip(self.lanes, seeds):
+            e.set_noise_seed(sd)
 
     def first_tokens(self, live, forced, sample_fn, q=None):
         lanes, toks = self.lanes, {}
@@ -250,7 +256,10 @@ class _LaneDriver:
         def begin(s_):
             for b in live:
                 if b % LANES_IN_FLIGHT == s_:
-                    lanes[b].decode_begin(self.ST, self.SD, forced[b], eligible.get(b), q=q.get(b))
+                    if self.dn:
+                        lanes[b].decode_begin(self.ST, self.SD, forced[b], q=q.get(b), spec_frame=eligible[b][0] if b in eligible else None)
+                    else:
+                        lanes[b].decode_begin(self.ST, self.SD, forced[b], eligible.get(b), q=q.get(b))
         slots = sorted({b % LANES_IN_FLIGHT for b in live})
         if self.pool is not None and len(slots) > 1:
             list(self.pool.map(begin, slots))
@@ -280,7 +289,10 @@ class _LaneDriver:
 
     def speech(self, rows):
         for b, (n_row, s_row) in rows.items():
-            self.lanes[b].step_speech(n_row, s_row)
+            if self.dn:
+                self.lanes[b].step_speech(None, None, frame=n_row)
+            else:
+                self.lanes[b].step_speech(n_row, s_row)
 
     def chunk(self, b):
         with torch.cuda.stream(self.lanes[b].stream):
@@ -319,6 +331,7 @@ class _RowDriver:
             self.lanes = [model._lane(b) for b in range(B)]
         self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
         self.groups, self.at = [], {}          # (row batch, its dialogues); dialogue -> (row batch, index in it)
+        self.dn = False                        # set_noise_seeds: `eligible` / `speech` rows are (frame index, None), graph H draws the noise
         self.prefixes = [None] * B             # generate(voice_prefix=): dialogue -> VoicePrefix or None
 
     def begin(self, prompts, voices, max_steps, valid):
@@ -342,6 +355,11 @@ class _RowDriver:
     def set_sampler(self, temperature, top_k, top_p):
         for rb, _ in self.groups:
             rb.set_sampler(temperature, top_k, top_p)
+
+    def set_noise_seeds(self, seeds):
+        self.dn = True
+        for rb, idxs in self.groups:
+            rb.set_noise_seeds([seeds[b] for b in idxs])
 
     def first_tokens(self, live, forced, sample_fn, q=None):
         at, toks = self.at, {}
@@ -383,7 +401,10 @@ class _RowDriver:
         for rb, lv in plan:
             rb.decode_begin(ST, SD, {loc[b]: forced[b] for b in lv}, q={loc[b]: q[b] for b in lv if b in q})
             if all(b in eligible for b in lv):
-                rb.speech_begin([loc[b] for b in lv], {loc[b]: eligible[b][0] for b in lv}, {loc[b]: eligible[b][1] for b in lv} if self.sde else None)
+                if self.dn:
+                    rb.speech_begin([loc[b] for b in lv], None, None, frames={loc[b]: eligible[b][0] for b in lv})
+                else:
+                    rb.speech_begin([loc[b] for b in lv], {loc[b]: eligible[b][0] for b in lv}, {loc[b]: eligible[b][1] for b in lv} if self.sde else None)
                 speculated.update(lv)
         deliver()                      # the previous step's chunks (their copies completed long ago), before the host waits for a sampler
         for rb, lv in plan:
@@ -416,7 +437,10 @@ class _RowDriver:
             mine = [b for b in idxs if b in rows]
             if mine:
                 loc = {b: self.at[b][1] for b in mine}
-                rb.speech([loc[b] for b in mine], {loc[b]: rows[b][0] for b in mine}, {loc[b]: rows[b][1] for b in mine} if self.sde else None)
+                if self.dn:
+                    rb.speech([loc[b] for b in mine], None, None, frames={loc[b]: rows[b][0] for b in mine})
+                else:
+                    rb.speech([loc[b] for b in mine], {loc[b]: rows[b][0] for b in mine}, {loc[b]: rows[b][1] for b in mine} if self.sde else None)
         for rb, _ in self.groups:
             rb.flush()                 # the conv tails are enqueued from worker threads: the chunk copies must queue behind them
 
@@ -441,7 +465,7 @@ class _RowDriver:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
-                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False):
+                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False):
         # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
         # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
         # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
@@ -473,6 +497,11 @@ class VibeVoiceForConditionalGenerationInference:
         # speculative frame launch as for greedy decoding.  Seeded calls keep their tokens and the generator its state.  Off by default;
         # generate(..., device_sampling=...) overrides it per call
         self.device_sampling = bool(device_sampling)
+        # diffusion noise drawn on the device (vv_noise_normal at the head of the frame's graph) as a function of (the dialogue's noise_seed,
+        # frame, solver step, element) instead of torch.randn on the host in the reference's order: nothing but a frame index is uploaded, every
+        # batched call may speculate its frames, and a dialogue sounds the same alone and in a batch.  Same distribution, another sequence than
+        # the reference's RNG stream.  Off by default; generate(..., device_noise=..., noise_seed=...) overrides it per call
+        self.device_noise = bool(device_noise)
         # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         self.weight_quant = weight_quant
@@ -525,7 +554,7 @@ class VibeVoiceForConditionalGenerationInference:
             device = "cuda:0"
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
                    use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
-                   device_sampling=kw.get("device_sampling", False))
+                   device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -661,12 +690,19 @@ class VibeVoiceForConditionalGenerationInference:
         sde_noise = kwargs.get("sde_noise")                  # extension: injected variance noise of the SDE solver [F, n_steps, latent]
         noise = None if noise is None else torch.as_tensor(noise)
         sde_noise = None if sde_noise is None else torch.as_tensor(sde_noise)
+        device_noise = bool(kwargs.get("device_noise", self.device_noise))      # extension: the diffusion noise is drawn on the device
+        noise_seed = kwargs.get("noise_seed")                # with it: an int (dialogue b: seed + b), one int per dialogue, or None (drawn)
+        if device_noise and (noise is not None or sde_noise is not None):
+            raise ValueError("device_noise=True draws the diffusion noise on the device: noise= / sde_noise= cannot be injected with it")
+        if noise_seed is not None and not device_noise:
+            raise ValueError("noise_seed= seeds the device-side noise: it needs device_noise=True")
         input_ids = torch.as_tensor(input_ids)
         in_dev = input_ids.device                            # callers may hand over device tensors (the reference moves them itself, modeling_vibevoice_inference.py:288,305-307)
         input_ids = input_ids.cpu()                          # ids / masks drive host-side bookkeeping only
         if input_ids.dim() == 1:
             input_ids = input_ids[None]
         B, Lp = input_ids.shape
+        noise_seeds = self._noise_seeds(noise_seed, B) if device_noise else None      # None: the call's first draw from the CPU generator
         attention_mask = torch.ones_like(input_ids) if attention_mask is None else torch.as_tensor(attention_mask).cpu()
         if speech_input_mask is not None:
             speech_input_mask = torch.as_tensor(speech_input_mask).cpu()
@@ -699,7 +735,7 @@ class VibeVoiceForConditionalGenerationInference:
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
                                        sample_fn=sample_fn, sampler=sampler, speculate=self.speculative_frames and self._use_graphs, return_speech=return_speech,
-                                       in_dev=in_dev)
+                                       in_dev=in_dev, noise_seeds=noise_seeds)
             try:
                 return batchloop.run(driver, input_ids, attention_mask, speech_input_mask, conn_all, call)
             finally:
@@ -713,10 +749,23 @@ class VibeVoiceForConditionalGenerationInference:
                 conn = conn_all[: int(sp.sum())]
         r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
                                stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler,
-                               prefix=None if vps is None else vps[0])
+                               prefix=None if vps is None else vps[0], noise_seed=None if noise_seeds is None else noise_seeds[0])
         if audio_streamer is not None:
             audio_streamer.end()
         return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
+
+    @staticmethod
+    def _noise_seeds(noise_seed, B: int) -> List[int]:
+        """generate(device_noise=True, noise_seed=): the B dialogues' 64-bit seeds.  An int: dialogue b uses (seed + b) mod 2^64; a list of B
+        ints: one each; None: B draws from torch's default CPU generator, so torch.manual_seed makes the call reproducible."""
+        if noise_seed is None:
+            return [int(v) for v in torch.randint(0, 2 ** 62, (B,))]
+        if isinstance(noise_seed, (list, tuple)) or (isinstance(noise_seed, (torch.Tensor, np.ndarray)) and noise_seed.ndim > 0):
+            seeds = [int(v) % 2 ** 64 for v in noise_seed]
+            if len(seeds) != B:
+                raise ValueError(f"noise_seed: {len(seeds)} seeds for {B} dialogues (an int, or one int per dialogue)")
+            return seeds
+        return [(int(noise_seed) + b) % 2 ** 64 for b in range(B)]
 
     def _apply_voice_prefixes(self, vps, input_ids, attention_mask, speech_input_mask, speech_tensors, speech_masks, speech_noise):
         """generate(voice_prefix=): every dialogue with a prefix is checked against it (VP.check: ValueError naming what differs) and loses its
@@ -780,15 +829,16 @@ class VibeVoiceForConditionalGenerationInference:
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
                       noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None,
-                      prefix: Optional[VoicePrefix] = None):
+                      prefix: Optional[VoicePrefix] = None, noise_seed: Optional[int] = None):
         eng, cfg = self.engine, self.config
+        dn = noise_seed is not None         # device noise: the engine draws frame f's noise from (noise_seed, f); draw / pending_nz / rewind are not used
         nv = len(set(batchloop.valid_token_ids(special)))
         if sampler is not None:
             eng.set_sampler(*sampler)
         # device-side do_sample with drawn noise: a speculated frame's noise is drawn BEFORE its token is known.  Kept for the next frame after
         # a mis-speculation (the greedy rule) it would sit in front of the token draws in between and reorder the generator's sequence, so the
         # generator is put back to where it stood before the noise draw and the rows are dropped
-        rewind = sampler is not None and (noise is None or (eng.sde and sde_noise is None))
+        rewind = not dn and sampler is not None and (noise is None or (eng.sde and sde_noise is None))
 
         def draw(frame):
             """The frame's random draws, in the reference's order: randn(2, latent) for the initial latent (:699), then - SDE solver
@@ -807,6 +857,8 @@ class VibeVoiceForConditionalGenerationInference:
         max_length, max_steps = batchloop.limits(cfg.max_pos, L0, max_new_tokens, max_length_times)
         eng.cfg_scale = float(cfg_scale)
         eng.begin_sequence(L0 + max(max_steps, 1) + 8, batchloop.valid_token_ids(special))
+        if dn:
+            eng.set_noise_seed(noise_seed)
         # prefix: its P positions come out of the store; only the rows after it are embedded and prefilled (every voice row lies inside it)
         x0 = _embed_prompt(eng, ids, None if conn is None else (sp_mask, conn)) if prefix is None else _embed_prompt(eng, ids[prefix.P:], None)
         seq = ids.tolist()
@@ -849,6 +901,13 @@ class VibeVoiceForConditionalGenerationInference:
                 tok = eng.first_token(ST_dev, SD, forced, sample_fn, q=q)
                 if tok == SD or not refresh_negative:
                     eng.commit_negative_prompt()         # the branch is in use from step 0 on (otherwise the row is overwritten by the next speech_start)
+            elif dn and speculate and prev_tok == SD:
+                # device noise: the speculated frame draws from its index; after a mis-speculation the next real frame has the same index and so
+                # the same noise - nothing to keep, nothing to rewind
+                tok = eng.step_decode_speculative(ST_dev, SD, forced, None, None, on_enqueued=hook, stage=audio_streamer is not None, q=q, frame=frame)
+                speculated = True
+                if tok != SD:
+                    eng.rollback_speech_state()
             elif speculate and prev_tok == SD and (pending_nz is not None or ((noise is None or frame < len(noise)) and
                                                                             (sde_noise is None or frame < len(sde_noise)))):
                 # steady state of a dialogue: the frame's diffusion tail is enqueued right behind the LLM step, the host waits
@@ -880,7 +939,9 @@ class VibeVoiceForConditionalGenerationInference:
                     eng.reset_speech_caches()
             if tok == SD:                                                                       # :571-670
                 slot = eng.spec_slot if speculated else None
-                if not speculated:
+                if not speculated and dn:
+                    slot = eng.step_speech(None, None, stage=audio_streamer is not None, frame=frame)
+                elif not speculated:
                     if pending_nz is None:
                         pending_nz = draw(frame)
                     slot = eng.step_speech(*pending_nz, stage=audio_streamer is not None)

@@ -81,6 +81,8 @@ class RowBatch:
             self.logits_host = torch.zeros(B, 8, dtype=torch.float32).pin_memory()
             self.q_dev = torch.ones(B, 8, **f32)          # device-side do_sample: every dialogue's exponential draws of the step
             self.noise_dev = torch.zeros(B, cfg.latent, **f32)
+            self.noise_seed_dev = torch.zeros(B, dtype=torch.int64, device=self.device)      # device noise: every dialogue's 64-bit seed (its bits)
+            self.noise_frame_dev = torch.zeros(B, **i32)                                       # and the index of the frame it draws next
             self.latent = torch.zeros(B, cfg.latent, **f32)
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
         self._pf_ws = None
@@ -90,6 +92,9 @@ class RowBatch:
         self.active_host = torch.ones(B, dtype=torch.int32).pin_memory()
         self.noise_host = torch.zeros(2, B, cfg.latent, dtype=torch.float32).pin_memory()
         self._noise_k = 0
+        self.noise_seed_host = torch.zeros(B, dtype=torch.int64).pin_memory()
+        self.noise_frame_host = torch.zeros(2, B, dtype=torch.int32).pin_memory()      # double-buffered like the noise rows
+        self._frame_k = 0
         self.q_host = torch.ones(2, B, 8, dtype=torch.float32).pin_memory()
         self._q_k = 0
         self._sampler, self._sampler_key = None, None
@@ -267,6 +272,15 @@ class RowBatch:
         self._sampler_key = (float(temperature), int(top_k), float(top_p))
         self._sampler = L.Sampler(*self._sampler_key)
 
+    def set_noise_seeds(self, seeds: List[int]):
+        """Device noise: the B dialogues' 64-bit seeds, once per batch (after begin); speech / speech_begin given `frames` then draw the noise of
+        every row inside graph H (Engine.set_noise_seed)."""
+        for b, sd in enumerate(seeds):
+            v = int(sd) & (2 ** 64 - 1)
+            self.noise_seed_host[b] = v - 2 ** 64 if v >= 2 ** 63 else v
+        with torch.cuda.stream(self.stream):
+            self.noise_seed_dev.copy_(self.noise_seed_host, non_blocking=True)
+
     def _upload_q(self, q: Dict[int, torch.Tensor]):
         """{dialogue: its exponential draws [nv]} -> q_dev through a pinned double-buffered [B][8] row (the other dialogues' rows are not read
         for a choice that counts: they are forced or finished)"""
@@ -370,8 +384,14 @@ class RowBatch:
                                             self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(),
                                             self.active_dev.data_ptr(), self.sp), "vv_llm_tail_batch")
 
-    def _seq_H(self, cfg_scale):
+    def _seq_H(self, cfg_scale, dn=None):
+        """dn == "dn": the noise of all B rows is drawn on the device first, from (noise_seed_dev, noise_frame_dev) - the rows of dialogues that
+        do not diffuse are drawn from whatever index they hold and dropped, as their samples are.  The marker is part of the graph's key."""
         eng, cfg = self.main, self.cfg
+        if dn:
+            self._ck(self.lib.vv_noise_normal(self.noise_dev.data_ptr(), cfg.latent, self.sde_noise_dev.data_ptr() if self.sde else None,
+                                              eng.n_steps * cfg.latent, self.B, cfg.latent, eng.n_steps if self.sde else 0,
+                                              self.noise_seed_dev.data_ptr(), self.noise_frame_dev.data_ptr(), self.sp), "vv_noise_normal")
         if self.sde:
             self._ck(self.lib.vv_head_sample_batch_sde(C.byref(eng.w.head), self.hidden.data_ptr(), cfg.hidden, self.noise_dev.data_ptr(), cfg.latent,
                                                        eng.temb.data_ptr(), eng._coefs, eng.n_steps, cfg_scale, self.latent.data_ptr(), cfg.latent, self.B,
@@ -464,14 +484,35 @@ class RowBatch:
             self._run("A2", self._seq_A2, int(tok_start), int(tok_diff))
             self._tok_event.record(self.stream)
 
-    def speech(self, which: List[int], noise: Dict[int, torch.Tensor], sde_noise: Optional[Dict[int, torch.Tensor]] = None):
+    def speech(self, which: List[int], noise: Optional[Dict[int, torch.Tensor]], sde_noise: Optional[Dict[int, torch.Tensor]] = None,
+               frames: Optional[Dict[int, int]] = None):
         """Diffusion sampling for the whole batch (graph H), then the conv tail of the dialogues in `which`, each on its own stream."""
-        self.speech_begin(which, noise, sde_noise)
+        self.speech_begin(which, noise, sde_noise, frames)
         self.speech_tails(which)
 
-    def speech_begin(self, which: List[int], noise: Dict[int, torch.Tensor], sde_noise: Optional[Dict[int, torch.Tensor]] = None):
-        """noise upload (the SDE solver: with every step's variance noise [n_steps, latent] per dialogue) + graph H on the main stream"""
+    def _speech_begin_dn(self, which: List[int], frames: Dict[int, int]):
+        """device noise: the frame indices of the dialogues in `which` (4 B bytes, the others keep theirs) + the graph H that draws first"""
+        with torch.cuda.stream(self.stream):
+            prev = self.noise_frame_host[self._frame_k]
+            self._frame_k ^= 1
+            fh = self.noise_frame_host[self._frame_k]
+            fh.copy_(prev)
+            for b in which:
+                fh[b] = int(frames[b])
+            self.noise_frame_dev.copy_(fh, non_blocking=True)
+            self._run("H", self._seq_H, float(self.cfg_scale), "dn")
+            self._head_event.record(self.stream)
+            if self._timing is not None and self._tcur is not None:
+                self._tcur["h1"] = torch.cuda.Event(enable_timing=True)
+                self._tcur["h1"].record(self.stream)
+
+    def speech_begin(self, which: List[int], noise: Optional[Dict[int, torch.Tensor]], sde_noise: Optional[Dict[int, torch.Tensor]] = None,
+                     frames: Optional[Dict[int, int]] = None):
+        """noise upload (the SDE solver: with every step's variance noise [n_steps, latent] per dialogue) + graph H on the main stream.
+        frames = {dialogue: frame index}: device noise (set_noise_seeds) - nothing but the indices is uploaded."""
         cfg = self.cfg
+        if frames is not None:
+            return self._speech_begin_dn(which, frames)
         if self.sde and (sde_noise is None or any(b not in sde_noise or sde_noise[b] is None for b in which)):
             raise L.VVError("the SDE solver needs the per-step variance noise [n_steps, latent] of every diffusing dialogue")
         with torch.cuda.stream(self.stream):
