@@ -101,6 +101,11 @@ typedef struct vv_lin_args {
 } vv_lin_args;
 
 int vv_linear(const vv_lin_args* a, vv_stream_t stream);
+/* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
+ * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
+ * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>"; otherwise "skinny", "gemm_f32" or,
+ * for m <= 8, "gemv".  Arguments vv_linear refuses return the same error. */
+int vv_linear_route(const vv_lin_args* a, char* name, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Qwen2 attention pieces (third-party math: transformers.models.qwen2.modeling_qwen2; reference call sites

@@ -375,9 +375,13 @@ def test_block_mid_two_launches_vs_torch(lib, C_, T):
                                         (1024, 256, 1024, False), (2500, 128, 512, False), (1300, 384, 96, True),
                                         (330, 1536, 8960, False), (203, 2048, 8192, False), (65, 3072, 2048, False), (203, 64, 14336, False), (64, 192, 8192, False)])
 def test_prefill_gemm_bf16_activations(lib, m, n, k, dual):
-    """vv_linear with VV_LIN_X_BF16 at prompt sizes (the direct-stream matrix-core GEMM of the prefill, 128-row strips) and at
-    voice-prompt sizes (>= 1024 rows: the 128 x 128 LDS-tiled GEMM; long K on few tiles: its 64 x 64 variant): bias / SwiGLU / residual epilogues against torch on the same
-    bf16 operands."""
+    """vv_linear with VV_LIN_X_BF16 at prompt and voice-prompt sizes: bias / SwiGLU / residual epilogues against torch on the same bf16 operands.
+    At today's thresholds (vv_linear_route) the cases reach four kernels: the 64 x 64 LDS-tiled GEMM - mfma_tiled<dual=0,bk=128,tm=64> for every
+    non-dual case with K >= 1024 and n % 128 == 0 (the narrow long-K entry for n = 64 / 192), mfma_tiled<dual=1,bk=64,tm=64> for
+    (200, 8960, 1536) and mfma_tiled<dual=1,bk=32,tm=64> for (1300, 384, 96) - and the direct-stream kernel with one 32-row tile per
+    workgroup: mfma_stream<dual=0,ksplit=0,xb=1,mt=1> for (128, 128, 32), <dual=1,ksplit=0,xb=1,mt=1> for (513, 256, 96) and
+    <dual=0,ksplit=1,xb=1,mt=1> for (1024, 256, 1024) and (2500, 128, 512).  The 128-row-strip (mt=4) kernel, the 128 x 128 tiles and every other
+    instantiation are pinned, per output tile, by tests/test_hip_mfma_gemm.py; this test stays as the wide-shape net."""
     L = lib
     l = L.load()
     g = torch.Generator().manual_seed(m + n + k)

@@ -57,6 +57,13 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
                  vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr);
                  // vv_kernels.hip: f1 / f2 = fragment-major copies of a->w / a->w2 or null; with fp8 companions q1 / q2 (q != NULL) of the fp8 codes
 int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s);     // vv_mfma_gemm.hip: 1 launched, 0 not covered, <0 error
+// the kernel of vv_mfma_gemm.hip a call takes, decided apart from the launch (vv_linear_route reports it without launching): kind 0 = not covered,
+// < 0 = error; stream: mfma_linear_kernel<dual, ksplit, xb, mt>, tiled: mfma_tiled_kernel<dual, bk, tm>
+enum { VV_MFMA_STREAM = 1, VV_MFMA_TILED = 2 };
+struct vv_mfma_route { int kind, dual, ksplit, xb, mt, bk, tm; };
+vv_mfma_route vv_mfma_decide(const vv_lin_args& a);
+int vv_launch_mfma_route(const vv_lin_args& a, const vv_mfma_route& r, hipStream_t s);   // 1 launched, < 0 error
+int vv_mfma_route_name(const vv_mfma_route& r, char* name, int cap);
 int vv_mfma_gemm_init();
 // vv_attn_decode.hip: bf16 KV cache, head_dim 128; part / tickets = split-key workspace ([R, heads, nsplit, 130] floats, [R, heads] zeroed ints) or null
 // part_cap: splits the partials workspace has room for (>= nsplit); the grouped kernel may use more splits than the per-head kernel's nsplit
@@ -102,6 +109,7 @@ void vv_convffn_set_rows(int c, int rows);
 void vv_convffn_set_c128(int on);
 bool vv_convffn_prefers(int wdt, int T, int C);
 int vv_launch_skinny(const vv_lin_args& a, hipStream_t s);       // resampling convs of a streaming frame: 1 launched, 0 not covered
+bool vv_skinny_covers(const vv_lin_args& a);                      // what vv_launch_skinny would launch (the same predicate, no launch)
 void vv_skinny_set(int on, int min_m, int max_m);
 int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s);
 

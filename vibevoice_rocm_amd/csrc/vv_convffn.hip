@@ -563,10 +563,16 @@ void vv_convffn_set_c128(int on) { g_c128 = on; }
 bool vv_convffn_prefers(int wdt, int T, int C) { return g_on && g_c128 && wdt == VV_BF16 && C == 128 && T >= 3 && T <= 1024; }
 void vv_skinny_set(int on, int min_m, int max_m) { g_skinny = on; if (min_m > 0) g_skinny_min_m = min_m; if (max_m > 0) g_skinny_max_m = max_m; }
 
+// what vv_launch_skinny covers (it and the route query share this predicate)
+bool vv_skinny_covers(const vv_lin_args& a) {
+  if (!g_skinny || a.wdt != VV_BF16 || a.w2 || a.pro != VV_PRO_NONE || a.act != VV_ACT_NONE || a.gate || a.res || a.mod_scale || a.flags) return false;
+  if (a.m < g_skinny_min_m || a.m > g_skinny_max_m || a.n % 16 || a.ldx % 4 || a.ldx == 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return false;
+  return a.k == 128 || a.k == 256 || a.k == 512 || a.k == 1024 || a.k == 2048 || a.k == 2560 || a.k == 5120;
+}
+
 // 1 = launched, 0 = not covered
 int vv_launch_skinny(const vv_lin_args& a, hipStream_t s) {
-  if (!g_skinny || a.wdt != VV_BF16 || a.w2 || a.pro != VV_PRO_NONE || a.act != VV_ACT_NONE || a.gate || a.res || a.mod_scale || a.flags) return 0;
-  if (a.m < g_skinny_min_m || a.m > g_skinny_max_m || a.n % 16 || a.ldx % 4 || a.ldx == 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return 0;
+  if (!vv_skinny_covers(a)) return 0;
   dim3 grid(a.n / 16, (a.m + 15) / 16);
   const bf16_t* W = reinterpret_cast<const bf16_t*>(a.w);
 #define VV_SK(NSTV, NBV) hipLaunchKernelGGL((skinny_kernel<NSTV, NBV>), grid, dim3(256), 0, s, a.x, a.ldx, a.m, W, a.k, a.bias, a.out, a.ldo)

@@ -531,13 +531,28 @@ static int launch_gemv_m(const vv_lin_args& a, hipStream_t s) {
   }
 }
 
+// The kernel family a bf16 / fp32-weight vv_linear call takes: decided here for the launch below and for vv_linear_route alike.  < 0 = error.
+enum { LIN_FAM_SKINNY = 1, LIN_FAM_GEMV, LIN_FAM_MFMA, LIN_FAM_GEMM_F32 };
+static int linear_family(const vv_lin_args& a, vv_mfma_route* r) {
+  if (vv_skinny_covers(a)) return LIN_FAM_SKINNY;                // a few rows x K = 512..2560, plain epilogue: the resampling convs (vv_convffn.hip)
+  if (a.m <= 8) return LIN_FAM_GEMV;
+  *r = vv_mfma_decide(a);                                        // bf16 weights: matrix-core path
+  if (r->kind < 0) return r->kind;
+  if (r->kind > 0) return LIN_FAM_MFMA;
+  if (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: bf16 hand-off not covered for this shape/alignment");
+  return LIN_FAM_GEMM_F32;
+}
+
 template <typename WT>
 static int launch_linear(const vv_lin_args& a, hipStream_t s) {
   const bool dual = a.w2 != nullptr;
   const size_t wsz = sizeof(WT);
   const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!dual || (uintptr_t)a.w2 % 16 == 0);
-  if (vv_launch_skinny(a, s)) return 0;                          // a few rows x K = 512..2560, plain epilogue: the resampling convs (vv_convffn.hip)
-  if (a.m <= 8) {
+  vv_mfma_route route = {};
+  const int fam = linear_family(a, &route);
+  if (fam < 0) return fam;
+  if (fam == LIN_FAM_SKINNY) return vv_launch_skinny(a, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: skinny GEMM declined its own route");
+  if (fam == LIN_FAM_GEMV) {
     if (a.m > 2 && g_rows_part) {                               // 3..8 rows on the matrix cores (process-wide scratch: see rows_scratch)
       const int rc = vv_launch_gemv_rows(a, g_rows_part, G_ROWS_PART_FLOATS, g_rows_tk, G_ROWS_TICKETS, s);
       if (rc) return rc < 0 ? rc : 0;
@@ -567,11 +582,9 @@ static int launch_linear(const vv_lin_args& a, hipStream_t s) {
     hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3(blocks), dim3(GEMV_THREADS), 0, s, a);
     return 0;
   }
-  {
-    const int rc = vv_launch_mfma_gemm(a, s);     // bf16 weights: matrix-core path
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-    if (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: bf16 hand-off not covered for this shape/alignment");
+  if (fam == LIN_FAM_MFMA) {
+    const int rc = vv_launch_mfma_route(a, route, s);
+    return rc < 0 ? rc : 0;
   }
   const bool vec = (a.k % 4 == 0) && (a.ldx % 4 == 0) && ((uintptr_t)a.x % 16 == 0) && w_al16;
   const long big_tiles = (long)((a.n + 63) / 64) * ((a.m + 63) / 64);
@@ -635,7 +648,7 @@ extern "C" int vv_prof_end(vv_prof_entry* out, int max_out, int* n_out) {
   return 0;
 }
 
-extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
+static int linear_check_args(const vv_lin_args* a) {
   if (!a || !a->x || !a->w || !a->out) return vv_set_error(VV_E_ARG, "vv_linear: null pointer");
   if (a->m <= 0 || a->n <= 0 || a->k <= 0) return vv_set_error(VV_E_ARG, "vv_linear: bad shape m=%d n=%d k=%d", a->m, a->n, a->k);
   if (a->act == VV_ACT_SWIGLU && !a->w2) return vv_set_error(VV_E_ARG, "vv_linear: SWIGLU needs w2");
@@ -653,6 +666,29 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
     return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..8 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
     return vv_set_error(VV_E_ARG, "vv_linear: bf16 activation hand-off needs bf16 weights, m > 8 and k %% 16 == 0");
+  return 0;
+}
+
+// The kernel family vv_linear would launch for these arguments under the current vv_tune state, by the same decisions (linear_check_args,
+// linear_family, vv_mfma_decide): host only, nothing is launched and no pointer is followed.  An argument set vv_linear refuses is refused here too.
+extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_linear_route: no room for the name");
+  name[0] = 0;
+  VV_TRY(linear_check_args(a));
+  if (a->wdt == VV_F32 || a->wdt == VV_BF16) {
+    vv_mfma_route route = {};
+    const int fam = linear_family(*a, &route);
+    if (fam < 0) return fam;
+    if (fam == LIN_FAM_MFMA) vv_mfma_route_name(route, name, cap);
+    else snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : fam == LIN_FAM_GEMV ? "gemv" : "gemm_f32");
+    return 0;
+  }
+  if ((a->wdt == VV_FP8 || a->wdt == VV_NF4) && a->m <= 8) { snprintf(name, (size_t)cap, "gemv"); return 0; }
+  return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_route: no kernel for wdt=%d m=%d", a->wdt, a->m);
+}
+
+extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
+  VV_TRY(linear_check_args(a));
   hipStream_t s = (hipStream_t)stream;
   int rc;
   ProfRec pr;

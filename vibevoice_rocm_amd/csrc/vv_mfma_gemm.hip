@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "vv_hip.h"
 #include "vv_common.h"
@@ -465,49 +466,48 @@ int launch_mt(const vv_lin_args& a, hipStream_t s, int mt) {
   return launch<DUAL, KSPLIT, XB, 1>(a, s);
 }
 
+template <bool DUAL, int BK, int TM>
+void launch_tiled(const vv_lin_args& a, hipStream_t s) {
+  dim3 grid(a.n / TM, (a.m + TM - 1) / TM);
+  constexpr size_t lds = tiled_lds<DUAL, BK, TM>();
+  hipLaunchKernelGGL((mfma_tiled_kernel<DUAL, BK, TM>), grid, dim3(256), lds, s, a);
+}
+
+vv_mfma_route tiled_route(bool dual, int bk, int tm) {
+  vv_mfma_route r = {};
+  r.kind = VV_MFMA_TILED; r.dual = dual; r.xb = 1; r.bk = bk; r.tm = tm;
+  return r;
+}
+
 }  // namespace
 
-// 1 = launched, 0 = shape/alignment not covered (caller falls back to the fp32 VALU GEMM), < 0 = error
-int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s) {
+// The one place that chooses a kernel of this file: kind 0 = shape/alignment not covered (the caller falls back to the fp32 VALU GEMM),
+// < 0 = error (vv_last_error set), else the instantiation vv_launch_mfma_route starts.  Host only: no launch, no device access.
+vv_mfma_route vv_mfma_decide(const vv_lin_args& a) {
+  vv_mfma_route r = {};
   const bool xb = (a.flags & VV_LIN_X_BF16) != 0;
-  if (a.wdt != VV_BF16 || a.m <= 8 || a.k % 16 || a.ldx % (xb ? 8 : 4)) return 0;
-  if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16) return 0;
-  if (xb && a.pro != VV_PRO_NONE) return vv_set_error(VV_E_ARG, "vv_linear: a bf16 x takes no prologue");
-  if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
-  if ((a.k * 2) % 16) return 0;
+  if (a.wdt != VV_BF16 || a.m <= 8 || a.k % 16 || a.ldx % (xb ? 8 : 4)) return r;
+  if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16) return r;
+  if (xb && a.pro != VV_PRO_NONE) { r.kind = vv_set_error(VV_E_ARG, "vv_linear: a bf16 x takes no prologue"); return r; }
+  if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
+  if ((a.k * 2) % 16) return r;
   // the tiled kernel needs enough 128 x 128 tiles to occupy the chip's memory system (prefill: 36-210, voice-prompt encode: hundreds,
   // hoisted adaLN: 36); a conv-stage GEMM with 4 tiles stays on the streaming kernel (T = 200, C = 256: 8 us there, 25 us tiled)
-  const bool enough_tiles = (long)(a.n / TG_BN) * ((a.m + TG_BM - 1) / TG_BM) >= 24;
+  const long tiles = (long)(a.n / TG_BN) * ((a.m + TG_BM - 1) / TG_BM);
+  const bool enough_tiles = tiles >= 24;
   // a narrow output over a very long K (the 2048 -> 64 head conv of a whole-utterance encode: K = 14336, 203 rows): a handful of
   // 64 x 64 tiles, each a fast 128-column-slab K loop, instead of 14 streaming workgroups walking K in 16-element steps (216 -> 50 us)
   if (g_tiled_rows > 0 && g_tiled_small > 0 && xb && !a.w2 && !enough_tiles && a.m >= 64 && a.n % 64 == 0 && a.k % 128 == 0 && a.k >= 8192 &&
-      a.ldx % 8 == 0) {
-    dim3 gq(a.n / 64, (a.m + 63) / 64);
-    hipLaunchKernelGGL((mfma_tiled_kernel<false, 128, 64>), gq, dim3(256), tiled_lds_q(), s, a);
-    return 1;
-  }
+      a.ldx % 8 == 0)
+    return tiled_route(false, 128, 64);
   if (g_tiled_rows > 0 && xb && a.m >= g_tiled_rows && enough_tiles && a.n % TG_BN == 0 && a.k % 32 == 0 && a.ldx % 8 == 0 && a.m <= 65535 * TG_BM) {
-    dim3 grid(a.n / TG_BN, (a.m + TG_BM - 1) / TG_BM);
-    const size_t lds_d = tiled_lds<true, 32>(), lds_l = tiled_lds<false, 128>(), lds_s = tiled_lds<false, 32>();
-    const size_t lds_q = tiled_lds<false, 128, 64>(), lds_qd = tiled_lds<true, 32, 64>(), lds_qd64 = tiled_lds<true, 64, 64>();
     // a long-K GEMM on a few dozen 128 x 128 tiles (prefill down-projection: 36 tiles x 70 K rounds; the T = 200 stage of a voice-
     // prompt encode: 32 tiles x 64 rounds) leaves most CUs idle behind a serial K loop: 64 x 64 tiles give 4x the workgroups,
     // each with a quarter of the MFMA / LDS work per round and a 4-slab-deep register prefetch
-    if (a.w2 && (long)grid.x * grid.y < g_tiled_small_dual) {
-      dim3 gq(a.n / 64, (a.m + 63) / 64);
-      if (a.k % 64 == 0 && g_tiled_dual_bk64) hipLaunchKernelGGL((mfma_tiled_kernel<true, 64, 64>), gq, dim3(256), lds_qd64, s, a);
-      else hipLaunchKernelGGL((mfma_tiled_kernel<true, 32, 64>), gq, dim3(256), lds_qd, s, a);
-      return 1;
-    }
-    if (!a.w2 && g_tiled_small > 0 && a.k % 128 == 0 && a.k >= g_tiled_small_k && (long)grid.x * grid.y < g_tiled_small) {
-      dim3 gq(a.n / 64, (a.m + 63) / 64);
-      hipLaunchKernelGGL((mfma_tiled_kernel<false, 128, 64>), gq, dim3(256), lds_q, s, a);
-      return 1;
-    }
-    if (a.w2) hipLaunchKernelGGL((mfma_tiled_kernel<true, 32, 128>), grid, dim3(256), lds_d, s, a);
-    else if (a.k % 128 == 0 && g_tiled_bk128) hipLaunchKernelGGL((mfma_tiled_kernel<false, 128, 128>), grid, dim3(256), lds_l, s, a);
-    else hipLaunchKernelGGL((mfma_tiled_kernel<false, 32, 128>), grid, dim3(256), lds_s, s, a);
-    return 1;
+    if (a.w2 && tiles < g_tiled_small_dual) return tiled_route(true, (a.k % 64 == 0 && g_tiled_dual_bk64) ? 64 : 32, 64);
+    if (!a.w2 && g_tiled_small > 0 && a.k % 128 == 0 && a.k >= g_tiled_small_k && tiles < g_tiled_small) return tiled_route(false, 128, 64);
+    if (a.w2) return tiled_route(true, 32, 128);
+    return tiled_route(false, (a.k % 128 == 0 && g_tiled_bk128) ? 128 : 32, 128);
   }
   // rows per workgroup.  MT > 1 (each weight fragment reused by MT 32-row tiles) was measured SLOWER on every shape of this
   // path on MI355X (19.8 vs 23.4 audio-s/s, first chunk 55 vs 51 ms): these GEMMs are latency bound, and fewer / fatter
@@ -517,19 +517,51 @@ int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s) {
   int mt = 1;
   if (g_mt_override > 0) mt = g_mt_override;
   else if (a.m >= 128 && a.k >= 1024 && a.n >= 1024) mt = xb ? g_mt_prefill_xb : g_mt_prefill;
+  mt = mt == 4 ? 4 : mt == 2 ? 2 : 1;
   const long nblocks = (a.n + 31) / 32, rtiles = (a.m + 32 * mt - 1) / (32 * mt);
   // a wave's K loop is a serial chain of 16-element steps: split K over the workgroup's 4 waves whenever K is long, or when
   // there are too few tiles to fill the chip anyway
-  const bool ksplit = a.k >= 512 || ((nblocks * rtiles < 256) && a.k >= 128);
+  r.kind = VV_MFMA_STREAM; r.dual = a.w2 != nullptr; r.xb = xb; r.mt = mt;
+  r.ksplit = a.k >= 512 || ((nblocks * rtiles < 256) && a.k >= 128);
+  return r;
+}
+
+// starts what vv_mfma_decide chose: 1 = launched, < 0 = error
+int vv_launch_mfma_route(const vv_lin_args& a, const vv_mfma_route& r, hipStream_t s) {
+  if (r.kind == VV_MFMA_TILED) {
+    if (r.dual) {
+      if (r.tm == 128) launch_tiled<true, 32, 128>(a, s);
+      else if (r.bk == 64) launch_tiled<true, 64, 64>(a, s);
+      else launch_tiled<true, 32, 64>(a, s);
+    } else {
+      if (r.tm == 64) launch_tiled<false, 128, 64>(a, s);
+      else if (r.bk == 128) launch_tiled<false, 128, 128>(a, s);
+      else launch_tiled<false, 32, 128>(a, s);
+    }
+    return 1;
+  }
+  if (r.kind != VV_MFMA_STREAM) return vv_set_error(VV_E_ARG, "vv_launch_mfma_route: no route");
   int rc;
-  if (xb) {
-    if (a.w2) rc = ksplit ? launch_mt<true, true, true>(a, s, mt) : launch_mt<true, false, true>(a, s, mt);
-    else rc = ksplit ? launch_mt<false, true, true>(a, s, mt) : launch_mt<false, false, true>(a, s, mt);
+  if (r.xb) {
+    if (r.dual) rc = r.ksplit ? launch_mt<true, true, true>(a, s, r.mt) : launch_mt<true, false, true>(a, s, r.mt);
+    else rc = r.ksplit ? launch_mt<false, true, true>(a, s, r.mt) : launch_mt<false, false, true>(a, s, r.mt);
   } else {
-    if (a.w2) rc = ksplit ? launch_mt<true, true, false>(a, s, mt) : launch_mt<true, false, false>(a, s, mt);
-    else rc = ksplit ? launch_mt<false, true, false>(a, s, mt) : launch_mt<false, false, false>(a, s, mt);
+    if (r.dual) rc = r.ksplit ? launch_mt<true, true, false>(a, s, r.mt) : launch_mt<true, false, false>(a, s, r.mt);
+    else rc = r.ksplit ? launch_mt<false, true, false>(a, s, r.mt) : launch_mt<false, false, false>(a, s, r.mt);
   }
   return rc ? rc : 1;
+}
+
+// 1 = launched, 0 = shape/alignment not covered (caller falls back to the fp32 VALU GEMM), < 0 = error
+int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s) {
+  const vv_mfma_route r = vv_mfma_decide(a);
+  return r.kind <= 0 ? r.kind : vv_launch_mfma_route(a, r, s);
+}
+
+// the instantiation's name as the route query reports it
+int vv_mfma_route_name(const vv_mfma_route& r, char* name, int cap) {
+  if (r.kind == VV_MFMA_TILED) return snprintf(name, (size_t)cap, "mfma_tiled<dual=%d,bk=%d,tm=%d>", r.dual, r.bk, r.tm);
+  return snprintf(name, (size_t)cap, "mfma_stream<dual=%d,ksplit=%d,xb=%d,mt=%d>", r.dual, r.ksplit, r.xb, r.mt);
 }
 
 #ifdef VV_MFMA_TIMING
