@@ -103,8 +103,14 @@ typedef struct vv_lin_args {
 int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
- * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>"; otherwise "skinny", "gemm_f32" or,
- * for m <= 8, "gemv".  Arguments vv_linear refuses return the same error. */
+ * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>"; "skinny" or "gemm_f32"; and for the
+ * m <= 8 family (fp8 and NF4 weights included) the kernel itself:
+ *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
+ *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
+ *   "gemv_hot<3>", "conv_hot_gemv<0>"                                      hot kernels, by table index
+ *   "gemv_stream<m=4,...> + gemv_stream<m=2,...>"                          5..8 rows as two streaming passes of 4 + rest rows
+ *   "gemv_lds<w=f32,m=3,dual=0,ks=4,np=2>", "gemv_generic<w=bf16>"         the LDS-staged and the generic fall-back
+ * Every name fits 128 bytes.  Arguments vv_linear refuses return the same error. */
 int vv_linear_route(const vv_lin_args* a, char* name, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------

@@ -33,22 +33,39 @@ struct vv_kv_args8 : vv_kv_args {
   vv_kv_args8(const vv_kv& a) : vv_kv_args(a), kscale(a.kscale), vscale(a.vscale) {}
 };
 
-int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s);   // vv_gemv_stream.hip: 1 = launched, 0 = not covered
+// The decode GEMV family (m <= 8).  Every launcher is a DECISION - a plain struct computed from the arguments and the vv_tune state, no pointer
+// followed, no HIP call, the only copy of the thresholds - and a LAUNCH of that struct; vv_linear_route prints the same struct, so the name it
+// reports is the kernel vv_linear starts.  kind 0 = not covered (the caller falls back).
+enum { VV_GEMV_STREAM = 1, VV_GEMV_HOT = 2, VV_GEMV_CONV_HOT = 3 };
+// vv_gemv_stream.hip: gemv_stream_kernel<m, dual, ksplit, ku, rw, wq> (wq: 0 bf16, 1 fp8, 2 NF4) on blocks x threads, or a hot kernel (table entry idx)
+struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, blocks, threads; };
+vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
+int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0
+int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
+int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s);   // decide + launch: 1 = launched, 0 = not covered
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
 // template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.
 struct vv_gemv_hot_shape { const char* name; int m, n, k, dual, pro, mod, bias, gate, res, act, flags; };
 extern "C" int vv_gemv_hot_shapes(vv_gemv_hot_shape* out, int cap);   // copies up to cap entries, returns the table's length (exported for the tests; not in vv_hip.h)
-int vv_launch_gemv_hot(const vv_lin_args& a, hipStream_t s);      // 1 = launched on a shape-specialised kernel, 0 = no enabled table entry matches
+int vv_gemv_hot_covers(const vv_lin_args& a);                     // index of the enabled table entry the call equals, or -1 (no launch)
+int vv_launch_gemv_hot(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_gemv_hot_covers: 1 = launched on that entry's kernel
 void vv_gemv_hot_set(int mask);                                   // tuning hook "gemv_hot"
 // vv_conv_hot.hip: the conv tokenizers' one-row stage and hand-over GEMVs on kernels of their own (table: vv_conv_hot_shapes, vv_hip.h); bit i of
 // vv_tune("conv_hot") switches entry i.  1 = launched, 0 = no enabled entry matches (the caller goes on to today's path)
-int vv_launch_conv_hot_gemv(const vv_lin_args& a, hipStream_t s);
+int vv_conv_hot_gemv_covers(const vv_lin_args& a);                // index of the enabled GEMV table entry the call equals, or -1 (no launch)
+int vv_launch_conv_hot_gemv(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_conv_hot_gemv_covers: 1 = launched
 int vv_launch_conv_hot_row(const vv_block& B, const float* x, float* y, float* hidden, float* hist_new, int C, float eps, hipStream_t s);
 void vv_conv_hot_set(int mask);                                   // tuning hook "conv_hot"
 // vv_gemv_rows.hip: 3..8 activation rows on the matrix cores; 1 launched, 0 not covered, < 0 error.  part / tickets: split-K workspace
 // (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry, left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
+// the same, decision apart from launch: gemv_rows_kernel<dual, nw, ks, pers, f8> on (gx, ksplit) blocks, spw weight loads per wave; atomic: the K
+// slices add into out.  have_ws: the caller has a partials workspace and tickets (their sizes follow); kind 1 = covered
+struct vv_rows_route { int kind, dual, nw, ks, pers, f8, ksplit, spw, atomic, n_groups, gx; };
+vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
+int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
+int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap);
 size_t vv_gemv_rows_part_floats(int n, int dual);
 size_t vv_gemv_rows_tickets(int n);
 int vv_gemv_rows_init();

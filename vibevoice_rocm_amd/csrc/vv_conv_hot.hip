@@ -309,13 +309,16 @@ extern "C" int vv_conv_hot_shapes(vv_conv_hot_shape* out, int cap) {
   return N_HOT;
 }
 
-// 1 = launched on a hot kernel, 0 = no enabled table entry matches (the caller goes on to the generic template).  The caller has checked
-// the 16-byte alignment of x and w.
-int vv_launch_conv_hot_gemv(const vv_lin_args& a, hipStream_t s) {
-  if (!(g_hot & ((1 << N_HOT) - 1)) || a.m != 1 || a.wdt != VV_BF16) return 0;
-  int id = -1;
+// The decision: index of the enabled GEMV table entry the call equals, or -1 (the caller goes on to the generic template).  No launch, no pointer followed.
+int vv_conv_hot_gemv_covers(const vv_lin_args& a) {
+  if (!(g_hot & ((1 << N_HOT) - 1)) || a.m != 1 || a.wdt != VV_BF16) return -1;
   for (int i = 0; i < N_HOT; ++i)
-    if ((g_hot >> i & 1) && matches(g_table[i], a)) { id = i; break; }
+    if ((g_hot >> i & 1) && matches(g_table[i], a)) return i;
+  return -1;
+}
+
+// The launch of table entry id (from vv_conv_hot_gemv_covers): 1 = launched.  The caller has checked the 16-byte alignment of x and w.
+int vv_launch_conv_hot_gemv(const vv_lin_args& a, int id, hipStream_t s) {
   const bool alt = (g_hot & 256) != 0;
   switch (id) {
     case 0:

@@ -35,6 +35,7 @@
 //   epilogue            bias / GELU / SwiGLU / per-row or per-channel gate / residual, one output per thread, operands requested up front.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "vv_hip.h"
 #include "vv_common.h"
@@ -393,41 +394,38 @@ int g_rows_dbg = 0;
 int g_rows_atomic = 1;      // tuning hook "gemv_rows_atomic": 0 = always fold K slices through the ticket (deterministic summation order)
 
 template <bool DUAL, int NW, int KS, bool PERS, bool F8 = false>
-int launch_cfg(const vv_lin_args& a, RowsAux x, int n_groups, hipStream_t s) {
+int launch_cfg(const vv_lin_args& a, const RowsAux& x, int gx, hipStream_t s) {
   const size_t lds = (size_t)NW * (F8 ? 2 * KS : KS) * 64 * 16;   // the LDS limit of every instantiation is raised in vv_gemv_rows_init (not capturable)
-  int gx = n_groups;
-  if (PERS && gx > g_rows_pers) {                       // the same number of row groups for every block
-    const int per = (n_groups + g_rows_pers - 1) / g_rows_pers;
-    gx = (n_groups + per - 1) / per;
-  }
-  x.n_groups = n_groups;
   hipLaunchKernelGGL((gemv_rows_kernel<DUAL, NW, KS, PERS, F8>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
   return 1;
+}
+
+// the decision's template choice: gemv_rows_kernel<dual, nw, ks, pers, f8> and its grid
+void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int f8) {
+  r.dual = dual; r.nw = nw; r.ks = ks; r.pers = pers; r.f8 = f8;
+  r.gx = r.n_groups;
+  if (pers && r.gx > g_rows_pers) {                     // the same number of row groups for every block
+    const int per = (r.n_groups + g_rows_pers - 1) / g_rows_pers;
+    r.gx = (r.n_groups + per - 1) / per;
+  }
+  r.kind = 1;
 }
 
 // fp8 fragment-major weights.  A 64-wide weight load costs 4 VGPRs per matrix (8 in flight per persistent buffer pair) and its two activation
 // fragments 8: KS = 4 holds the whole K <= 2048 row in 8 waves and leaves the persistent dual form 64 weight + 32 fragment VGPRs, so fp8 runs
 // persistent at every whole-row width; the single-matrix split-K form goes up to 8 loads (8 KB in flight per wave, as the bf16 form's 8 - 12).
-int launch_fp8(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s) {
+void decide_fp8(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets, vv_rows_route& r) {
   const bool dual = a.w2 != nullptr;
   const int steps = a.k / 64, n_groups = a.n / 16;
-  RowsAux x;
-  x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = n_groups; x.atomic = 0;
+  r.n_groups = n_groups; r.atomic = 0;
   if (steps <= 32) {                                  // K <= 2048: whole rows per block
-    x.ksplit = 1;
-    x.spw = (steps + 7) / 8;
-    if (dual) {
-      if (n_groups > g_rows_pers) {
-        if (x.spw <= 2) return launch_cfg<true, 8, 2, true, true>(a, x, n_groups, s);
-        return launch_cfg<true, 8, 4, true, true>(a, x, n_groups, s);
-      }
-      if (x.spw <= 2) return launch_cfg<true, 8, 2, false, true>(a, x, n_groups, s);
-      return launch_cfg<true, 8, 4, false, true>(a, x, n_groups, s);
-    }
-    if (x.spw <= 2) return launch_cfg<false, 8, 2, false, true>(a, x, n_groups, s);
-    return launch_cfg<false, 8, 4, false, true>(a, x, n_groups, s);
+    r.ksplit = 1;
+    r.spw = (steps + 7) / 8;
+    if (dual) rows_cfg(r, 1, 8, r.spw <= 2 ? 2 : 4, n_groups > g_rows_pers, 1);
+    else rows_cfg(r, 0, 8, r.spw <= 2 ? 2 : 4, 0, 1);
+    return;
   }
-  if (a.mod_scale) return 0;
+  if (a.mod_scale) return;
   const int NW = dual ? 8 : 4, kscap = dual ? 4 : 6, ksmax = dual ? 4 : 8;
   int ksplit = 0, spw = 0;
   for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
@@ -438,20 +436,14 @@ int launch_fp8(const vv_lin_args& a, float* part, size_t part_floats, int* ticke
     const int w = (steps + sp * NW - 1) / (sp * NW);
     if (w <= ksmax) { ksplit = sp; spw = w; }
   }
-  if (!ksplit) return 0;
+  if (!ksplit) return;
   while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;
   const size_t pst = dual ? 264 : 136;
-  x.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
-  if (!x.atomic && (!part || !tickets || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return 0;
-  x.ksplit = ksplit; x.spw = spw;
-  if (dual) {
-    if (spw <= 2) return launch_cfg<true, 8, 2, false, true>(a, x, n_groups, s);
-    return launch_cfg<true, 8, 4, false, true>(a, x, n_groups, s);
-  }
-  if (spw <= 2) return launch_cfg<false, 4, 2, false, true>(a, x, n_groups, s);
-  if (spw <= 4) return launch_cfg<false, 4, 4, false, true>(a, x, n_groups, s);
-  if (spw <= 6) return launch_cfg<false, 4, 6, false, true>(a, x, n_groups, s);
-  return launch_cfg<false, 4, 8, false, true>(a, x, n_groups, s);
+  r.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
+  if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return;
+  r.ksplit = ksplit; r.spw = spw;
+  if (dual) rows_cfg(r, 1, 8, spw <= 2 ? 2 : 4, 0, 1);
+  else rows_cfg(r, 0, 4, spw <= 2 ? 2 : spw <= 4 ? 4 : spw <= 6 ? 6 : 8, 0, 1);
 }
 
 }  // namespace
@@ -487,44 +479,36 @@ int vv_gemv_rows_init() {
   return 0;
 }
 
-// 1 launched, 0 not covered (the caller falls back), < 0 error.  part / tickets: split-K workspace (tickets zeroed by the caller once; every
-// launch leaves them zero) or null (then only shapes that need no K split are taken).  fp8 weights: fragment-major only (VV_LIN_W_FRAG).
-int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s) {
+// The decision: which instantiation the call takes, its K split and grid; kind 0 = not covered (the caller falls back).  have_ws: a split-K
+// workspace of part_floats floats and n_tickets tickets exists (without one only shapes that need no K split, or the atomic form, are taken).
+// fp8 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
+vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets) {
+  vv_rows_route r = {};
   const bool f8 = a.wdt == VV_FP8;
-  if (!g_rows_on || (a.wdt != VV_BF16 && !f8) || a.m < 3 || a.m > 8 || a.k % 32 || a.k < 32) return 0;
-  if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return 0;
-  if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16 || a.ldx % 4) return 0;
-  if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
-  if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return 0;
+  if (!g_rows_on || (a.wdt != VV_BF16 && !f8) || a.m < 3 || a.m > 8 || a.k % 32 || a.k < 32) return r;
+  if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return r;
+  if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16 || a.ldx % 4) return r;
+  if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
+  if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return r;
   if (f8) {
-    if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale)) return 0;
-    return launch_fp8(a, part, part_floats, tickets, n_tickets, s);
+    if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale)) return r;
+    decide_fp8(a, have_ws, part_floats, n_tickets, r);
+    return r;
   }
-  if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return 0;
+  if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return r;
   const bool dual = a.w2 != nullptr;
   const int steps = a.k / 32, n_groups = (a.n + 15) / 16;
-  RowsAux x;
-  x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = n_groups; x.atomic = 0;
+  r.n_groups = n_groups; r.atomic = 0;
   // whole rows per block when K <= 2048 (8 waves x <= 8 steps): no cross-block reduction at all
   if (steps <= 64) {
-    x.ksplit = 1;
-    x.spw = (steps + 7) / 8;
-    const bool pers = dual && n_groups > g_rows_pers && x.spw <= 6;      // 8 steps x 2 matrices x 2 buffers do not fit the registers
-    if (dual) {
-      if (pers) {
-        if (x.spw <= 4) return launch_cfg<true, 8, 4, true>(a, x, n_groups, s);
-        return launch_cfg<true, 8, 6, true>(a, x, n_groups, s);
-      }
-      if (x.spw <= 4) return launch_cfg<true, 8, 4, false>(a, x, n_groups, s);
-      if (x.spw <= 6) return launch_cfg<true, 8, 6, false>(a, x, n_groups, s);
-      return launch_cfg<true, 8, 8, false>(a, x, n_groups, s);
-    }
-    if (x.spw <= 4) return launch_cfg<false, 8, 4, false>(a, x, n_groups, s);
-    if (x.spw <= 6) return launch_cfg<false, 8, 6, false>(a, x, n_groups, s);
-    return launch_cfg<false, 8, 8, false>(a, x, n_groups, s);
+    r.ksplit = 1;
+    r.spw = (steps + 7) / 8;
+    const bool pers = dual && n_groups > g_rows_pers && r.spw <= 6;      // 8 steps x 2 matrices x 2 buffers do not fit the registers
+    rows_cfg(r, dual, 8, r.spw <= 4 ? 4 : r.spw <= 6 ? 6 : 8, pers, 0);
+    return r;
   }
   // long rows: K slices across blocks, folded by the last arriver
-  if (a.mod_scale) return 0;                          // the modulated prologue needs the whole row's statistic up front
+  if (a.mod_scale) return r;                          // the modulated prologue needs the whole row's statistic up front
   const int NW = dual ? 8 : 4, kscap = dual ? 8 : 9, ksmax = dual ? 8 : 12;
   int ksplit = 0, spw = 0;
   for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
@@ -535,19 +519,42 @@ int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, i
     const int w = (steps + sp * NW - 1) / (sp * NW);
     if (w <= ksmax) { ksplit = sp; spw = w; }
   }
-  if (!ksplit) return 0;
+  if (!ksplit) return r;
   while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;     // drop K slices that would start past the end
   const size_t pst = dual ? 264 : 136;
-  x.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
-  if (!x.atomic && (!part || !tickets || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return 0;
-  x.ksplit = ksplit; x.spw = spw;
-  if (dual) {
-    if (spw <= 4) return launch_cfg<true, 8, 4, false>(a, x, n_groups, s);
-    if (spw <= 6) return launch_cfg<true, 8, 6, false>(a, x, n_groups, s);
-    return launch_cfg<true, 8, 8, false>(a, x, n_groups, s);
-  }
-  if (spw <= 3) return launch_cfg<false, 4, 3, false>(a, x, n_groups, s);
-  if (spw <= 6) return launch_cfg<false, 4, 6, false>(a, x, n_groups, s);
-  if (spw <= 9) return launch_cfg<false, 4, 9, false>(a, x, n_groups, s);
-  return launch_cfg<false, 4, 12, false>(a, x, n_groups, s);
+  r.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
+  if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return r;
+  r.ksplit = ksplit; r.spw = spw;
+  if (dual) rows_cfg(r, 1, 8, spw <= 4 ? 4 : spw <= 6 ? 6 : 8, 0, 0);
+  else rows_cfg(r, 0, 4, spw <= 3 ? 3 : spw <= 6 ? 6 : spw <= 9 ? 9 : 12, 0, 0);
+  return r;
+}
+
+// The launch of a decided route: 1 = launched, 0 = r.kind == 0 or an instantiation that is not built.  part / tickets: the split-K workspace
+// the decision was told about (tickets zeroed by the caller once; every launch leaves them zero) or null.
+int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s) {
+  if (r.kind != 1) return 0;
+  RowsAux x;
+  x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = r.n_groups; x.atomic = r.atomic; x.ksplit = r.ksplit; x.spw = r.spw;
+#define VV_ROWS_CASE(D, NW, KS, P, F8) \
+  if (r.dual == D && r.nw == NW && r.ks == KS && r.pers == P && r.f8 == F8) return launch_cfg<(D != 0), NW, KS, (P != 0), (F8 != 0)>(a, x, r.gx, s);
+  VV_ROWS_CASE(0, 4, 3, 0, 0) VV_ROWS_CASE(0, 4, 6, 0, 0) VV_ROWS_CASE(0, 4, 9, 0, 0) VV_ROWS_CASE(0, 4, 12, 0, 0)
+  VV_ROWS_CASE(0, 8, 4, 0, 0) VV_ROWS_CASE(0, 8, 6, 0, 0) VV_ROWS_CASE(0, 8, 8, 0, 0)
+  VV_ROWS_CASE(1, 8, 4, 0, 0) VV_ROWS_CASE(1, 8, 6, 0, 0) VV_ROWS_CASE(1, 8, 8, 0, 0)
+  VV_ROWS_CASE(1, 8, 4, 1, 0) VV_ROWS_CASE(1, 8, 6, 1, 0)
+  VV_ROWS_CASE(0, 8, 2, 0, 1) VV_ROWS_CASE(0, 8, 4, 0, 1)
+  VV_ROWS_CASE(1, 8, 2, 0, 1) VV_ROWS_CASE(1, 8, 4, 0, 1) VV_ROWS_CASE(1, 8, 2, 1, 1) VV_ROWS_CASE(1, 8, 4, 1, 1)
+  VV_ROWS_CASE(0, 4, 2, 0, 1) VV_ROWS_CASE(0, 4, 4, 0, 1) VV_ROWS_CASE(0, 4, 6, 0, 1) VV_ROWS_CASE(0, 4, 8, 0, 1)
+#undef VV_ROWS_CASE
+  return 0;
+}
+
+// the name vv_linear_route reports for this file's route: spelled here and nowhere else
+int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap) {
+  return snprintf(name, (size_t)cap, "gemv_rows<dual=%d,nw=%d,ks=%d,pers=%d,f8=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.f8, r.ksplit, r.atomic);
+}
+
+// decide + launch: 1 launched, 0 not covered (the caller falls back), < 0 error
+int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s) {
+  return vv_launch_gemv_rows_route(a, vv_gemv_rows_decide(a, part && tickets, part_floats, n_tickets), part, tickets, s);
 }

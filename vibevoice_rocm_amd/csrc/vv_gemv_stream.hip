@@ -13,6 +13,7 @@
 //                      in a fixed order (long K: 1.5B down-projections, every 7B matrix)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "vv_hip.h"
 #include "vv_common.h"
@@ -574,12 +575,28 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
 }
 
 int g_dual_rw = 1;            // weight rows per wave step for the dual (SwiGLU) kernel: 1 keeps 4 waves/SIMD resident
+int g_small_rw = 2;           // rows per wave step for narrow non-dual matrices (tuning hook)
 
-template <int M, bool DUAL, int KSPLIT, int KU, int RW>
-void launch_rw(const vv_lin_args& a, hipStream_t s) {
-  // persistent grid, sized from measurements on MI355X (tools/mb_gemv.py): ~1.5-2 blocks per CU is the sweet spot for the
-  // wave-per-row layout (more blocks only add prologue copies and a ragged last round), one block per row group when the
-  // block's waves split K
+// Which (dual, ksplit, ku) forms of the M = 1 / 2 / 4 kernels are built - read by the launch ladder (if constexpr) and by the decision alike:
+// whole rows at 1..5 units, 4 / 8 / 16 waves splitting K at 2..5 units per wave; the dual kernel holds two weight streams, so its K-split forms
+// stop at 8 waves and 3 units
+constexpr bool stream_built(bool dual, int ksplit, int ku) {
+  if (ksplit != 1 && ksplit != 4 && ksplit != 8 && ksplit != 16) return false;
+  if (ku < 1 || ku > 5 || (ku == 1 && ksplit != 1)) return false;
+  if (dual && (ksplit == 16 || (ksplit != 1 && ku > 3))) return false;
+  return true;
+}
+// NF4: <= 2 rows, <= 8 waves (LDS), the dual kernel at <= 4 units per wave (registers)
+constexpr bool stream_built_nf4(int m, bool dual, int ksplit, int ku) { return stream_built(dual, ksplit, ku) && m <= 2 && ksplit <= 8 && !(dual && ku > 4); }
+// 5..8 rows: the fragment is 8 rows x KU x 8 floats, so K is split until KU <= 2 (16 waves x 8 rows does not fit the 128-VGPR budget of a 1024-thread block)
+constexpr bool stream_built_m8(int ksplit, int ku, int rw) { return (ksplit == 1 && (ku == 1 || ku == 2) && rw == 1) || ((ksplit == 4 || ksplit == 8) && ku == 2 && rw == 2); }
+
+// persistent grid, sized from measurements on MI355X (tools/mb_gemv.py): ~1.5-2 blocks per CU is the sweet spot for the
+// wave-per-row layout (more blocks only add prologue copies and a ragged last round), one block per row group when the
+// block's waves split K
+void stream_grid(const vv_lin_args& a, vv_stream_route& r) {
+  const int RW = r.rw, KSPLIT = r.ksplit;
+  const bool DUAL = r.dual != 0;
   const int n_groups = (a.n + RW - 1) / RW;
   const int waves = (KSPLIT == 1 && g_waves_override >= 3 && g_waves_override <= 8) ? g_waves_override : 4;
   const int work = (KSPLIT == 1) ? (n_groups + waves - 1) / waves : n_groups;       // blocks if each wave did exactly one group
@@ -588,69 +605,73 @@ void launch_rw(const vv_lin_args& a, hipStream_t s) {
   const int cap = (KSPLIT == 1) ? (DUAL ? (RW == 1 ? 512 : 448) : 512) : (a.k > 6144 ? g_long_cap : 1024);
   int blocks = work < cap ? work : cap;
   if (g_blocks_override > 0) blocks = g_blocks_override < work ? g_blocks_override : work;
-  const int threads = KSPLIT == 1 ? 64 * waves : 64 * KSPLIT;
+  r.n_groups = n_groups;
+  r.blocks = blocks;
+  r.threads = KSPLIT == 1 ? 64 * waves : 64 * KSPLIT;
+}
+
+template <int M, bool DUAL, int KSPLIT, int KU, int RW>
+void launch_rw(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  const dim3 blocks(r.blocks), threads(r.threads);
+  const int n_groups = r.n_groups;
   if constexpr (RW == 4) {                       // NF4 weights (launch_one): 4 rows per code load
-    hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 2>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+    hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 2>), blocks, threads, 0, s, a, n_groups, g_opt);
     return;
   }
   if constexpr (M <= 2) {                        // fp8 weights: decode rows only
-    if (a.wdt == VV_FP8) {
-      hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 1>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+    if (r.wq == 1) {
+      hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 1>), blocks, threads, 0, s, a, n_groups, g_opt);
       return;
     }
   }
-  hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 0>), dim3(blocks), dim3(threads), 0, s, a, n_groups, g_opt);
+  hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 0>), blocks, threads, 0, s, a, n_groups, g_opt);
 }
 
-int g_small_rw = 2;           // rows per wave step for narrow non-dual matrices (tuning hook)
-
 template <int M, bool DUAL, int KSPLIT, int KU>
-bool launch_one(const vv_lin_args& a, hipStream_t s) {
-  if (a.wdt == VV_NF4) {   // NF4: <= 2 rows, <= 8 waves (LDS), the dual kernel at <= 4 units per wave (registers); never a bf16 read of codes
-    if constexpr (M <= 2 && KSPLIT <= 8 && !(DUAL && KU > 4)) { launch_rw<M, DUAL, KSPLIT, KU, 4>(a, s); return true; }
+bool launch_one(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  if (r.wq == 2) {         // never a bf16 read of codes
+    if constexpr (stream_built_nf4(M, DUAL, KSPLIT, KU)) { launch_rw<M, DUAL, KSPLIT, KU, 4>(a, r, s); return true; }
     return false;
   }
-  if (DUAL && g_dual_rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, s);
-  else if (!DUAL && KSPLIT == 1 && a.n <= 4096 && g_small_rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, s);
-  else launch_rw<M, DUAL, KSPLIT, KU, 2>(a, s);
+  if (r.rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, r, s);
+  else launch_rw<M, DUAL, KSPLIT, KU, 2>(a, r, s);
   return true;
 }
 
 template <int M, bool DUAL, int KSPLIT>
-bool launch_kus(const vv_lin_args& a, hipStream_t s, int ku) {
-  switch (ku) {
-    case 1: if constexpr (KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 1>(a, s); else return false;
-    case 2: return launch_one<M, DUAL, KSPLIT, 2>(a, s);
-    case 3: return launch_one<M, DUAL, KSPLIT, 3>(a, s);
-    case 4: if constexpr (!DUAL || KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 4>(a, s); else return false;
-    case 5: if constexpr (!DUAL || KSPLIT == 1) return launch_one<M, DUAL, KSPLIT, 5>(a, s); else return false;
+bool launch_kus(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  switch (r.ku) {
+    case 1: if constexpr (stream_built(DUAL, KSPLIT, 1)) return launch_one<M, DUAL, KSPLIT, 1>(a, r, s); else return false;
+    case 2: return launch_one<M, DUAL, KSPLIT, 2>(a, r, s);
+    case 3: return launch_one<M, DUAL, KSPLIT, 3>(a, r, s);
+    case 4: if constexpr (stream_built(DUAL, KSPLIT, 4)) return launch_one<M, DUAL, KSPLIT, 4>(a, r, s); else return false;
+    case 5: if constexpr (stream_built(DUAL, KSPLIT, 5)) return launch_one<M, DUAL, KSPLIT, 5>(a, r, s); else return false;
   }
   return false;
 }
 
 template <int M, bool DUAL>
-bool launch_ku(const vv_lin_args& a, hipStream_t s, int ksplit, int ku) {
-  switch (ksplit) {
-    case 1: return launch_kus<M, DUAL, 1>(a, s, ku);
-    case 4: return launch_kus<M, DUAL, 4>(a, s, ku);
-    case 8: return launch_kus<M, DUAL, 8>(a, s, ku);
-    case 16: if constexpr (!DUAL) return launch_kus<M, false, 16>(a, s, ku); else return false;
+bool launch_ku(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  switch (r.ksplit) {
+    case 1: return launch_kus<M, DUAL, 1>(a, r, s);
+    case 4: return launch_kus<M, DUAL, 4>(a, r, s);
+    case 8: return launch_kus<M, DUAL, 8>(a, r, s);
+    case 16: if constexpr (stream_built(DUAL, 16, 2)) return launch_kus<M, false, 16>(a, r, s); else return false;
   }
   return false;
 }
 
-// 5..8 activation rows (the conv tokenizers' T = 8 stage, C = 1024): the fragment is 8 rows x KU x 8 floats, so K is split
-// until KU <= 2; one pass over the weights instead of two 4-row passes
-bool launch_m8(const vv_lin_args& a, hipStream_t s, int ksplit, int ku) {
-  if (ksplit == 1) {
-    if (ku == 1) launch_rw<8, false, 1, 1, 1>(a, s); else launch_rw<8, false, 1, 2, 1>(a, s);
+// 5..8 activation rows (the conv tokenizers' T = 8 stage, C = 1024): one pass over the weights instead of two 4-row passes
+bool launch_m8(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  if (r.ksplit == 1) {
+    if (r.ku == 1) launch_rw<8, false, 1, 1, 1>(a, r, s); else launch_rw<8, false, 1, 2, 1>(a, r, s);
     return true;
   }
-  switch (ksplit) {
-    case 4: launch_rw<8, false, 4, 2, 2>(a, s); return true;
-    case 8: launch_rw<8, false, 8, 2, 2>(a, s); return true;
+  switch (r.ksplit) {
+    case 4: launch_rw<8, false, 4, 2, 2>(a, r, s); return true;
+    case 8: launch_rw<8, false, 8, 2, 2>(a, r, s); return true;
   }
-  return false;   // 16 waves x 8 rows does not fit the 128-VGPR budget of a 1024-thread block: the caller splits the rows
+  return false;
 }
 
 }  // namespace
@@ -662,35 +683,48 @@ void vv_gemv_stream_set_long(int cap, int ku) { if (cap > 0) g_long_cap = cap; i
 void vv_gemv_stream_set_dual_rw(int r) { g_dual_rw = r; }
 void vv_gemv_stream_set_small_rw(int r) { g_small_rw = r; }
 
-// returns 1 when the call was launched here, 0 when the shape/alignment is not covered (caller falls back)
-int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
-  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4) || a.m > 8 || a.k % 8) return 0;
+// The decision: which kernel of this file (or which hot kernel) the call takes, and on what grid.  kind 0 = the shape / alignment is not covered
+// (the caller falls back).  Reads the arguments' values and alignments and the tune state only.
+vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
+  vv_stream_route r = {};
+  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4) || a.m > 8 || a.k % 8) return r;
   // NF4: decode rows only, whole 64-blocks, scales for every matrix, 16-byte aligned codes (vv_hip.h)
   if (a.wdt == VV_NF4 && (a.m > 2 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) ||
                           (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4) || (a.flags & VV_LIN_W_FRAG)))
-    return 0;
-  if (a.wdt == VV_FP8 && (a.m > 2 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 8 || (a.w2 && (uintptr_t)a.w2 % 8))) return 0;
+    return r;
+  if (a.wdt == VV_FP8 && (a.m > 2 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 8 || (a.w2 && (uintptr_t)a.w2 % 8))) return r;
+  r.wq = a.wdt == VV_NF4 ? 2 : a.wdt == VV_FP8 ? 1 : 0;
   if (a.m > 4) {
-    if (a.w2 || a.wdt != VV_BF16) return 0;
-    if ((uintptr_t)a.w % 16 || (uintptr_t)a.x % 16 || a.ldx % 4) return 0;
-    if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
-    if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return 0;
+    if (a.w2 || a.wdt != VV_BF16) return r;
+    if ((uintptr_t)a.w % 16 || (uintptr_t)a.x % 16 || a.ldx % 4) return r;
+    if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
+    if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return r;
     const int units8 = (a.k + 511) / 512;
     int ks = 0, ku8 = 0;
     for (int w : {1, 4, 8}) {
       if ((units8 + w - 1) / w <= 2) { ks = w; ku8 = (units8 + w - 1) / w; break; }
     }
-    if (!ks) return 0;
+    if (!ks) return r;
     if (ks > 1) ku8 = 2;
-    return launch_m8(a, s, ks, ku8) ? 1 : 0;
+    r.m = 8; r.ksplit = ks; r.ku = ku8; r.rw = ks == 1 ? 1 : 2;
+    if (!stream_built_m8(r.ksplit, r.ku, r.rw)) return r;
+    stream_grid(a, r);
+    r.kind = VV_GEMV_STREAM;
+    return r;
   }
-  if (a.wdt == VV_BF16 && ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16))) return 0;
-  if ((uintptr_t)a.x % 16) return 0;
-  if (a.m > 1 && a.ldx % 4) return 0;
-  if (a.norm_w && (uintptr_t)a.norm_w % 16) return 0;
-  if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return 0;
-  if (a.m == 2 && a.wdt == VV_BF16 && vv_launch_gemv_hot(a, s)) return 1;   // the six hot 1.5B shapes: their own kernels (vv_gemv_hot.hip)
-  if (a.m == 1 && a.wdt == VV_BF16 && vv_launch_conv_hot_gemv(a, s)) return 1;   // the conv tokenizers' one-row W2 and hand-over GEMVs (vv_conv_hot.hip)
+  if (a.wdt == VV_BF16 && ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16))) return r;
+  if ((uintptr_t)a.x % 16) return r;
+  if (a.m > 1 && a.ldx % 4) return r;
+  if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
+  if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return r;
+  if (a.m == 2 && a.wdt == VV_BF16) {            // the six hot 1.5B shapes: their own kernels (vv_gemv_hot.hip)
+    const int id = vv_gemv_hot_covers(a);
+    if (id >= 0) { r.kind = VV_GEMV_HOT; r.idx = id; return r; }
+  }
+  if (a.m == 1 && a.wdt == VV_BF16) {            // the conv tokenizers' one-row W2 and hand-over GEMVs (vv_conv_hot.hip)
+    const int id = vv_conv_hot_gemv_covers(a);
+    if (id >= 0) { r.kind = VV_GEMV_CONV_HOT; r.idx = id; return r; }
+  }
   const int units = (a.k + 511) / 512;
   const bool dual = a.w2 != nullptr;
   // smallest wave count whose per-wave slice fits the register-resident activation fragment (KU <= 5 units; <= 3 for the
@@ -702,13 +736,45 @@ int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
     for (int w : {4, 8, 16}) {
       if ((units + w - 1) / w <= kumax) { ksplit = w; ku = (units + w - 1) / w; break; }
     }
-    if (!ksplit) return 0;
+    if (!ksplit) return r;
     if (ku < 2) ku = 2;
   }
-  if (a.wdt == VV_NF4 && ksplit > 8) return 0;   // 16 waves of table slots would not fit the block's LDS: not built
+  r.m = a.m == 1 ? 1 : a.m == 2 ? 2 : 4;
+  r.dual = dual; r.ksplit = ksplit; r.ku = ku;
+  if (r.wq == 2) {                               // NF4: 4 rows per 16-byte code load; 16 waves of table slots would not fit the block's LDS
+    if (!stream_built_nf4(r.m, dual, ksplit, ku)) return r;
+    r.rw = 4;
+  } else {
+    if (!stream_built(dual, ksplit, ku)) return r;
+    if (dual) r.rw = g_dual_rw == 1 ? 1 : 2;
+    else r.rw = (ksplit == 1 && a.n <= 4096 && g_small_rw == 1) ? 1 : 2;
+  }
+  stream_grid(a, r);
+  r.kind = VV_GEMV_STREAM;
+  return r;
+}
+
+int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  if (r.kind == VV_GEMV_HOT) return vv_launch_gemv_hot(a, r.idx, s);
+  if (r.kind == VV_GEMV_CONV_HOT) return vv_launch_conv_hot_gemv(a, r.idx, s);
+  if (r.kind != VV_GEMV_STREAM) return 0;
   bool ok;
-  if (a.m == 1) ok = dual ? launch_ku<1, true>(a, s, ksplit, ku) : launch_ku<1, false>(a, s, ksplit, ku);
-  else if (a.m == 2) ok = dual ? launch_ku<2, true>(a, s, ksplit, ku) : launch_ku<2, false>(a, s, ksplit, ku);
-  else ok = dual ? launch_ku<4, true>(a, s, ksplit, ku) : launch_ku<4, false>(a, s, ksplit, ku);
+  if (r.m == 8) ok = launch_m8(a, r, s);
+  else if (r.m == 1) ok = r.dual ? launch_ku<1, true>(a, r, s) : launch_ku<1, false>(a, r, s);
+  else if (r.m == 2) ok = r.dual ? launch_ku<2, true>(a, r, s) : launch_ku<2, false>(a, r, s);
+  else ok = r.dual ? launch_ku<4, true>(a, r, s) : launch_ku<4, false>(a, r, s);
   return ok ? 1 : 0;
+}
+
+// the names vv_linear_route reports for this file's routes: spelled here and nowhere else
+int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap) {
+  if (r.kind == VV_GEMV_HOT) return snprintf(name, (size_t)cap, "gemv_hot<%d>", r.idx);
+  if (r.kind == VV_GEMV_CONV_HOT) return snprintf(name, (size_t)cap, "conv_hot_gemv<%d>", r.idx);
+  return snprintf(name, (size_t)cap, "gemv_stream<m=%d,dual=%d,ksplit=%d,ku=%d,rw=%d,wq=%s>", r.m, r.dual, r.ksplit, r.ku, r.rw,
+                  r.wq == 2 ? "nf4" : r.wq == 1 ? "fp8" : "bf16");
+}
+
+// returns 1 when the call was launched here, 0 when the shape/alignment is not covered (caller falls back)
+int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
+  return vv_launch_gemv_stream_route(a, vv_gemv_stream_decide(a), s);
 }

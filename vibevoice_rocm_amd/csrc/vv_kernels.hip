@@ -496,39 +496,158 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
 // ---------------------------------------------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------------------------------------------
-template <typename WT, int M, bool DUAL>
-static int launch_gemv(const vv_lin_args& a, hipStream_t s) {
-  const int K = a.k, N = a.n;
+// The m <= 8 family's decision (vv_linear launches it, vv_linear_route prints it): the 3..8-row matrix-core GEMV when the process-wide scratch is
+// on, the weight-streaming GEMV (or a hot kernel), two streaming passes of 4 + rest rows, the LDS-staged gemv_kernel<WT, M, DUAL, KS, NP> or the
+// generic kernel.  Plain values only: no pointer is followed, nothing is launched; the thresholds live here and in the two deciders it calls.
+enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC };
+struct gemv_route {
+  int kind;
+  vv_rows_route rows;
+  vv_stream_route st, st2;          // GEMV_SPLIT: rows 0..3 and the rest
+  int m, dual, ks, np, kc, blocks;  // GEMV_LDS: gemv_kernel<WT, m, dual, ks, np> staging kc columns at a time; GEMV_GENERIC: blocks
+  size_t lds;
+};
+
+// rows 4.. of a 5..8-row call as a call of its own (the second pass of GEMV_SPLIT): every per-row operand advances by 4 rows
+static vv_lin_args split_hi(const vv_lin_args& a) {
+  vv_lin_args hi = a;
+  hi.m = a.m - 4;
+  hi.x = a.x + 4 * a.ldx;
+  hi.out = a.out + 4 * a.ldo;
+  if (a.res) hi.res = a.res + 4 * a.ldres;
+  if (a.gate && a.gate_ld) hi.gate = a.gate + 4 * a.gate_ld;
+  if (a.mod_scale) { hi.mod_scale = a.mod_scale + 4 * a.ld_mod; hi.mod_shift = a.mod_shift + 4 * a.ld_mod; }
+  return hi;
+}
+
+static void lds_decide(const vv_lin_args& a, gemv_route* g) {
+  const int K = a.k, N = a.n, M = a.m;
+  const bool DUAL = a.w2 != nullptr;
   int KC = (8192 / M) & ~1023;                 // <= 32 KB of staged x
   if (KC < 1024) KC = 1024;
   if (KC > K) KC = (K + 7) & ~7;
-  const size_t lds = (size_t)(256 + M * KC) * sizeof(float);
+  g->kind = GEMV_LDS;
+  g->m = M; g->dual = DUAL; g->kc = KC;
+  g->lds = (size_t)(256 + M * KC) * sizeof(float);
   const bool splitk = (N < 4096 && K >= 2048);
   if (splitk) {
-    if (N >= 1024) { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 2>), dim3((N + 1) / 2), dim3(GEMV_THREADS), lds, s, a, KC); }
-    else           { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 1>), dim3(N), dim3(GEMV_THREADS), lds, s, a, KC); }
+    g->ks = 4;
+    if (N >= 1024) { g->np = 2; g->blocks = (N + 1) / 2; }
+    else           { g->np = 1; g->blocks = N; }
   } else {
-    if ((int64_t)N >= 8192 && M <= 4 && !(DUAL && M > 2)) {
-      hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 2>), dim3((N + 7) / 8), dim3(GEMV_THREADS), lds, s, a, KC);
-    } else {
-      hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 1>), dim3((N + 3) / 4), dim3(GEMV_THREADS), lds, s, a, KC);
+    g->ks = 1;
+    if ((int64_t)N >= 8192 && M <= 4 && !(DUAL && M > 2)) { g->np = 2; g->blocks = (N + 7) / 8; }
+    else { g->np = 1; g->blocks = (N + 3) / 4; }
+  }
+}
+
+// < 0 = error (the call is refused: nothing may be launched)
+static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
+  *g = gemv_route{};
+  if (a.wdt == VV_FP8 && (a.flags & VV_LIN_W_FRAG)) {
+    // fp8 fragment-major weights: the 3..8-row matrix-core GEMV (process-wide split-K scratch as for bf16, see rows_scratch)
+    if (g_rows_part) g->rows = vv_gemv_rows_decide(a, true, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
+    if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)", a.m, a.n, a.k);
+  }
+  if (a.wdt == VV_FP8 || a.wdt == VV_NF4) {
+    // weight-only fp8 / NF4 exist for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix (of the effective weights)
+    g->st = vv_gemv_stream_decide(a);
+    if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
+    if (a.wdt == VV_FP8) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 weights need m <= 2, k %% 8 == 0, scales and 8-byte aligned rows (m=%d k=%d)", a.m, a.k);
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights need m <= 2, k %% 64 == 0, scales and 16-byte aligned codes (m=%d k=%d)", a.m, a.k);
+  }
+  const bool dual = a.w2 != nullptr;
+  const size_t wsz = a.wdt == VV_F32 ? sizeof(float) : sizeof(bf16_t);
+  const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!dual || (uintptr_t)a.w2 % 16 == 0);
+  if (a.m > 2 && g_rows_part) {                               // 3..8 rows on the matrix cores (process-wide scratch: see rows_scratch)
+    g->rows = vv_gemv_rows_decide(a, true, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
+    if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
+  }
+  if (a.flags & VV_LIN_W_FRAG)                                // only the 3..8-row matrix-core GEMV reads the fragment-major layout
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_LIN_W_FRAG weights are read by the 3..8-row matrix-core GEMV only (m=%d n=%d k=%d not covered)", a.m, a.n, a.k);
+  g->st = vv_gemv_stream_decide(a);                           // bf16 weight-streaming fast path (<= 4 rows; 5..8 rows when K splits to <= 2 units per wave)
+  if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
+  if (a.m > 4 && a.wdt == VV_BF16 && a.ldx != 0) {
+    // 5..8 rows not covered above: two streaming passes of <= 4 rows (the LDS-staged kernel below is LDS-bandwidth bound at M = 8)
+    vv_lin_args lo = a;
+    lo.m = 4;
+    g->st = vv_gemv_stream_decide(lo);
+    if (g->st.kind) {
+      g->st2 = vv_gemv_stream_decide(split_hi(a));
+      if (!g->st2.kind) return vv_set_error(VV_E_HIP, "vv_linear: split GEMV second half not covered");
+      g->kind = GEMV_SPLIT;
+      return 0;
     }
+  }
+  const bool fast = (a.k % 8 == 0) && w_al16 && ((a.k * wsz) % 16 == 0);
+  if (fast) { lds_decide(a, g); return 0; }
+  g->kind = GEMV_GENERIC;
+  g->blocks = (a.n + 3) / 4;
+  if (g->blocks > 2048) g->blocks = 2048;
+  return 0;
+}
+
+// the names of this file's two fall-back kernels and of the two-pass split: spelled here and nowhere else
+static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* name, int cap) {
+  const char* w = a.wdt == VV_F32 ? "f32" : "bf16";
+  if (g.kind == GEMV_ROWS) vv_gemv_rows_route_name(g.rows, name, cap);
+  else if (g.kind == GEMV_STREAM) vv_gemv_stream_route_name(g.st, name, cap);
+  else if (g.kind == GEMV_SPLIT) {
+    char lo[96], hi[96];
+    vv_gemv_stream_route_name(g.st, lo, sizeof(lo));
+    vv_gemv_stream_route_name(g.st2, hi, sizeof(hi));
+    snprintf(name, (size_t)cap, "%s + %s", lo, hi);
+  }
+  else if (g.kind == GEMV_LDS) snprintf(name, (size_t)cap, "gemv_lds<w=%s,m=%d,dual=%d,ks=%d,np=%d>", w, g.m, g.dual, g.ks, g.np);
+  else snprintf(name, (size_t)cap, "gemv_generic<w=%s>", w);
+}
+
+template <typename WT, int M, bool DUAL>
+static int launch_gemv(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
+  const dim3 grid(g.blocks);
+  const int KC = g.kc;
+  if (g.ks == 4) {
+    if (g.np == 2) { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 2>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
+    else           { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 1>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
+  } else {
+    if (g.np == 2) { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 2>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
+    else           { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 1>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
   }
   return 0;
 }
 
 template <typename WT, bool DUAL>
-static int launch_gemv_m(const vv_lin_args& a, hipStream_t s) {
-  switch (a.m) {
-    case 1: return launch_gemv<WT, 1, DUAL>(a, s);
-    case 2: return launch_gemv<WT, 2, DUAL>(a, s);
-    case 3: return launch_gemv<WT, 3, DUAL>(a, s);
-    case 4: return launch_gemv<WT, 4, DUAL>(a, s);
-    case 5: return launch_gemv<WT, 5, DUAL>(a, s);
-    case 6: return launch_gemv<WT, 6, DUAL>(a, s);
-    case 7: return launch_gemv<WT, 7, DUAL>(a, s);
-    default: return launch_gemv<WT, 8, DUAL>(a, s);
+static int launch_gemv_m(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
+  switch (g.m) {
+    case 1: return launch_gemv<WT, 1, DUAL>(a, g, s);
+    case 2: return launch_gemv<WT, 2, DUAL>(a, g, s);
+    case 3: return launch_gemv<WT, 3, DUAL>(a, g, s);
+    case 4: return launch_gemv<WT, 4, DUAL>(a, g, s);
+    case 5: return launch_gemv<WT, 5, DUAL>(a, g, s);
+    case 6: return launch_gemv<WT, 6, DUAL>(a, g, s);
+    case 7: return launch_gemv<WT, 7, DUAL>(a, g, s);
+    default: return launch_gemv<WT, 8, DUAL>(a, g, s);
   }
+}
+
+// the launch of a decided m <= 8 route (WT: float or bf16_t weights for the two fall-back kernels of this file)
+template <typename WT>
+static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
+  switch (g.kind) {
+    case GEMV_ROWS: return vv_launch_gemv_rows_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: rows GEMV declined its own route");
+    case GEMV_STREAM: return vv_launch_gemv_stream_route(a, g.st, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: streaming GEMV declined its own route");
+    case GEMV_SPLIT: {
+      vv_lin_args lo = a;
+      lo.m = 4;
+      if (!vv_launch_gemv_stream_route(lo, g.st, s) || !vv_launch_gemv_stream_route(split_hi(a), g.st2, s))
+        return vv_set_error(VV_E_HIP, "vv_linear: split GEMV declined its own route");
+      return 0;
+    }
+    case GEMV_LDS: return g.dual ? launch_gemv_m<WT, true>(a, g, s) : launch_gemv_m<WT, false>(a, g, s);
+    case GEMV_GENERIC: hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3(g.blocks), dim3(GEMV_THREADS), 0, s, a); return 0;
+  }
+  return vv_set_error(VV_E_HIP, "vv_linear: undecided GEMV route");
 }
 
 // The kernel family a bf16 / fp32-weight vv_linear call takes: decided here for the launch below and for vv_linear_route alike.  < 0 = error.
@@ -546,41 +665,15 @@ static int linear_family(const vv_lin_args& a, vv_mfma_route* r) {
 template <typename WT>
 static int launch_linear(const vv_lin_args& a, hipStream_t s) {
   const bool dual = a.w2 != nullptr;
-  const size_t wsz = sizeof(WT);
   const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!dual || (uintptr_t)a.w2 % 16 == 0);
   vv_mfma_route route = {};
   const int fam = linear_family(a, &route);
   if (fam < 0) return fam;
   if (fam == LIN_FAM_SKINNY) return vv_launch_skinny(a, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: skinny GEMM declined its own route");
   if (fam == LIN_FAM_GEMV) {
-    if (a.m > 2 && g_rows_part) {                               // 3..8 rows on the matrix cores (process-wide scratch: see rows_scratch)
-      const int rc = vv_launch_gemv_rows(a, g_rows_part, G_ROWS_PART_FLOATS, g_rows_tk, G_ROWS_TICKETS, s);
-      if (rc) return rc < 0 ? rc : 0;
-    }
-    if (a.flags & VV_LIN_W_FRAG)                                // only the 3..8-row matrix-core GEMV reads the fragment-major layout
-      return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_LIN_W_FRAG weights are read by the 3..8-row matrix-core GEMV only (m=%d n=%d k=%d not covered)", a.m, a.n, a.k);
-    if (vv_launch_gemv_stream(a, s)) return 0;                  // bf16 weight-streaming fast path (<= 4 rows; 5..8 rows when K splits to <= 2 units per wave)
-    if (a.m > 4 && a.wdt == VV_BF16 && a.ldx != 0) {
-      // 5..8 rows not covered above: two streaming passes of <= 4 rows (the LDS-staged kernel below is LDS-bandwidth bound at M = 8)
-      vv_lin_args lo = a, hi = a;
-      lo.m = 4;
-      hi.m = a.m - 4;
-      hi.x = a.x + 4 * a.ldx;
-      hi.out = a.out + 4 * a.ldo;
-      if (a.res) hi.res = a.res + 4 * a.ldres;
-      if (a.gate && a.gate_ld) hi.gate = a.gate + 4 * a.gate_ld;
-      if (a.mod_scale) { hi.mod_scale = a.mod_scale + 4 * a.ld_mod; hi.mod_shift = a.mod_shift + 4 * a.ld_mod; }
-      if (vv_launch_gemv_stream(lo, s)) {
-        if (vv_launch_gemv_stream(hi, s)) return 0;
-        return vv_set_error(VV_E_HIP, "vv_linear: split GEMV second half not covered");
-      }
-    }
-    const bool fast = (a.k % 8 == 0) && w_al16 && ((a.k * wsz) % 16 == 0);
-    if (fast) return dual ? launch_gemv_m<WT, true>(a, s) : launch_gemv_m<WT, false>(a, s);
-    int blocks = (a.n + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((gemv_generic_kernel<WT>), dim3(blocks), dim3(GEMV_THREADS), 0, s, a);
-    return 0;
+    gemv_route g;
+    VV_TRY(gemv_decide(a, &g));
+    return launch_gemv_route<WT>(a, g, s);
   }
   if (fam == LIN_FAM_MFMA) {
     const int rc = vv_launch_mfma_route(a, route, s);
@@ -669,22 +762,28 @@ static int linear_check_args(const vv_lin_args* a) {
   return 0;
 }
 
-// The kernel family vv_linear would launch for these arguments under the current vv_tune state, by the same decisions (linear_check_args,
-// linear_family, vv_mfma_decide): host only, nothing is launched and no pointer is followed.  An argument set vv_linear refuses is refused here too.
+// The kernel vv_linear would launch for these arguments under the current vv_tune state, by the same decisions (linear_check_args,
+// linear_family, vv_mfma_decide, gemv_decide): host only, nothing is launched and no pointer is followed.  An argument set vv_linear refuses is
+// refused here too, with the same error.
 extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
   if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_linear_route: no room for the name");
   name[0] = 0;
   VV_TRY(linear_check_args(a));
+  int fam = LIN_FAM_GEMV;
   if (a->wdt == VV_F32 || a->wdt == VV_BF16) {
     vv_mfma_route route = {};
-    const int fam = linear_family(*a, &route);
+    fam = linear_family(*a, &route);
     if (fam < 0) return fam;
     if (fam == LIN_FAM_MFMA) vv_mfma_route_name(route, name, cap);
-    else snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : fam == LIN_FAM_GEMV ? "gemv" : "gemm_f32");
-    return 0;
+    else if (fam != LIN_FAM_GEMV) snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : "gemm_f32");
   }
-  if ((a->wdt == VV_FP8 || a->wdt == VV_NF4) && a->m <= 8) { snprintf(name, (size_t)cap, "gemv"); return 0; }
-  return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_route: no kernel for wdt=%d m=%d", a->wdt, a->m);
+  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  if (fam == LIN_FAM_GEMV) {
+    gemv_route g;
+    VV_TRY(gemv_decide(*a, &g));
+    gemv_route_name(*a, g, name, cap);
+  }
+  return 0;
 }
 
 extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
@@ -700,19 +799,10 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   }
   if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
-  else if (a->wdt == VV_FP8 && (a->flags & VV_LIN_W_FRAG)) {
-    // fp8 fragment-major weights: the 3..8-row matrix-core GEMV (process-wide split-K scratch as for bf16, see rows_scratch)
-    rc = g_rows_part ? vv_launch_gemv_rows(*a, g_rows_part, G_ROWS_PART_FLOATS, g_rows_tk, G_ROWS_TICKETS, s) : 0;
-    rc = rc < 0 ? rc : rc == 1 ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)",
-                                                 a->m, a->n, a->k);
-  }
-  else if (a->wdt == VV_FP8) {
-    // weight-only fp8 exists for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix
-    rc = vv_launch_gemv_stream(*a, s) ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 weights need m <= 2, k %% 8 == 0, scales and 8-byte aligned rows (m=%d k=%d)", a->m, a->k);
-  }
-  else if (a->wdt == VV_NF4) {
-    // weight-only NF4: the streaming GEMV's NF4 instantiation (<= 2 rows); GEMM-shaped calls use the bf16 matrix of the effective weights
-    rc = vv_launch_gemv_stream(*a, s) ? 0 : vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights need m <= 2, k %% 64 == 0, scales and 16-byte aligned codes (m=%d k=%d)", a->m, a->k);
+  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4) {             // weight-only fp8 / NF4: the rows or the streaming GEMV, or refused (gemv_decide)
+    gemv_route g;
+    rc = gemv_decide(*a, &g);
+    if (!rc) rc = launch_gemv_route<bf16_t>(*a, g, s);
   }
   else return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (rc) return rc;
