@@ -5,7 +5,8 @@ Each case first asks `vv_linear_route` which kernel its arguments take and asser
 reach, under default tuning or under a named `vv_tune` setting, the generator picks the smallest k (units of 512 columns for the streaming kernel,
 32- or 64-wide steps for the matrix-core kernel) that selects it, alternating a whole number of units with a ragged end, and walks n, m, the
 operands and the layout through the edge forms (n = 1, odd n, n below the block's wave count, broadcast rows, pitches larger than the row ...).
-The compiled set is enumerated from the same rules (`ALL_INSTANTIATIONS`); what no setting reaches is listed in `UNREACHABLE` with its rule.
+The compiled set is enumerated from the same rules (`ALL_INSTANTIATIONS`, 378 kernels): every one of them is reached by a case, and
+`test_built_library_holds_exactly_the_enumerated_kernels` reads the built code objects' symbol tables and finds exactly that set.
 
 The reference (`ref_fp64`) is plain torch fp64 on the operands as the device received them and knows nothing of waves, units or tiles: bf16
 weights widened exactly, fp8 codes times row scale, NF4 the effective matrix `quantize_nf4` returns, activations fp32 and unrounded - except on
@@ -414,92 +415,6 @@ Instantiation -> case ids (generated: `python tests/test_hip_gemv.py --table`; `
   gemv_lds<w=bf16,m=8,dual=1,ks=1,np=1>                lds_bf16_m8_d1_ks1_np1_n5_k1032_silu_b_swiglu
   gemv_generic<w=f32>                                  gen_f32_m1_k13_plain, gen_f32_m3_k100_rms_now_res, ... (4 cases)
   gemv_generic<w=bf16>                                 gen_bf16_m2_k13_swiglu_gr_res, gen_bf16_m8_k1001_rms_now_swiglu_inpl, ... (4 cases)
-Compiled but unreachable under any setting:
-  84 instantiations - rw = 4 is the NF4 code layout: launch_rw<.., RW = 4> returns after the NF4 launch, its bf16 / fp8 launches behind it are dead:
-    gemv_stream<m=1,dual=0,ksplit=1,ku=1,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=1,ku=1,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=1,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=1,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=1,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=1,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=1,ku=4,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=1,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=1,ku=5,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=1,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=4,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=5,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=4,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=5,rw=4,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=1,ku=1,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=1,ku=1,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=1,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=1,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=1,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=1,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=1,ku=4,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=1,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=4,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=4,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=4,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=4,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=8,ku=2,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=8,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=1,dual=1,ksplit=8,ku=3,rw=4,wq=bf16>  gemv_stream<m=1,dual=1,ksplit=8,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=1,ku=1,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=1,ku=1,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=1,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=1,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=1,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=1,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=1,ku=4,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=1,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=1,ku=5,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=1,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=4,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=5,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=4,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=5,rw=4,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=5,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=1,ku=1,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=1,ku=1,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=1,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=1,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=1,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=1,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=1,ku=4,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=1,ku=4,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=4,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=4,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=4,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=4,ku=3,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=8,ku=2,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=8,ku=2,rw=4,wq=fp8>
-    gemv_stream<m=2,dual=1,ksplit=8,ku=3,rw=4,wq=bf16>  gemv_stream<m=2,dual=1,ksplit=8,ku=3,rw=4,wq=fp8>
-  60 instantiations - rw = 1 is chosen for dual kernels (gemv_dual_rw) and whole-row non-dual ones (gemv_small_rw) only: K-split non-dual is always rw = 2:
-    gemv_stream<m=1,dual=0,ksplit=4,ku=2,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=3,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=4,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=4,ku=5,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=4,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=2,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=3,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=4,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=8,ku=5,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=8,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=16,ku=2,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=16,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=16,ku=3,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=16,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=16,ku=4,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=16,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=1,dual=0,ksplit=16,ku=5,rw=1,wq=bf16>  gemv_stream<m=1,dual=0,ksplit=16,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=2,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=4,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=4,ku=5,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=4,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=2,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=3,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=4,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=8,ku=5,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=8,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=16,ku=2,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=16,ku=2,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=16,ku=3,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=16,ku=3,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=16,ku=4,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=16,ku=4,rw=1,wq=fp8>
-    gemv_stream<m=2,dual=0,ksplit=16,ku=5,rw=1,wq=bf16>  gemv_stream<m=2,dual=0,ksplit=16,ku=5,rw=1,wq=fp8>
-    gemv_stream<m=4,dual=0,ksplit=4,ku=2,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=4,ku=3,rw=1,wq=bf16>
-    gemv_stream<m=4,dual=0,ksplit=4,ku=4,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=4,ku=5,rw=1,wq=bf16>
-    gemv_stream<m=4,dual=0,ksplit=8,ku=2,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=8,ku=3,rw=1,wq=bf16>
-    gemv_stream<m=4,dual=0,ksplit=8,ku=4,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=8,ku=5,rw=1,wq=bf16>
-    gemv_stream<m=4,dual=0,ksplit=16,ku=2,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=16,ku=3,rw=1,wq=bf16>
-    gemv_stream<m=4,dual=0,ksplit=16,ku=4,rw=1,wq=bf16>  gemv_stream<m=4,dual=0,ksplit=16,ku=5,rw=1,wq=bf16>
-  20 instantiations - two rows per wave without K split is taken for m <= 4 (dual: m <= 2) only:
-    gemv_lds<w=f32,m=3,dual=1,ks=1,np=2>  gemv_lds<w=f32,m=4,dual=1,ks=1,np=2>
-    gemv_lds<w=f32,m=5,dual=0,ks=1,np=2>  gemv_lds<w=f32,m=5,dual=1,ks=1,np=2>
-    gemv_lds<w=f32,m=6,dual=0,ks=1,np=2>  gemv_lds<w=f32,m=6,dual=1,ks=1,np=2>
-    gemv_lds<w=f32,m=7,dual=0,ks=1,np=2>  gemv_lds<w=f32,m=7,dual=1,ks=1,np=2>
-    gemv_lds<w=f32,m=8,dual=0,ks=1,np=2>  gemv_lds<w=f32,m=8,dual=1,ks=1,np=2>
-    gemv_lds<w=bf16,m=3,dual=1,ks=1,np=2>  gemv_lds<w=bf16,m=4,dual=1,ks=1,np=2>
-    gemv_lds<w=bf16,m=5,dual=0,ks=1,np=2>  gemv_lds<w=bf16,m=5,dual=1,ks=1,np=2>
-    gemv_lds<w=bf16,m=6,dual=0,ks=1,np=2>  gemv_lds<w=bf16,m=6,dual=1,ks=1,np=2>
-    gemv_lds<w=bf16,m=7,dual=0,ks=1,np=2>  gemv_lds<w=bf16,m=7,dual=1,ks=1,np=2>
-    gemv_lds<w=bf16,m=8,dual=0,ks=1,np=2>  gemv_lds<w=bf16,m=8,dual=1,ks=1,np=2>
 """
 import ctypes as C
 import functools
@@ -516,7 +431,7 @@ import torch
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import rel_rms
-from test_hip_mfma_gemm import NAN, _FAKE, _epilogue, _gapped, _lib, _need_gpu, _prologue, _same_bits, bf16_round64
+from test_hip_mfma_gemm import NAN, _FAKE, _epilogue, _gapped, _lib, _need_gpu, _prologue, _same_bits, bf16_round64, built_kernels, instantiations_of
 
 EPS = 1e-5
 
@@ -580,41 +495,40 @@ ROWS_FORMS = [(0, 4, 3, 0, 0), (0, 4, 6, 0, 0), (0, 4, 9, 0, 0), (0, 4, 12, 0, 0
               (0, 4, 2, 0, 1), (0, 4, 4, 0, 1), (0, 4, 6, 0, 1), (0, 4, 8, 0, 1)]
 
 
+def stream_exists(m, dual, ksplit, ku, rw, wq):
+    """stream_exists of vv_gemv_stream.hip: the kernels the launch ladder instantiates"""
+    if m == 8:
+        return wq == "bf16" and not dual and (ksplit, ku, rw) in M8_FORMS
+    if m not in (1, 2, 4):
+        return False
+    if wq == "nf4":
+        return rw == 4 and stream_built_nf4(m, dual, ksplit, ku)
+    if wq == "fp8" and m > 2:
+        return False
+    if rw not in (1, 2) or (rw == 1 and not dual and ksplit != 1):
+        return False
+    return stream_built(dual, ksplit, ku)
+
+
+def lds_built(m, dual, ks, np_):
+    """lds_built of vv_kernels.hip: two whole rows per wave (ks = 1, np = 2) exist for m <= 4 (dual: m <= 2) only"""
+    return ks == 4 or np_ == 1 or (m <= 4 and not (dual and m > 2))
+
+
 def _compiled():
-    """Every instantiation the launch ladders compile, by their rules: launch_one instantiates rw = 1 and rw = 2 for every form (a run-time
-    choice), and rw = 4 where NF4 is built; launch_rw instantiates bf16 for every rw, fp8 for m <= 2, NF4 for rw = 4."""
-    out = []
-    for m in (1, 2, 4):
-        for dual, ksplit, ku in itertools.product((0, 1), (1, 4, 8, 16), range(1, 6)):
-            if not stream_built(dual, ksplit, ku):
-                continue
-            for rw in (1, 2) + ((4,) if stream_built_nf4(m, dual, ksplit, ku) else ()):
-                for wq in ("bf16",) + (("fp8",) if m <= 2 else ()) + (("nf4",) if rw == 4 else ()):
-                    out.append(_stream(m, dual, ksplit, ku, rw, wq))
+    """Every instantiation the launch ladders compile, by their predicates: what is compiled is what a call can reach, under default tuning or
+    under a vv_tune setting (test_built_library_holds_exactly_the_enumerated_kernels reads the binary)."""
+    out = [_stream(m, dual, ksplit, ku, rw, wq) for m in (1, 2, 4) for dual, ksplit, ku in itertools.product((0, 1), (1, 4, 8, 16), range(1, 6))
+           for rw in (1, 2, 4) for wq in WQS if stream_exists(m, dual, ksplit, ku, rw, wq)]
     out += [_stream(8, 0, ks, ku, rw, "bf16") for ks, ku, rw in M8_FORMS]
     out += [_rows(*f) for f in ROWS_FORMS]
-    out += [_lds(w, m, dual, ks, np_) for w in ("f32", "bf16") for m in range(1, 9) for dual in (0, 1) for ks, np_ in ((4, 2), (4, 1), (1, 2), (1, 1))]
+    out += [_lds(w, m, dual, ks, np_) for w in ("f32", "bf16") for m in range(1, 9) for dual in (0, 1) for ks, np_ in ((4, 2), (4, 1), (1, 2), (1, 1))
+            if lds_built(m, dual, ks, np_)]
     out += ["gemv_generic<w=f32>", "gemv_generic<w=bf16>"]
     return out
 
 
 ALL_INSTANTIATIONS = _compiled()
-
-
-def unreachable_rule(inst):
-    """The rule that keeps a compiled instantiation from ever being launched, or None"""
-    f = dict(p.split("=") for p in inst[inst.index("<") + 1: inst.index(">")].split(","))
-    if inst.startswith("gemv_stream") and f["m"] != "8":
-        if f["rw"] == "4" and f["wq"] != "nf4":
-            return "rw = 4 is the NF4 code layout: launch_rw<.., RW = 4> returns after the NF4 launch, its bf16 / fp8 launches behind it are dead"
-        if f["dual"] == "0" and f["ksplit"] != "1" and f["rw"] == "1":
-            return "rw = 1 is chosen for dual kernels (gemv_dual_rw) and whole-row non-dual ones (gemv_small_rw) only: K-split non-dual is always rw = 2"
-    if inst.startswith("gemv_lds") and f["ks"] == "1" and f["np"] == "2" and (int(f["m"]) > 4 or (f["dual"] == "1" and int(f["m"]) > 2)):
-        return "two rows per wave without K split is taken for m <= 4 (dual: m <= 2) only"
-    return None
-
-
-UNREACHABLE = {i: unreachable_rule(i) for i in ALL_INSTANTIATIONS if unreachable_rule(i)}
 
 
 def stream_decide(m, n, k, dual, wq, tune):
@@ -749,7 +663,7 @@ def _cases():
                                       {"chan": "gc", "row": "gr"}.get(o.get("gate"), ""), {"out": "res", "inplace": "inpl"}.get(o.get("res"), ""),
                                       "bcast" if o.get("ldx") == 0 else ""])) or "plain"
 
-    # ---- streaming kernel: every reachable instantiation once, the smallest k that selects it; whole units and ragged ends alternate -------
+    # ---- streaming kernel: every instantiation once, the smallest k that selects it; whole units and ragged ends alternate -----------------
     reach = {}                                            # instantiation -> (units, hooks)
     for wq, m, dual in itertools.product(WQS, (1, 2, 4), (0, 1)):
         if wq != "bf16" and m > 2:
@@ -875,7 +789,7 @@ def _cases():
     # ---- LDS-staged kernel: fp32 weights at every M, dual and not, the four (KS, NP) forms; bf16 weights where the streaming kernel declines ----
     for w, m, dual, (ks, np_) in itertools.product(("f32", "bf16"), range(1, 9), (0, 1), ((4, 2), (4, 1), (1, 2), (1, 1))):
         inst = _lds(w, m, dual, ks, np_)
-        if inst in UNREACHABLE:
+        if not lds_built(m, dual, ks, np_):
             continue
         i = next(count)
         n, k = {(4, 2): (1026, 2056), (4, 1): (NS[i % len(NS)], 2048 + 8 * (i % 3)), (1, 2): (8193, 24), (1, 1): (NS[i % len(NS)], 1032 if m == 8 else 520)}[(ks, np_)]
@@ -906,19 +820,11 @@ HYGIENE = [(3, 33, 13 * 512, 0, _stream(4, 0, 4, 4, 2, "bf16")), (2, 33, 1024, 1
 def instantiation_table():
     lines = []
     for inst in ALL_INSTANTIATIONS:
-        if inst in UNREACHABLE:
-            continue
         ids = [c.id for c in CASES if inst in c.route.split(" + ")]
         sets = [sorted(set(c.hooks) - {"gemv_rows_scratch"}) for c in CASES if c.route == inst]      # reached under default tuning, or under which setting
         hooks = [] if (not sets or [] in sets) else sets[0]
         text = ", ".join(ids[:2]) + (f", ... ({len(ids)} cases)" if len(ids) > 2 else "") + (f"   [{', '.join(hooks)}]" if hooks else "")
         lines.append(f"  {inst:<52} {text}")
-    lines.append("Compiled but unreachable under any setting:")
-    for rule in dict.fromkeys(UNREACHABLE.values()):
-        insts = [i for i in UNREACHABLE if UNREACHABLE[i] == rule]
-        lines.append(f"  {len(insts)} instantiations - {rule}:")
-        for j in range(0, len(insts), 2):
-            lines.append("    " + "  ".join(insts[j: j + 2]))
     return "\n".join(lines)
 
 
@@ -1052,15 +958,25 @@ def test_bars_sit_between_floor_and_dropped_chunk(cid):
 
 
 def test_docstring_table_is_current():
-    """the instantiation -> case table of the docstring is the one the parametrisation generates; every compiled instantiation is reached by a
-    case or listed as unreachable with its rule, and DESIGN.md carries the same unreachable list"""
-    table = instantiation_table()
-    assert table in __doc__
+    """the instantiation -> case table of the docstring is the one the parametrisation generates, and the instantiations the cases reach are
+    exactly the compiled ones: 246 streaming, 22 rows, 108 LDS-staged, 2 generic"""
+    assert instantiation_table() in __doc__
     reached = {r for c in CASES for r in c.route.split(" + ")}
-    assert reached | set(UNREACHABLE) == set(ALL_INSTANTIATIONS), sorted((reached | set(UNREACHABLE)) ^ set(ALL_INSTANTIATIONS))
-    assert not reached & set(UNREACHABLE)
-    design = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md")).read()
-    assert table[table.index("Compiled but unreachable under any setting:"):] in design
+    assert reached == set(ALL_INSTANTIATIONS), sorted(reached ^ set(ALL_INSTANTIATIONS))
+    assert len(set(ALL_INSTANTIATIONS)) == len(ALL_INSTANTIATIONS) == 378
+    assert [sum(i.startswith(p) for i in ALL_INSTANTIATIONS) for p in ("gemv_stream<", "gemv_rows<", "gemv_lds<", "gemv_generic<")] == [246, 22, 108, 2]
+
+
+def test_built_library_holds_exactly_the_enumerated_kernels(tmp_path):
+    """What is compiled is what can be launched: the gfx950 code objects of the three units hold one kernel per entry of ALL_INSTANTIATIONS and no
+    other instantiation of the four templates (CPU only: reads the symbol tables of the object files build() left).  The device side is read
+    because the host side proves nothing: launch stubs behind a dead branch vanish while their kernels are still generated."""
+    names = {"gemv_stream_kernel": lambda m, dual, ksplit, ku, rw, wq: _stream(m, dual, ksplit, ku, rw, WQS[wq]),
+             "gemv_rows_kernel": _rows, "gemv_kernel": _lds, "gemv_generic_kernel": lambda w: f"gemv_generic<w={w}>"}
+    got = set()
+    for unit in ("vv_gemv_stream.hip", "vv_gemv_rows.hip", "vv_kernels.hip"):
+        got |= instantiations_of(built_kernels(unit, tmp_path), names)
+    assert got == set(ALL_INSTANTIATIONS), sorted(got ^ set(ALL_INSTANTIATIONS))
 
 
 def test_reference_agrees_with_ref_linear_of_the_parity_suite():

@@ -65,6 +65,9 @@ import ctypes as C
 import functools
 import math
 import os
+import re
+import shutil
+import subprocess
 import sys
 import zlib
 
@@ -460,6 +463,50 @@ def test_docstring_table_is_current():
     assert instantiation_table() in __doc__
     routes = {c.route for c in CASES}
     assert routes == set(ALL_INSTANTIATIONS) and len(ALL_INSTANTIATIONS) == 30, routes ^ set(ALL_INSTANTIATIONS)
+
+
+def built_kernels(unit, tmp_path):
+    """(kernel template, [template arguments]) of every kernel descriptor (*.kd) in the gfx950 code object of one translation unit's object file
+    under build.OBJDIR - what the device compiler generated, whatever the host side still launches.  Symbol names only: the .hip_fatbin section is
+    copied out, the gfx950 bundle unpacked and its symbol table listed, with the LLVM tools that sit next to hipcc."""
+    from vibevoice_rocm_amd import build as vb
+    obj = vb._obj(os.path.join(vb.HERE, "csrc", unit))
+    assert os.path.exists(obj), f"{obj} is missing: build() leaves one object file per translation unit there"
+    hip = os.path.dirname(os.path.realpath(vb.find_hipcc()))
+    dirs = [os.environ.get("HIP_CLANG_PATH"), os.path.join(hip, "..", "lib", "llvm", "bin"), os.path.join(hip, "..", "llvm", "bin"), hip]
+
+    def tool(name):
+        found = next((os.path.join(d, name) for d in dirs if d and os.path.exists(os.path.join(d, name))), None) or shutil.which(name)
+        assert found, f"{name} not found next to hipcc"
+        return found
+
+    fatbin, co = str(tmp_path / (unit + ".fatbin")), str(tmp_path / (unit + ".co"))
+    subprocess.run([tool("llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj, fatbin], check=True)
+    subprocess.run([tool("clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fatbin,
+                    "--output=" + co], check=True)
+    syms = subprocess.run([tool("llvm-readelf"), "--symbols", "--wide", "--demangle", co], check=True, capture_output=True, text=True).stdout
+    out = []
+    for line in syms[syms.index("Symbol table '.symtab'"):].splitlines():      # the listing holds .dynsym too: every kernel would come twice
+        hit = re.search(r"(\w+)<(.*)>\(.*\) \(\.kd\)$", line)
+        if hit:
+            out.append((hit.group(1), hit.group(2).split(", ")))
+    return out
+
+
+def instantiations_of(kernels, names):
+    """The route names of the built kernels whose template is a key of `names` (template -> function of its arguments as ints; bools 0 / 1, the
+    weight types by name); every name once, or the build holds a kernel twice"""
+    val = {"true": 1, "false": 0, "float": "f32", "unsigned short": "bf16"}
+    got = [names[k](*[val[a] if a in val else int(a) for a in args]) for k, args in kernels if k in names]
+    assert len(set(got)) == len(got)
+    return set(got)
+
+
+def test_built_library_holds_exactly_the_enumerated_kernels(tmp_path):
+    """vv_mfma_gemm.hip's code object holds the 30 kernels of ALL_INSTANTIATIONS and no other instantiation of the two templates (CPU only: reads
+    the symbol table of the object file build() left)"""
+    got = instantiations_of(built_kernels("vv_mfma_gemm.hip", tmp_path), {"mfma_linear_kernel": _stream, "mfma_tiled_kernel": _tiled})
+    assert got == set(ALL_INSTANTIATIONS), sorted(got ^ set(ALL_INSTANTIATIONS))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -40,9 +40,8 @@ enum { VV_GEMV_STREAM = 1, VV_GEMV_HOT = 2, VV_GEMV_CONV_HOT = 3 };
 // vv_gemv_stream.hip: gemv_stream_kernel<m, dual, ksplit, ku, rw, wq> (wq: 0 bf16, 1 fp8, 2 NF4) on blocks x threads, or a hot kernel (table entry idx)
 struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, blocks, threads; };
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
-int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0
+int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
-int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s);   // decide + launch: 1 = launched, 0 = not covered
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
 // template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.

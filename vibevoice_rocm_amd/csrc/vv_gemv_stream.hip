@@ -577,7 +577,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
 int g_dual_rw = 1;            // weight rows per wave step for the dual (SwiGLU) kernel: 1 keeps 4 waves/SIMD resident
 int g_small_rw = 2;           // rows per wave step for narrow non-dual matrices (tuning hook)
 
-// Which (dual, ksplit, ku) forms of the M = 1 / 2 / 4 kernels are built - read by the launch ladder (if constexpr) and by the decision alike:
+// Which (dual, ksplit, ku) forms of the M = 1 / 2 / 4 kernels are built (the pieces of stream_exists below):
 // whole rows at 1..5 units, 4 / 8 / 16 waves splitting K at 2..5 units per wave; the dual kernel holds two weight streams, so its K-split forms
 // stop at 8 waves and 3 units
 constexpr bool stream_built(bool dual, int ksplit, int ku) {
@@ -590,6 +590,21 @@ constexpr bool stream_built(bool dual, int ksplit, int ku) {
 constexpr bool stream_built_nf4(int m, bool dual, int ksplit, int ku) { return stream_built(dual, ksplit, ku) && m <= 2 && ksplit <= 8 && !(dual && ku > 4); }
 // 5..8 rows: the fragment is 8 rows x KU x 8 floats, so K is split until KU <= 2 (16 waves x 8 rows does not fit the 128-VGPR budget of a 1024-thread block)
 constexpr bool stream_built_m8(int ksplit, int ku, int rw) { return (ksplit == 1 && (ku == 1 || ku == 2) && rw == 1) || ((ksplit == 4 || ksplit == 8) && ku == 2 && rw == 2); }
+// Every kernel of this file that exists, as (m, dual, ksplit, ku, rw, wq): the launch ladder instantiates under this predicate and nothing else, and
+// the decision checks its finished route against it, so neither can name a kernel the other does not have.
+//   m = 8      bf16 only, one weight stream
+//   NF4        rw = 4 (four rows per 16-byte code load), and no other weight type has rw = 4
+//   bf16, fp8  rw = 1 or 2; fp8 for decode rows (m <= 2) only; rw = 1 for the dual kernels (gemv_dual_rw) and the whole-row ones (gemv_small_rw):
+//              a non-dual K-split kernel is always rw = 2
+constexpr bool stream_exists(int m, bool dual, int ksplit, int ku, int rw, int wq) {
+  if (m == 8) return wq == 0 && !dual && stream_built_m8(ksplit, ku, rw);
+  if (m != 1 && m != 2 && m != 4) return false;
+  if (wq == 2) return rw == 4 && stream_built_nf4(m, dual, ksplit, ku);
+  if (wq != 0 && !(wq == 1 && m <= 2)) return false;
+  if (rw != 1 && rw != 2) return false;
+  if (rw == 1 && !dual && ksplit != 1) return false;
+  return stream_built(dual, ksplit, ku);
+}
 
 // persistent grid, sized from measurements on MI355X (tools/mb_gemv.py): ~1.5-2 blocks per CU is the sweet spot for the
 // wave-per-row layout (more blocks only add prologue copies and a ragged last round), one block per row group when the
@@ -610,42 +625,47 @@ void stream_grid(const vv_lin_args& a, vv_stream_route& r) {
   r.threads = KSPLIT == 1 ? 64 * waves : 64 * KSPLIT;
 }
 
+// The launch ladder: one run-time switch per template argument, and at its foot the only place a kernel is instantiated - under stream_exists, so
+// what is compiled is what can be launched.  A route outside the predicate is declined (false), never served by a neighbouring kernel on a grid
+// sized for another rw.
+template <int M, bool DUAL, int KSPLIT, int KU, int RW, int WQ>
+bool launch_one(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  if constexpr (stream_exists(M, DUAL, KSPLIT, KU, RW, WQ)) {
+    hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, WQ>), dim3(r.blocks), dim3(r.threads), 0, s, a, r.n_groups, g_opt);
+    return true;
+  } else {
+    return false;
+  }
+}
+
 template <int M, bool DUAL, int KSPLIT, int KU, int RW>
-void launch_rw(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
-  const dim3 blocks(r.blocks), threads(r.threads);
-  const int n_groups = r.n_groups;
-  if constexpr (RW == 4) {                       // NF4 weights (launch_one): 4 rows per code load
-    hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 2>), blocks, threads, 0, s, a, n_groups, g_opt);
-    return;
+bool launch_wq(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  switch (r.wq) {
+    case 0: return launch_one<M, DUAL, KSPLIT, KU, RW, 0>(a, r, s);
+    case 1: return launch_one<M, DUAL, KSPLIT, KU, RW, 1>(a, r, s);
+    case 2: return launch_one<M, DUAL, KSPLIT, KU, RW, 2>(a, r, s);   // never a bf16 read of codes
   }
-  if constexpr (M <= 2) {                        // fp8 weights: decode rows only
-    if (r.wq == 1) {
-      hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 1>), blocks, threads, 0, s, a, n_groups, g_opt);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((gemv_stream_kernel<M, DUAL, KSPLIT, KU, RW, 0>), blocks, threads, 0, s, a, n_groups, g_opt);
+  return false;
 }
 
 template <int M, bool DUAL, int KSPLIT, int KU>
-bool launch_one(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
-  if (r.wq == 2) {         // never a bf16 read of codes
-    if constexpr (stream_built_nf4(M, DUAL, KSPLIT, KU)) { launch_rw<M, DUAL, KSPLIT, KU, 4>(a, r, s); return true; }
-    return false;
+bool launch_rw(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  switch (r.rw) {
+    case 1: return launch_wq<M, DUAL, KSPLIT, KU, 1>(a, r, s);
+    case 2: return launch_wq<M, DUAL, KSPLIT, KU, 2>(a, r, s);
+    case 4: return launch_wq<M, DUAL, KSPLIT, KU, 4>(a, r, s);
   }
-  if (r.rw == 1) launch_rw<M, DUAL, KSPLIT, KU, 1>(a, r, s);
-  else launch_rw<M, DUAL, KSPLIT, KU, 2>(a, r, s);
-  return true;
+  return false;
 }
 
 template <int M, bool DUAL, int KSPLIT>
 bool launch_kus(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
   switch (r.ku) {
-    case 1: if constexpr (stream_built(DUAL, KSPLIT, 1)) return launch_one<M, DUAL, KSPLIT, 1>(a, r, s); else return false;
-    case 2: return launch_one<M, DUAL, KSPLIT, 2>(a, r, s);
-    case 3: return launch_one<M, DUAL, KSPLIT, 3>(a, r, s);
-    case 4: if constexpr (stream_built(DUAL, KSPLIT, 4)) return launch_one<M, DUAL, KSPLIT, 4>(a, r, s); else return false;
-    case 5: if constexpr (stream_built(DUAL, KSPLIT, 5)) return launch_one<M, DUAL, KSPLIT, 5>(a, r, s); else return false;
+    case 1: return launch_rw<M, DUAL, KSPLIT, 1>(a, r, s);
+    case 2: return launch_rw<M, DUAL, KSPLIT, 2>(a, r, s);
+    case 3: return launch_rw<M, DUAL, KSPLIT, 3>(a, r, s);
+    case 4: return launch_rw<M, DUAL, KSPLIT, 4>(a, r, s);
+    case 5: return launch_rw<M, DUAL, KSPLIT, 5>(a, r, s);
   }
   return false;
 }
@@ -656,22 +676,14 @@ bool launch_ku(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
     case 1: return launch_kus<M, DUAL, 1>(a, r, s);
     case 4: return launch_kus<M, DUAL, 4>(a, r, s);
     case 8: return launch_kus<M, DUAL, 8>(a, r, s);
-    case 16: if constexpr (stream_built(DUAL, 16, 2)) return launch_kus<M, false, 16>(a, r, s); else return false;
+    case 16: return launch_kus<M, DUAL, 16>(a, r, s);
   }
   return false;
 }
 
-// 5..8 activation rows (the conv tokenizers' T = 8 stage, C = 1024): one pass over the weights instead of two 4-row passes
-bool launch_m8(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
-  if (r.ksplit == 1) {
-    if (r.ku == 1) launch_rw<8, false, 1, 1, 1>(a, r, s); else launch_rw<8, false, 1, 2, 1>(a, r, s);
-    return true;
-  }
-  switch (r.ksplit) {
-    case 4: launch_rw<8, false, 4, 2, 2>(a, r, s); return true;
-    case 8: launch_rw<8, false, 8, 2, 2>(a, r, s); return true;
-  }
-  return false;
+template <int M>
+bool launch_m(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
+  return r.dual ? launch_ku<M, true>(a, r, s) : launch_ku<M, false>(a, r, s);
 }
 
 }  // namespace
@@ -707,7 +719,7 @@ vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
     if (!ks) return r;
     if (ks > 1) ku8 = 2;
     r.m = 8; r.ksplit = ks; r.ku = ku8; r.rw = ks == 1 ? 1 : 2;
-    if (!stream_built_m8(r.ksplit, r.ku, r.rw)) return r;
+    if (!stream_exists(r.m, r.dual, r.ksplit, r.ku, r.rw, r.wq)) return r;
     stream_grid(a, r);
     r.kind = VV_GEMV_STREAM;
     return r;
@@ -741,14 +753,10 @@ vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
   }
   r.m = a.m == 1 ? 1 : a.m == 2 ? 2 : 4;
   r.dual = dual; r.ksplit = ksplit; r.ku = ku;
-  if (r.wq == 2) {                               // NF4: 4 rows per 16-byte code load; 16 waves of table slots would not fit the block's LDS
-    if (!stream_built_nf4(r.m, dual, ksplit, ku)) return r;
-    r.rw = 4;
-  } else {
-    if (!stream_built(dual, ksplit, ku)) return r;
-    if (dual) r.rw = g_dual_rw == 1 ? 1 : 2;
-    else r.rw = (ksplit == 1 && a.n <= 4096 && g_small_rw == 1) ? 1 : 2;
-  }
+  if (r.wq == 2) r.rw = 4;                       // NF4: 4 rows per 16-byte code load
+  else if (dual) r.rw = g_dual_rw == 1 ? 1 : 2;
+  else r.rw = (ksplit == 1 && a.n <= 4096 && g_small_rw == 1) ? 1 : 2;
+  if (!stream_exists(r.m, dual, ksplit, ku, r.rw, r.wq)) return r;   // no such kernel (NF4: 16 waves of table slots would not fit the block's LDS)
   stream_grid(a, r);
   r.kind = VV_GEMV_STREAM;
   return r;
@@ -758,12 +766,13 @@ int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, 
   if (r.kind == VV_GEMV_HOT) return vv_launch_gemv_hot(a, r.idx, s);
   if (r.kind == VV_GEMV_CONV_HOT) return vv_launch_conv_hot_gemv(a, r.idx, s);
   if (r.kind != VV_GEMV_STREAM) return 0;
-  bool ok;
-  if (r.m == 8) ok = launch_m8(a, r, s);
-  else if (r.m == 1) ok = r.dual ? launch_ku<1, true>(a, r, s) : launch_ku<1, false>(a, r, s);
-  else if (r.m == 2) ok = r.dual ? launch_ku<2, true>(a, r, s) : launch_ku<2, false>(a, r, s);
-  else ok = r.dual ? launch_ku<4, true>(a, r, s) : launch_ku<4, false>(a, r, s);
-  return ok ? 1 : 0;
+  switch (r.m) {
+    case 1: return launch_m<1>(a, r, s);
+    case 2: return launch_m<2>(a, r, s);
+    case 4: return launch_m<4>(a, r, s);
+    case 8: return launch_m<8>(a, r, s);   // 5..8 activation rows (the conv tokenizers' T = 8 stage, C = 1024): one pass over the weights instead of two 4-row passes
+  }
+  return 0;
 }
 
 // the names vv_linear_route reports for this file's routes: spelled here and nowhere else
@@ -772,9 +781,4 @@ int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap) {
   if (r.kind == VV_GEMV_CONV_HOT) return snprintf(name, (size_t)cap, "conv_hot_gemv<%d>", r.idx);
   return snprintf(name, (size_t)cap, "gemv_stream<m=%d,dual=%d,ksplit=%d,ku=%d,rw=%d,wq=%s>", r.m, r.dual, r.ksplit, r.ku, r.rw,
                   r.wq == 2 ? "nf4" : r.wq == 1 ? "fp8" : "bf16");
-}
-
-// returns 1 when the call was launched here, 0 when the shape/alignment is not covered (caller falls back)
-int vv_launch_gemv_stream(const vv_lin_args& a, hipStream_t s) {
-  return vv_launch_gemv_stream_route(a, vv_gemv_stream_decide(a), s);
 }

@@ -520,6 +520,14 @@ static vv_lin_args split_hi(const vv_lin_args& a) {
   return hi;
 }
 
+// Which gemv_kernel<WT, M, DUAL, KS, NP> forms exist - read by the decision and by the launch (if constexpr) alike: four waves splitting K at one or
+// two rows per wave pair, whole rows at one row per wave, and two whole rows per wave while their accumulators fit (m <= 4, dual: m <= 2)
+constexpr bool lds_built(int m, bool dual, int ks, int np) {
+  if (m < 1 || m > 8 || (np != 1 && np != 2)) return false;
+  if (ks == 4) return true;
+  return ks == 1 && (np == 1 || (m <= 4 && !(dual && m > 2)));
+}
+
 static void lds_decide(const vv_lin_args& a, gemv_route* g) {
   const int K = a.k, N = a.n, M = a.m;
   const bool DUAL = a.w2 != nullptr;
@@ -536,7 +544,7 @@ static void lds_decide(const vv_lin_args& a, gemv_route* g) {
     else           { g->np = 1; g->blocks = N; }
   } else {
     g->ks = 1;
-    if ((int64_t)N >= 8192 && M <= 4 && !(DUAL && M > 2)) { g->np = 2; g->blocks = (N + 7) / 8; }
+    if ((int64_t)N >= 8192 && lds_built(M, DUAL, 1, 2)) { g->np = 2; g->blocks = (N + 7) / 8; }
     else { g->np = 1; g->blocks = (N + 3) / 4; }
   }
 }
@@ -603,18 +611,23 @@ static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* nam
   else snprintf(name, (size_t)cap, "gemv_generic<w=%s>", w);
 }
 
+template <typename WT, int M, bool DUAL, int KS, int NP>
+static int launch_gemv_form(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
+  if constexpr (lds_built(M, DUAL, KS, NP)) {
+    hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, KS, NP>), dim3(g.blocks), dim3(GEMV_THREADS), g.lds, s, a, g.kc);
+    return 0;
+  } else {
+    return vv_set_error(VV_E_HIP, "vv_linear: undecided GEMV route");
+  }
+}
+
 template <typename WT, int M, bool DUAL>
 static int launch_gemv(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
-  const dim3 grid(g.blocks);
-  const int KC = g.kc;
-  if (g.ks == 4) {
-    if (g.np == 2) { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 2>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
-    else           { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 4, 1>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
-  } else {
-    if (g.np == 2) { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 2>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
-    else           { hipLaunchKernelGGL((gemv_kernel<WT, M, DUAL, 1, 1>), grid, dim3(GEMV_THREADS), g.lds, s, a, KC); }
-  }
-  return 0;
+  if (g.ks == 4 && g.np == 2) return launch_gemv_form<WT, M, DUAL, 4, 2>(a, g, s);
+  if (g.ks == 4 && g.np == 1) return launch_gemv_form<WT, M, DUAL, 4, 1>(a, g, s);
+  if (g.ks == 1 && g.np == 2) return launch_gemv_form<WT, M, DUAL, 1, 2>(a, g, s);
+  if (g.ks == 1 && g.np == 1) return launch_gemv_form<WT, M, DUAL, 1, 1>(a, g, s);
+  return vv_set_error(VV_E_HIP, "vv_linear: undecided GEMV route");
 }
 
 template <typename WT, bool DUAL>
