@@ -370,6 +370,13 @@ size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int B);
 int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
                              const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
                              const float* sde_noise, int64_t ld_sde, vv_stream_t stream);
+/* The same two samplers with one guidance scale PER UTTERANCE, read on the device: cfg_rows[B] (device memory; utterance b's scale) takes the
+ * place of cfg_scale, so a captured graph serves any scales and utterances with different scales share a call.  sde_noise == NULL: the ODE
+ * solver with the workspace of vv_head_ws_bytes_batch; else the SDE solver with that of vv_head_ws_bytes_batch_sde.  Same limits and argument
+ * errors as those; cfg_rows == NULL returns VV_E_ARG.  With cfg_rows[b] == c for all b the sample is that of the scalar entry point at c. */
+int vv_head_sample_batch_cfg(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                             const vv_dpm_coef* coef, int n_steps, const float* cfg_rows /* device, [B] */, float* latent_out, int64_t ld_latent,
+                             int B, void* ws, const float* sde_noise /* NULL: ODE */, int64_t ld_sde, vv_stream_t stream);
 /* The samplers' Gaussian noise drawn on the device, one launch for B utterances: noise[b * ld_noise + e], e < n, is the initial latent (kind 0) and,
  * when sde_noise is given, sde_noise[b * ld_sde + s * n + e] the variance noise of solver step s < n_steps (kind 1 + s) - the buffers
  * vv_head_sample and vv_head_sample_batch(_sde) read.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85)

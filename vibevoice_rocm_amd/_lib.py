@@ -163,6 +163,7 @@ PROTOTYPES = {
     "vv_head_sample_batch": (C.c_int, [C.POINTER(Head), vp, i64, vp, i64, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, i64, C.c_int, vp, vp]),
     "vv_head_ws_bytes_batch_sde": (C.c_size_t, [C.POINTER(Head), C.c_int, C.c_int]),
     "vv_head_sample_batch_sde": (C.c_int, [C.POINTER(Head), vp, i64, vp, i64, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, i64, C.c_int, vp, vp, i64, vp]),
+    "vv_head_sample_batch_cfg": (C.c_int, [C.POINTER(Head), vp, i64, vp, i64, vp, C.POINTER(DpmCoef), C.c_int, vp, vp, i64, C.c_int, vp, vp, i64, vp]),
     "vv_noise_normal": (C.c_int, [vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vv_head_sample": (C.c_int, [C.POINTER(Head), vp, i64, vp, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, vp, vp, vp]),
     "vv_head_forward": (C.c_int, [C.POINTER(Head), vp, vp, vp, C.c_int, vp, vp, vp]),

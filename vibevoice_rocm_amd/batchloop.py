@@ -24,9 +24,13 @@ like a greedy one.
 
 Diffusion noise on the device (BatchCall.noise_seeds): the driver is told every dialogue's seed once (`set_noise_seeds(seeds)`, after begin) and
 draws a frame's noise itself from (seed, frame index); `eligible` and the rows of `speech` then carry `(frame index, None)` in place of the
-noise rows, every dialogue in its steady state may be speculated, and the loop makes no draw of its own."""
+noise rows, every dialogue in its steady state may be speculated, and the loop makes no draw of its own.
+
+`Session` (below `run`) is the same loop for serving: slots that are refilled between two steps, every dialogue with batch-of-one semantics
+(modeling._SessionDriver; under a recording fake in tests/test_host_session.py)."""
 from __future__ import annotations
 
+import time
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
 
@@ -294,3 +298,314 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
     rows = [torch.cat([input_ids[b][~keep[b]], torch.tensor(seq[b], dtype=torch.long)]) for b in range(B)]
     audios = [(torch.cat(c)[None] if c else None) for c in chunks]
     return pack_output(rows, audios, reach, call.pad_id, call.in_dev, call.return_speech)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# serving sessions: the row batches' slots refilled between two steps
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SessionRequest:
+    """What submit() fixes for one dialogue of a session: its unpadded prompt (`head`: the left padding the caller's row carried, put back in front
+    of the returned sequence), its voice rows `(mask, rows)` or voice prefix, its guidance scale, limits, schedule, noise and streamer."""
+    prompt: torch.Tensor
+    head: Optional[torch.Tensor] = None
+    voice: Optional[tuple] = None
+    prefix: object = None
+    cfg_scale: float = 1.0
+    max_new_tokens: Optional[int] = None
+    max_length_times: float = 2
+    forced_tokens: Optional[list] = None
+    noise: Optional[torch.Tensor] = None          # [F, latent] (host-noise sessions)
+    sde_noise: Optional[torch.Tensor] = None      # [F, n_steps, latent]
+    noise_seed: Optional[int] = None              # device-noise sessions; None: drawn from the CPU generator at submit
+    audio_streamer: object = None                 # a batch-of-one streamer of this request's own
+    stop_check_fn: Optional[Callable[[], bool]] = None
+    in_dev: object = "cpu"
+
+
+class SessionHandle:
+    """One submitted dialogue: `done`, the `slot` it runs / ran in (None while queued), `cancel()` - it leaves at the session's next step - and
+    `result()`, the VibeVoiceGenerationOutput of a batch of one."""
+
+    def __init__(self, req: SessionRequest):
+        self.request, self.done, self.slot, self.cancelled, self._out = req, False, None, False, None
+
+    def cancel(self):
+        self.cancelled = True
+
+    def result(self) -> VibeVoiceGenerationOutput:
+        if not self.done:
+            raise RuntimeError("SessionHandle.result(): the dialogue has not finished (Session.step() / run())")
+        return self._out
+
+
+class _Dialogue:
+    def __init__(self, handle: SessionHandle, max_length: int, max_steps: int):
+        r = handle.request
+        self.handle, self.req = handle, r
+        self.L0, self.max_length, self.max_steps = int(r.prompt.shape[0]), max_length, max_steps
+        self.seq = r.prompt.tolist()
+        self.chunks, self.frame, self.prev_tok, self.step, self.reach = [], 0, None, 0, False
+
+
+class Session:
+    """`run`'s loop turned inside out for serving: a fixed number of slots (the row batches' dialogues) that are refilled between two steps, so a
+    finished dialogue costs nothing further and a queued one starts as soon as a slot is free.  Every dialogue is served with BATCH-OF-ONE
+    semantics - its limits from its own unpadded prompt, its own step counter from its admission, no _BatchCoupling (both of that class's
+    effects only mimic the reference's batched call) - so it receives, in order, the driver calls `run` makes for it alone; speech_end resets,
+    turn switches, the negative commit, speculation and rollback are `run`'s.
+
+    The driver is `run`'s (module docstring) without `begin`, opened by the caller, plus
+      admit(b, request)          slot b starts afresh for this request: its positions, conv state, guidance scale, noise seed and prompt embeddings
+      synchronize(b)             everything enqueued for slot b has completed (its samples may be read)
+    and `decode(live, ...)` leaves the slots outside `live` where they are.  One step(): (1) queued requests are admitted in FIFO order while
+    a slot is free, lowest free slot first - admit, first_tokens([b]) (the prefill and the first token), that token handled - synchronously;
+    (2) one decode for every live dialogue; (3) tokens, speech, chunk delivery.
+
+    Noise is the session's: `device_noise` (default) gives every request its own seed and draws on the device, a frame's noise a function of
+    (seed, frame) - the dialogue sounds the same whoever shares the session; noise= / sde_noise= are refused.  Without it noise is injected per
+    request or drawn on the host as `run` draws it, and drawn noise then depends on who else diffuses in the step (not reproducible per
+    dialogue).  Tokens: greedy, forced per request, or sampled with the session's one sampler (`sample_fn` on the host or `sampler` = the
+    device's warpers); the draws of a step are made in ascending slot order."""
+
+    def __init__(self, driver, slots: int, special: dict, pad_id: int, max_pos: int, latent: int, max_context: int, device_noise: bool = True,
+                 sample_fn=None, sampler: Optional[tuple] = None, speculate: bool = True, verbose: bool = False, on_close=None):
+        if not isinstance(slots, int) or not 2 <= slots <= 16:
+            raise ValueError(f"Session: slots={slots!r} (2..16)")
+        if max_context is None or int(max_context) <= 0:
+            raise ValueError(f"Session: max_context={max_context!r} (tokens per dialogue, required)")
+        if sampler is not None and sample_fn is not None:
+            raise ValueError("Session: sampler (device) and sample_fn (host) exclude each other")
+        self.driver, self.slots, self.special, self.pad_id, self.max_pos, self.latent = driver, slots, special, int(pad_id), int(max_pos), int(latent)
+        self.max_context, self.device_noise, self.sample_fn, self.sampler, self.verbose = int(max_context), bool(device_noise), sample_fn, sampler, verbose
+        self.speculate = bool(speculate) and sample_fn is None
+        self.nv = len(set(valid_token_ids(special)))
+        self.queue: List[SessionHandle] = []
+        self.live: Dict[int, _Dialogue] = {}
+        self.pending = []                 # (dialogue, slot, ring slot) of chunks not yet handed to their streamers
+        self.admissions = []              # (slot, dialogues live at the time) per admission, in order
+        self.admission_ms = []            # and how long the host spent on it (admit + prefill + first token, synchronous)
+        self.closed, self._on_close = False, on_close
+        if sampler is not None:
+            driver.set_sampler(*sampler)
+
+    # ---- requests ---------------------------------------------------------------------------------------------------
+    def limits_of(self, prompt_len: int, max_new_tokens, max_length_times):
+        return limits(self.max_pos, prompt_len, max_new_tokens, max_length_times)
+
+    def validate(self, req: SessionRequest):
+        """submit()'s refusals, without queueing or drawing anything"""
+        if self.closed:
+            raise RuntimeError("Session.submit(): the session is closed")
+        if self.device_noise:
+            if req.noise is not None or req.sde_noise is not None:
+                raise ValueError("this session draws the diffusion noise on the device (device_noise=True): noise= / sde_noise= cannot be injected")
+        elif req.noise_seed is not None:
+            raise ValueError("noise_seed= seeds the device-side noise: it needs a session opened with device_noise=True")
+        L0 = int(req.prompt.shape[0])
+        if L0 < 1:
+            raise ValueError("Session.submit(): empty prompt")
+        _, max_steps = self.limits_of(L0, req.max_new_tokens, req.max_length_times)
+        if L0 + max(max_steps, 1) + 8 > self.max_context:
+            raise ValueError(f"Session.submit(): prompt of {L0} tokens + step limit {max_steps} + 8 = {L0 + max(max_steps, 1) + 8} exceeds the session's "
+                             f"max_context={self.max_context} (lower max_new_tokens / max_length_times, or open the session with a larger max_context)")
+
+    def submit(self, req: SessionRequest) -> SessionHandle:
+        """Queue one dialogue.  ValueError: a prompt whose context (prompt + step limit + 8) does not fit max_context - nothing is clipped -,
+        injected noise or a seed in the wrong kind of session."""
+        self.validate(req)
+        if self.device_noise and req.noise_seed is None:
+            req.noise_seed = int(torch.randint(0, 2 ** 62, (1,)))
+        h = SessionHandle(req)
+        self.queue.append(h)
+        return h
+
+    # ---- chunk delivery and retirement ------------------------------------------------------------------------------
+    def _deliver(self, only: Optional[_Dialogue] = None):
+        """the staged chunks go to their requests' streamers (only: those of one dialogue - it leaves, the others' wait for the next decode)"""
+        keep = []
+        for d, b, k in self.pending:
+            if only is not None and d is not only:
+                keep.append((d, b, k))
+                continue
+            d.req.audio_streamer.put(self.driver.take_chunk(b, k)[None, None], torch.tensor([0]))      # as run puts them: [samples, 1, T], sample indices
+        self.pending[:] = keep
+
+    def _retire(self, b: Optional[int], d: _Dialogue, eos: bool = False):
+        """The dialogue leaves: run's finish() (on EOS / its step limit) and run's epilogue for a batch of one."""
+        if eos or d.reach:
+            self.driver.finished(b)
+        self._deliver(only=d)
+        if b is not None:
+            self.driver.synchronize(b)
+            del self.live[b]
+        if d.req.audio_streamer is not None:
+            d.req.audio_streamer.end()
+        r = d.req
+        seq = torch.tensor(d.seq, dtype=torch.long)
+        rows = [seq if r.head is None or not r.head.numel() else torch.cat([r.head, seq])]
+        d.handle._out = pack_output(rows, [torch.cat(d.chunks)[None] if d.chunks else None], [d.reach], self.pad_id, r.in_dev, True)
+        d.handle.done = True
+
+    def _stopped(self, d: _Dialogue) -> bool:
+        """what ends a dialogue from outside, polled where run polls it: ahead of the dialogue's step"""
+        r = d.req
+        if d.handle.cancelled:
+            return True
+        if r.stop_check_fn is not None and r.stop_check_fn():
+            if self.verbose:
+                print(f"Generation stopped externally at step {d.step + 1}")
+            return True
+        st = r.audio_streamer
+        return st is not None and hasattr(st, "finished_flags") and any(st.finished_flags)      # its stream was ended by someone else (:441-445)
+
+    # ---- one step ---------------------------------------------------------------------------------------------------
+    def _forced(self, d: _Dialogue):
+        f = d.req.forced_tokens
+        return f[d.step] if (f is not None and d.step < len(f)) else None
+
+    def _eligible(self, d: _Dialogue, sde: bool):
+        if not (self.speculate and d.prev_tok == self.special["speech_diffusion"]):
+            return None
+        if self.device_noise:
+            return (d.frame, None)
+        nz, snz = d.req.noise, d.req.sde_noise
+        if nz is not None and d.frame < len(nz) and (not sde or (snz is not None and d.frame < len(snz))):
+            return (nz[d.frame], snz[d.frame] if sde else None)
+        return None
+
+    def _handle(self, toks: Dict[int, int], speculated: set):
+        """run's per-step token handling (:517-670) for the slots in `toks`, every dialogue on its own step counter"""
+        drv, sp = self.driver, self.special
+        SE, SD, EOS = sp["speech_end"], sp["speech_diffusion"], sp["eos"]
+        sde, diffusing = drv.sde, []
+        for b in sorted(toks):
+            d, tok = self.live[b], toks[b]
+            if b in speculated and tok != SD:
+                drv.rollback(b)
+                speculated.discard(b)
+            d.prev_tok = tok
+            d.seq.append(tok)
+            if tok == EOS:
+                if self.verbose:
+                    print(f"Samples [{b}] reached EOS token at step {d.step + 1}.", flush=True)
+                self._retire(b, d, eos=True)
+                continue
+            if d.step >= d.max_steps:                      # :528-537 (a batch of one runs out of steps first; kept as run has it)
+                d.reach = True
+                self._retire(b, d)
+                continue
+            if tok == SE:
+                drv.reset_speech(b)
+            if tok == SD:
+                diffusing.append(b)
+            else:
+                drv.embed(b)
+        need = []
+        if not self.device_noise:
+            need = [b for b in diffusing if b not in speculated and
+                    (self.live[b].req.noise is None or self.live[b].frame >= len(self.live[b].req.noise))]
+        if need:
+            n = len(need)
+            drawn = torch.randn(2 * n, self.latent)[:n]
+            sdrawn = torch.stack([torch.randn(2 * n, self.latent)[:n] for _ in range(drv.n_steps)], dim=1) if sde else None
+        rows = {}
+        for b in diffusing:
+            d = self.live[b]
+            if b in need:
+                i = need.index(b)
+                rows[b] = (drawn[i], sdrawn[i] if sde else None)
+            elif b not in speculated:
+                rows[b] = (d.frame, None) if self.device_noise else (d.req.noise[d.frame], d.req.sde_noise[d.frame] if sde else None)
+        if diffusing:
+            drv.speech(rows)
+        for b in diffusing:
+            d = self.live[b]
+            d.chunks.append(drv.chunk(b))
+            if d.req.audio_streamer is not None:
+                self.pending.append((d, b, drv.stage_chunk(b)))
+            d.frame += 1
+        for b in sorted(toks):
+            d = self.live.get(b)
+            if d is not None:                              # still here: on to its next step
+                d.step += 1
+                if d.step >= d.max_steps or d.L0 + d.step >= d.max_length:      # run's loop runs out of steps (:452-457 for the length)
+                    d.reach = d.reach or d.step < d.max_steps
+                    self._retire(b, d)
+
+    def _admit(self) -> List[int]:
+        """returns the slots it filled"""
+        drv, new = self.driver, []
+        while self.queue and len(self.live) < self.slots:
+            h = self.queue.pop(0)
+            r = h.request
+            max_length, max_steps = self.limits_of(int(r.prompt.shape[0]), r.max_new_tokens, r.max_length_times)
+            d = _Dialogue(h, max_length, max_steps)
+            if self._stopped(d) or max_steps <= 0:
+                self._retire(None, d)
+                continue
+            b = min(set(range(self.slots)) - set(self.live))
+            self.admissions.append((b, sorted(self.live)))
+            t0 = time.perf_counter()
+            h.slot = b
+            self.live[b] = d
+            drv.admit(b, r)
+            forced = {b: self._forced(d)}
+            kw = {} if self.sampler is None else dict(q={b: draw_q(self.nv)} if forced[b] is None else {})
+            toks = drv.first_tokens([b], forced, self.sample_fn, **kw)
+            self.admission_ms.append((time.perf_counter() - t0) * 1e3)
+            self._handle({b: toks[b]}, set())
+            new.append(b)
+        return new
+
+    def step(self) -> bool:
+        """Admissions, one decode step of every live dialogue, its tokens and frames.  False once nothing is live or queued."""
+        if self.closed:
+            return False
+        drv = self.driver
+        for b in sorted(self.live):                        # who leaves from outside does so ahead of its step, and frees its slot for this step's admissions
+            if self._stopped(self.live[b]):
+                self._retire(b, self.live[b])
+        for h in [h for h in self.queue if h.cancelled]:
+            self.queue.remove(h)
+            self._retire(None, _Dialogue(h, 0, 0))
+        for b in self._admit():                            # a newcomer takes its second step with the others: polled ahead of it like them
+            if b in self.live and self._stopped(self.live[b]):
+                self._retire(b, self.live[b])
+        live = sorted(self.live)
+        if live:
+            forced = {b: self._forced(self.live[b]) for b in live}
+            eligible = {}
+            for b in live:
+                row = self._eligible(self.live[b], drv.sde)
+                if row is not None:
+                    eligible[b] = row
+            kw = {} if self.sampler is None else dict(q={b: draw_q(self.nv) for b in live if forced[b] is None})
+            toks, speculated = drv.decode(live, forced, eligible, self.sample_fn, self._deliver, **kw)
+            self._handle({b: toks[b] for b in live}, set(speculated))
+        return bool(self.live or self.queue)
+
+    def run(self):
+        while self.step():
+            pass
+
+    def close(self):
+        """Whoever is still live or queued is retired as cancelled (its stream ended, its result what it has so far)."""
+        if self.closed:
+            return
+        for b in sorted(self.live):
+            self._retire(b, self.live[b])
+        for h in self.queue:
+            self._retire(None, _Dialogue(h, 0, 0))
+        self.queue = []
+        self.driver.synchronize()
+        self.closed = True
+        if self._on_close is not None:
+            self._on_close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -99,7 +99,8 @@ int vv_head_boundary_fused(const vv_head* h, const float* hrows, int64_t ldh, co
 int vv_head_boundary_batch(const vv_head* h, const float* hrows, int64_t ldh, const float* shift, const float* scale, int64_t ld_mod, float cfg,
                            const vv_dpm_coef* k, float* Xs, float* Ms, int64_t state_stride, float* h_out, int64_t ldh_out, float* latent_out,
                            int64_t latent_stride, int B, hipStream_t s,   // B dialogues per launch: rows 2 b, 2 b + 1; state / sample of b at b * stride
-                           const float* nx = nullptr, int64_t nx_stride = 0);   // SDE: + k->cn * (this step's NX of b at nx + b * nx_stride)
+                           const float* nx = nullptr, int64_t nx_stride = 0,    // SDE: + k->cn * (this step's NX of b at nx + b * nx_stride)
+                           const float* cfg_rows = nullptr);                    // device [B]: utterance b's guidance scale, read by its blocks (cfg is not used)
 int vv_head_sde_proj_fused(const vv_head* h, const float* sde_noise, int64_t ld_sde, int n_steps, int B, float* NX, hipStream_t s);   // NX[b][i] = [P n ; n], n = sde_noise + b * ld_sde + i * latent
 int vv_fused_init();
 int vv_head_pre_fused(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, int n_steps, void* c_bf16, const float* noise,

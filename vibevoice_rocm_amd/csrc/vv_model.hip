@@ -385,7 +385,7 @@ extern "C" size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int 
 // entry point vv_head_sample_batch, which refuses SDE coefficients
 static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
                              const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
-                             const float* sde_noise, int64_t ld_sde, vv_stream_t stream) {
+                             const float* sde_noise, int64_t ld_sde, vv_stream_t stream, const float* cfg_rows = nullptr) {
   const char* fn = sde_fn ? sde_fn : "vv_head_sample_batch";
   if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
   if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 4) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..4)", fn, n_steps, h->layers, B);
@@ -443,7 +443,7 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
     VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,
-                                  NX ? NX + (size_t)i * sst : nullptr, (int64_t)n_steps * sst));
+                                  NX ? NX + (size_t)i * sst : nullptr, (int64_t)n_steps * sst, cfg_rows));
   }
   return 0;
 }
@@ -460,6 +460,16 @@ extern "C" int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int
                                         const float* sde_noise, int64_t ld_sde, vv_stream_t stream) {
   return head_sample_batch("vv_head_sample_batch_sde", h, cond, ld_cond, noise, ld_noise, temb, coef, n_steps, cfg_scale, latent_out, ld_latent, B, ws,
                            sde_noise, ld_sde, stream);
+}
+
+// guidance per utterance: cfg_rows[B] on the device, read by the solver boundary's blocks (the only place the batched sampler reads the scale);
+// every other launch is vv_head_sample_batch's (sde_noise == NULL) or vv_head_sample_batch_sde's
+extern "C" int vv_head_sample_batch_cfg(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
+                                        const vv_dpm_coef* coef, int n_steps, const float* cfg_rows, float* latent_out, int64_t ld_latent, int B, void* ws,
+                                        const float* sde_noise, int64_t ld_sde, vv_stream_t stream) {
+  if (!cfg_rows) return vv_set_error(VV_E_ARG, "vv_head_sample_batch_cfg: null cfg_rows");
+  return head_sample_batch("vv_head_sample_batch_cfg", h, cond, ld_cond, noise, ld_noise, temb, coef, n_steps, 0.f, latent_out, ld_latent, B, ws,
+                           sde_noise, ld_sde, stream, cfg_rows);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

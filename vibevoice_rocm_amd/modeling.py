@@ -184,6 +184,17 @@ def _make_sampler(gen_cfg: dict):
     return sample
 
 
+def _cfg_scales(cfg_scale, B: int) -> Optional[List[float]]:
+    """generate(cfg_scale=): None for a scalar (today's path), the B floats of a sequence (one guidance scale per dialogue); ValueError when
+    their number is not the batch's."""
+    if isinstance(cfg_scale, (list, tuple)) or (isinstance(cfg_scale, (torch.Tensor, np.ndarray)) and cfg_scale.ndim > 0):
+        rows = [float(c) for c in cfg_scale]
+        if len(rows) != B:
+            raise ValueError(f"cfg_scale: {len(rows)} guidance scales for {B} dialogues (a number, or one per dialogue)")
+        return rows
+    return None
+
+
 def _embed_prompt(eng: Engine, ids: torch.Tensor, voice, after: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """Prompt embeddings of one dialogue on eng's stream, the voice rows `(mask, rows)` scattered over their placeholders (`after`: the
     stream that produced the rows)."""
@@ -201,8 +212,10 @@ class _LaneDriver:
     before any token is awaited, so the B dependent chains fill each other's bubbles on the GPU; a sample is the same computation as in a
     batch of one - bit for bit with injected noise."""
 
-    def __init__(self, model, B: int, cfg_scale: float, ST: int, SD: int):
-        self.model, self.cfg_scale, self.ST, self.SD = model, float(cfg_scale), ST, SD
+    def __init__(self, model, B: int, cfg_scale, ST: int, SD: int):
+        """cfg_scale: a number, or B of them - every lane then runs with its own scalar"""
+        rows = _cfg_scales(cfg_scale, B)
+        self.model, self.cfg_scale, self.ST, self.SD = model, (rows or [float(cfg_scale)] * B), ST, SD
         self.lanes = [model._lane(b) for b in range(B)]
         self.prefixes = [None] * B          # generate(voice_prefix=): dialogue -> VoicePrefix or None
         for e in self.lanes[1:]:
@@ -216,8 +229,8 @@ class _LaneDriver:
 
     def begin(self, prompts, voices, max_steps, valid):
         self.x0 = []
-        for eng, ids, voice, vp in zip(self.lanes, prompts, voices, self.prefixes):
-            eng.cfg_scale = self.cfg_scale
+        for eng, ids, voice, vp, scale in zip(self.lanes, prompts, voices, self.prefixes, self.cfg_scale):
+            eng.cfg_scale = scale
             eng.begin_sequence(len(ids) + max(max_steps, 1) + 8, valid)
             if vp is not None:
                 ids, voice = ids[vp.P:], None           # the rows after the prefix; every voice row lies inside it (VP.check)
@@ -321,8 +334,11 @@ class _RowDriver:
     drawn in ascending dialogue order, so a seeded call draws what the lanes draw; results agree with the lanes to the rounding of the
     matrix-core GEMV (activations as bf16 hi + lo, ~2e-6 relative per product)."""
 
-    def __init__(self, model, B: int, cfg_scale: float, ST: int, SD: int):
-        self.model, self.main, self.cfg_scale, self.ST, self.SD = model, model.engine, float(cfg_scale), ST, SD
+    def __init__(self, model, B: int, cfg_scale, ST: int, SD: int):
+        """cfg_scale: a number (the scale is a launch argument of graph H and part of its key), or B of them: every row batch keeps its
+        dialogues' scales on the device and runs the graph H that reads them there (RowBatch.begin(cfg_rows=))"""
+        self.cfg_rows = _cfg_scales(cfg_scale, B)
+        self.model, self.main, self.cfg_scale, self.ST, self.SD = model, model.engine, (1.0 if self.cfg_rows else float(cfg_scale)), ST, SD
         if B > 4:
             # two row batches: no dialogue's conv tail on the main stream (lanes 0, 4, 8, ... live there) - the main stream then runs A and H of
             # the two batches back to back while all tails run beside it on the three side streams (8 dialogues: 108 -> 119 audio-sec/s, 6: 88 -> 99)
@@ -344,7 +360,8 @@ class _RowDriver:
             rb = model._rowbatch.get(key)
             if rb is None:
                 rb = model._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.main.stream)
-            rb.begin(max(len(prompts[b]) for b in idxs) + max(max_steps, 1) + 8, valid, self.cfg_scale)
+            rb.begin(max(len(prompts[b]) for b in idxs) + max(max_steps, 1) + 8, valid, self.cfg_scale,
+                     cfg_rows=[self.cfg_rows[b] for b in idxs] if self.cfg_rows else None)
             self.groups.append((rb, idxs))
             for b in idxs:
                 self.at[b] = (rb, b - off)
@@ -462,6 +479,150 @@ class _RowDriver:
         pass
 
 
+class _SessionDriver(_RowDriver):
+    """batchloop.Session's driver: the row batches of _RowDriver with `slots` dialogues' worth of rows, opened once (`open`: KV caches sized
+    for max_context tokens per dialogue, cache keys of their own in model._rowbatch) and refilled slot by slot (`admit`).  Every row batch keeps its
+    slots' guidance scales on the device, so one graph H serves whatever scales its occupants bring."""
+
+    def __init__(self, model, slots: int, ST: int, SD: int, device_noise: bool):
+        super().__init__(model, slots, [1.0] * slots, ST, SD)
+        self.dn = bool(device_noise)
+        self.x0 = [None] * slots
+
+    def open(self, max_context: int, valid):
+        from .rowbatch import RowBatch
+        model, lanes, B, off = self.model, self.lanes, len(self.lanes), 0
+        n_groups = -(-B // 4)                                                                       # as _RowDriver.begin partitions a batch
+        for n in [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]:
+            idxs = list(range(off, off + n))
+            key = (n, off, "session") if lanes[0] is model._lanes[0] else (n, off, "session", "side")
+            rb = model._rowbatch.get(key)
+            if rb is None:
+                rb = model._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.main.stream)
+            rb.begin(max_context, valid, 1.0, cfg_rows=[1.0] * n)
+            for loc in range(n):
+                rb.set_active(loc, False)              # a free slot's rows are computed and dropped; its positions stay
+            self.groups.append((rb, idxs))
+            for b in idxs:
+                self.at[b] = (rb, b - off)
+            off += n
+
+    def admit(self, b, req):
+        rb, loc = self.at[b]
+        rb.admit(loc, req.cfg_scale, req.noise_seed if self.dn else None)
+        vp = self.prefixes[b] = req.prefix
+        self.x0[b] = _embed_prompt(self.main, req.prompt, req.voice) if vp is None else _embed_prompt(self.main, req.prompt[vp.P:], None)
+
+    def decode(self, live, forced, eligible, sample_fn, deliver, q=None):
+        for rb, idxs in self.groups:
+            for b in idxs:
+                rb.set_active(self.at[b][1], b in forced)      # who is not in this step (free, or retired without an EOS) does not advance
+        return super().decode(live, forced, eligible, sample_fn, deliver, q=q)
+
+    def synchronize(self, b=None):
+        if b is None:
+            return super().synchronize()
+        self.at[b][0].flush()
+        self.lanes[b].stream.synchronize()
+
+
+class VibeVoiceSession:
+    """An open serving session of one model (model.open_session): dialogues are submitted one by one, each with its own guidance scale, limits,
+    schedule, noise seed and streamer; `step()` admits queued dialogues into free row-batch slots and advances every live one by a token.  Each
+    dialogue is served as generate() serves it alone (batchloop.Session).  The sampler (generation_config, device_sampling) and the solver are
+    the session's; admission is synchronous (a newcomer's prefill runs between two steps on the main stream)."""
+
+    def __init__(self, model, tokenizer, slots, max_context, generation_config, device_noise, device_sampling):
+        self.model, cfg = model, model.config
+        gen_cfg = dict(generation_config or {})
+        do_sample = bool(gen_cfg.get("do_sample", False))
+        on_device = model.device_sampling if device_sampling is None else bool(device_sampling)
+        sampler = batchloop.sampler_params(gen_cfg) if do_sample and on_device else None
+        sample_fn = _make_sampler(gen_cfg) if do_sample and sampler is None else None
+        self.special = dict(speech_start=tokenizer.speech_start_id, speech_end=tokenizer.speech_end_id, speech_diffusion=tokenizer.speech_diffusion_id,
+                            eos=tokenizer.eos_token_id, bos=getattr(tokenizer, "bos_token_id", None))
+        pad_id = getattr(tokenizer, "pad_id", None)
+        self.driver = _SessionDriver(model, slots, self.special["speech_start"], self.special["speech_diffusion"], device_noise)
+        model.engine.sync_in()
+        with torch.cuda.stream(model.engine.stream):
+            self.driver.open(int(max_context), batchloop.valid_token_ids(self.special))
+            self._s = batchloop.Session(self.driver, slots, self.special, self.special["eos"] if pad_id is None else pad_id, cfg.max_pos, cfg.latent,
+                                        max_context, device_noise=device_noise, sample_fn=sample_fn, sampler=sampler,
+                                        speculate=model.speculative_frames and model._use_graphs, on_close=self._closed)
+
+    slots = property(lambda self: self._s.slots)
+    admission_ms = property(lambda self: self._s.admission_ms)      # host time of every admission (prefill + first token, synchronous): the stall of the running dialogues
+    closed = property(lambda self: self._s.closed)
+
+    @torch.no_grad()
+    def submit(self, input_ids=None, attention_mask=None, speech_tensors=None, speech_masks=None, speech_input_mask=None, cfg_scale: float = 1.0,
+               max_new_tokens: Optional[int] = None, max_length_times=2, forced_tokens=None, noise=None, sde_noise=None, noise_seed=None,
+               voice_prefix=None, audio_streamer=None, stop_check_fn=None, speech_noise=None) -> batchloop.SessionHandle:
+        """Queue one dialogue (the arguments generate() takes for a batch of one) and return its handle.  The voice encode - or the restore of its
+        voice_prefix - runs here; nothing else does.  ValueError when prompt + step limit + 8 exceeds the session's max_context (nothing is
+        clipped), and for noise= / sde_noise= in a device-noise session."""
+        model = self.model
+        input_ids = torch.as_tensor(input_ids)
+        in_dev = input_ids.device
+        input_ids = input_ids.cpu()
+        if input_ids.dim() == 1:
+            input_ids = input_ids[None]
+        if input_ids.shape[0] != 1:
+            raise ValueError(f"submit(): one dialogue per request, not a batch of {input_ids.shape[0]}")
+        attention_mask = torch.ones_like(input_ids) if attention_mask is None else torch.as_tensor(attention_mask).cpu().reshape(1, -1)
+        keep = attention_mask[0].bool()
+        ids = input_ids[0][keep]
+        req = batchloop.SessionRequest(prompt=ids, head=input_ids[0][~keep], cfg_scale=float(cfg_scale), max_new_tokens=max_new_tokens,
+                                       max_length_times=max_length_times, forced_tokens=forced_tokens,
+                                       noise=None if noise is None else torch.as_tensor(noise), sde_noise=None if sde_noise is None else torch.as_tensor(sde_noise),
+                                       noise_seed=noise_seed, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, in_dev=in_dev)
+        self._s.validate(req)              # before any work on the device
+        if speech_input_mask is not None:
+            speech_input_mask = torch.as_tensor(speech_input_mask).cpu().reshape(1, -1)
+        vps = VP.per_dialogue(voice_prefix, 1)
+        for rb, _ in self.driver.groups:
+            rb.flush()                     # the voice encode runs on the lanes' streams too: no worker thread may still be feeding one
+        model.engine.sync_in()
+        with torch.cuda.stream(model.engine.stream):
+            if vps is not None:
+                speech_tensors, speech_masks, speech_noise, speech_input_mask = model._apply_voice_prefixes(
+                    vps, input_ids, attention_mask, speech_input_mask, speech_tensors, speech_masks, speech_noise)
+                req.prefix = vps[0]
+            if speech_tensors is not None and speech_masks is not None and speech_input_mask is not None:
+                sp = speech_input_mask[0][keep].bool()
+                if int(sp.sum()):
+                    _, conn = model._process_speech_inputs(torch.as_tensor(speech_tensors).float(), torch.as_tensor(speech_masks).bool(), *(speech_noise or (None, None)))
+                    req.voice = (sp, conn[: int(sp.sum())])
+        return self._s.submit(req)
+
+    @torch.no_grad()
+    def step(self) -> bool:
+        """One step of the session; False once nothing is live or queued."""
+        eng = self.model.engine
+        eng.sync_in()
+        with torch.cuda.stream(eng.stream):
+            return self._s.step()
+
+    def run(self):
+        while self.step():
+            pass
+
+    def close(self):
+        with torch.cuda.stream(self.model.engine.stream):
+            self._s.close()
+
+    def _closed(self):
+        self.model.engine.stream.synchronize()
+        self.model._session = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
@@ -492,6 +653,7 @@ class VibeVoiceForConditionalGenerationInference:
         self.row_batch = os.environ.get("VV_ROW_BATCH", "1") != "0"
         self.row_batch_min = int(os.environ.get("VV_ROW_BATCH_MIN", "2"))      # 2 dialogues: 64 vs 58 audio-sec/s on the lanes
         self._rowbatch = {}
+        self._session = None              # the open serving session (open_session), at most one
         # do_sample: draw the token inside the LLM step's tail launch from exponential draws the host makes before it enqueues the step
         # (vv_sampler), instead of reading the logits back for a host softmax / multinomial: one graph and one 4-byte read-back per token, and
         # speculative frame launch as for greedy decoding.  Seeded calls keep their tokens and the generator its state.  Off by default;
@@ -658,6 +820,37 @@ class VibeVoiceForConditionalGenerationInference:
                 vp = eng.save_prefix(ids)
         return vp
 
+    # ---- serving sessions ---------------------------------------------------------------------------------------
+    def open_session(self, tokenizer=None, slots: int = 8, max_context: Optional[int] = None, generation_config=None, device_noise: bool = True,
+                     device_sampling: Optional[bool] = None) -> "VibeVoiceSession":
+        """Open a serving session: `slots` (2..16) row-batch slots - ceil(slots / 4) row batches, as a batched generate() partitions them - whose
+        KV caches are sized once for `max_context` tokens per dialogue (required).  Dialogues are submitted to the session one by one and a
+        finished one frees its slot for the next between two steps (VibeVoiceSession, batchloop.Session).  Needs what row batching needs -
+        bf16, weight_quant None or "fp8", a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
+        per model; generate() raises RuntimeError until it is closed."""
+        if getattr(self, "_session", None) is not None:
+            raise RuntimeError("open_session(): this model already has an open session (one per model); close() it first")
+        if tokenizer is None:
+            raise ValueError("open_session() needs tokenizer= (for the speech_start/end/diffusion and eos ids)")
+        if not isinstance(slots, int) or not 2 <= slots <= 16:
+            raise ValueError(f"open_session(): slots={slots!r} (2..16)")
+        if max_context is None or int(max_context) <= 0:
+            raise ValueError("open_session(): max_context= (tokens per dialogue: prompt + generated + 8) is required")
+        why = None
+        if self.dtype != torch.bfloat16:
+            why = f"torch_dtype={self.dtype} (bf16 only)"
+        elif self.weight_quant not in (None, "fp8"):
+            why = f"weight_quant={self.weight_quant!r} (None or 'fp8')"
+        elif self.kv_cache_dtype == "fp8":
+            why = "kv_cache_dtype='fp8' (the row-batched decode step has no fp8-KV form)"
+        elif not self._use_graphs:
+            why = "use_graphs=False (the session replays captured graphs)"
+        if why is not None:
+            raise ValueError(f"open_session(): a session runs on the row-batched decode path, which this model cannot take: {why}")
+        sess = VibeVoiceSession(self, tokenizer, slots, int(max_context), generation_config, bool(device_noise), device_sampling)
+        self._session = sess
+        return sess
+
     # ---- generation --------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
@@ -665,6 +858,12 @@ class VibeVoiceForConditionalGenerationInference:
                  speech_input_mask: Optional[torch.Tensor] = None, tokenizer=None, generation_config=None,
                  max_new_tokens: Optional[int] = None, cfg_scale: float = 1.0, audio_streamer=None,
                  stop_check_fn: Optional[Callable[[], bool]] = None, return_speech: bool = True, **kwargs):
+        if getattr(self, "_session", None) is not None:
+            raise RuntimeError("generate(): a serving session is open on this model (its lanes and their conv state are the session's); close() it first")
+        ids_ = torch.as_tensor(input_ids)
+        rows_ = _cfg_scales(cfg_scale, 1 if ids_.dim() == 1 else int(ids_.shape[0]))      # ValueError before anything runs
+        if rows_ is not None and len(rows_) == 1:
+            cfg_scale = rows_[0]
         self.engine.sync_in()
         with torch.cuda.stream(self.engine.stream):   # all torch glue (gathers, scatters, copies) rides the engine stream
             out = self._generate(input_ids, attention_mask, speech_tensors, speech_masks, speech_input_mask, tokenizer,

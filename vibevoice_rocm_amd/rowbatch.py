@@ -15,7 +15,8 @@ B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in on
 The conv tokenizers (acoustic decode, semantic encode) and the connectors stay per dialogue - each has its own streaming state - and run as
 B concurrent hipGraphs on the lanes' streams between H and the next A (events fork / join them), exactly the launch sequences the lanes use.
 They are enqueued only once H has finished: a lane queue that sits on a cross-stream wait while the main queue runs A and H slows every dependent
-launch there.  The host loop, token state machine, speculation and rollback are the one batched loop's (batchloop.run), which drives row batches through
+launch there.  A serving session (modeling.open_session) keeps a row batch open and refills its slots one by one (`admit`),
+with every dialogue's guidance scale on the device (`begin(cfg_rows=)`, graph "Hc": vv_head_sample_batch_cfg).  The host loop, token state machine, speculation and rollback are the one batched loop's (batchloop.run), which drives row batches through
 modeling._RowDriver."""
 from __future__ import annotations
 
@@ -84,6 +85,7 @@ class RowBatch:
             self.noise_seed_dev = torch.zeros(B, dtype=torch.int64, device=self.device)      # device noise: every dialogue's 64-bit seed (its bits)
             self.noise_frame_dev = torch.zeros(B, **i32)                                       # and the index of the frame it draws next
             self.latent = torch.zeros(B, cfg.latent, **f32)
+            self.cfg_dev = torch.ones(B, **f32)           # guidance per dialogue, read on the device (begin(cfg_rows=) / admit): graph "Hc"
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
         self._pf_ws = None
         self._pf_rows = 0
@@ -95,6 +97,8 @@ class RowBatch:
         self.noise_seed_host = torch.zeros(B, dtype=torch.int64).pin_memory()
         self.noise_frame_host = torch.zeros(2, B, dtype=torch.int32).pin_memory()      # double-buffered like the noise rows
         self._frame_k = 0
+        self.cfg_host = torch.ones(B, dtype=torch.float32).pin_memory()
+        self.cfg_rows = False           # this batch's graph H reads cfg_dev (vv_head_sample_batch_cfg) instead of taking cfg_scale as a launch argument
         self.q_host = torch.ones(2, B, 8, dtype=torch.float32).pin_memory()
         self._q_k = 0
         self._sampler, self._sampler_key = None, None
@@ -166,11 +170,20 @@ class RowBatch:
         self._ck(self.lib.vv_graph_launch(g, self.sp), "graph launch")
 
     # -----------------------------------------------------------------------------------------------------------------
-    def begin(self, s_max: int, valid_ids: List[int], cfg_scale: float):
-        """Fresh batch: one KV cache with 2 B rows sized for s_max tokens, every lane's conv state zeroed."""
+    def begin(self, s_max: int, valid_ids: List[int], cfg_scale: float, cfg_rows: Optional[List[float]] = None):
+        """Fresh batch: one KV cache with 2 B rows sized for s_max tokens, every lane's conv state zeroed.  cfg_rows: one guidance scale per
+        dialogue, kept on the device - the batch then runs the graph H whose key has no scale in it (cfg_scale is not used)."""
         cfg, eng, B = self.cfg, self.main, self.B
         s_max = (int(s_max) + 63) // 64 * 64
         self.cfg_scale = float(cfg_scale)
+        self.cfg_rows = cfg_rows is not None
+        if self.cfg_rows:
+            if len(cfg_rows) != B:
+                raise L.VVError(f"RowBatch.begin: {len(cfg_rows)} guidance scales for {B} dialogues")
+            for b, c in enumerate(cfg_rows):
+                self.cfg_host[b] = float(c)
+            with torch.cuda.stream(self.stream):
+                self.cfg_dev.copy_(self.cfg_host, non_blocking=True)
         for b, e in enumerate(self.lanes):
             if not self._on_main[b]:
                 e.sync_in()
@@ -222,6 +235,34 @@ class RowBatch:
             with torch.cuda.stream(e.stream):
                 e.reset_speech_caches()
         self._lane_dirty = [False] * B
+
+    def admit(self, b: int, cfg_scale: float, noise_seed: Optional[int] = None):
+        """Slot b starts afresh for a new dialogue while the other slots go on (sessions; begin(cfg_rows=) opened the batch): lane b's outstanding
+        work is awaited, its positions, frame counter and noise frame index go to zero, forced = none, active, its conv state is zeroed as
+        begin zeroes every lane's, and its guidance scale (and noise seed) are written.  No other slot's state is touched and no graph is dropped.
+        K / V / vt rows the previous occupant left beyond the new positions are never read: attention covers [0, lens] of a row."""
+        if not self.cfg_rows:
+            raise L.VVError("RowBatch.admit: the batch was not begun with cfg_rows (its graph H has the scale baked in)")
+        self._wait_jobs()
+        e = self.lanes[b]
+        e.stream.synchronize()
+        self._lane_dirty[b] = False
+        self.cfg_host[b] = float(cfg_scale)
+        if noise_seed is not None:
+            v = int(noise_seed) & (2 ** 64 - 1)
+            self.noise_seed_host[b] = v - 2 ** 64 if v >= 2 ** 63 else v
+        self.noise_frame_host[:, b] = 0
+        with torch.cuda.stream(self.stream):
+            self.lens[2 * b: 2 * b + 2].zero_()
+            self.frame_ctr[b: b + 1].zero_()
+            self.noise_frame_dev[b: b + 1].zero_()
+            self.cfg_dev.copy_(self.cfg_host, non_blocking=True)
+            if noise_seed is not None:
+                self.noise_seed_dev.copy_(self.noise_seed_host, non_blocking=True)
+            self._set_forced({b: None})
+        self.set_active(b, True)
+        with torch.cuda.stream(e.stream):
+            e.reset_speech_caches()
 
     def prefill(self, b: int, embeds: torch.Tensor, neg: bool = False, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None, prefix=None):
         """Prompt prefill of dialogue b on cache row 2 b (neg: 2 b + 1), on the main stream; hidden[row] = last hidden state.  neg_embed [1, H]:
@@ -402,6 +443,24 @@ class RowBatch:
                                                eng.temb.data_ptr(), eng._coefs, eng.n_steps, cfg_scale, self.latent.data_ptr(), cfg.latent, self.B,
                                                self._head_ws.data_ptr(), self.sp), "vv_head_sample_batch")
 
+    def _seq_Hc(self, dn=None):
+        """_seq_H with every dialogue's guidance scale read from cfg_dev (vv_head_sample_batch_cfg): no scale in the graph's key"""
+        eng, cfg = self.main, self.cfg
+        if dn:
+            self._ck(self.lib.vv_noise_normal(self.noise_dev.data_ptr(), cfg.latent, self.sde_noise_dev.data_ptr() if self.sde else None,
+                                              eng.n_steps * cfg.latent, self.B, cfg.latent, eng.n_steps if self.sde else 0,
+                                              self.noise_seed_dev.data_ptr(), self.noise_frame_dev.data_ptr(), self.sp), "vv_noise_normal")
+        self._ck(self.lib.vv_head_sample_batch_cfg(C.byref(eng.w.head), self.hidden.data_ptr(), cfg.hidden, self.noise_dev.data_ptr(), cfg.latent,
+                                                   eng.temb.data_ptr(), eng._coefs, eng.n_steps, self.cfg_dev.data_ptr(), self.latent.data_ptr(), cfg.latent,
+                                                   self.B, self._head_ws.data_ptr(), self.sde_noise_dev.data_ptr() if self.sde else None,
+                                                   eng.n_steps * cfg.latent if self.sde else 0, self.sp), "vv_head_sample_batch_cfg")
+
+    def _run_H(self, dn: bool):
+        if self.cfg_rows:
+            self._run("Hc", self._seq_Hc, *(("dn",) if dn else ()))
+        else:
+            self._run("H", self._seq_H, float(self.cfg_scale), *(("dn",) if dn else ()))
+
     def _seq_conv(self, b, uid):
         """acoustic decode -> semantic encode -> connectors of dialogue b on ITS stream, into rows 2 b, 2 b + 1 of the next step's input"""
         e, cfg = self.lanes[b], self.cfg
@@ -500,7 +559,7 @@ class RowBatch:
             for b in which:
                 fh[b] = int(frames[b])
             self.noise_frame_dev.copy_(fh, non_blocking=True)
-            self._run("H", self._seq_H, float(self.cfg_scale), "dn")
+            self._run_H(True)
             self._head_event.record(self.stream)
             if self._timing is not None and self._tcur is not None:
                 self._tcur["h1"] = torch.cuda.Event(enable_timing=True)
@@ -527,7 +586,7 @@ class RowBatch:
                 for b in which:
                     sh[b].copy_(sde_noise[b].reshape(n_steps, -1)[:, : cfg.latent])
                 self.sde_noise_dev.copy_(sh, non_blocking=True)
-            self._run("H", self._seq_H, float(self.cfg_scale))
+            self._run_H(False)
             self._head_event.record(self.stream)
             if self._timing is not None and self._tcur is not None:
                 self._tcur["h1"] = torch.cuda.Event(enable_timing=True)
