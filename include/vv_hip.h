@@ -43,6 +43,21 @@ enum { VV_NF4 = 3 };
  * vv_llm_forward with R in 3..8, vv_head_sample_batch(_sde), vv_llm_tail_batch) uses the bf16 matrices (row-major or their bf16 fragment-major
  * f_* copies), which hold the same effective values. */
 enum { VV_WQ_NF4 = 0x100 };
+/* VV_MXFP4: weight-only OCP Microscaling (MX v1.0) FP4, streaming GEMV only (csrc/vv_gemv_mx.hip): m <= 2, k % 32 == 0, no VV_LIN_W_FRAG, no bf16
+ * hand-off.  A block is 32 consecutive k of one row with one E8M0 scale byte e worth 2^(e - 127); elements are e2m1 codes - codes 0..7 mean
+ * +0, 0.5, 1, 1.5, 2, 3, 4, 6 and codes 8..15 the same values negated.  Effective weight W[n][k] = value(code) * 2^(e - 127): exact in bf16.
+ * Valid scale bytes are 2 <= e <= 252 (every non-zero effective weight is then a normal, finite fp32); the entry points do not read the bytes.
+ *   w / w2:           packed codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B], 16-byte aligned: code of (4 q + r, 512 u + 8 l + i) is
+ *                     nibble i (bits 4 i .. 4 i + 3) of dword r of the 16 bytes at ((q * ceil(K/512) + u) * 64 + l) * 16
+ *   wscale / w2scale: the ADDRESS of the scale bytes, read as uint8_t (not as float), 16-byte aligned: [ceil(N/4)][ceil(K/512)][16 blocks][4 rows],
+ *                     i.e. the byte of row 4 q + r, block b of unit u (k = 512 u + 32 b .. + 31) at ((q * ceil(K/512) + u) * 16 + b) * 4 + r
+ * Padding (rows past N, k past K) holds code 0 and scale byte 127.  Rows of at most 40 units of 512 k (SwiGLU, w2 != NULL: 24).  Any other
+ * MXFP4 call (m > 2, k % 32, a missing scale pointer, a misaligned pointer, VV_LIN_W_FRAG, VV_LIN_X_BF16 / VV_LIN_OUT_BF16) returns
+ * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike. */
+enum { VV_MXFP4 = 4 };
+/* VV_WQ_MXFP4: as VV_WQ_NF4, for companions that hold MXFP4 (codes in q, the scale bytes' address in scale, the VV_MXFP4 layouts above).  The
+ * 1..2-row GEMVs stream them; every 3..8-row path and the prefill use the bf16 matrices, which hold exactly the same effective values. */
+enum { VV_WQ_MXFP4 = 0x200 };
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
@@ -96,7 +111,7 @@ typedef struct vv_lin_args {
   float* out;
   int64_t ldo;
   int flags;   /* VV_LIN_* */
-  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); else ignored */
+  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
   const float* w2scale;
 } vv_lin_args;
 
@@ -104,8 +119,9 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
  * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>"; "skinny" or "gemm_f32"; and for the
- * m <= 8 family (fp8 and NF4 weights included) the kernel itself:
+ * m <= 8 family (fp8, NF4 and MXFP4 weights included) the kernel itself:
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
+ *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)
  *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
  *   "gemv_hot<3>", "conv_hot_gemv<0>"                                      hot kernels, by table index
  *   "gemv_stream<m=4,...> + gemv_stream<m=2,...>"                          5..8 rows as two streaming passes of 4 + rest rows
@@ -224,6 +240,8 @@ int vv_advance_lens(int* lens, const int* token, int tok_start, int tok_diffusio
  * ------------------------------------------------------------------------------------------------------------ */
 /* Optional weight-only fp8 companion of a matrix for the batch-1/2 decode GEMVs: e4m3fn bytes [N, K] and one
  * fp32 scale per output row.  q == NULL: not quantised.  The bf16 matrix stays the operand of every GEMM-shaped use (prefill, T > 2). */
+/* With VV_WQ_NF4 / VV_WQ_MXFP4 in the descriptor's wdt the same pair holds an NF4 or MXFP4 companion: q = the packed codes, scale = the block absmax
+ * (NF4, fp32) or the address of the E8M0 scale bytes (MXFP4, read as uint8_t), in the VV_NF4 / VV_MXFP4 layouts above. */
 typedef struct vv_w8 { const void* q; const float* scale; } vv_w8;
 
 typedef struct vv_llm_layer {

@@ -42,6 +42,12 @@ struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, b
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
 int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
+// vv_gemv_mx.hip: gemv_mx_kernel<m, dual, ksplit, ku> on blocks x threads - the streaming GEMV on VV_MXFP4 weights (m <= 2); kind 1 = covered, 0 = refused
+struct vv_mx_route { int kind, m, dual, ksplit, ku, n_groups, blocks, threads; };
+vv_mx_route vv_gemv_mx_decide(const vv_lin_args& a);
+int vv_launch_gemv_mx_route(const vv_lin_args& a, const vv_mx_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
+int vv_gemv_mx_route_name(const vv_mx_route& r, char* name, int cap);
+void vv_gemv_mx_set_blocks(int b);                                // tuning hook "gemv_mx_blocks": persistent blocks of the MXFP4 GEMV (0 = the built-in rule)
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
 // template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.

@@ -33,7 +33,7 @@ inline vv_lin_args lin_base(const float* x, int64_t ldx, int m, const void* w, i
 // ---------------------------------------------------------------------------------------------------------------
 // Qwen2 decoder stack
 // ---------------------------------------------------------------------------------------------------------------
-// weight-only fp8 or NF4 companions (vv_w8; wq = VV_FP8 / VV_NF4, the descriptor's kind) replace the bf16 matrix on the weight-streaming
+// weight-only fp8, NF4 or MXFP4 companions (vv_w8; wq = VV_FP8 / VV_NF4 / VV_MXFP4, the descriptor's kind) replace the bf16 matrix on the weight-streaming
 // GEMVs (<= 2 activation rows)
 static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q2 = nullptr) {
   if (a.m > 2 || !q.q || !q.scale || (a.w2 && (!q2 || !q2->q || !q2->scale))) return;
@@ -41,12 +41,12 @@ static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q
   if (a.w2) { a.w2 = q2->q; a.w2scale = q2->scale; }
 }
 
-// VV_WQ_NF4 (vv_hip.h) rides on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
+// VV_WQ_NF4 / VV_WQ_MXFP4 (vv_hip.h) ride on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
 // the matrix dtype, and keeps the companions' kind in `wq`
 #define VV_WQ_STRIP(T, p)                                                   \
   T p##_plain_ = *(p);                                                      \
-  const int wq = (p##_plain_.wdt & VV_WQ_NF4) ? VV_NF4 : VV_FP8;            \
-  p##_plain_.wdt &= ~VV_WQ_NF4;                                             \
+  const int wq = (p##_plain_.wdt & VV_WQ_MXFP4) ? VV_MXFP4 : (p##_plain_.wdt & VV_WQ_NF4) ? VV_NF4 : VV_FP8; \
+  p##_plain_.wdt &= ~(VV_WQ_NF4 | VV_WQ_MXFP4);                             \
   p = &p##_plain_;                                                          \
   (void)wq
 

@@ -145,6 +145,79 @@ def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict
     return out
 
 
+# OCP Microscaling (MX v1.0) FP4: e2m1 element values by code (codes 8..15 are the negated values), 32-element blocks with one E8M0 scale byte
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MXFP4_BLOCK = 32
+MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """Weight-only MXFP4 of a [N, K] matrix (K % 32 == 0), the OCP MX v1.0 conversion:
+      * blocks are 32 consecutive weights along K within an output row;
+      * scale byte e = clamp(floor(log2(max |w|)) - 2 + 127, 2, 252), worth 2^(e - 127) (2 = the exponent of e2m1's largest value 6); an
+        all-zero block gets 127;
+      * element = w / scale rounded to nearest, ties to even, on the e2m1 grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6; a value that
+        rounds to zero takes code 0 (never the negative zero, code 8);
+      * effective weight = value(code) * 2^(e - 127): exact in bf16 (and so in fp32).
+    Returns (codes uint8 [N, K], scale bytes uint8 [N, K / 32], effective weights fp32 [N, K])."""
+    n, k = w.shape
+    if k % MXFP4_BLOCK:
+        raise ValueError(f"MXFP4 needs K % {MXFP4_BLOCK} == 0 (K={k})")
+    wf = w.detach().float().reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    zero = amax == 0
+    ex = torch.frexp(torch.where(zero, torch.ones_like(amax), amax))[1] - 1      # floor(log2(amax)), exact: amax = m 2^ex', m in [0.5, 1)
+    e = torch.where(zero, torch.full_like(ex, MXFP4_SCALE_ONE), (ex - 2 + 127).clamp(MXFP4_SCALE_MIN, MXFP4_SCALE_MAX))
+    # w / 2^(e - 127) in fp64: the quotient by a power of two is exact there for every fp32 w and every scale byte
+    x = wf.double() * torch.exp2((127 - e).double())[..., None]
+    a = x.abs()
+    # round to nearest even on the grid: spacing 0.5 below 2, 1 below 4, 2 below 6 (torch.round is half-to-even); above 6 saturates
+    q = torch.where(a < 2.0, torch.round(a * 2.0) / 2.0, torch.where(a < 4.0, torch.round(a), torch.round(a / 2.0) * 2.0)).clamp_max(6.0)
+    grid = torch.tensor(MXFP4_VALUES, dtype=torch.float64, device=q.device)
+    mag = torch.searchsorted(grid, q.contiguous()).to(torch.uint8)               # q is on the grid: its index
+    codes = torch.where((x < 0) & (mag > 0), mag + 8, mag).to(torch.uint8)
+    eff = (torch.where(x < 0, -q, q) * torch.exp2((e - 127).double())[..., None]).float()
+    eff = torch.where(mag == 0, torch.zeros_like(eff), eff)                      # +0, as code 0 decodes
+    return codes.reshape(n, k).contiguous(), e.to(torch.uint8).contiguous(), eff.reshape(n, k).contiguous()
+
+
+def pack_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
+    """(codes uint8 [N, K], scale bytes uint8 [N, K / 32]) -> the VV_MXFP4 layout (include/vv_hip.h), padded with code 0 / scale byte 127:
+    codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B] - nibble i of dword r of lane l's 16 bytes is code (4 q + r, 512 u + 8 l + i) -
+    and scale bytes [ceil(N/4)][ceil(K/512)][16 blocks][4 rows].  Returns (uint8 1-D, uint8 1-D)."""
+    n, k = codes.shape
+    nq, ku = (n + 3) // 4, (k + 511) // 512
+    c = torch.zeros(nq * 4, ku * 512, dtype=torch.uint8, device=codes.device)
+    c[:n, :k] = codes
+    c = c.view(nq, 4, ku, 64, 4, 2).permute(0, 2, 3, 1, 4, 5)           # [q, u, lane, r, byte, nibble]
+    packed = (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
+    s = torch.full((nq * 4, ku * 16), MXFP4_SCALE_ONE, dtype=torch.uint8, device=scales.device)
+    s[:n, : k // MXFP4_BLOCK] = scales
+    sb = s.view(nq, 4, ku, 16).permute(0, 2, 3, 1).contiguous().view(-1)  # [q, u, block, r]
+    return packed, sb
+
+
+def unpack_mxfp4(packed: torch.Tensor, sb: torch.Tensor, n: int, k: int):
+    """Inverse of pack_mxfp4: (codes uint8 [N, K], scale bytes uint8 [N, K / 32])."""
+    nq, ku = (n + 3) // 4, (k + 511) // 512
+    b = packed.view(nq, ku, 64, 4, 4)
+    c = torch.stack([b & 15, b >> 4], dim=-1)                           # [q, u, lane, r, byte, nibble]
+    codes = c.permute(0, 3, 1, 2, 4, 5).reshape(nq * 4, ku * 512)[:n, :k].contiguous()
+    scales = sb.view(nq, ku, 16, 4).permute(0, 3, 1, 2).reshape(nq * 4, ku * 16)[:n, : k // MXFP4_BLOCK].contiguous()
+    return codes, scales
+
+
+def mxfp4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The state dict a weight_quant="mxfp4" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
+    K % 32 == 0 replaced by the effective MXFP4 weights of its bf16 rounding (fp32 tensors; q/k/v quantise the same fused or apart, the blocks
+    lie inside rows).  A matrix with another K is left as it is."""
+    out = dict(sd)
+    for name in fp8_matrix_names(cfg):
+        if sd[name].shape[1] % MXFP4_BLOCK == 0:
+            out[name] = quantize_mxfp4(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
+    return out
+
+
 class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
@@ -153,8 +226,9 @@ class DeviceWeights:
         """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
         are imported as they are (vv_nf4_import) and need quant="nf4"."""
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
-        if quant not in (None, "fp8", "nf4"):
-            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3) or 'nf4' (weight-only 4-bit NF4), decode GEMVs, is built")
+        if quant not in (None, "fp8", "nf4", "mxfp4"):
+            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3), 'nf4' (weight-only 4-bit NF4) or 'mxfp4' (weight-only OCP "
+                             "MXFP4), decode GEMVs, is built")
         if quant is not None and wdtype != torch.bfloat16:
             raise ValueError(f"weight_quant={quant!r} keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
         if prequant and quant != "nf4":
@@ -163,8 +237,8 @@ class DeviceWeights:
         self._pre = dict(prequant or {})
         self._fp8_names = set(fp8_matrix_names(cfg)) if quant is not None else set()     # the matrices that get a companion
         self.wdt = _wdt(wdtype)
-        # the descriptors' wdt: VV_WQ_NF4 marks their vv_w8 companions as NF4 (vv_hip.h); self.wdt stays the plain matrix dtype
-        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else 0)
+        # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 mark their vv_w8 companions as NF4 / MXFP4 (vv_hip.h); self.wdt stays the plain matrix dtype
+        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else L.VV_WQ_MXFP4 if quant == "mxfp4" else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
         # the fragment-major copies (ensure_frag) live here: one dict object shared by every fork, as the ctypes layer arrays they are
         # written into are, so they are built once per process whichever fork asks first
@@ -236,7 +310,8 @@ class DeviceWeights:
     def _mat_q(self, t: torch.Tensor, quantise: bool):
         """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
         mode it holds the effective weights bf16(table[code] * absmax) and the companion the packed codes and block scales (pack_nf4).
-        An NF4 matrix with K % 64 != 0 gets no companion."""
+        An NF4 matrix with K % 64 != 0 gets no companion.  In mxfp4 mode the bf16 copy holds value(code) * 2^(e - 127) (exact) and the
+        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion."""
         w8 = L.W8()
         if self.quant == "nf4" and quantise and t.shape[1] % NF4_BLOCK == 0:
             codes, absmax, eff = quantize_nf4(t.to(device=self.device, dtype=torch.bfloat16))    # the bf16 weight, widened
@@ -244,6 +319,13 @@ class DeviceWeights:
             packed = self._aligned(packed)
             self._keep.append(packed)
             w8.q, w8.scale = L.ptr(packed), L.ptr(self._vec(scales))
+            return self._mat(eff), w8
+        if self.quant == "mxfp4" and quantise and t.shape[1] % MXFP4_BLOCK == 0:
+            codes, sbytes, eff = quantize_mxfp4(t.to(device=self.device, dtype=torch.bfloat16))   # the bf16 weight, widened
+            packed, sb = pack_mxfp4(codes, sbytes)
+            packed, sb = self._aligned(packed), self._aligned(sb)
+            self._keep += [packed, sb]
+            w8.q, w8.scale = L.ptr(packed), L.ptr(sb)          # vv_w8.scale carries the address of the scale BYTES (vv_hip.h, VV_MXFP4)
             return self._mat(eff), w8
         if not (quantise and self.quant == "fp8"):
             return self._mat(t), w8
