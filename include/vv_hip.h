@@ -164,6 +164,13 @@ int vv_rope_store(float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv,
                   const int* lens, const int* cache_rows, vv_stream_t stream);
 int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const int* lens,
             const int* cache_rows, float* out, int64_t ldo, vv_stream_t stream);
+/* The kernel vv_attn would launch for these arguments under the current vv_tune state, written to name[cap]: decided by the very code vv_attn
+ * launches through, without a launch and without touching the device (qkv, out and the cache pointers count for their alignment only):
+ *   "attn_prefill_mfma"            both products on the matrix cores (bf16 cache with vt, head_dim 128, R >= 16, s_max % 32 == 0, 16-byte rows)
+ *   "attn_group<bf16,nq6,g16>"     one block per (row, KV head), R >= 8, 2 / 6 / 7 q heads per KV head; g = lanes per key when head_dim is 128, else 0
+ *   "attn_head<f32>"               one block per (row, q head): everything else
+ * Arguments vv_attn refuses return the same error. */
+int vv_attn_route(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, const float* out, int64_t ldo, char* name, int cap);
 /* vv_attn_decode: vv_rope_store + vv_attn fused for the per-frame step (row r appends to cache row r): qkv is the raw
  * projection (pre-RoPE); q and the new k are rotated in registers, k/v appended at slot lens[r], attention over 0..lens[r]. */
 int vv_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table,

@@ -129,6 +129,7 @@ PROTOTYPES = {
     "vv_rope_table": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "vv_rope_store": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, vp]),
     "vv_attn": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp]),
+    "vv_attn_route": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), vp, i64, C.c_char_p, C.c_int]),
     "vv_attn_decode": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp]),
     "vv_attn_decode_part_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vv_attn_decode_split": (C.c_int, [vp, i64, C.c_int, C.c_int, C.POINTER(KV), C.c_int, vp, vp, vp, i64, vp, vp, C.c_int, C.c_int, vp]),

@@ -181,14 +181,20 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int6
 
 }  // namespace
 
-// 1 launched, 0 not covered (caller falls back), < 0 error
+// what the kernel covers: decided here and nowhere else (vv_attn's route decision asks; no launch, the pointers count for their alignment only)
+bool vv_attn_prefill_covers(const float* qkv, int64_t ld_qkv, int R, const vv_kv* kv, const float* out, int64_t ldo) {
+  if (kv->kvdt != VV_BF16 || kv->head_dim != 128 || !kv->vt || R < 16) return false;
+  if ((kv->s_max % 32) || ((uintptr_t)qkv % 16) || (ld_qkv % 4) || ((uintptr_t)out % 16) || (ldo % 4) || ((uintptr_t)kv->k % 16) || ((uintptr_t)kv->vt % 8)) return false;
+  return true;
+}
+
+// a call vv_attn_prefill_covers accepts: 0 launched, < 0 error
 int vv_launch_attn_prefill(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const int* lens, const int* cache_rows,
                            float* out, int64_t ldo, hipStream_t s) {
-  if (kv->kvdt != VV_BF16 || kv->head_dim != 128 || !kv->vt || R < 16) return 0;
-  if ((kv->s_max % 32) || ((uintptr_t)qkv % 16) || (ld_qkv % 4) || ((uintptr_t)out % 16) || (ldo % 4) || ((uintptr_t)kv->k % 16) || ((uintptr_t)kv->vt % 8)) return 0;
+  if (!vv_attn_prefill_covers(qkv, ld_qkv, R, kv, out, ldo)) return vv_set_error(VV_E_ARG, "vv_attn (prefill): call not covered by the matrix-core kernel");
   const int nqt = (R + 31) / 32;
   hipLaunchKernelGGL(attn_prefill_kernel, dim3(nqt, heads), dim3(64), 0, s, qkv, ld_qkv, heads, *kv, layer, lens, cache_rows, R, out, ldo);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_attn (prefill): %s", hipGetErrorString(e));
-  return 1;
+  return 0;
 }

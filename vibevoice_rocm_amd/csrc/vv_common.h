@@ -94,7 +94,9 @@ int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, co
 int vv_attn_decode_ws(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float* rope_table, const int* lens, float* out,
                       int64_t ldo, float* part, int* tickets, int nsplit, int part_cap, vv_stream_t stream);
 int vv_launch_kv_quantize(const vv_kv* src, const vv_kv* dst, int src_row, int dst_row, int len, int flags, hipStream_t s);   // vv_attn_decode.hip
-// vv_attn_prefill.hip: matrix-core prompt attention (bf16 cache + kv->vt, head_dim 128); 1 launched, 0 not covered, < 0 error
+// vv_attn_prefill.hip: matrix-core prompt attention (bf16 cache + kv->vt, head_dim 128).  vv_attn_prefill_covers is the only copy of what the
+// kernel covers (vv_attn's route decision asks it, vv_attn_route reports it without a launch); the launch of a covered call: 0 launched, < 0 error
+bool vv_attn_prefill_covers(const float* qkv, int64_t ld_qkv, int R, const vv_kv* kv, const float* out, int64_t ldo);
 int vv_launch_attn_prefill(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const int* lens, const int* cache_rows,
                            float* out, int64_t ldo, hipStream_t s);
 // vv_fused.hip

@@ -1145,11 +1145,9 @@ __global__ __launch_bounds__(256) void attn_group_kernel(const float* qkv, int64
 }
 
 template <int NQ>
-bool launch_attn_group(const float* qkv, int64_t ld, const vv_kv* kv, int layer, const int* lens, const int* cache_rows, float* out,
-                       int64_t ldo, int R, hipStream_t s) {
-  const int d = kv->head_dim, epl = kv->kvdt == VV_F32 ? 4 : 8, ng = 4 * (64 / (d / epl));
-  const size_t lds = ((size_t)ng * NQ * (d + 2) + (size_t)NQ * ng) * sizeof(float);
-  if (lds > 65536 || NQ * ng > 256) return false;
+void launch_attn_group(const float* qkv, int64_t ld, const vv_kv* kv, int layer, const int* lens, const int* cache_rows, float* out,
+                       int64_t ldo, int R, size_t lds, hipStream_t s) {
+  const int d = kv->head_dim;
   dim3 grid(kv->kv_heads, R);
   if (kv->kvdt == VV_F32) {
     if (d == 128) hipLaunchKernelGGL((attn_group_kernel<float, 4, NQ, 32>), grid, dim3(256), lds, s, qkv, ld, *kv, layer, lens, cache_rows, out, ldo);
@@ -1158,38 +1156,71 @@ bool launch_attn_group(const float* qkv, int64_t ld, const vv_kv* kv, int layer,
     if (d == 128) hipLaunchKernelGGL((attn_group_kernel<bf16_t, 8, NQ, 16>), grid, dim3(256), lds, s, qkv, ld, *kv, layer, lens, cache_rows, out, ldo);
     else hipLaunchKernelGGL((attn_group_kernel<bf16_t, 8, NQ, 0>), grid, dim3(256), lds, s, qkv, ld, *kv, layer, lens, cache_rows, out, ldo);
   }
-  return true;
 }
 
 int g_attn_group = 1;      // tuning hook "attn_group": 0 = one block per q head for every row count
 
+// The kernel a vv_attn call takes: decided here for the launch below and for vv_attn_route alike - no pointer to device memory followed, no
+// HIP call, the only copy of the thresholds.  kind < 0 = error (set).  nq / gt: the grouped kernel's template arguments; lds: its (or the
+// per-head kernel's) dynamic LDS bytes.
+enum { VV_ATTN_PREFILL = 1, VV_ATTN_GROUP = 2, VV_ATTN_HEAD = 3 };
+struct vv_attn_route_t { int kind, f32, nq, gt; size_t lds; };
+static vv_attn_route_t vv_attn_decide(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, const float* out, int64_t ldo) {
+  vv_attn_route_t rt = {0, 0, 0, 0, 0};
+  if (!qkv || !kv || !out) { rt.kind = vv_set_error(VV_E_ARG, "vv_attn: null pointer"); return rt; }
+  if (R <= 0 || heads <= 0 || kv->kv_heads <= 0 || heads % kv->kv_heads) { rt.kind = vv_set_error(VV_E_ARG, "vv_attn: bad layer/R/heads"); return rt; }
+  if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) { rt.kind = vv_set_error(VV_E_UNSUPPORTED, "vv_attn: an fp8 KV cache is read by vv_attn_decode only (kv dtype %d): prompt attention runs on a bf16 cache", kv->kvdt); return rt; }
+  const int d = kv->head_dim;
+  const int epl = kv->kvdt == VV_F32 ? 4 : 8;
+  if (d <= 0 || d % epl || 64 % (d / epl) || d / epl > 64) { rt.kind = vv_set_error(VV_E_UNSUPPORTED, "vv_attn: head_dim %d unsupported for kv dtype %d", d, kv->kvdt); return rt; }
+  const int G = d / epl, ng = 4 * (64 / G);
+  const size_t lds = (size_t)ng * (d + 2) * sizeof(float);
+  if (lds > 65536) { rt.kind = vv_set_error(VV_E_UNSUPPORTED, "vv_attn: LDS %zu too large", lds); return rt; }
+  rt.f32 = kv->kvdt == VV_F32;
+  // prompt rows against a bf16 cache with a transposed value copy: both products on the matrix cores (vv_attn_prefill.hip)
+  if (vv_attn_prefill_covers(qkv, ld_qkv, R, kv, out, ldo)) { rt.kind = VV_ATTN_PREFILL; return rt; }
+  if (g_attn_group && R >= 8 && ((uintptr_t)qkv % 16 == 0) && (ld_qkv % 4 == 0)) {      // prompt-sized row counts: share K/V loads across the GQA group
+    const int nq = heads / kv->kv_heads;
+    const size_t glds = ((size_t)ng * nq * (d + 2) + (size_t)nq * ng) * sizeof(float);
+    if ((nq == 2 || nq == 6 || nq == 7) && glds <= 65536 && nq * ng <= 256) {
+      rt.kind = VV_ATTN_GROUP; rt.nq = nq; rt.gt = d == 128 ? G : 0; rt.lds = glds;
+      return rt;
+    }
+  }
+  rt.kind = VV_ATTN_HEAD; rt.lds = lds;
+  return rt;
+}
+
+extern "C" int vv_attn_route(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, const float* out, int64_t ldo, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_attn_route: no room for the name");
+  name[0] = 0;
+  const vv_attn_route_t rt = vv_attn_decide(qkv, ld_qkv, R, heads, kv, out, ldo);
+  if (rt.kind < 0) return rt.kind;
+  const char* dt = rt.f32 ? "f32" : "bf16";
+  if (rt.kind == VV_ATTN_PREFILL) snprintf(name, cap, "attn_prefill_mfma");
+  else if (rt.kind == VV_ATTN_GROUP) snprintf(name, cap, "attn_group<%s,nq%d,g%d>", dt, rt.nq, rt.gt);
+  else snprintf(name, cap, "attn_head<%s>", dt);
+  return 0;
+}
+
 extern "C" int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const int* lens,
                        const int* cache_rows, float* out, int64_t ldo, vv_stream_t stream) {
   if (!qkv || !kv || !lens || !out) return vv_set_error(VV_E_ARG, "vv_attn: null pointer");
-  if (layer < 0 || layer >= kv->layers || R <= 0 || heads % kv->kv_heads) return vv_set_error(VV_E_ARG, "vv_attn: bad layer/R/heads");
-  if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn: an fp8 KV cache is read by vv_attn_decode only (kv dtype %d): prompt attention runs on a bf16 cache", kv->kvdt);
-  const int d = kv->head_dim;
-  const int epl = kv->kvdt == VV_F32 ? 4 : 8;
-  if (d % epl || 64 % (d / epl) || d / epl > 64) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn: head_dim %d unsupported for kv dtype %d", d, kv->kvdt);
-  const int G = d / epl, ng = 4 * (64 / G);
-  const size_t lds = (size_t)ng * (d + 2) * sizeof(float);
-  if (lds > 65536) return vv_set_error(VV_E_UNSUPPORTED, "vv_attn: LDS %zu too large", lds);
+  if (layer < 0 || layer >= kv->layers) return vv_set_error(VV_E_ARG, "vv_attn: bad layer/R/heads");
+  const vv_attn_route_t rt = vv_attn_decide(qkv, ld_qkv, R, heads, kv, out, ldo);
+  if (rt.kind < 0) return rt.kind;
   hipStream_t s = (hipStream_t)stream;
-  {   // prompt rows against a bf16 cache with a transposed value copy: both products on the matrix cores (vv_attn_prefill.hip)
-    const int rc = vv_launch_attn_prefill(qkv, ld_qkv, R, heads, kv, layer, lens, cache_rows, out, ldo, s);
-    if (rc) return rc < 0 ? rc : 0;
-  }
-  if (g_attn_group && R >= 8 && ((uintptr_t)qkv % 16 == 0) && (ld_qkv % 4 == 0)) {      // prompt-sized row counts: share K/V loads across the GQA group
-    const int nq = heads / kv->kv_heads;
-    bool done = false;
-    if (nq == 2) done = launch_attn_group<2>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, s);
-    else if (nq == 6) done = launch_attn_group<6>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, s);
-    else if (nq == 7) done = launch_attn_group<7>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, s);
-    if (done) { VV_CHECK_LAUNCH("vv_attn"); return 0; }
+  if (rt.kind == VV_ATTN_PREFILL) return vv_launch_attn_prefill(qkv, ld_qkv, R, heads, kv, layer, lens, cache_rows, out, ldo, s);
+  if (rt.kind == VV_ATTN_GROUP) {
+    if (rt.nq == 2) launch_attn_group<2>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, rt.lds, s);
+    else if (rt.nq == 6) launch_attn_group<6>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, rt.lds, s);
+    else launch_attn_group<7>(qkv, ld_qkv, kv, layer, lens, cache_rows, out, ldo, R, rt.lds, s);
+    VV_CHECK_LAUNCH("vv_attn");
+    return 0;
   }
   dim3 grid(heads, R);
-  if (kv->kvdt == VV_F32) hipLaunchKernelGGL((attn_kernel<float, 4>), grid, dim3(256), lds, s, qkv, ld_qkv, heads, *kv, layer, lens, cache_rows, out, ldo);
-  else hipLaunchKernelGGL((attn_kernel<bf16_t, 8>), grid, dim3(256), lds, s, qkv, ld_qkv, heads, *kv, layer, lens, cache_rows, out, ldo);
+  if (rt.f32) hipLaunchKernelGGL((attn_kernel<float, 4>), grid, dim3(256), rt.lds, s, qkv, ld_qkv, heads, *kv, layer, lens, cache_rows, out, ldo);
+  else hipLaunchKernelGGL((attn_kernel<bf16_t, 8>), grid, dim3(256), rt.lds, s, qkv, ld_qkv, heads, *kv, layer, lens, cache_rows, out, ldo);
   VV_CHECK_LAUNCH("vv_attn");
   return 0;
 }
