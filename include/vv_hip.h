@@ -56,8 +56,26 @@ enum { VV_WQ_NF4 = 0x100 };
  * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike. */
 enum { VV_MXFP4 = 4 };
 /* VV_WQ_MXFP4: as VV_WQ_NF4, for companions that hold MXFP4 (codes in q, the scale bytes' address in scale, the VV_MXFP4 layouts above).  The
- * 1..2-row GEMVs stream them; every 3..8-row path and the prefill use the bf16 matrices, which hold exactly the same effective values. */
+ * 1..2-row GEMVs stream them; every 3..8-row path (unless VV_WQ_FRAG4, below) and the prefill use the bf16 matrices, which hold exactly the same
+ * effective values. */
 enum { VV_WQ_MXFP4 = 0x200 };
+/* VV_MXFP4_FRAG: the same OCP MXFP4 values (codes, E8M0 scale bytes 2..252, effective weight value(code) * 2^(e - 127)) in FRAGMENT-MAJOR order, for the
+ * 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows_mx.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding occurs), fp32
+ * activations and outputs.
+ *   w / w2:           codes [N / 16][K / 128][64 lanes][16 B], 16-byte aligned: dword h (0..3) of lane 16 c + n of 128-wide step J of row group g holds
+ *                     W[16 g + n][128 J + 32 h + 8 c + i] in nibble i (bits 4 i .. 4 i + 3, the nibble order of VV_MXFP4) - dword h is the B fragment of
+ *                     32-wide k step 4 J + h in the lane assignment of the bf16 fragment-major layout; one 1 KB wave load carries four MFMA steps
+ *   wscale / w2scale: the ADDRESS of the scale bytes, read as uint8_t, 4-byte aligned: [N / 16][K / 128][16 rows][4 B], i.e. byte h of the dword at
+ *                     ((g * K/128 + J) * 16 + n) * 4 is the E8M0 byte of block 4 J + h (k = 128 J + 32 h .. + 31) of row 16 g + n
+ * Any other call with this code (m <= 2, m > 8, the flag missing, a missing scale pointer, a misaligned pointer, VV_LIN_X_BF16 / VV_LIN_OUT_BF16,
+ * k > 2048 without split-K scratch) returns VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, the output untouched. */
+enum { VV_MXFP4_FRAG = 5 };
+/* VV_WQ_FRAG4: ORed into vv_llm.wdt / vv_head.wdt next to VV_WQ_MXFP4 - a layer's f_* pointers then hold the VV_MXFP4_FRAG form of its MXFP4
+ * companions: the codes, and the scale bytes behind them in the same allocation at byte offset N * K / 2 (a multiple of 1024).  vv_llm_forward
+ * with R in 3..8, vv_linear_ws, vv_head_sample_batch(_sde / _cfg) and the row-batched step around vv_llm_tail_batch then run the MX rows kernel
+ * for every matrix that has a copy; a matrix the form cannot take (N % 16, K % 128) keeps f_* = NULL and the bf16 row-major fallback.  The
+ * prefill and the m <= 2 calls are unchanged.  No bf16 fragment copy may sit in f_* under this bit. */
+enum { VV_WQ_FRAG4 = 0x400 };
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
@@ -111,7 +129,7 @@ typedef struct vv_lin_args {
   float* out;
   int64_t ldo;
   int flags;   /* VV_LIN_* */
-  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
+  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4 / VV_MXFP4_FRAG: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
   const float* w2scale;
 } vv_lin_args;
 
@@ -123,6 +141,7 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)
  *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
+ *   "gemv_rows_mx<dual=0,nw=4,ks=3,pers=0> ksplit=6 atomic=0"              the same on VV_MXFP4_FRAG weights (ks: 128-wide weight loads per wave)
  *   "gemv_hot<3>", "conv_hot_gemv<0>"                                      hot kernels, by table index
  *   "gemv_stream<m=4,...> + gemv_stream<m=2,...>"                          5..8 rows as two streaming passes of 4 + rest rows
  *   "gemv_lds<w=f32,m=3,dual=0,ks=4,np=2>", "gemv_generic<w=bf16>"         the LDS-staged and the generic fall-back
@@ -268,7 +287,9 @@ typedef struct vv_llm_layer {
    *   K % 32 == 0.
    *   fp8 (the matrix HAS an fp8 companion, q_*.q != NULL): f_* is then the fragment-major copy of the companion's e4m3fn CODES (its scale is
    *   q_*.scale), [N / 16][K / 64][4][16][2][8] bytes, i.e. code (16 g + n, 64 j + 32 h + 8 c + e) at ((g * K/64 + j) * 64 + 16 c + n) * 16 +
-   *   8 h + e - one 1 KB wave load carries the B fragments of two 32-wide k steps.  N % 16 == 0, K % 64 == 0.  Never a bf16 copy. */
+   *   8 h + e - one 1 KB wave load carries the B fragments of two 32-wide k steps.  N % 16 == 0, K % 64 == 0.  Never a bf16 copy.
+   *   MXFP4 (VV_WQ_FRAG4 in the descriptor's wdt): f_* is the VV_MXFP4_FRAG form of the MXFP4 companion, codes then scale bytes.  N % 16 == 0,
+   *   K % 128 == 0.  Never a bf16 copy. */
   const void* f_qkv; const void* f_o; const void* f_gate; const void* f_up; const void* f_down;
 } vv_llm_layer;
 
@@ -379,7 +400,7 @@ int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const 
                    const float* sde_noise /* [n_steps, latent] per-step variance noise of the SDE solver (dpm_solver.py:993-998) or NULL */,
                    vv_stream_t stream);
 /* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights, with
- * their fp8 companions' fragment-major codes where the layers carry them): cond[2 B, cond_dim] = rows
+ * their fp8 companions' fragment-major codes where the layers carry them, or - VV_WQ_FRAG4 - the VV_MXFP4_FRAG form of their MXFP4 companions): cond[2 B, cond_dim] = rows
  * {positive, negative} of utterance b at 2 b, 2 b + 1; noise[b * ld_noise ..], latent_out[b * ld_latent ..].  Every head matrix is streamed once
  * per solver step for all utterances.  ws: vv_head_ws_bytes_batch(h, n_steps, B) bytes. */
 size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B);
@@ -493,6 +514,10 @@ int vv_graph_destroy(void* graph_exec);
 /* ------------------------------------------------------------------------------------------------------------
  * Per-launch timing of vv_linear with HIP events recorded on the launch stream (eager mode only, never during
  * graph capture).  vv_prof_begin arms it; vv_prof_end synchronises and aggregates by (m, n, k, dual, wdt).
+ * The 3..8-row launches the composites make themselves (not through vv_linear) are recorded only for a
+ * descriptor that carries VV_WQ_FRAG4, under the dtype they stream (VV_MXFP4_FRAG, or VV_BF16 for a matrix
+ * without a copy); without the bit the record is what it always was.  The record list is locked: a row
+ * batch's lanes call vv_linear from threads of their own.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct vv_prof_entry { int m, n, k, dual, wdt, count; double total_ms; } vv_prof_entry;
 int vv_prof_begin(int max_records);

@@ -75,9 +75,18 @@ size_t vv_gemv_rows_part_floats(int n, int dual);
 size_t vv_gemv_rows_tickets(int n);
 int vv_gemv_rows_init();
 void vv_gemv_rows_set(int on, int blocks, int pers);            // tuning hooks (negative / zero: keep)
+// vv_gemv_rows_mx.hip: gemv_rows_mx_kernel<dual, nw, ks, pers> - the same GEMV on VV_MXFP4_FRAG weights (vv_hip.h); ks / spw count 128-wide weight
+// loads per wave, the route's f8 field is 0.  Workspace, tickets and return values as above; the tune hooks of vv_gemv_rows.hip are mirrored here
+vv_rows_route vv_gemv_rows_mx_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
+int vv_launch_gemv_rows_mx_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
+int vv_launch_gemv_rows_mx(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
+int vv_gemv_rows_mx_route_name(const vv_rows_route& r, char* name, int cap);
+int vv_gemv_rows_mx_init();
+void vv_gemv_rows_mx_set(int on, int blocks, int pers, int atomic);   // negative (blocks / pers: zero too): keep
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets,
-                 vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr);
-                 // vv_kernels.hip: f1 / f2 = fragment-major copies of a->w / a->w2 or null; with fp8 companions q1 / q2 (q != NULL) of the fp8 codes
+                 vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr, bool frag4 = false);
+                 // vv_kernels.hip: f1 / f2 = fragment-major copies of a->w / a->w2 or null; with fp8 companions q1 / q2 (q != NULL) of the fp8 codes;
+                 // frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form, codes then scale bytes at byte offset n * k / 2
 int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s);     // vv_mfma_gemm.hip: 1 launched, 0 not covered, <0 error
 // the kernel of vv_mfma_gemm.hip a call takes, decided apart from the launch (vv_linear_route reports it without launching): kind 0 = not covered,
 // < 0 = error; stream: mfma_linear_kernel<dual, ksplit, xb, mt>, tiled: mfma_tiled_kernel<dual, bk, tm>

@@ -37,6 +37,7 @@ extern "C" int vv_init(void) {
   VV_TRY(vv_block1d_init());
   VV_TRY(vv_convffn_init());
   VV_TRY(vv_gemv_rows_init());
+  VV_TRY(vv_gemv_rows_mx_init());
   return vv_fused_init();
 }
 // process-wide split-K scratch of the 3..8-row matrix-core GEMV for PUBLIC vv_linear calls (micro-benchmarks and tests only, switched on by
@@ -79,12 +80,12 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
   if (key && !strcmp(key, "gemv_blocks")) { vv_gemv_stream_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_mx_blocks")) { vv_gemv_mx_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_waves")) { vv_gemv_stream_set_waves(value); return 0; }
-  if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); return 0; }
-  if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); return 0; }
-  if (key && !strcmp(key, "gemv_rows_pers")) { vv_gemv_rows_set(-1, 0, value); return 0; }
+  if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); vv_gemv_rows_mx_set(value, 0, -1, -1); return 0; }
+  if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); vv_gemv_rows_mx_set(-1, value, -1, -1); return 0; }
+  if (key && !strcmp(key, "gemv_rows_pers")) { vv_gemv_rows_set(-1, 0, value); vv_gemv_rows_mx_set(-1, 0, value, -1); return 0; }
   if (key && !strcmp(key, "gemv_rows_scratch")) return rows_scratch(value);
   if (key && !strcmp(key, "gemv_rows_dbg")) { vv_gemv_rows_set_dbg(value); return 0; }
-  if (key && !strcmp(key, "gemv_rows_atomic")) { vv_gemv_rows_set_atomic(value); return 0; }
+  if (key && !strcmp(key, "gemv_rows_atomic")) { vv_gemv_rows_set_atomic(value); vv_gemv_rows_mx_set(-1, 0, -1, value != 0); return 0; }
   if (key && !strcmp(key, "gemv_opt")) { vv_gemv_stream_set_opt(value); return 0; }
   if (key && !strcmp(key, "gemv_dual_rw")) { vv_gemv_stream_set_dual_rw(value); return 0; }
   if (key && !strcmp(key, "gemv_small_rw")) { vv_gemv_stream_set_small_rw(value); return 0; }
@@ -500,10 +501,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
 // The m <= 8 family's decision (vv_linear launches it, vv_linear_route prints it): the 3..8-row matrix-core GEMV when the process-wide scratch is
 // on, the weight-streaming GEMV (or a hot kernel), two streaming passes of 4 + rest rows, the LDS-staged gemv_kernel<WT, M, DUAL, KS, NP> or the
 // generic kernel.  Plain values only: no pointer is followed, nothing is launched; the thresholds live here and in the two deciders it calls.
-enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX };
+enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX, GEMV_ROWS_MX };
 struct gemv_route {
   int kind;
-  vv_rows_route rows;
+  vv_rows_route rows;                // GEMV_ROWS, or GEMV_ROWS_MX: the same GEMV on VV_MXFP4_FRAG weights (vv_gemv_rows_mx.hip)
   vv_stream_route st, st2;          // GEMV_SPLIT: rows 0..3 and the rest
   vv_mx_route mx;                   // GEMV_MX: the MXFP4 streaming GEMV (vv_gemv_mx.hip)
   int m, dual, ks, np, kc, blocks;  // GEMV_LDS: gemv_kernel<WT, m, dual, ks, np> staging kc columns at a time; GEMV_GENERIC: blocks
@@ -560,6 +561,14 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
     if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)", a.m, a.n, a.k);
   }
+  if (a.wdt == VV_MXFP4_FRAG) {
+    // fragment-major MXFP4: the 3..8-row matrix-core GEMV of vv_gemv_rows_mx.hip and nothing else (process-wide split-K scratch as for bf16)
+    g->rows = vv_gemv_rows_mx_decide(a, g_rows_part != nullptr, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
+    if (g->rows.kind) { g->kind = GEMV_ROWS_MX; return 0; }
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights need VV_LIN_W_FRAG, 3..8 rows, n %% 16 == 0, k %% 128 == 0, scale bytes, 16-byte aligned codes "
+                        "and activations, 4-byte aligned scales, fp32 activations and outputs, and split-K scratch for k > 2048 (m=%d n=%d k=%d flags=%d)",
+                        a.m, a.n, a.k, a.flags);
+  }
   if (a.wdt == VV_MXFP4) {
     // weight-only MXFP4 has a streaming GEMV of its own (<= 2 rows, vv_gemv_mx.hip) and nothing else
     g->mx = vv_gemv_mx_decide(a);
@@ -609,6 +618,7 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
 static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* name, int cap) {
   const char* w = a.wdt == VV_F32 ? "f32" : "bf16";
   if (g.kind == GEMV_ROWS) vv_gemv_rows_route_name(g.rows, name, cap);
+  else if (g.kind == GEMV_ROWS_MX) vv_gemv_rows_mx_route_name(g.rows, name, cap);
   else if (g.kind == GEMV_STREAM) vv_gemv_stream_route_name(g.st, name, cap);
   else if (g.kind == GEMV_MX) vv_gemv_mx_route_name(g.mx, name, cap);
   else if (g.kind == GEMV_SPLIT) {
@@ -659,6 +669,7 @@ template <typename WT>
 static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
   switch (g.kind) {
     case GEMV_ROWS: return vv_launch_gemv_rows_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: rows GEMV declined its own route");
+    case GEMV_ROWS_MX: return vv_launch_gemv_rows_mx_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP4 rows GEMV declined its own route");
     case GEMV_STREAM: return vv_launch_gemv_stream_route(a, g.st, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: streaming GEMV declined its own route");
     case GEMV_MX: return vv_launch_gemv_mx_route(a, g.mx, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP4 GEMV declined its own route");
     case GEMV_SPLIT: {
@@ -723,15 +734,33 @@ static int launch_linear(const vv_lin_args& a, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------------------------
 // optional per-launch timing of vv_linear with HIP events (eager mode only; used by bench.py's roofline leg)
 // ---------------------------------------------------------------------------------------------------------------
+#include <atomic>
+#include <mutex>
 #include <vector>
 namespace {
 struct ProfRec { hipEvent_t e0, e1; int m, n, k, dual, wdt; };
 std::vector<ProfRec> g_prof;
-bool g_prof_on = false;
+std::atomic<bool> g_prof_on{false};   // read without the lock: a launch outside a profiling window pays one load
 size_t g_prof_cap = 0;
+std::mutex g_prof_mu;      // a row batch's lanes call vv_linear from worker threads of their own while the main thread runs the batched step
+// does a launch get a record?  The list is read under its lock: the lanes' threads append to it at the same time
+bool prof_wanted() {
+  if (!g_prof_on.load(std::memory_order_relaxed)) return false;
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  return g_prof_on && g_prof.size() < g_prof_cap;
+}
+// keep a finished record (false: no room left - the record's events are destroyed)
+bool prof_keep(const ProfRec& pr) {
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  if (g_prof.size() < g_prof_cap) { g_prof.push_back(pr); return true; }
+  (void)hipEventDestroy(pr.e0);
+  (void)hipEventDestroy(pr.e1);
+  return false;
+}
 }
 extern "C" int vv_prof_begin(int max_records) {
   if (max_records <= 0) return vv_set_error(VV_E_ARG, "vv_prof_begin: max_records");
+  std::lock_guard<std::mutex> lk(g_prof_mu);
   g_prof.clear();
   g_prof.reserve(max_records);
   g_prof_cap = (size_t)max_records;
@@ -739,6 +768,7 @@ extern "C" int vv_prof_begin(int max_records) {
   return 0;
 }
 extern "C" int vv_prof_end(vv_prof_entry* out, int max_out, int* n_out) {
+  std::lock_guard<std::mutex> lk(g_prof_mu);
   g_prof_on = false;
   if (!out || !n_out) return vv_set_error(VV_E_ARG, "vv_prof_end: null");
   int n = 0;
@@ -782,7 +812,11 @@ static int linear_check_args(const vv_lin_args* a) {
   if (a->wdt == VV_MXFP4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 32 || !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights exist for the streaming GEMV alone: m <= 2, k %% 32 == 0, wscale (w2scale), "
                         "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
-  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
+  if (a->wdt == VV_MXFP4_FRAG && (!(a->flags & VV_LIN_W_FRAG) || (a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 128 ||
+                                  !a->wscale || (a->w2 && !a->w2scale)))
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights exist for the 3..8-row matrix-core GEMV alone: VV_LIN_W_FRAG, 3 <= m <= 8, n %% 16 == 0, "
+                        "k %% 128 == 0, wscale (w2scale), no bf16 hand-off (m=%d n=%d k=%d flags=%d)", a->m, a->n, a->k, a->flags);
+  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && a->wdt != VV_MXFP4_FRAG && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
     return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..8 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
     return vv_set_error(VV_E_ARG, "vv_linear: bf16 activation hand-off needs bf16 weights, m > 8 and k %% 16 == 0");
@@ -804,7 +838,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     if (fam == LIN_FAM_MFMA) vv_mfma_route_name(route, name, cap);
     else if (fam != LIN_FAM_GEMV) snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : "gemm_f32");
   }
-  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
     VV_TRY(gemv_decide(*a, &g));
@@ -818,7 +852,7 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   int rc;
   ProfRec pr;
-  const bool prof = g_prof_on && g_prof.size() < g_prof_cap;
+  const bool prof = prof_wanted();
   if (prof) {
     pr.m = a->m; pr.n = a->n; pr.k = a->k; pr.dual = a->w2 != nullptr; pr.wdt = a->wdt;
     if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
@@ -826,33 +860,52 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   }
   if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
-  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4) {   // weight-only fp8 / NF4 / MXFP4: the rows or a streaming GEMV, or refused (gemv_decide)
+  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4 || a->wdt == VV_MXFP4_FRAG) {   // weight-only fp8 / NF4 / MXFP4: the rows or a streaming GEMV, or refused (gemv_decide)
     gemv_route g;
     rc = gemv_decide(*a, &g);
     if (!rc) rc = launch_gemv_route<bf16_t>(*a, g, s);
   }
   else return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (rc) return rc;
-  if (prof) { (void)hipEventRecord(pr.e1, s); g_prof.push_back(pr); }
+  if (prof) { (void)hipEventRecord(pr.e1, s); prof_keep(pr); }
   VV_CHECK_LAUNCH("vv_linear");
   return 0;
 }
 
 // vv_linear for the composites of a row-batched step: 3..8 rows go to the matrix-core GEMV with the caller's split-K workspace, on the
 // fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices.
-// q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*)
+// q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*).
+// frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form (codes, scale bytes behind them) and go to vv_gemv_rows_mx.hip; a matrix without
+// such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
-                 const vv_w8* q1, const vv_w8* q2) {
+                 const vv_w8* q1, const vv_w8* q2, bool frag4) {
   if (a && a->wdt == VV_BF16 && a->m > 2 && a->m <= 8 && a->x && a->w && a->out) {
     vv_lin_args b = *a;
-    const bool f8 = q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
-    if (f8) {                 // fp8 companions: their fragment-major codes or nothing (never a bf16 read of an fp8 copy)
+    const bool f8 = !frag4 && q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
+    const bool mx = frag4 && f1 && (!b.w2 || f2);
+    if (mx) {                 // VV_WQ_FRAG4: the copies are VV_MXFP4_FRAG codes, their scale bytes behind them in the same allocation
+      const size_t codes = (size_t)b.n * b.k / 2;
+      b.w = f1; b.wscale = reinterpret_cast<const float*>(static_cast<const char*>(f1) + codes); b.wdt = VV_MXFP4_FRAG; b.flags |= VV_LIN_W_FRAG;
+      if (b.w2) { b.w2 = f2; b.w2scale = reinterpret_cast<const float*>(static_cast<const char*>(f2) + codes); }
+    } else if (f8) {          // fp8 companions: their fragment-major codes or nothing (never a bf16 read of an fp8 copy)
       if (f1 && (!b.w2 || f2)) {
         b.w = f1; b.wscale = q1->scale; b.wdt = VV_FP8; b.flags |= VV_LIN_W_FRAG;
         if (b.w2) { b.w2 = f2; b.w2scale = q2->scale; }
       }
-    } else if (f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
-    const int rc = vv_launch_gemv_rows(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream);
+    } else if (!frag4 && f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
+    ProfRec pr;               // vv_prof_begin: a VV_WQ_FRAG4 model's rows launches are recorded under the weight type they stream (other models: none, as before)
+    const bool prof = frag4 && prof_wanted();
+    if (prof) {
+      pr.m = b.m; pr.n = b.n; pr.k = b.k; pr.dual = b.w2 != nullptr; pr.wdt = b.wdt;
+      if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
+      (void)hipEventRecord(pr.e0, (hipStream_t)stream);
+    }
+    const int rc = mx ? vv_launch_gemv_rows_mx(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream)
+                      : vv_launch_gemv_rows(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream);
+    if (prof) {
+      if (rc == 1) { (void)hipEventRecord(pr.e1, (hipStream_t)stream); prof_keep(pr); }
+      else { (void)hipEventDestroy(pr.e0); (void)hipEventDestroy(pr.e1); }
+    }
     if (rc < 0) return rc;
     if (rc == 1) { VV_CHECK_LAUNCH("vv_linear(rows)"); return 0; }
   }

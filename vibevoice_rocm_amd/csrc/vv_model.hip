@@ -42,13 +42,14 @@ static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q
 }
 
 // VV_WQ_NF4 / VV_WQ_MXFP4 (vv_hip.h) ride on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
-// the matrix dtype, and keeps the companions' kind in `wq`
+// the matrix dtype, and keeps the companions' kind in `wq`; `frag4`: VV_WQ_FRAG4, the layers' f_* copies hold the VV_MXFP4_FRAG form
 #define VV_WQ_STRIP(T, p)                                                   \
   T p##_plain_ = *(p);                                                      \
   const int wq = (p##_plain_.wdt & VV_WQ_MXFP4) ? VV_MXFP4 : (p##_plain_.wdt & VV_WQ_NF4) ? VV_NF4 : VV_FP8; \
-  p##_plain_.wdt &= ~(VV_WQ_NF4 | VV_WQ_MXFP4);                             \
+  const bool frag4 = wq == VV_MXFP4 && (p##_plain_.wdt & VV_WQ_FRAG4) != 0; \
+  p##_plain_.wdt &= ~(VV_WQ_NF4 | VV_WQ_MXFP4 | VV_WQ_FRAG4);               \
   p = &p##_plain_;                                                          \
-  (void)wq
+  (void)wq; (void)frag4
 
 // from this many rows on, a bf16-weight LLM forward is a prompt prefill: activations are cast to bf16 once per GEMM and both
 // operands stream from global on the matrix cores with 128-row tiles (every weight fragment reused by 4 row tiles)
@@ -133,8 +134,9 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
   // rows8 with fp8 companions: f_* are the fragment-major copies of their codes (vv_llm_layer)
   auto lin = [&](vv_lin_args& a, const void* f1, const void* f2, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr) -> int {
     if (!rows8) return vv_linear(&a, stream);
-    // NF4 companions never reach the 3..8-row kernel: f1 / f2 are then bf16 fragment-major copies of the effective matrices (or NULL)
-    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr);
+    // NF4 / MXFP4 companions never reach the 3..8-row kernel: f1 / f2 are then bf16 fragment-major copies of the effective matrices (or NULL) -
+    // or, under VV_WQ_FRAG4, the VV_MXFP4_FRAG form of the MXFP4 companions
+    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr, frag4);
   };
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
@@ -422,7 +424,7 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
   if (NX) VV_TRY(vv_head_sde_proj_fused(h, sde_noise, ld_sde, n_steps, B, NX, s));
   // step-invariant work: cond_proj on all rows, silu(cond_proj(cond) + t_emb(t_i)) as bf16 rows [step][2 B], every adaLN modulation
   vv_lin_args a = lin_base(cond, ld_cond, R2, h->cond_proj, D, h->cond_dim, h->wdt, c0, D);
-  VV_TRY(vv_linear_ws(&a, nullptr, nullptr, rpart, rpart_n, rtick, rtick_n, stream));
+  VV_TRY(vv_linear_ws(&a, nullptr, nullptr, rpart, rpart_n, rtick, rtick_n, stream, nullptr, nullptr, frag4));   // no companion, no copy: bf16 rows; frag4 only for the profiler's record
   VV_TRY(vv_add_rows_silu_bf16(c0, D, temb, D, c, (int)R, R2, D, stream));
   VV_TRY(head_modulations(h, c, (int)R, mod, modf, true, true, stream));
   for (int b = 0; b < B; ++b)
@@ -436,10 +438,10 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
       a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
       a.w2 = L.wup; a.act = VV_ACT_SWIGLU; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_gate : nullptr, f8q ? &L.q_up : nullptr));
+      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_gate : nullptr, f8q ? &L.q_up : nullptr, frag4));
       a = lin_base(act, h->ffn, R2, L.wdown, D, h->ffn, h->wdt, hc, D);
       a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hc; a.ldres = D; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_down : nullptr));
+      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_down : nullptr, nullptr, frag4));
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
     VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,

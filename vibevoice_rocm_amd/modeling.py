@@ -626,7 +626,7 @@ class VibeVoiceSession:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
-                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False):
+                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False):
         # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
         # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
         # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
@@ -641,6 +641,12 @@ class VibeVoiceForConditionalGenerationInference:
             if weight_quant not in (None, "nf4"):
                 raise ValueError(f"a pre-quantized bitsandbytes NF4 checkpoint runs as weight_quant='nf4', not {weight_quant!r}")
             weight_quant, torch_dtype = "nf4", torch.bfloat16
+        # mxfp4_row_batch=True (weight_quant="mxfp4" only): batches of row_batch_min..16 dialogues and serving sessions run the row-batched path on
+        # fragment-major copies of the MXFP4 codes and scale bytes (csrc/vv_gemv_rows_mx.hip; +0.53 B per copied weight).
+        # Off by default: the batch then runs on the lanes and open_session refuses the mode, as before
+        if mxfp4_row_batch and weight_quant != "mxfp4":
+            raise ValueError(f"mxfp4_row_batch=True needs weight_quant='mxfp4', not {weight_quant!r}")
+        self.mxfp4_row_batch = bool(mxfp4_row_batch)
         missing = [k for k in shapes if k not in state_dict and k not in (prequant or {})]
         if missing:
             raise KeyError(f"state dict is missing {len(missing)} tensors, e.g. {missing[:4]}")
@@ -667,10 +673,10 @@ class VibeVoiceForConditionalGenerationInference:
         # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         # "mxfp4": weight-only OCP MXFP4 companions (e2m1 codes, one power-of-two scale byte per 32 k) decoded by the vector ALU's own
-        # conversion instruction (batches of >= 2 run on the lanes, sessions refuse it)
+        # conversion instruction (batches of >= 2 run on the lanes, sessions refuse it - unless mxfp4_row_batch=True)
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
-                             prequant=prequant, kv_cache_dtype=kv_cache_dtype)
+                             prequant=prequant, kv_cache_dtype=kv_cache_dtype, mxfp4_row_batch=self.mxfp4_row_batch)
         self.device = self.engine.device
         # batches run in lock step on one Engine per sample (own HIP stream, KV cache and conv state; matrices already in the streamed
         # dtype on the device are shared, not copied): lanes beyond the first are built on first use from this state dict
@@ -718,7 +724,8 @@ class VibeVoiceForConditionalGenerationInference:
             device = "cuda:0"
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
                    use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
-                   device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False))
+                   device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False),
+                   mxfp4_row_batch=kw.get("mxfp4_row_batch", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -822,13 +829,17 @@ class VibeVoiceForConditionalGenerationInference:
                 vp = eng.save_prefix(ids)
         return vp
 
+    def _rows_quant_ok(self) -> bool:
+        """the row-batched decode path serves this model's weights: bf16, weight-only fp8, or MXFP4 with the fragment-major opt-in"""
+        return self.weight_quant in (None, "fp8") or (self.weight_quant == "mxfp4" and self.mxfp4_row_batch)
+
     # ---- serving sessions ---------------------------------------------------------------------------------------
     def open_session(self, tokenizer=None, slots: int = 8, max_context: Optional[int] = None, generation_config=None, device_noise: bool = True,
                      device_sampling: Optional[bool] = None) -> "VibeVoiceSession":
         """Open a serving session: `slots` (2..16) row-batch slots - ceil(slots / 4) row batches, as a batched generate() partitions them - whose
         KV caches are sized once for `max_context` tokens per dialogue (required).  Dialogues are submitted to the session one by one and a
         finished one frees its slot for the next between two steps (VibeVoiceSession, batchloop.Session).  Needs what row batching needs -
-        bf16, weight_quant None or "fp8", a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
+        bf16, weight_quant None or "fp8" (or "mxfp4" on a model built with mxfp4_row_batch=True), a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
         per model; generate() raises RuntimeError until it is closed."""
         if getattr(self, "_session", None) is not None:
             raise RuntimeError("open_session(): this model already has an open session (one per model); close() it first")
@@ -841,7 +852,7 @@ class VibeVoiceForConditionalGenerationInference:
         why = None
         if self.dtype != torch.bfloat16:
             why = f"torch_dtype={self.dtype} (bf16 only)"
-        elif self.weight_quant not in (None, "fp8"):
+        elif not self._rows_quant_ok():
             why = f"weight_quant={self.weight_quant!r} (None or 'fp8')"
         elif self.kv_cache_dtype == "fp8":
             why = "kv_cache_dtype='fp8' (the row-batched decode step has no fp8-KV form)"
@@ -928,7 +939,7 @@ class VibeVoiceForConditionalGenerationInference:
                 raise NotImplementedError("refresh_negative=False is built for batch size 1 only")
             # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py), or one engine lane each
             rows = kwargs.get("row_batch", self.row_batch) and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and \
-                self.weight_quant in (None, "fp8") and self.kv_cache_dtype != "fp8"      # fp8 KV: on the lanes (RowBatch needs a bf16 cache)
+                self._rows_quant_ok() and self.kv_cache_dtype != "fp8"      # fp8 KV: on the lanes (RowBatch needs a bf16 cache)
             driver = (_RowDriver if rows else _LaneDriver)(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"])
             if vps is not None:
                 driver.prefixes = vps

@@ -5,7 +5,8 @@ B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in on
 
   graph A   Qwen2 decode step with R = 2 B rows (dialogue b = rows {2 b: positive, 2 b + 1: negative} of x, lens and one KV cache with 2 B
             rows): every weight matrix is read once for all dialogues (4..8 rows: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
-            fragment-major weight copies - of the e4m3 codes with weight_quant="fp8"), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
+            fragment-major weight copies - of the e4m3 codes with weight_quant="fp8", of the MXFP4 codes and scale bytes with weight_quant="mxfp4" and
+            mxfp4_row_batch=True (csrc/vv_gemv_rows_mx.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
             bookkeeping per dialogue.  With do_sample it splits as Engine.step_decode does: A1 = the decode step and the constrained logits
             (no position bookkeeping), one host read-back of every row batch's logits, the tokens drawn on the host, A2 = the bookkeeping with
             those tokens as forced tokens;
@@ -62,8 +63,9 @@ class RowBatch:
         eng = self.main = lanes[0]
         self.lib, self.cfg, self.device, self.stream = eng.lib, eng.cfg, eng.device, (stream or eng.stream)
         self._on_main = [e.stream.cuda_stream == self.stream.cuda_stream for e in lanes]
-        if eng.dtype != torch.bfloat16 or eng.kv_dtype != torch.bfloat16 or getattr(eng, "kv_fp8", False) or eng.w.quant not in (None, "fp8"):
-            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions) and a bf16 KV cache "
+        if eng.dtype != torch.bfloat16 or eng.kv_dtype != torch.bfloat16 or getattr(eng, "kv_fp8", False) or \
+                not (eng.w.quant in (None, "fp8") or (eng.w.quant == "mxfp4" and eng.w.mxfp4_row_batch)):
+            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions, or MXFP4 ones with mxfp4_row_batch=True) and a bf16 KV cache "
                             "(kv_cache_dtype='fp8' batches run on the lanes: the row-batched decode step has no fp8-KV form)")
         self.uid = next(_UID)
         cfg, H = self.cfg, self.cfg.hidden

@@ -149,6 +149,10 @@ def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict
 MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 MXFP4_BLOCK = 32
 MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
+# limits of the MX rows kernel's decision (csrc/vv_gemv_rows_mx.hip, vv_gemv_rows_mx_decide) that the host acts on: the adaLN-modulated prologue
+# is served on whole rows only (K <= 2048); the SwiGLU pair splits K two ways at most inside the row-batched step's partials workspace
+# (csrc/vv_model.hip, rows_part_floats), 2 slices x 8 waves x 2 loads x 128 = 4096
+MXFP4_ROWS_MOD_K, MXFP4_ROWS_MAX_HIDDEN = 2048, 4096
 
 
 def quantize_mxfp4(w: torch.Tensor):
@@ -222,9 +226,16 @@ class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
     def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None,
-                 prequant: Optional[Dict[str, object]] = None):
+                 prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False):
         """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
-        are imported as they are (vv_nf4_import) and need quant="nf4"."""
+        are imported as they are (vv_nf4_import) and need quant="nf4".  mxfp4_row_batch (quant="mxfp4" only): the 3..8-row paths stream the
+        MXFP4 companions in fragment-major form (VV_WQ_FRAG4 on the LLM's and the head's descriptors; ensure_frag builds the copies)."""
+        if mxfp4_row_batch and quant != "mxfp4":
+            raise ValueError(f"mxfp4_row_batch=True serves the MXFP4 companions on the row-batched path: it needs weight_quant='mxfp4', not {quant!r}")
+        if mxfp4_row_batch and cfg.hidden > MXFP4_ROWS_MAX_HIDDEN:
+            raise ValueError(f"mxfp4_row_batch=True serves LLM hidden sizes up to {MXFP4_ROWS_MAX_HIDDEN}, not {cfg.hidden}: beyond, the SwiGLU pair "
+                             "would need a three-way K split, which the row-batched step's partials workspace has no room for")
+        self.mxfp4_row_batch = bool(mxfp4_row_batch)
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
         if quant not in (None, "fp8", "nf4", "mxfp4"):
             raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3), 'nf4' (weight-only 4-bit NF4) or 'mxfp4' (weight-only OCP "
@@ -239,10 +250,13 @@ class DeviceWeights:
         self.wdt = _wdt(wdtype)
         # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 mark their vv_w8 companions as NF4 / MXFP4 (vv_hip.h); self.wdt stays the plain matrix dtype
         self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else L.VV_WQ_MXFP4 if quant == "mxfp4" else 0)
+        # vv_llm / vv_head: VV_WQ_FRAG4 says their layers' f_* copies hold the VV_MXFP4_FRAG form (never a bf16 fragment copy)
+        self.desc_wdt_rows = self.desc_wdt | (L.VV_WQ_FRAG4 if self.mxfp4_row_batch else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
         # the fragment-major copies (ensure_frag) live here: one dict object shared by every fork, as the ctypes layer arrays they are
         # written into are, so they are built once per process whichever fork asks first
-        self._frag_state: Dict[str, object] = {"done": False, "tensors": []}
+        # mxfp4_*: the VRAM record of the VV_MXFP4_FRAG copies - weights copied, bytes they take (0.5 + 1 / 32 = 0.53125 B per weight)
+        self._frag_state: Dict[str, object] = {"done": False, "tensors": [], "mxfp4_weights": 0, "mxfp4_bytes": 0}
         self._sd = sd
         self.state_tensors: Dict[str, List[torch.Tensor]] = {"acoustic_dec": [], "semantic_enc": []}
         # every streaming-state tensor (conv left contexts, mixer histories) is a 256-byte aligned view into ONE arena, so the
@@ -401,18 +415,57 @@ class DeviceWeights:
             return None
         return q.view(n // 16, 16, k // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
 
+    @staticmethod
+    def frag_major_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> Optional[torch.Tensor]:
+        """(e2m1 codes uint8 [N, K], E8M0 scale bytes uint8 [N, K / 32]) -> the VV_MXFP4_FRAG form (include/vv_hip.h) as ONE uint8 tensor: the
+        codes [N / 16][K / 128][64 lanes][16 B] - nibble i of dword h of lane 16 c + n of 128-wide step J of row group g is code
+        (16 g + n, 128 J + 32 h + 8 c + i) - then, at byte offset N K / 2, the scale bytes [N / 16][K / 128][16 rows][4 B] - byte h of the dword
+        of (g, J, n) is the byte of block 4 J + h of row 16 g + n.  None when N % 16 or K % 128."""
+        n, k = codes.shape
+        if n % 16 or k % 128 or codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or tuple(scales.shape) != (n, k // MXFP4_BLOCK):
+            return None
+        c = codes.view(n // 16, 16, k // 128, 4, 4, 4, 2).permute(0, 2, 4, 1, 3, 5, 6)       # [g, n, J, h, c, byte, nibble] -> [g, J, c, n, h, byte, nibble]
+        packed = (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
+        sb = scales.view(n // 16, 16, k // 128, 4).permute(0, 2, 1, 3).contiguous().view(-1)  # [g, J, n, h]
+        return torch.cat([packed, sb])
+
+    @staticmethod
+    def unfrag_mxfp4(f: torch.Tensor, n: int, k: int):
+        """Inverse of frag_major_mxfp4: (codes uint8 [N, K], scale bytes uint8 [N, K / 32])."""
+        b = f[: n * k // 2].view(n // 16, k // 128, 4, 16, 4, 4)                              # [g, J, c, n, h, byte]
+        c = torch.stack([b & 15, b >> 4], dim=-1)                                             # ... nibble
+        codes = c.permute(0, 3, 1, 4, 2, 5, 6).reshape(n, k).contiguous()
+        scales = f[n * k // 2:].view(n // 16, k // 128, 16, 4).permute(0, 2, 1, 3).reshape(n, k // MXFP4_BLOCK).contiguous()
+        return codes, scales
+
     def ensure_frag(self) -> None:
         """Fragment-major copies of the LLM's and the diffusion head's per-frame matrices for the row-batched decode step (rowbatch.py): built
         once per process (for this weight set and all its forks), on first use, next to the row-major matrices (which the prefill GEMMs and the
         1..4-row GEMVs keep using).  bf16: copies of the bf16 matrices, +2.9 GB at 1.5B.  weight_quant="fp8": copies of the e4m3 codes of the
         matrices' fp8 companions instead (+1.45 GB at 1.5B) - a layer's f_* then points at fp8 codes (the vv_llm_layer rule); a matrix whose
-        shape the fp8 form cannot take (N % 16, K % 64) gets no copy and keeps the row-major fallback."""
+        shape the fp8 form cannot take (N % 16, K % 64) gets no copy and keeps the row-major fallback.  weight_quant="mxfp4" with
+        mxfp4_row_batch: the VV_MXFP4_FRAG form of the MXFP4 companions (frag_major_mxfp4: +0.53 B per copied weight, recorded in
+        _frag_state["mxfp4_weights"] / ["mxfp4_bytes"] and counted by nbytes()), never a bf16 copy: a matrix without a companion or with
+        N % 16 / K % 128 keeps f_* = NULL and the row-major bf16 fallback, and so does the head's gate / up pair beyond K = 2048 (MXFP4_ROWS_MOD_K:
+        it is called with the adaLN prologue, which the MX rows kernel serves on whole rows only - a copy would never be read)."""
         st = self._frag_state
         if st["done"] or self.wdtype != torch.bfloat16:
             return
         by_ptr = {t.data_ptr(): t for t in self._keep if isinstance(t, torch.Tensor)}
 
         def frag_of(p, w8, n, k):
+            if self.mxfp4_row_batch:            # MXFP4 companion: its codes and scale bytes, re-laid (the companion's own layout is pack_mxfp4's)
+                packed, sb = by_ptr.get(int(w8.q or 0)), by_ptr.get(int(w8.scale or 0))
+                if packed is None or sb is None or k % MXFP4_BLOCK:
+                    return None
+                f = self.frag_major_mxfp4(*unpack_mxfp4(packed, sb, n, k))
+                if f is None:
+                    return None
+                f = self._aligned(f)
+                st["tensors"].append(f)
+                st["mxfp4_weights"] += n * k
+                st["mxfp4_bytes"] += f.numel()
+                return f.data_ptr()
             if w8.q and self.quant == "fp8":    # fp8 companion: the copy is of its codes, or none (NF4: the bf16 effective matrix)
                 t, fm = by_ptr.get(int(w8.q)), self.frag_major_fp8
             else:
@@ -437,8 +490,11 @@ class DeviceWeights:
             lay.f_down = frag_of(lay.wdown, lay.q_down, cfg.hidden, cfg.inter)
         for l in range(cfg.head_layers):
             lay = self.head.layer[l]
-            lay.f_gate = frag_of(lay.wgate, lay.q_gate, cfg.head_ffn, cfg.head_hidden)
-            lay.f_up = frag_of(lay.wup, lay.q_up, cfg.head_ffn, cfg.head_hidden)
+            if self.mxfp4_row_batch and cfg.head_hidden > MXFP4_ROWS_MOD_K:     # no MX rows route takes the modulated pair at this K: no copy
+                lay.f_gate = lay.f_up = None
+            else:
+                lay.f_gate = frag_of(lay.wgate, lay.q_gate, cfg.head_ffn, cfg.head_hidden)
+                lay.f_up = frag_of(lay.wup, lay.q_up, cfg.head_ffn, cfg.head_hidden)
             lay.f_down = frag_of(lay.wdown, lay.q_down, cfg.head_hidden, cfg.head_ffn)
         st["done"] = True
 
@@ -482,7 +538,7 @@ class DeviceWeights:
         inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, cfg.head_dim, 2, dtype=torch.float) / cfg.head_dim))
         self.inv_freq = self._vec(inv_freq)
         m = L.Llm()
-        m.wdt, m.hidden, m.inter, m.layers = self.desc_wdt, cfg.hidden, cfg.inter, cfg.layers
+        m.wdt, m.hidden, m.inter, m.layers = self.desc_wdt_rows, cfg.hidden, cfg.inter, cfg.layers
         m.heads, m.kv_heads, m.head_dim, m.rms_eps = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.rms_eps
         m.inv_freq = L.ptr(self.inv_freq)
         m.final_norm = L.ptr(self._vec(sd[p + "norm.weight"]))
@@ -506,7 +562,7 @@ class DeviceWeights:
                 setattr(lay, qf, w8)
             lay.adaln = L.ptr(self._mat(self._w(q + "adaLN_modulation.1.weight")))
         h = L.Head()
-        h.wdt, h.D, h.ffn, h.layers, h.latent, h.cond_dim = self.desc_wdt, cfg.head_hidden, cfg.head_ffn, cfg.head_layers, cfg.latent, cfg.hidden
+        h.wdt, h.D, h.ffn, h.layers, h.latent, h.cond_dim = self.desc_wdt_rows, cfg.head_hidden, cfg.head_ffn, cfg.head_layers, cfg.latent, cfg.hidden
         h.eps = cfg.head_eps
         h.noisy_proj = L.ptr(self._mat(self._w(p + "noisy_images_proj.weight")))
         h.cond_proj = L.ptr(self._mat(self._w(p + "cond_proj.weight")))
