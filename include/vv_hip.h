@@ -351,6 +351,28 @@ int vv_llm_tail_batch_sample(const vv_llm* m, const float* h, int64_t ldh, int B
 int vv_sample_ids(const float* logits, int n, const int* ids, const vv_sampler* sampler, const float* q, int* token_out, const int* forced_token,
                   vv_stream_t stream);
 
+/* Seeded token draws: per-dialogue warpers and draws that are formed on the device, so that one captured step serves dialogues with different
+ * samplers - greedy ones included - and a dialogue's tokens are a function of (its seed, the position, its own logits) alone.
+ * The draw q[i], i < nv <= 8, of the dialogue with the 64-bit `seed` at draw index p = the position of the token whose hidden state gives the
+ * logits: Philox4x32-10 as in vv_noise_normal with key = (seed & 0xffffffff, seed >> 32) and counter = (i / 4, (uint32) p, 0, 1) - the fourth
+ * word is 1 where the noise has 0, so one seed may serve both -, x = output word i % 4, u = (float) x * 2^-32 + 2^-33 in (0, 1], q = -logf(u),
+ * and the smallest positive normal float where that is 0 (u == 1).  The choice itself is steps 1-5 above.
+ * vv_token_draws: q[b * ldq + i] = the draw of (seeds[b], pos[b * ld_pos] + pos_bias), i < nv; columns nv .. ldq are not written.  seeds, pos
+ * are device arrays.  VV_E_ARG, nothing launched: NULL q / seeds / pos, B <= 0, nv outside 1..8, ldq < nv, ld_pos < 0. */
+int vv_token_draws(float* q, int64_t ldq, int B, int nv, const uint64_t* seeds, const int* pos, int64_t ld_pos, int pos_bias, vv_stream_t stream);
+/* vv_llm_tail_sample / vv_llm_tail_batch_sample with samplers[1] / samplers[B] and seeds[1] / seeds[B] in DEVICE memory in place of the by-value
+ * sampler and q: block b reads its own row and seed and forms q from (seeds[b], lens[2 b] as it stands at entry) as vv_token_draws does, bit for
+ * bit.  A row with temperature <= 0 is greedy: the argmax of vv_llm_tail (first maximum, smallest id on ties).  *forced_token >= 0 still wins,
+ * active == 0 still keeps the positions; out, logits_out, lens and frame_counter are those of vv_llm_tail(_batch) with the chosen token forced.
+ * Nothing of the draw is a launch argument: a captured launch serves whatever the arrays hold when it runs.  The caller validates the rows
+ * (temperature >= 0, 0 < top_p <= 1); any other row is still memory-safe.  VV_E_ARG, nothing launched: NULL lens / samplers / seeds, nv > 8. */
+int vv_llm_tail_sample_rows(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                            float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
+                            const vv_sampler* samplers, const uint64_t* seeds, vv_stream_t stream);
+int vv_llm_tail_batch_sample_rows(const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                                  float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                                  int* frame_counter, const int* active, const vv_sampler* samplers, const uint64_t* seeds, vv_stream_t stream);
+
 typedef struct vv_head_layer {
   const float* norm_w;
   const void* wgate;  /* [ffn, D] */

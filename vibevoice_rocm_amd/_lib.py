@@ -161,6 +161,9 @@ PROTOTYPES = {
     "vv_llm_tail_sample": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(Sampler), vp, vp]),
     "vv_llm_tail_batch_sample": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(Sampler), vp, vp]),
     "vv_sample_ids": (C.c_int, [vp, C.c_int, vp, C.POINTER(Sampler), vp, vp, vp, vp]),
+    "vv_token_draws": (C.c_int, [vp, i64, C.c_int, C.c_int, vp, vp, i64, C.c_int, vp]),
+    "vv_llm_tail_sample_rows": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "vv_llm_tail_batch_sample_rows": (C.c_int, [C.POINTER(Llm), vp, i64, C.c_int, vp, i64, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "vv_head_ws_bytes": (C.c_size_t, [C.POINTER(Head), C.c_int]),
     "vv_head_ws_bytes_batch": (C.c_size_t, [C.POINTER(Head), C.c_int, C.c_int]),
     "vv_head_sample_batch": (C.c_int, [C.POINTER(Head), vp, i64, vp, i64, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, i64, C.c_int, vp, vp]),

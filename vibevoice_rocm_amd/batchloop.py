@@ -22,6 +22,10 @@ do_sample on the device (BatchCall.sampler): the driver is told the warpers once
 first_tokens / decode get `q=` {dialogue: its exponential draws [nv]} for the live dialogues without a forced token; the token comes back
 like a greedy one.
 
+Seeded token draws (BatchCall.token_sampling): the driver is told every dialogue's own warpers and 64-bit token seed once
+(`set_token_sampling(samplers, seeds)`, after begin; a greedy dialogue's row is (0, 0, 1)) and draws each token on the device from (the
+dialogue's seed, the position, its logits): sample_fn is None, no `q` is passed and the loop makes no draw of its own.
+
 Diffusion noise on the device (BatchCall.noise_seeds): the driver is told every dialogue's seed once (`set_noise_seeds(seeds)`, after begin) and
 draws a frame's noise itself from (seed, frame index); `eligible` and the rows of `speech` then carry `(frame index, None)` in place of the
 noise rows, every dialogue in its steady state may be speculated, and the loop makes no draw of its own.
@@ -62,6 +66,7 @@ class BatchCall:
     verbose: bool = False
     sample_fn: Optional[Callable] = None
     sampler: Optional[tuple] = None       # do_sample on the device: the warpers (temperature, top_k, top_p); sample_fn is None then
+    token_sampling: Optional[tuple] = None    # seeded token draws: ([(temperature, top_k, top_p)] * B, [64-bit seed] * B); sampler / sample_fn are None then
     noise_seeds: Optional[List[int]] = None   # diffusion noise on the device: one 64-bit seed per dialogue; noise / sde_noise are None then
     speculate: bool = True                # frames may be launched before their token is known (never with sample_fn)
     return_speech: bool = True
@@ -77,6 +82,21 @@ def valid_token_ids(special: dict) -> List[int]:
 def sampler_params(gen_cfg: dict) -> tuple:
     """(temperature, top_k, top_p) as modeling._make_sampler reads them from a generation_config dict"""
     return (float(gen_cfg.get("temperature", 1.0) or 1.0), int(gen_cfg.get("top_k", 0) or 0), float(gen_cfg.get("top_p", 1.0) or 1.0))
+
+
+GREEDY_ROW = (0.0, 0, 1.0)      # the sampler row of a dialogue that takes the argmax (seeded token draws)
+
+
+def sampler_row(gen_cfg: Optional[dict]) -> tuple:
+    """The vv_sampler row of one dialogue's generation_config under seeded token draws: GREEDY_ROW without do_sample, else its warpers.
+    ValueError for warpers outside the kernels' contract (temperature > 0 when sampling, 0 < top_p <= 1)."""
+    g = dict(gen_cfg or {})
+    if not g.get("do_sample", False):
+        return GREEDY_ROW
+    t, k, p = sampler_params(g)
+    if not (0.0 < t < float("inf")) or not (0.0 < p <= 1.0):
+        raise ValueError(f"generation_config: temperature={t!r} (> 0) / top_p={p!r} (0 < top_p <= 1)")
+    return (t, max(k, 0), p)
 
 
 def draw_q(nv: int) -> torch.Tensor:
@@ -186,6 +206,13 @@ def run(driver, input_ids: torch.Tensor, attention_mask: torch.Tensor, speech_in
         if sample_fn is not None:
             raise ValueError("BatchCall: sampler (device) and sample_fn (host) exclude each other")
         driver.set_sampler(*call.sampler)
+    if call.token_sampling is not None:
+        if sample_fn is not None or call.sampler is not None:
+            raise ValueError("BatchCall: token_sampling (seeded draws on the device) excludes sampler and sample_fn")
+        rows_, seeds_ = call.token_sampling
+        if len(rows_) != B or len(seeds_) != B:
+            raise ValueError(f"BatchCall: token_sampling has {len(rows_)} sampler rows and {len(seeds_)} seeds for {B} dialogues")
+        driver.set_token_sampling([tuple(r) for r in rows_], [int(s_) for s_ in seeds_])
     dn = call.noise_seeds is not None
     if dn:
         if noise is not None or sde_noise is not None:
@@ -318,6 +345,8 @@ class SessionRequest:
     noise: Optional[torch.Tensor] = None          # [F, latent] (host-noise sessions)
     sde_noise: Optional[torch.Tensor] = None      # [F, n_steps, latent]
     noise_seed: Optional[int] = None              # device-noise sessions; None: drawn from the CPU generator at submit
+    sampler: Optional[tuple] = None               # seeded-token sessions: this request's (temperature, top_k, top_p), GREEDY_ROW = greedy; None: the session's
+    token_seed: Optional[int] = None              # seeded-token sessions; None: drawn from the CPU generator at submit, after the noise seed
     audio_streamer: object = None                 # a batch-of-one streamer of this request's own
     stop_check_fn: Optional[Callable[[], bool]] = None
     in_dev: object = "cpu"
@@ -356,7 +385,7 @@ class Session:
     turn switches, the negative commit, speculation and rollback are `run`'s.
 
     The driver is `run`'s (module docstring) without `begin`, opened by the caller, plus
-      admit(b, request)          slot b starts afresh for this request: its positions, conv state, guidance scale, noise seed and prompt embeddings
+      admit(b, request)          slot b starts afresh for this request: its positions, conv state, guidance scale, noise seed, sampler row / token seed and prompt embeddings
       synchronize(b)             everything enqueued for slot b has completed (its samples may be read)
     and `decode(live, ...)` leaves the slots outside `live` where they are.  One step(): (1) queued requests are admitted in FIFO order while
     a slot is free, lowest free slot first - admit, first_tokens([b]) (the prefill and the first token), that token handled - synchronously;
@@ -366,16 +395,26 @@ class Session:
     (seed, frame) - the dialogue sounds the same whoever shares the session; noise= / sde_noise= are refused.  Without it noise is injected per
     request or drawn on the host as `run` draws it, and drawn noise then depends on who else diffuses in the step (not reproducible per
     dialogue).  Tokens: greedy, forced per request, or sampled with the session's one sampler (`sample_fn` on the host or `sampler` = the
-    device's warpers); the draws of a step are made in ascending slot order."""
+    device's warpers); the draws of a step are made in ascending slot order.  `seeded_tokens`: every request brings its own warpers
+    (`SessionRequest.sampler`, default the session's `sampler`, greedy without one) and token seed, which reach the driver through `admit`; the
+    tokens are drawn on the device from (seed, position, logits), first_tokens / decode get neither `q` nor a sample_fn and no draw is made here -
+    a dialogue's tokens are the same whoever shares the session."""
 
     def __init__(self, driver, slots: int, special: dict, pad_id: int, max_pos: int, latent: int, max_context: int, device_noise: bool = True,
-                 sample_fn=None, sampler: Optional[tuple] = None, speculate: bool = True, verbose: bool = False, on_close=None):
+                 sample_fn=None, sampler: Optional[tuple] = None, speculate: bool = True, verbose: bool = False, on_close=None,
+                 seeded_tokens: bool = False):
         if not isinstance(slots, int) or not 2 <= slots <= 16:
             raise ValueError(f"Session: slots={slots!r} (2..16)")
         if max_context is None or int(max_context) <= 0:
             raise ValueError(f"Session: max_context={max_context!r} (tokens per dialogue, required)")
         if sampler is not None and sample_fn is not None:
             raise ValueError("Session: sampler (device) and sample_fn (host) exclude each other")
+        if seeded_tokens and sample_fn is not None:
+            raise ValueError("Session: seeded_tokens draws the tokens on the device: it excludes sample_fn (the host sampler)")
+        self.seeded_tokens = bool(seeded_tokens)
+        self.default_row = (tuple(sampler) if sampler is not None else GREEDY_ROW) if self.seeded_tokens else None
+        if self.seeded_tokens:
+            sampler = None                # no session-wide warpers on the driver, no q: every request's row travels with its admission
         self.driver, self.slots, self.special, self.pad_id, self.max_pos, self.latent = driver, slots, special, int(pad_id), int(max_pos), int(latent)
         self.max_context, self.device_noise, self.sample_fn, self.sampler, self.verbose = int(max_context), bool(device_noise), sample_fn, sampler, verbose
         self.speculate = bool(speculate) and sample_fn is None
@@ -402,6 +441,8 @@ class Session:
                 raise ValueError("this session draws the diffusion noise on the device (device_noise=True): noise= / sde_noise= cannot be injected")
         elif req.noise_seed is not None:
             raise ValueError("noise_seed= seeds the device-side noise: it needs a session opened with device_noise=True")
+        if not self.seeded_tokens and (req.sampler is not None or req.token_seed is not None):
+            raise ValueError("generation_config= / token_seed= per request need a session opened with seeded_tokens=True (this session has one sampler)")
         L0 = int(req.prompt.shape[0])
         if L0 < 1:
             raise ValueError("Session.submit(): empty prompt")
@@ -416,6 +457,11 @@ class Session:
         self.validate(req)
         if self.device_noise and req.noise_seed is None:
             req.noise_seed = int(torch.randint(0, 2 ** 62, (1,)))
+        if self.seeded_tokens:
+            if req.sampler is None:
+                req.sampler = self.default_row
+            if req.token_seed is None:
+                req.token_seed = int(torch.randint(0, 2 ** 62, (1,)))
         h = SessionHandle(req)
         self.queue.append(h)
         return h

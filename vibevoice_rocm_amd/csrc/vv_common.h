@@ -176,6 +176,49 @@ __device__ __forceinline__ float vv_gelu_as(float v) {
   return 0.5f * v * (1.0f + copysignf(erf_abs, x));
 }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), the counter-based generator of the device-side draws:
+// the diffusion noise (vv_noise.hip: counter (quad, frame, kind, 0)) and the token draws (vv_token_draw below: counter (quad, position, 0, 1)).
+struct philox4 { unsigned x, y, z, w; };
+
+__host__ __device__ __forceinline__ unsigned mulhi32(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
+
+// Philox4x32 with 10 rounds; the key is bumped by the Weyl constants before every round but the first
+__host__ __device__ __forceinline__ philox4 philox4x32_10(philox4 c, unsigned k0, unsigned k1) {
+  constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = mulhi32(M0, c.x), lo0 = M0 * c.x, hi1 = mulhi32(M1, c.z), lo1 = M1 * c.z;
+    c = philox4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
+    k0 += W0;
+    k1 += W1;
+  }
+  return c;
+}
+
+__device__ __forceinline__ float noise_uniform(unsigned x) { return (float)x * 0x1p-32f + 0x1p-33f; }
+
+// Seeded token draws (vv_hip.h, vv_token_draws): the four exponential draws of quad j (elements 4 j .. 4 j + 3) of the dialogue with `seed` at
+// draw index p - the position of the token whose hidden state gives the logits.  Counter (j, p, 0, 1): the fourth word is 1 where the noise
+// has 0, so one seed used for both never meets a Philox block twice.  q = -logf(u) with the noise's uniform u in (0, 1]; u == 1 gives 0, which
+// becomes the smallest positive normal float: the choice compares p / q.
+__device__ __forceinline__ float vv_token_draw_exp(unsigned x) {
+  const float q = -logf(noise_uniform(x));
+  return q > 0.f ? q : 0x1p-126f;
+}
+__device__ __forceinline__ float4 vv_token_draw(uint64_t seed, unsigned p, unsigned j) {
+  const philox4 x = philox4x32_10(philox4{j, p, 0u, 1u}, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32));
+  return make_float4(vv_token_draw_exp(x.x), vv_token_draw_exp(x.y), vv_token_draw_exp(x.z), vv_token_draw_exp(x.w));
+}
+// q[0 .. nv) of (seed, p), q[nv .. 8) = 1 (vv_sample_choice's masked entries); the second Philox block only when nv reaches it
+__device__ __forceinline__ void vv_token_draws8(uint64_t seed, unsigned p, int nv, float (&q)[8]) {
+  const float4 a = vv_token_draw(seed, p, 0u);
+  float4 b = make_float4(1.f, 1.f, 1.f, 1.f);
+  if (nv > 4) b = vv_token_draw(seed, p, 1u);
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) q[i] = i < nv ? v[i] : 1.f;
+}
+
 // do_sample token choice over nv <= 8 constrained logits (vv_hip.h, vv_sampler: the arithmetic and its order): index of the chosen id.
 // One thread; every array index is a compile-time constant after unrolling, so the eight values stay in registers (no scratch): ranks by
 // counting instead of a sort - rank_i = #{j : z_j < z_i, or z_j == z_i and j < i} is i's place in the ascending stable sort - and the walk

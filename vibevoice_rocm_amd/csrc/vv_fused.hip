@@ -120,179 +120,59 @@ template <int KU> void launch_boundary(const BoundaryArgs& a, int B, hipStream_t
 // ---------------------------------------------------------------------------------------------------------------
 // LLM step tail
 // ---------------------------------------------------------------------------------------------------------------
-// SAMPLE: the token is drawn (vv_sampler, vv_hip.h: warpers + argmax p / q over the host's exponential draws q) instead of the argmax; the
-// argmax instantiation is the code it was.
+// MODE TAIL_SAMPLE: the token is drawn (vv_sampler, vv_hip.h: warpers + argmax p / q over the host's exponential draws q) instead of the argmax; the
+// argmax instantiation (TAIL_ARGMAX) is the code it was.  TAIL_ROWS: the warpers are the dialogue's row of a device array and q is formed here
+// from (its seed, lens[0] at entry) by vv_token_draw - nothing of the draw is a launch argument; a row with temperature <= 0 takes the argmax.
+// The bodies are shared text (vv_llm_tail.inc, vv_llm_tail_fast.inc); the kernels that existed keep their signatures and compile to the code they had.
+enum { TAIL_ARGMAX = 0, TAIL_SAMPLE = 1, TAIL_ROWS = 2 };
+
 template <typename WT, bool SAMPLE>
 __global__ __launch_bounds__(256) void llm_tail_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out, int64_t ldo,
                                                        const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out, const int* forced,
                                                        int* lens, int tok_start, int tok_diff, int* frame_ctr, const vv_sampler smp, const float* q) {
-  extern __shared__ float hn0[];          // [H] normalised row 0 (the positive branch: the only row logits are taken from)
-  __shared__ float red[4];
-  __shared__ float lg[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int r = 0; r < R; ++r) {
-    const float* xr = h + (int64_t)r * ldh;
-    float s = 0.f;
-    for (int c = tid; c < H; c += 256) { const float v = xr[c]; s = fmaf(v, v, s); }
-    s = vv_wave_sum(s);
-    __syncthreads();
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    const float rstd = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)H + eps);
-    for (int c = tid; c < H; c += 256) {
-      const float v = xr[c] * rstd * norm_w[c];
-      out[(int64_t)r * ldo + c] = v;
-      if (r == 0) hn0[c] = v;
-    }
-  }
-  __syncthreads();
-  for (int i = wave; i < nv; i += 4) {                // one wave per constrained vocabulary row
-    const WT* wr = w_valid + (int64_t)i * H;
-    float s = 0.f;
-    for (int c = lane; c < H; c += 64) s = fmaf(ldw(wr + c), hn0[c], s);
-    s = vv_wave_sum(s);
-    if (lane == 0) { lg[i] = s; logits_out[i] = s; }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int best = 0;
-    if constexpr (SAMPLE) {
-      float l8[8], q8[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { l8[i] = i < nv ? lg[i] : 0.f; q8[i] = i < nv ? q[i] : 1.f; }
-      best = vv_sample_choice(l8, nv, smp, q8);
-    } else {
-    for (int i = 1; i < nv; ++i)
-      if (lg[i] > lg[best] || (lg[i] == lg[best] && ids[i] < ids[best])) best = i;     // first maximum in ascending id order, as torch.argmax over the masked vocabulary
-    }
-    const int f = forced ? *forced : -1;
-    const int t = f >= 0 ? f : ids[best];
-    *token_out = t;
-    if (lens) {
-      lens[0] += 1;
-      if (tok_start < 0) { lens[1] += 1; if (t == tok_diff && frame_ctr) *frame_ctr += 1; }      // refresh_negative=False: the negative row consumes every token
-      else if (t == tok_start) lens[1] = 0;
-      else if (t == tok_diff) { lens[1] += 1; if (frame_ctr) *frame_ctr += 1; }
-    }
-  }
+  constexpr int MODE = SAMPLE ? TAIL_SAMPLE : TAIL_ARGMAX;
+  const vv_sampler* samplers = nullptr;
+  const uint64_t* seeds = nullptr;
+#include "vv_llm_tail.inc"
+}
+
+template <typename WT>
+__global__ __launch_bounds__(256) void llm_tail_rows_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out, int64_t ldo,
+                                                            const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out, const int* forced,
+                                                            int* lens, int tok_start, int tok_diff, int* frame_ctr, const vv_sampler* __restrict__ samplers,
+                                                            const uint64_t* __restrict__ seeds) {
+  constexpr int MODE = TAIL_ROWS;
+  const vv_sampler smp = {1.f, 0, 1.f};
+  const float* q = nullptr;
+#include "vv_llm_tail.inc"
 }
 
 // The decode shape (R <= 2 rows, <= 8 constrained ids, H <= 4096): every operand - the rows, the norm weight, this thread's 4-column
 // slices of the constrained vocabulary rows, ids, forced token - is requested in one burst, then two barriers: row statistics,
 // logit partials.  The general kernel above walks rows and vocabulary rows one after the other (5-6 dependent trips, 21 us).
 // SAMPLE as above; the draws q ([8] per block) are requested by thread 0 with the other operands, the choice runs in thread 0 alone behind the
-// last barrier, where the argmax ran.
+// last barrier, where the argmax ran.  TAIL_ROWS: block b's sampler row, seed and position are read-only loads at the head of the burst, ahead of
+// the weight rows; thread 0 turns (seed, position) into q - two Philox blocks and nv logf - while the weight rows are in flight.
 template <typename WT, bool SAMPLE>
 __global__ __launch_bounds__(256) void llm_tail_fast_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out, int64_t ldo,
                                                             const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out, const int* forced,
                                                             int* lens, int tok_start, int tok_diff, int* frame_ctr, const int* active,
                                                             const vv_sampler smp, const float* q) {
-  {   // dialogues of a row-batched step: block b owns rows 2 b, 2 b + 1 and the b-th token / forced token / counters
-    const int b = blockIdx.x;
-    h += (int64_t)2 * b * ldh; out += (int64_t)2 * b * ldo; logits_out += 8 * b; token_out += b;
-    if (forced) forced += b;
-    if (lens) lens += 2 * b;
-    if (frame_ctr) frame_ctr += b;
-    if (active) active += b;
-    if constexpr (SAMPLE) q += 8 * b;
-  }
-  constexpr int NC = 4, NV = 8;                    // column chunks (of 4) per thread per row, constrained ids
-  __shared__ float red[4][2];
-  __shared__ float lgp[4][NV];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int H4 = H >> 2;
-  float4 xv[2][NC], nw[NC], wv[NV][NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int ch = tid + 256 * c;
-    const int k = ch < H4 ? 4 * ch : 0;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) xv[r][c] = *reinterpret_cast<const float4*>(h + (int64_t)(r < R ? r : 0) * ldh + k);
-    nw[c] = *reinterpret_cast<const float4*>(norm_w + k);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const WT* wr = w_valid + (int64_t)(i < nv ? i : 0) * H + k;
-      if constexpr (sizeof(WT) == 2) {
-        const uint2 p = *reinterpret_cast<const uint2*>(wr);
-        wv[i][c] = make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16), __uint_as_float(p.y & 0xffff0000u));
-      } else {
-        wv[i][c] = *reinterpret_cast<const float4*>(wr);
-      }
-    }
-  }
-  int idv[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) idv[i] = ids[i < nv ? i : 0];
-  const int fv = forced ? *forced : -1;
-  const int live = active ? *active : 1;
-  float qv[NV];
-  if constexpr (SAMPLE) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) qv[i] = (tid == 0 && i < nv) ? q[i] : 1.f;
-  }
-  const int l0 = lens ? lens[0] : 0, l1 = lens ? lens[1] : 0, fc = frame_ctr ? *frame_ctr : 0;
-  float ss[2] = {0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const bool cv = tid + 256 * c < H4;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float4 v = xv[r][c];
-      ss[r] += cv ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
-    }
-  }
-  ss[0] = vv_wave_sum(ss[0]); ss[1] = vv_wave_sum(ss[1]);
-  if (lane == 0) { red[wave][0] = ss[0]; red[wave][1] = ss[1]; }
-  __syncthreads();
-  float lg[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) lg[i] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    if (r >= R) break;
-    const float rstd = rsqrtf(((red[0][r] + red[1][r]) + (red[2][r] + red[3][r])) / (float)H + eps);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int ch = tid + 256 * c;
-      if (ch >= H4) continue;
-      const float4 v = make_float4(xv[r][c].x * rstd * nw[c].x, xv[r][c].y * rstd * nw[c].y, xv[r][c].z * rstd * nw[c].z, xv[r][c].w * rstd * nw[c].w);
-      *reinterpret_cast<float4*>(out + (int64_t)r * ldo + 4 * ch) = v;
-      if (r == 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) lg[i] += (wv[i][c].x * v.x + wv[i][c].y * v.y) + (wv[i][c].z * v.z + wv[i][c].w * v.w);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float t = vv_wave_sum(lg[i]);
-    if (lane == 0) lgp[wave][i] = t;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float l[NV];
-    int best = 0;
-    for (int i = 0; i < nv; ++i) {
-      l[i] = (lgp[0][i] + lgp[1][i]) + (lgp[2][i] + lgp[3][i]);
-      logits_out[i] = l[i];
-      if (!SAMPLE && i && (l[i] > l[best] || (l[i] == l[best] && idv[i] < idv[best]))) best = i;
-    }
-    if constexpr (SAMPLE) {
-      if (fv < 0) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) if (i >= nv) l[i] = 0.f;
-        best = vv_sample_choice(l, nv, smp, qv);
-      }
-    }
-    const int t = fv >= 0 ? fv : idv[best];
-    *token_out = t;
-    if (lens && live) {                              // a finished dialogue of the batch keeps its positions (its rows are computed and dropped)
-      lens[0] = l0 + 1;
-      if (tok_start < 0) { lens[1] = l1 + 1; if (t == tok_diff && frame_ctr) *frame_ctr = fc + 1; }   // refresh_negative=False: the negative row consumes every token
-      else if (t == tok_start) lens[1] = 0;
-      else if (t == tok_diff) { lens[1] = l1 + 1; if (frame_ctr) *frame_ctr = fc + 1; }
-    }
-  }
+  constexpr int MODE = SAMPLE ? TAIL_SAMPLE : TAIL_ARGMAX;
+  const vv_sampler* samplers = nullptr;
+  const uint64_t* seeds = nullptr;
+#include "vv_llm_tail_fast.inc"
+}
+
+template <typename WT>
+__global__ __launch_bounds__(256) void llm_tail_fast_rows_kernel(const float* h, int64_t ldh, int R, int H, const float* norm_w, float eps, float* out,
+                                                                 int64_t ldo, const WT* w_valid, int nv, const int* ids, float* logits_out, int* token_out,
+                                                                 const int* forced, int* lens, int tok_start, int tok_diff, int* frame_ctr, const int* active,
+                                                                 const vv_sampler* __restrict__ samplers, const uint64_t* __restrict__ seeds) {
+  constexpr int MODE = TAIL_ROWS;
+  const vv_sampler smp = {1.f, 0, 1.f};
+  const float* q = nullptr;
+#include "vv_llm_tail_fast.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -790,21 +670,31 @@ static int check_sampler(const char* name, const vv_sampler* smp, const float* q
 #define VV_TAIL_GEN(WT, SAMPLE)                                                                                                                         \
   hipLaunchKernelGGL((llm_tail_kernel<WT, SAMPLE>), dim3(1), dim3(256), lds, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const WT*)w_valid, nv, ids, \
                      logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, sv, q)
+// the _rows forms: the warpers and the seed are rows of device arrays, the draws are formed in the kernel
+#define VV_TAIL_FAST_ROWS(WT, grid, R_, act)                                                                                                             \
+  hipLaunchKernelGGL((llm_tail_fast_rows_kernel<WT>), dim3(grid), dim3(256), 0, s, h, ldh, R_, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const WT*)w_valid, nv, \
+                     ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, act, rows, seeds)
+#define VV_TAIL_GEN_ROWS(WT)                                                                                                                            \
+  hipLaunchKernelGGL((llm_tail_rows_kernel<WT>), dim3(1), dim3(256), lds, s, h, ldh, R, m->hidden, m->final_norm, m->rms_eps, out, ldo, (const WT*)w_valid, nv, ids, \
+                     logits_out, token_out, forced_token, lens, tok_start, tok_diffusion, frame_counter, rows, seeds)
 
+// smp: the sampling form with the by-value warpers and the host's draws q; rows (with seeds): the _rows form; neither: the argmax
 static int llm_tail_launch(const char* name, const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
                            float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
-                           const vv_sampler* smp, const float* q, hipStream_t s) {
+                           const vv_sampler* smp, const float* q, hipStream_t s, const vv_sampler* rows = nullptr, const uint64_t* seeds = nullptr) {
   const vv_sampler sv = smp ? *smp : vv_sampler{1.f, 0, 1.f};
   const size_t lds = (size_t)m->hidden * sizeof(float);
   auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
   if (R <= 2 && nv <= 8 && m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
       ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0 && (m->wdt == VV_F32 || m->hidden % 4 == 0)) {
-    if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, 1, R, (const int*)nullptr); else VV_TAIL_FAST(float, false, 1, R, (const int*)nullptr); }
+    if (rows) { if (m->wdt == VV_F32) VV_TAIL_FAST_ROWS(float, 1, R, (const int*)nullptr); else VV_TAIL_FAST_ROWS(bf16_t, 1, R, (const int*)nullptr); }
+    else if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, 1, R, (const int*)nullptr); else VV_TAIL_FAST(float, false, 1, R, (const int*)nullptr); }
     else { if (smp) VV_TAIL_FAST(bf16_t, true, 1, R, (const int*)nullptr); else VV_TAIL_FAST(bf16_t, false, 1, R, (const int*)nullptr); }
     VV_CHECK_LAUNCH(name);
     return 0;
   }
-  if (m->wdt == VV_F32) { if (smp) VV_TAIL_GEN(float, true); else VV_TAIL_GEN(float, false); }
+  if (rows) { if (m->wdt == VV_F32) VV_TAIL_GEN_ROWS(float); else VV_TAIL_GEN_ROWS(bf16_t); }
+  else if (m->wdt == VV_F32) { if (smp) VV_TAIL_GEN(float, true); else VV_TAIL_GEN(float, false); }
   else { if (smp) VV_TAIL_GEN(bf16_t, true); else VV_TAIL_GEN(bf16_t, false); }
   VV_CHECK_LAUNCH(name);
   return 0;
@@ -812,19 +702,23 @@ static int llm_tail_launch(const char* name, const vv_llm* m, const float* h, in
 
 static int llm_tail_batch_launch(const char* name, const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv,
                                  const int* ids, float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
-                                 int* frame_counter, const int* active, const vv_sampler* smp, const float* q, hipStream_t s) {
+                                 int* frame_counter, const int* active, const vv_sampler* smp, const float* q, hipStream_t s,
+                                 const vv_sampler* rows = nullptr, const uint64_t* seeds = nullptr) {
   const vv_sampler sv = smp ? *smp : vv_sampler{1.f, 0, 1.f};
   auto a16 = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
   if (!(m->hidden % 4 == 0 && m->hidden <= 4096 && a16(h) && ldh % 4 == 0 && a16(out) && ldo % 4 == 0 && a16(m->final_norm) &&
         ((uintptr_t)w_valid % (m->wdt == VV_F32 ? 16 : 8)) == 0))
     return vv_set_error(VV_E_UNSUPPORTED, "%s: hidden=%d / alignment not covered", name, m->hidden);
-  if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, B, 2, active); else VV_TAIL_FAST(float, false, B, 2, active); }
+  if (rows) { if (m->wdt == VV_F32) VV_TAIL_FAST_ROWS(float, B, 2, active); else VV_TAIL_FAST_ROWS(bf16_t, B, 2, active); }
+  else if (m->wdt == VV_F32) { if (smp) VV_TAIL_FAST(float, true, B, 2, active); else VV_TAIL_FAST(float, false, B, 2, active); }
   else { if (smp) VV_TAIL_FAST(bf16_t, true, B, 2, active); else VV_TAIL_FAST(bf16_t, false, B, 2, active); }
   VV_CHECK_LAUNCH(name);
   return 0;
 }
 #undef VV_TAIL_FAST
 #undef VV_TAIL_GEN
+#undef VV_TAIL_FAST_ROWS
+#undef VV_TAIL_GEN_ROWS
 
 extern "C" int vv_llm_tail(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
                            float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
@@ -863,6 +757,29 @@ extern "C" int vv_llm_tail_batch_sample(const vv_llm* m, const float* h, int64_t
   VV_TRY(check_sampler("vv_llm_tail_batch_sample", sampler, q, nv));
   return llm_tail_batch_launch("vv_llm_tail_batch_sample", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start,
                                tok_diffusion, frame_counter, active, sampler, q, (hipStream_t)stream);
+}
+
+// The seeded forms (vv_hip.h): sampler rows and seeds on the device, the draws formed in the tail from (seed, lens[2 b] at entry).  Row contents
+// are the host's to validate; the kernel stays memory-safe on any row (a temperature that is not > 0 takes the argmax, top_k / top_p only compare).
+extern "C" int vv_llm_tail_sample_rows(const vv_llm* m, const float* h, int64_t ldh, int R, float* out, int64_t ldo, const void* w_valid, int nv, const int* ids,
+                                       float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
+                                       int* frame_counter, const vv_sampler* samplers, const uint64_t* seeds, vv_stream_t stream) {
+  if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_sample_rows: null pointer");
+  if (R <= 0 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_sample_rows: R=%d nv=%d (<= 8)", R, nv);
+  if (!lens || !samplers || !seeds) return vv_set_error(VV_E_ARG, "vv_llm_tail_sample_rows: null lens / samplers / seeds");
+  return llm_tail_launch("vv_llm_tail_sample_rows", m, h, ldh, R, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion,
+                         frame_counter, nullptr, nullptr, (hipStream_t)stream, samplers, seeds);
+}
+
+extern "C" int vv_llm_tail_batch_sample_rows(const vv_llm* m, const float* h, int64_t ldh, int B, float* out, int64_t ldo, const void* w_valid, int nv,
+                                             const int* ids, float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start,
+                                             int tok_diffusion, int* frame_counter, const int* active, const vv_sampler* samplers, const uint64_t* seeds,
+                                             vv_stream_t stream) {
+  if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: null pointer");
+  if (B <= 0 || B > 4 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: B=%d (1..4) nv=%d (<= 8)", B, nv);
+  if (!lens || !samplers || !seeds) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: null lens / samplers / seeds");
+  return llm_tail_batch_launch("vv_llm_tail_batch_sample_rows", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start,
+                               tok_diffusion, frame_counter, active, nullptr, nullptr, (hipStream_t)stream, samplers, seeds);
 }
 
 int vv_conv_ctx_batch(const vv_conv_ctx_item* items, int n, int scatter, hipStream_t s) {

@@ -1891,6 +1891,30 @@ extern "C" int vv_sample_ids(const float* logits, int n, const int* ids, const v
   return 0;
 }
 
+// the seeded token draws on their own (vv_token_draw, vv_common.h: what the _rows step tails form in place): one thread per (dialogue, quad),
+// elements >= nv of the last quad are dropped, columns nv .. ldq are not written
+__global__ __launch_bounds__(64) void token_draws_kernel(float* __restrict__ q, int64_t ldq, int nv, int quads, int total, const uint64_t* __restrict__ seeds,
+                                                         const int* __restrict__ pos, int64_t ld_pos, int pos_bias) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= total) return;
+  const int j = t % quads, b = t / quads;
+  const float4 z = vv_token_draw(seeds[b], (unsigned)(pos[(int64_t)b * ld_pos] + pos_bias), (unsigned)j);
+  float* o = q + (int64_t)b * ldq + 4 * j;
+  if (4 * j + 0 < nv) o[0] = z.x;
+  if (4 * j + 1 < nv) o[1] = z.y;
+  if (4 * j + 2 < nv) o[2] = z.z;
+  if (4 * j + 3 < nv) o[3] = z.w;
+}
+extern "C" int vv_token_draws(float* q, int64_t ldq, int B, int nv, const uint64_t* seeds, const int* pos, int64_t ld_pos, int pos_bias, vv_stream_t stream) {
+  if (!q || !seeds || !pos) return vv_set_error(VV_E_ARG, "vv_token_draws: null q, seeds or pos");
+  if (B <= 0 || B > (1 << 20) || nv <= 0 || nv > 8 || ldq < nv || ld_pos < 0)
+    return vv_set_error(VV_E_ARG, "vv_token_draws: bad shape (B %d, nv %d (1..8), ldq %lld, ld_pos %lld)", B, nv, (long long)ldq, (long long)ld_pos);
+  const int quads = (nv + 3) / 4, total = B * quads;
+  hipLaunchKernelGGL(token_draws_kernel, dim3((total + 63) / 64), dim3(64), 0, (hipStream_t)stream, q, ldq, nv, quads, total, seeds, pos, ld_pos, pos_bias);
+  VV_CHECK_LAUNCH("vv_token_draws");
+  return 0;
+}
+
 __global__ void dpm_step_kernel(const float* v, int64_t ldv, int ns, int latent, float cfg, float alpha_s, float sigma_s, float cx,
                                 float cd, float rinv, int order, float* x, float* m_prev) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

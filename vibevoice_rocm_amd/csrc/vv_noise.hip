@@ -15,25 +15,7 @@
 
 namespace {
 
-struct philox4 { unsigned x, y, z, w; };
-
-__host__ __device__ __forceinline__ unsigned mulhi32(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
-
-// Philox4x32 with 10 rounds; the key is bumped by the Weyl constants before every round but the first
-__host__ __device__ __forceinline__ philox4 philox4x32_10(philox4 c, unsigned k0, unsigned k1) {
-  constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = mulhi32(M0, c.x), lo0 = M0 * c.x, hi1 = mulhi32(M1, c.z), lo1 = M1 * c.z;
-    c = philox4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += W0;
-    k1 += W1;
-  }
-  return c;
-}
-
-__device__ __forceinline__ float noise_uniform(unsigned x) { return (float)x * 0x1p-32f + 0x1p-33f; }
-
+// philox4x32_10 and noise_uniform live in vv_common.h: the seeded token draws (vv_token_draw) share them
 // grid ceil(total / 64) x 64 threads, total = B * kinds * quads; thread t = ((b * kinds) + kind) * quads + j
 __global__ __launch_bounds__(64) void noise_normal_kernel(float* __restrict__ noise, int64_t ld_noise, float* __restrict__ sde_noise, int64_t ld_sde, int n,
                                                           int kinds, int quads, int total, const uint64_t* __restrict__ seeds, const int* __restrict__ frames) {

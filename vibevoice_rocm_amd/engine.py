@@ -46,6 +46,24 @@ def check_kv_cache_dtype(kv_cache_dtype: Optional[str], dtype: torch.dtype, head
     return True
 
 
+def write_sampler_row(host: torch.Tensor, b: int, temperature, top_k, top_p) -> tuple:
+    """One vv_sampler row {float temperature, int top_k, float top_p} of a pinned fp32 [B, 3] mirror; returns the validated row.  ValueError for a
+    row outside the kernels' contract (temperature >= 0 - 0 is greedy -, 0 < top_p <= 1)."""
+    t, k, p = float(temperature), int(top_k), float(top_p)
+    if not (t >= 0.0 and t < float("inf")) or not (0.0 < p <= 1.0):
+        raise ValueError(f"sampler row: temperature={temperature!r} (>= 0, 0 = greedy), top_p={top_p!r} (0 < top_p <= 1)")
+    host[b, 0], host[b, 2] = t, p
+    host.view(torch.int32)[b, 1] = max(k, 0)
+    return (t, max(k, 0), p)
+
+
+def write_seed_rows(host: torch.Tensor, seeds) -> None:
+    """64-bit seeds into a pinned int64 mirror, bit for bit (a seed >= 2^63 is held as its two's complement)"""
+    for b, sd in enumerate(seeds):
+        v = int(sd) & (2 ** 64 - 1)
+        host[b] = v - 2 ** 64 if v >= 2 ** 63 else v
+
+
 class Engine:
     def __init__(self, cfg: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", dtype=torch.bfloat16,
                  kv_dtype: Optional[torch.dtype] = None, use_graphs: bool = True, bf16_timestep_quirk: Optional[bool] = None,
@@ -98,6 +116,10 @@ class Engine:
             # device-side diffusion noise (vv_noise_normal): the dialogue's 64-bit seed (its bits in an int64) and the index of the frame to draw
             self.noise_seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
             self.noise_frame_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+            # seeded token draws (vv_llm_tail_sample_rows): the dialogue's vv_sampler row {temperature, top_k, top_p} and 64-bit token seed, read
+            # on the device - the warpers are no launch argument and the draws are formed there from (seed, position)
+            self.sampler_dev = torch.zeros(1, 3, **f32)
+            self.tok_seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.token_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.logits_host = torch.zeros(8, dtype=torch.float32).pin_memory()
         self.forced_host = torch.full((1,), -1, dtype=torch.int32).pin_memory()
@@ -110,6 +132,11 @@ class Engine:
         self.q_host = torch.ones(2, 8, dtype=torch.float32).pin_memory()                 # double-buffered like the noise rows
         self._q_k = 0
         self._sampler, self._sampler_key = None, None     # set_sampler
+        self.sampler_host = torch.zeros(1, 3, dtype=torch.float32).pin_memory()          # the pinned mirrors of sampler_dev / tok_seed_dev
+        self.sampler_host[0, 2] = 1.0                                                    # greedy: (0, 0, 1)
+        self.tok_seed_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._sampler_rows = [(0.0, 0, 1.0)]              # set_sampler_row: what sampler_dev holds, for the first token's vv_sample_ids
+        self._seeded = False                              # set_token_seeds: this sequence draws its tokens from (token seed, position)
         self._tok_event = torch.cuda.Event()
         # streaming delivery: a frame's 3200 samples go device -> pinned ring asynchronously, an event per
         # slot says when the host may hand them to the AudioStreamer; generate() never blocks the launch queue on a D2H copy
@@ -223,6 +250,7 @@ class Engine:
             self.lens.zero_()
             self.frame_ctr.zero_()
             self.reset_speech_caches()
+        self._seeded = False
 
     def _ensure_kv(self, s_max: int):
         """The KV cache (rows {positive, negative}) with room for s_max tokens; call it under `torch.cuda.stream(self.stream)`."""
@@ -409,6 +437,18 @@ class Engine:
                                              self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(),
                                              C.byref(smp), self.q_dev.data_ptr(), self.sp), "vv_llm_tail_sample")
 
+    def _seq_Ar(self, tok_start, tok_diff):
+        """_seq_A with the seeded tail (vv_llm_tail_sample_rows): the warpers and the token seed are read from sampler_dev / tok_seed_dev and
+        the draws formed in the kernel from (seed, lens[0]), so the graph's key holds no warpers and nothing is uploaded per step; a greedy
+        row (temperature 0) takes the argmax in the same graph."""
+        nv = len(self.valid_ids)
+        self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(self.kv), self.x2.data_ptr(), self.cfg.hidden, 2,
+                                         self.lens.data_ptr(), None, None, 0, self._llm_ws.data_ptr(), self.sp), "vv_llm_forward")
+        self._ck(self.lib.vv_llm_tail_sample_rows(C.byref(self.w.llm), self._llm_ws.data_ptr(), self.cfg.hidden, 2, self.hidden2.data_ptr(), self.cfg.hidden,
+                                                  self._w_valid.data_ptr(), nv, self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(),
+                                                  self.forced_dev.data_ptr(), self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(),
+                                                  self.sampler_dev.data_ptr(), self.tok_seed_dev.data_ptr(), self.sp), "vv_llm_tail_sample_rows")
+
     def _seq_A1(self):
         self._ck(self.lib.vv_llm_forward(C.byref(self.w.llm), C.byref(self.kv), self.x2.data_ptr(), self.cfg.hidden, 2,
                                          self.lens.data_ptr(), None, self.hidden2.data_ptr(), self.cfg.hidden,
@@ -529,6 +569,21 @@ class Engine:
         self._sampler_key = (float(temperature), int(top_k), float(top_p))
         self._sampler = L.Sampler(*self._sampler_key)
 
+    def set_sampler_row(self, b: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0):
+        """Seeded token draws: the dialogue's own warpers, kept on the device (b is 0: an Engine runs one dialogue).  Greedy = (0, 0, 1).  The
+        row is validated here - the kernel only promises memory safety for anything else."""
+        self._sampler_rows[b] = write_sampler_row(self.sampler_host, b, temperature, top_k, top_p)
+        with torch.cuda.stream(self.stream):
+            self.sampler_dev.copy_(self.sampler_host, non_blocking=True)
+
+    def set_token_seeds(self, seeds):
+        """Seeded token draws: the 64-bit token seed of the dialogue this engine runs next, once per sequence (after begin_sequence).  Every
+        step then draws its token on the device from (seed, position, its own logits): graph "Ar", no q, no upload."""
+        write_seed_rows(self.tok_seed_host, seeds)
+        with torch.cuda.stream(self.stream):
+            self.tok_seed_dev.copy_(self.tok_seed_host, non_blocking=True)
+        self._seeded = True
+
     def _upload_q(self, q: torch.Tensor):
         """The step's exponential draws (CPU fp32 [nv]): pinned staging row + async copy on the engine stream, like _upload_noise."""
         if self._sampler is None:
@@ -539,8 +594,10 @@ class Engine:
         self.q_dev.copy_(qh, non_blocking=True)
 
     def _phase_A(self, tok_start: int, tok_diff: int, q: Optional[torch.Tensor]):
-        """graph A; with draws `q` its sampling variant"""
-        if q is None:
+        """graph A; with draws `q` its sampling variant; after set_token_seeds the seeded one, whose key holds no warpers"""
+        if self._seeded:
+            self._run("Ar", self._seq_Ar, int(tok_start), int(tok_diff))
+        elif q is None:
             self._run("A", self._seq_A, int(tok_start), int(tok_diff))
         else:
             self._upload_q(q)
@@ -575,7 +632,24 @@ class Engine:
         return int(self.token_host[0])
 
     def first_token(self, tok_start: int, tok_diff: int, forced: Optional[int] = None, sample_fn=None, q=None) -> int:
-        """Token selection right after prefill (hidden2[0] already holds the last prompt state); `q`: drawn on the device (step_decode)."""
+        """Token selection right after prefill (hidden2[0] already holds the last prompt state); `q`: drawn on the device (step_decode).
+        After set_token_seeds the draws come from vv_token_draws at the last prompt position (lens[0] - 1) and the choice is the row's own
+        sampler's (vv_sample_ids), or the argmax for a greedy row."""
+        if self._seeded and forced is None:
+            nv = len(self.valid_ids)
+            with torch.cuda.stream(self.stream):
+                self._set_forced(None)
+                self._logits()
+                if self._sampler_rows[0][0] > 0:
+                    self._ck(self.lib.vv_token_draws(self.q_dev.data_ptr(), 8, 1, nv, self.tok_seed_dev.data_ptr(), self.lens.data_ptr(), 2, -1, self.sp),
+                             "vv_token_draws")
+                    self._ck(self.lib.vv_sample_ids(self.logits.data_ptr(), nv, self._ids_dev.data_ptr(), C.byref(L.Sampler(*self._sampler_rows[0])),
+                                                    self.q_dev.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(), self.sp), "vv_sample_ids")
+                else:
+                    self._pick()
+                self.token_host.copy_(self.token_dev, non_blocking=True)
+            self.stream.synchronize()
+            return int(self.token_host[0])
         if q is not None and forced is None:
             with torch.cuda.stream(self.stream):
                 self._set_forced(None)

@@ -245,6 +245,11 @@ class _LaneDriver:
         for e, sd in zip(self.lanes, seeds):
             e.set_noise_seed(sd)
 
+    def set_token_sampling(self, samplers, seeds):
+        for e, row, sd in zip(self.lanes, samplers, seeds):
+            e.set_sampler_row(0, *row)
+            e.set_token_seeds([sd])
+
     def first_tokens(self, live, forced, sample_fn, q=None):
         lanes, toks = self.lanes, {}
         for b in live:
@@ -378,6 +383,12 @@ class _RowDriver:
         for rb, idxs in self.groups:
             rb.set_noise_seeds([seeds[b] for b in idxs])
 
+    def set_token_sampling(self, samplers, seeds):
+        for rb, idxs in self.groups:
+            for loc, b in enumerate(idxs):
+                rb.set_sampler_row(loc, *samplers[b])
+            rb.set_token_seeds([seeds[b] for b in idxs])
+
     def first_tokens(self, live, forced, sample_fn, q=None):
         at, toks = self.at, {}
         st_embed = self.main.embed_ids(torch.tensor([self.ST]))
@@ -509,7 +520,7 @@ class _SessionDriver(_RowDriver):
 
     def admit(self, b, req):
         rb, loc = self.at[b]
-        rb.admit(loc, req.cfg_scale, req.noise_seed if self.dn else None)
+        rb.admit(loc, req.cfg_scale, req.noise_seed if self.dn else None, sampler=req.sampler, token_seed=req.token_seed)
         vp = self.prefixes[b] = req.prefix
         self.x0[b] = _embed_prompt(self.main, req.prompt, req.voice) if vp is None else _embed_prompt(self.main, req.prompt[vp.P:], None)
 
@@ -530,13 +541,20 @@ class VibeVoiceSession:
     """An open serving session of one model (model.open_session): dialogues are submitted one by one, each with its own guidance scale, limits,
     schedule, noise seed and streamer; `step()` admits queued dialogues into free row-batch slots and advances every live one by a token.  Each
     dialogue is served as generate() serves it alone (batchloop.Session).  The sampler (generation_config, device_sampling) and the solver are
-    the session's; admission is synchronous (a newcomer's prefill runs between two steps on the main stream)."""
+    the session's - opened with seeded_tokens=True, every request may bring its own generation_config and token_seed instead (submit) -; admission is synchronous (a newcomer's prefill runs between two steps on the main stream)."""
 
-    def __init__(self, model, tokenizer, slots, max_context, generation_config, device_noise, device_sampling):
+    def __init__(self, model, tokenizer, slots, max_context, generation_config, device_noise, device_sampling, seeded_tokens=False):
         self.model, cfg = model, model.config
         gen_cfg = dict(generation_config or {})
         do_sample = bool(gen_cfg.get("do_sample", False))
         on_device = model.device_sampling if device_sampling is None else bool(device_sampling)
+        self.seeded_tokens = bool(seeded_tokens)
+        if self.seeded_tokens:
+            if device_sampling is not None and not device_sampling:
+                raise ValueError("open_session(): seeded_tokens=True draws the tokens on the device: device_sampling=False cannot go with it")
+            on_device = True
+            if do_sample:
+                batchloop.sampler_row(gen_cfg)             # ValueError for warpers the kernels do not take
         sampler = batchloop.sampler_params(gen_cfg) if do_sample and on_device else None
         sample_fn = _make_sampler(gen_cfg) if do_sample and sampler is None else None
         self.special = dict(speech_start=tokenizer.speech_start_id, speech_end=tokenizer.speech_end_id, speech_diffusion=tokenizer.speech_diffusion_id,
@@ -548,7 +566,8 @@ class VibeVoiceSession:
             self.driver.open(int(max_context), batchloop.valid_token_ids(self.special))
             self._s = batchloop.Session(self.driver, slots, self.special, self.special["eos"] if pad_id is None else pad_id, cfg.max_pos, cfg.latent,
                                         max_context, device_noise=device_noise, sample_fn=sample_fn, sampler=sampler,
-                                        speculate=model.speculative_frames and model._use_graphs, on_close=self._closed)
+                                        speculate=model.speculative_frames and model._use_graphs, on_close=self._closed,
+                                        seeded_tokens=self.seeded_tokens)
 
     slots = property(lambda self: self._s.slots)
     admission_ms = property(lambda self: self._s.admission_ms)      # host time of every admission (prefill + first token, synchronous): the stall of the running dialogues
@@ -557,10 +576,13 @@ class VibeVoiceSession:
     @torch.no_grad()
     def submit(self, input_ids=None, attention_mask=None, speech_tensors=None, speech_masks=None, speech_input_mask=None, cfg_scale: float = 1.0,
                max_new_tokens: Optional[int] = None, max_length_times=2, forced_tokens=None, noise=None, sde_noise=None, noise_seed=None,
-               voice_prefix=None, audio_streamer=None, stop_check_fn=None, speech_noise=None) -> batchloop.SessionHandle:
+               voice_prefix=None, audio_streamer=None, stop_check_fn=None, speech_noise=None, generation_config=None,
+               token_seed=None) -> batchloop.SessionHandle:
         """Queue one dialogue (the arguments generate() takes for a batch of one) and return its handle.  The voice encode - or the restore of its
         voice_prefix - runs here; nothing else does.  ValueError when prompt + step limit + 8 exceeds the session's max_context (nothing is
-        clipped), and for noise= / sde_noise= in a device-noise session."""
+        clipped), and for noise= / sde_noise= in a device-noise session.  In a session opened with seeded_tokens=True, generation_config= gives this
+        request its own do_sample / temperature / top_k / top_p (None: the session's) and token_seed= its own token seed (None: drawn here, after the
+        noise seed); in any other session either raises ValueError."""
         model = self.model
         input_ids = torch.as_tensor(input_ids)
         in_dev = input_ids.device
@@ -575,7 +597,11 @@ class VibeVoiceSession:
         req = batchloop.SessionRequest(prompt=ids, head=input_ids[0][~keep], cfg_scale=float(cfg_scale), max_new_tokens=max_new_tokens,
                                        max_length_times=max_length_times, forced_tokens=forced_tokens,
                                        noise=None if noise is None else torch.as_tensor(noise), sde_noise=None if sde_noise is None else torch.as_tensor(sde_noise),
-                                       noise_seed=noise_seed, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, in_dev=in_dev)
+                                       noise_seed=noise_seed, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, in_dev=in_dev,
+                                       sampler=None if generation_config is None or not self.seeded_tokens else batchloop.sampler_row(generation_config),
+                                       token_seed=None if token_seed is None else int(token_seed) % 2 ** 64)
+        if generation_config is not None and not self.seeded_tokens:
+            raise ValueError("submit(generation_config=) needs a session opened with seeded_tokens=True (this session has one sampler)")
         self._s.validate(req)              # before any work on the device
         if speech_input_mask is not None:
             speech_input_mask = torch.as_tensor(speech_input_mask).cpu().reshape(1, -1)
@@ -626,7 +652,8 @@ class VibeVoiceSession:
 class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
-                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False):
+                 kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
+                 seeded_tokens: bool = False):
         # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
         # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
         # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
@@ -670,6 +697,12 @@ class VibeVoiceForConditionalGenerationInference:
         # batched call may speculate its frames, and a dialogue sounds the same alone and in a batch.  Same distribution, another sequence than
         # the reference's RNG stream.  Off by default; generate(..., device_noise=..., noise_seed=...) overrides it per call
         self.device_noise = bool(device_noise)
+        # do_sample tokens drawn on the device from a counter-based generator (vv_token_draws) as a function of (the dialogue's token_seed, the
+        # position, its own logits), under warpers that are the dialogue's own row of a device array: one captured graph A serves dialogues with
+        # different generation_configs - greedy ones too - and a dialogue's tokens are the same alone, on a lane, in a row batch or in a
+        # session.  Implies device sampling.  Same distribution, another sequence than the reference's RNG stream.  Off by default;
+        # generate(..., seeded_tokens=..., token_seed=...) overrides it per call
+        self.seeded_tokens = bool(seeded_tokens)
         # weight_quant="fp8": weight-only e4m3 companions for the per-frame weight-streaming GEMVs;
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         # "mxfp4": weight-only OCP MXFP4 companions (e2m1 codes, one power-of-two scale byte per 32 k) decoded by the vector ALU's own
@@ -725,7 +758,7 @@ class VibeVoiceForConditionalGenerationInference:
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
                    use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
                    device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False),
-                   mxfp4_row_batch=kw.get("mxfp4_row_batch", False))
+                   mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -835,12 +868,13 @@ class VibeVoiceForConditionalGenerationInference:
 
     # ---- serving sessions ---------------------------------------------------------------------------------------
     def open_session(self, tokenizer=None, slots: int = 8, max_context: Optional[int] = None, generation_config=None, device_noise: bool = True,
-                     device_sampling: Optional[bool] = None) -> "VibeVoiceSession":
+                     device_sampling: Optional[bool] = None, seeded_tokens: bool = False) -> "VibeVoiceSession":
         """Open a serving session: `slots` (2..16) row-batch slots - ceil(slots / 4) row batches, as a batched generate() partitions them - whose
         KV caches are sized once for `max_context` tokens per dialogue (required).  Dialogues are submitted to the session one by one and a
         finished one frees its slot for the next between two steps (VibeVoiceSession, batchloop.Session).  Needs what row batching needs -
         bf16, weight_quant None or "fp8" (or "mxfp4" on a model built with mxfp4_row_batch=True), a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
-        per model; generate() raises RuntimeError until it is closed."""
+        per model; generate() raises RuntimeError until it is closed.  seeded_tokens=True: every request may bring its own generation_config and token_seed
+        (submit), greedy and sampled requests share the one graph A, and a dialogue's tokens do not depend on who shares the session."""
         if getattr(self, "_session", None) is not None:
             raise RuntimeError("open_session(): this model already has an open session (one per model); close() it first")
         if tokenizer is None:
@@ -860,7 +894,7 @@ class VibeVoiceForConditionalGenerationInference:
             why = "use_graphs=False (the session replays captured graphs)"
         if why is not None:
             raise ValueError(f"open_session(): a session runs on the row-batched decode path, which this model cannot take: {why}")
-        sess = VibeVoiceSession(self, tokenizer, slots, int(max_context), generation_config, bool(device_noise), device_sampling)
+        sess = VibeVoiceSession(self, tokenizer, slots, int(max_context), generation_config, bool(device_noise), device_sampling, bool(seeded_tokens))
         self._session = sess
         return sess
 
@@ -877,6 +911,7 @@ class VibeVoiceForConditionalGenerationInference:
         rows_ = _cfg_scales(cfg_scale, 1 if ids_.dim() == 1 else int(ids_.shape[0]))      # ValueError before anything runs
         if rows_ is not None and len(rows_) == 1:
             cfg_scale = rows_[0]
+        self._token_sampling_args(generation_config, kwargs, 1 if ids_.dim() == 1 else int(ids_.shape[0]))      # ValueError before anything runs
         self.engine.sync_in()
         with torch.cuda.stream(self.engine.stream):   # all torch glue (gathers, scatters, copies) rides the engine stream
             out = self._generate(input_ids, attention_mask, speech_tensors, speech_masks, speech_input_mask, tokenizer,
@@ -888,8 +923,9 @@ class VibeVoiceForConditionalGenerationInference:
                   max_new_tokens, cfg_scale, audio_streamer, stop_check_fn, return_speech, **kwargs):
         if tokenizer is None:
             raise ValueError("generate() needs tokenizer= (for the speech_start/end/diffusion and eos ids)")
-        gen_cfg = dict(generation_config or {})
-        do_sample = bool(gen_cfg.get("do_sample", False))
+        tok_rows = self._token_sampling_args(generation_config, kwargs, 1 if torch.as_tensor(input_ids).dim() == 1 else int(torch.as_tensor(input_ids).shape[0]))
+        gen_cfg = dict((generation_config[0] if isinstance(generation_config, (list, tuple)) else generation_config) or {})
+        do_sample = bool(gen_cfg.get("do_sample", False)) and tok_rows is None
         sampler = batchloop.sampler_params(gen_cfg) if do_sample and kwargs.get("device_sampling", self.device_sampling) else None
         sample_fn = _make_sampler(gen_cfg) if do_sample and sampler is None else None
         verbose = kwargs.get("verbose", False)
@@ -915,6 +951,8 @@ class VibeVoiceForConditionalGenerationInference:
             input_ids = input_ids[None]
         B, Lp = input_ids.shape
         noise_seeds = self._noise_seeds(noise_seed, B) if device_noise else None      # None: the call's first draw from the CPU generator
+        # seeded token draws: the dialogues' sampler rows and token seeds (drawn, when not given, right after the noise seeds)
+        token_sampling = None if tok_rows is None else (tok_rows, self._noise_seeds(kwargs.get("token_seed"), B, what="token_seed"))
         attention_mask = torch.ones_like(input_ids) if attention_mask is None else torch.as_tensor(attention_mask).cpu()
         if speech_input_mask is not None:
             speech_input_mask = torch.as_tensor(speech_input_mask).cpu()
@@ -947,7 +985,7 @@ class VibeVoiceForConditionalGenerationInference:
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
                                        sample_fn=sample_fn, sampler=sampler, speculate=self.speculative_frames and self._use_graphs, return_speech=return_speech,
-                                       in_dev=in_dev, noise_seeds=noise_seeds)
+                                       in_dev=in_dev, noise_seeds=noise_seeds, token_sampling=token_sampling)
             try:
                 return batchloop.run(driver, input_ids, attention_mask, speech_input_mask, conn_all, call)
             finally:
@@ -961,13 +999,36 @@ class VibeVoiceForConditionalGenerationInference:
                 conn = conn_all[: int(sp.sum())]
         r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
                                stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler,
-                               prefix=None if vps is None else vps[0], noise_seed=None if noise_seeds is None else noise_seeds[0])
+                               prefix=None if vps is None else vps[0], noise_seed=None if noise_seeds is None else noise_seeds[0],
+                               token_sampling=None if token_sampling is None else (token_sampling[0][0], token_sampling[1][0]))
         if audio_streamer is not None:
             audio_streamer.end()
         return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
 
+    def _token_sampling_args(self, generation_config, kwargs, B: int) -> Optional[List[tuple]]:
+        """generate()'s seeded-token arguments, checked without touching the device or the generator.  Returns None when the call draws no token
+        that way - seeded_tokens off, or do_sample false for every dialogue (nothing changes and nothing is drawn then) - else the B dialogues'
+        sampler rows (batchloop.sampler_row).  ValueError: a generation_config list without seeded_tokens or of the wrong length, token_seed
+        without seeded_tokens, seeded_tokens with device_sampling=False given explicitly, warpers the kernels do not take."""
+        seeded = bool(kwargs.get("seeded_tokens", self.seeded_tokens))
+        per = isinstance(generation_config, (list, tuple))
+        if per and not seeded:
+            raise ValueError("generation_config: one dict per dialogue needs seeded_tokens=True (a call has one sampler otherwise)")
+        if per and len(generation_config) != B:
+            raise ValueError(f"generation_config: {len(generation_config)} entries for {B} dialogues (a dict, or one per dialogue)")
+        if kwargs.get("token_seed") is not None and not seeded:
+            raise ValueError("token_seed= seeds the device-side token draws: it needs seeded_tokens=True")
+        if not seeded:
+            return None
+        if kwargs.get("device_sampling") is not None and not kwargs.get("device_sampling"):
+            raise ValueError("seeded_tokens=True draws the tokens on the device: device_sampling=False cannot go with it")
+        if isinstance(kwargs.get("token_seed"), (list, tuple)) and len(kwargs["token_seed"]) != B:
+            raise ValueError(f"token_seed: {len(kwargs['token_seed'])} seeds for {B} dialogues (an int, or one int per dialogue)")
+        rows = [batchloop.sampler_row(g) for g in (generation_config if per else [generation_config] * B)]
+        return rows if any(r != batchloop.GREEDY_ROW for r in rows) else None
+
     @staticmethod
-    def _noise_seeds(noise_seed, B: int) -> List[int]:
+    def _noise_seeds(noise_seed, B: int, what: str = "noise_seed") -> List[int]:
         """generate(device_noise=True, noise_seed=): the B dialogues' 64-bit seeds.  An int: dialogue b uses (seed + b) mod 2^64; a list of B
         ints: one each; None: B draws from torch's default CPU generator, so torch.manual_seed makes the call reproducible."""
         if noise_seed is None:
@@ -975,7 +1036,7 @@ class VibeVoiceForConditionalGenerationInference:
         if isinstance(noise_seed, (list, tuple)) or (isinstance(noise_seed, (torch.Tensor, np.ndarray)) and noise_seed.ndim > 0):
             seeds = [int(v) % 2 ** 64 for v in noise_seed]
             if len(seeds) != B:
-                raise ValueError(f"noise_seed: {len(seeds)} seeds for {B} dialogues (an int, or one int per dialogue)")
+                raise ValueError(f"{what}: {len(seeds)} seeds for {B} dialogues (an int, or one int per dialogue)")
             return seeds
         return [(int(noise_seed) + b) % 2 ** 64 for b in range(B)]
 
@@ -1041,7 +1102,7 @@ class VibeVoiceForConditionalGenerationInference:
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
                       noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None,
-                      prefix: Optional[VoicePrefix] = None, noise_seed: Optional[int] = None):
+                      prefix: Optional[VoicePrefix] = None, noise_seed: Optional[int] = None, token_sampling: Optional[tuple] = None):
         eng, cfg = self.engine, self.config
         dn = noise_seed is not None         # device noise: the engine draws frame f's noise from (noise_seed, f); draw / pending_nz / rewind are not used
         nv = len(set(batchloop.valid_token_ids(special)))
@@ -1071,6 +1132,9 @@ class VibeVoiceForConditionalGenerationInference:
         eng.begin_sequence(L0 + max(max_steps, 1) + 8, batchloop.valid_token_ids(special))
         if dn:
             eng.set_noise_seed(noise_seed)
+        if token_sampling is not None:      # seeded token draws: (sampler row, token seed) - the steps take no q, the engine runs graph "Ar"
+            eng.set_sampler_row(0, *token_sampling[0])
+            eng.set_token_seeds([token_sampling[1]])
         # prefix: its P positions come out of the store; only the rows after it are embedded and prefilled (every voice row lies inside it)
         x0 = _embed_prompt(eng, ids, None if conn is None else (sp_mask, conn)) if prefix is None else _embed_prompt(eng, ids[prefix.P:], None)
         seq = ids.tolist()

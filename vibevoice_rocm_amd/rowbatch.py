@@ -29,7 +29,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib as L
-from .engine import Engine
+from .engine import Engine, write_sampler_row, write_seed_rows
 
 _UID = itertools.count(1)
 # One worker thread per HIP stream, shared by every RowBatch of the process: two row batches of one generate() call (5..8 dialogues) put their
@@ -87,6 +87,8 @@ class RowBatch:
             self.noise_seed_dev = torch.zeros(B, dtype=torch.int64, device=self.device)      # device noise: every dialogue's 64-bit seed (its bits)
             self.noise_frame_dev = torch.zeros(B, **i32)                                       # and the index of the frame it draws next
             self.latent = torch.zeros(B, cfg.latent, **f32)
+            self.sampler_dev = torch.zeros(B, 3, **f32)   # seeded token draws: every dialogue's vv_sampler row and 64-bit token seed, read by
+            self.tok_seed_dev = torch.zeros(B, dtype=torch.int64, device=self.device)         # its block of the step tail (graph "Ar")
             self.cfg_dev = torch.ones(B, **f32)           # guidance per dialogue, read on the device (begin(cfg_rows=) / admit): graph "Hc"
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
         self._pf_ws = None
@@ -104,6 +106,11 @@ class RowBatch:
         self.q_host = torch.ones(2, B, 8, dtype=torch.float32).pin_memory()
         self._q_k = 0
         self._sampler, self._sampler_key = None, None
+        self.sampler_host = torch.zeros(B, 3, dtype=torch.float32).pin_memory()
+        self.sampler_host[:, 2] = 1.0                     # greedy rows: (0, 0, 1)
+        self.tok_seed_host = torch.zeros(B, dtype=torch.int64).pin_memory()
+        self._sampler_rows = [(0.0, 0, 1.0)] * B
+        self._seeded = False            # set_token_seeds / admit(sampler=): the batch draws its tokens from (token seed, position) - graph "Ar"
         self._forced_val = [-1] * B
         self._active_val = [1] * B
         self._tok_event = torch.cuda.Event()
@@ -179,6 +186,7 @@ class RowBatch:
         s_max = (int(s_max) + 63) // 64 * 64
         self.cfg_scale = float(cfg_scale)
         self.cfg_rows = cfg_rows is not None
+        self._seeded = False
         if self.cfg_rows:
             if len(cfg_rows) != B:
                 raise L.VVError(f"RowBatch.begin: {len(cfg_rows)} guidance scales for {B} dialogues")
@@ -238,10 +246,11 @@ class RowBatch:
                 e.reset_speech_caches()
         self._lane_dirty = [False] * B
 
-    def admit(self, b: int, cfg_scale: float, noise_seed: Optional[int] = None):
+    def admit(self, b: int, cfg_scale: float, noise_seed: Optional[int] = None, sampler: Optional[tuple] = None, token_seed: Optional[int] = None):
         """Slot b starts afresh for a new dialogue while the other slots go on (sessions; begin(cfg_rows=) opened the batch): lane b's outstanding
         work is awaited, its positions, frame counter and noise frame index go to zero, forced = none, active, its conv state is zeroed as
-        begin zeroes every lane's, and its guidance scale (and noise seed) are written.  No other slot's state is touched and no graph is dropped.
+        begin zeroes every lane's, and its guidance scale (and noise seed) are written.  sampler = (temperature, top_k, top_p) with token_seed: the
+        slot's own warpers and token seed (seeded token draws: the batch then runs graph "Ar").  No other slot's state is touched and no graph is dropped.
         K / V / vt rows the previous occupant left beyond the new positions are never read: attention covers [0, lens] of a row."""
         if not self.cfg_rows:
             raise L.VVError("RowBatch.admit: the batch was not begun with cfg_rows (its graph H has the scale baked in)")
@@ -254,7 +263,17 @@ class RowBatch:
             v = int(noise_seed) & (2 ** 64 - 1)
             self.noise_seed_host[b] = v - 2 ** 64 if v >= 2 ** 63 else v
         self.noise_frame_host[:, b] = 0
+        if sampler is not None:
+            if token_seed is None:
+                raise L.VVError("RowBatch.admit: sampler= needs token_seed=")
+            self._sampler_rows[b] = write_sampler_row(self.sampler_host, b, *sampler)
+            v = int(token_seed) & (2 ** 64 - 1)
+            self.tok_seed_host[b] = v - 2 ** 64 if v >= 2 ** 63 else v
+            self._seeded = True
         with torch.cuda.stream(self.stream):
+            if sampler is not None:
+                self.sampler_dev.copy_(self.sampler_host, non_blocking=True)
+                self.tok_seed_dev.copy_(self.tok_seed_host, non_blocking=True)
             self.lens[2 * b: 2 * b + 2].zero_()
             self.frame_ctr[b: b + 1].zero_()
             self.noise_frame_dev[b: b + 1].zero_()
@@ -315,6 +334,20 @@ class RowBatch:
         self._sampler_key = (float(temperature), int(top_k), float(top_p))
         self._sampler = L.Sampler(*self._sampler_key)
 
+    def set_sampler_row(self, b: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0):
+        """Seeded token draws: dialogue b's own warpers, kept on the device (Engine.set_sampler_row); greedy = (0, 0, 1)."""
+        self._sampler_rows[b] = write_sampler_row(self.sampler_host, b, temperature, top_k, top_p)
+        with torch.cuda.stream(self.stream):
+            self.sampler_dev.copy_(self.sampler_host, non_blocking=True)
+
+    def set_token_seeds(self, seeds: List[int]):
+        """Seeded token draws: the B dialogues' 64-bit token seeds, once per batch (after begin).  decode_begin then runs graph "Ar" - every
+        dialogue's token drawn in its block of the tail from (its seed, its position, its logits) under its own sampler row - and takes no q."""
+        write_seed_rows(self.tok_seed_host, seeds)
+        with torch.cuda.stream(self.stream):
+            self.tok_seed_dev.copy_(self.tok_seed_host, non_blocking=True)
+        self._seeded = True
+
     def set_noise_seeds(self, seeds: List[int]):
         """Device noise: the B dialogues' 64-bit seeds, once per batch (after begin); speech / speech_begin given `frames` then draw the noise of
         every row inside graph H (Engine.set_noise_seed)."""
@@ -346,6 +379,21 @@ class RowBatch:
             a.w, a.n, a.k, a.wdt = self._w_valid.data_ptr(), nv, self.cfg.hidden, L.VV_BF16
             a.out, a.ldo = self.logits[b].data_ptr(), nv
             self._ck(self.lib.vv_linear(C.byref(a), self.sp), "lm_head")
+        if self._seeded and forced is None:
+            # seeded token draws: the draws of (the dialogue's seed, the last prompt position = lens[2 b] - 1), then its own sampler's choice
+            with torch.cuda.stream(self.stream):
+                self._set_forced({b: None})
+                if self._sampler_rows[b][0] > 0:
+                    self._ck(self.lib.vv_token_draws(self.q_dev[b].data_ptr(), 8, 1, nv, self.tok_seed_dev[b:].data_ptr(), self.lens[2 * b:].data_ptr(), 2, -1,
+                                                     self.sp), "vv_token_draws")
+                    self._ck(self.lib.vv_sample_ids(self.logits[b].data_ptr(), nv, self._ids_dev.data_ptr(), C.byref(L.Sampler(*self._sampler_rows[b])),
+                                                    self.q_dev[b].data_ptr(), self.token_dev[b:].data_ptr(), self.forced_dev[b:].data_ptr(), self.sp), "vv_sample_ids")
+                else:
+                    self._ck(self.lib.vv_argmax_ids(self.logits[b].data_ptr(), nv, self._ids_dev.data_ptr(), self.token_dev[b:].data_ptr(),
+                                                    self.forced_dev[b:].data_ptr(), self.sp), "vv_argmax_ids")
+                self.token_host.copy_(self.token_dev, non_blocking=True)
+            self.stream.synchronize()
+            return int(self.token_host[b])
         if sample_fn is not None and forced is None:
             forced = int(sample_fn(self.read_logits()[b, :nv].clone(), self.valid_ids))
         if q is not None and forced is None:
@@ -408,6 +456,18 @@ class RowBatch:
                                                    self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(),
                                                    self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.active_dev.data_ptr(),
                                                    C.byref(smp), self.q_dev.data_ptr(), self.sp), "vv_llm_tail_batch_sample")
+
+    def _seq_Ar(self, tok_start, tok_diff):
+        """_seq_A with the seeded tail (vv_llm_tail_batch_sample_rows): block b reads dialogue b's sampler row and token seed from sampler_dev /
+        tok_seed_dev and forms its draws from (seed, lens[2 b]); no warpers in the graph's key, greedy and sampled dialogues side by side"""
+        eng, B, H = self.main, self.B, self.cfg.hidden
+        nv = len(self.valid_ids)
+        self._ck(self.lib.vv_llm_forward(C.byref(eng.w.llm), C.byref(self.kv), self.x.data_ptr(), H, 2 * B, self.lens.data_ptr(), None, None, 0,
+                                         self._llm_ws.data_ptr(), self.sp), "vv_llm_forward")
+        self._ck(self.lib.vv_llm_tail_batch_sample_rows(C.byref(eng.w.llm), self._llm_ws.data_ptr(), H, B, self.hidden.data_ptr(), H, self._w_valid.data_ptr(), nv,
+                                                        self._ids_dev.data_ptr(), self.logits.data_ptr(), self.token_dev.data_ptr(), self.forced_dev.data_ptr(),
+                                                        self.lens.data_ptr(), tok_start, tok_diff, self.frame_ctr.data_ptr(), self.active_dev.data_ptr(),
+                                                        self.sampler_dev.data_ptr(), self.tok_seed_dev.data_ptr(), self.sp), "vv_llm_tail_batch_sample_rows")
 
     def _seq_A1(self):
         """the decode step and the constrained logits of every dialogue; positions stay (lens / frame_counter NULL)"""
@@ -504,7 +564,9 @@ class RowBatch:
                 self._tcur = dict(a0=torch.cuda.Event(enable_timing=True), a1=torch.cuda.Event(enable_timing=True), h1=None, t=[])
                 self._timing.append(self._tcur)
                 self._tcur["a0"].record(self.stream)
-            if q:
+            if self._seeded:
+                self._run("Ar", self._seq_Ar, int(tok_start), int(tok_diff))
+            elif q:
                 self._upload_q(q)
                 self._run("AS", self._seq_AS, int(tok_start), int(tok_diff), *self._sampler_key)
             else:
