@@ -60,7 +60,7 @@ enum { VV_MXFP4 = 4 };
  * effective values. */
 enum { VV_WQ_MXFP4 = 0x200 };
 /* VV_MXFP4_FRAG: the same OCP MXFP4 values (codes, E8M0 scale bytes 2..252, effective weight value(code) * 2^(e - 127)) in FRAGMENT-MAJOR order, for the
- * 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows_mx.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding occurs), fp32
+ * 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding occurs), fp32
  * activations and outputs.
  *   w / w2:           codes [N / 16][K / 128][64 lanes][16 B], 16-byte aligned: dword h (0..3) of lane 16 c + n of 128-wide step J of row group g holds
  *                     W[16 g + n][128 J + 32 h + 8 c + i] in nibble i (bits 4 i .. 4 i + 3, the nibble order of VV_MXFP4) - dword h is the B fragment of

@@ -1,4 +1,4 @@
-"""GPU parity of MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows_mx.hip).
+"""GPU parity of MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows.hip).
 
 1. the kernel: decode read back exactly (every code in every nibble position, scale bytes 2 / 127 / 252), then vv_linear on VV_MXFP4_FRAG codes
    against vv_linear on the bf16 fragment-major copy of the effective matrix - bit for bit wherever both forms cut K alike (ticketed split,
@@ -38,7 +38,7 @@ def lib():
 
 
 class _tuned:
-    """vv_tune hooks for one case (both rows units read them), restored to the defaults on exit"""
+    """vv_tune hooks for one case (the rows unit's one tune state), restored to the defaults on exit"""
     DEFAULTS = {"gemv_rows_blocks": 448, "gemv_rows_pers": 192, "gemv_rows_atomic": 1}
 
     def __init__(self, lb, hooks):

@@ -1,7 +1,7 @@
-"""CPU tests of MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows_mx.hip):
+"""CPU tests of MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows.hip):
 the fragment-major VV_MXFP4_FRAG packing against the header's index formula, its inverse, the shapes it refuses, the opt-in keyword and the
 descriptor bit, the fragment copies ensure_frag builds (on the CPU, at `tiny`), the decision's rules restated (shared with
-tests/test_hip_rowbatch_mxfp4.py) and the kernel set of the built unit."""
+tests/test_hip_rowbatch_mxfp4.py) and the MXFP4 kernel set of the built unit."""
 import os
 import re
 
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the decision's rules, restated (vv_gemv_rows_mx.hip: vv_gemv_rows_mx_decide; vv_gemv_rows.hip: the bf16 form's K cut)
+# the decision's rules, restated (vv_gemv_rows.hip: vv_gemv_rows_decide on VV_MXFP4_FRAG weights, and the bf16 form's K cut)
 # ---------------------------------------------------------------------------------------------------------------
 MAXSPLIT = 16
 
@@ -25,7 +25,7 @@ def _mxr(dual, nw, ks, pers):
     return f"gemv_rows_mx<dual={dual},nw={nw},ks={ks},pers={pers}>"
 
 
-# every kernel of the unit: whole rows (8 waves, 1 or 2 loads of 128 k per wave; SwiGLU also persistent), the SwiGLU K split (the same two
+# every MXFP4 kernel of the unit (gemv_rows_kernel<dual, nw, ks, pers, 2>): whole rows (8 waves, 1 or 2 loads of 128 k per wave; SwiGLU also persistent), the SwiGLU K split (the same two
 # kernels), the single-matrix K split (4 waves, 1..4 loads)
 ALL_ROWS_MX = [_mxr(0, 8, 1, 0), _mxr(0, 8, 2, 0), _mxr(1, 8, 1, 0), _mxr(1, 8, 2, 0), _mxr(1, 8, 1, 1), _mxr(1, 8, 2, 1),
                _mxr(0, 4, 1, 0), _mxr(0, 4, 2, 0), _mxr(0, 4, 3, 0), _mxr(0, 4, 4, 0)]
@@ -103,8 +103,13 @@ def test_decision_reaches_exactly_the_enumerated_kernels():
 
 def test_built_unit_holds_exactly_the_enumerated_kernels(tmp_path):
     """What is compiled is what can launch (reads the symbol table of the object file build() left): the gfx950 code object of
-    vv_gemv_rows_mx.hip holds one gemv_rows_mx_kernel per entry of ALL_ROWS_MX and no other instantiation of the template."""
-    got = instantiations_of(built_kernels("vv_gemv_rows_mx.hip", tmp_path), {"gemv_rows_mx_kernel": _mxr})
+    vv_gemv_rows.hip holds one gemv_rows_kernel of weight format 2 (MXFP4) per entry of ALL_ROWS_MX and no other.  The unit's kernels of
+    formats 0 and 1 (bf16, fp8) are the 22 of tests/test_hip_gemv.py's ALL_INSTANTIATIONS, held to exactly that set by its
+    test_built_library_holds_exactly_the_enumerated_kernels: between the two lists every gemv_rows_kernel of the binary is claimed by one of
+    them and nothing is left over - 32 kernels, no other format."""
+    kernels = [args for k, args in built_kernels("vv_gemv_rows.hip", tmp_path) if k == "gemv_rows_kernel"]
+    assert sorted({args[4] for args in kernels}) == ["0", "1", "2"] and len(kernels) == 22 + len(ALL_ROWS_MX), kernels
+    got = instantiations_of([("mx", args[:4]) for args in kernels if args[4] == "2"], {"mx": _mxr})
     assert got == set(ALL_ROWS_MX), sorted(got ^ set(ALL_ROWS_MX))
 
 

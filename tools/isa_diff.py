@@ -1,38 +1,65 @@
-"""Compare the instruction streams of the kernels in two `hipcc --cuda-device-only -S` outputs: python tools/isa_diff.py old.s new.s
+"""Compare the instruction streams of the kernels in two sets of `hipcc --cuda-device-only -S` outputs:
+    python tools/isa_diff.py old.s[,old2.s...] new.s[,new2.s...]
 Kernels are matched by their demangled base name and template arguments' order of appearance; labels and symbol names are normalised, so a
-renamed parameter type does not count, while any changed instruction, operand or kernel-argument offset does."""
+renamed parameter type does not count, while any changed instruction, operand or kernel-argument offset does.  The rows GEMV's kernels are
+matched by their template arguments, the weight format as a number (gemv_rows_kernel's bool F8 -> 0 / 1, a gemv_rows_mx_kernel -> 2): a kernel
+whose stream differs is listed with the registers, LDS, scratch and spill counts of its metadata on both sides."""
 import re
 import sys
 
+META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
 
-def bodies(path):
-    out, name, cur = [], None, []
-    for line in open(path):
-        m = re.match(r"^(_Z\w+):\s", line)
-        if m and name is None:
-            name, cur = m.group(1), []
-            continue
-        if name is not None:
-            if line.startswith(".Lfunc_end"):
-                out.append((name, cur))
-                name = None
+
+def bodies(paths):
+    out = []
+    for path in paths.split(","):
+        name, cur = None, []
+        for line in open(path):
+            m = re.match(r"^(_Z\w+):\s", line)
+            if m and name is None:
+                name, cur = m.group(1), []
                 continue
-            t = line.split(";")[0].strip()
-            if not t or t.startswith("."):
-                t = re.sub(r"^\.LBB\d+_(\d+):", r"L\1:", t) if t.startswith(".LBB") else ""
-            t = re.sub(r"\.LBB\d+_(\d+)", r"L\1", t)
-            t = re.sub(r"_Z\w+", "SYM", t)
-            if t:
-                cur.append(t)
+            if name is not None:
+                if line.startswith(".Lfunc_end"):
+                    out.append((name, cur))
+                    name = None
+                    continue
+                t = line.split(";")[0].strip()
+                if not t or t.startswith("."):
+                    t = re.sub(r"^\.LBB\d+_(\d+):", r"L\1:", t) if t.startswith(".LBB") else ""
+                t = re.sub(r"\.LBB\d+_(\d+)", r"L\1", t)
+                t = re.sub(r"_Z\w+", "SYM", t)
+                if t:
+                    cur.append(t)
+    return out
+
+
+def meta(paths):
+    """kernel symbol -> {field: value} of the amdhsa.kernels metadata"""
+    out = {}
+    for path in paths.split(","):
+        text = open(path).read()
+        for block in text[text.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", block).group(1)
+            out[name] = {f: int(re.search(rf"\.{f}:\s+(\d+)", block).group(1)) for f in META}
     return out
 
 
 def base(n):
+    m = re.search(r"\d+gemv_rows(_mx)?_kernelI((?:L[bi]\d+E)+)E", n)
+    if m:
+        args = re.findall(r"L[bi](\d+)E", m.group(2)) + (["2"] if m.group(1) else [])
+        return "gemv_rows_kernel<" + ",".join(args) + ">"
     m = re.search(r"\d+(attn\w*kernel|rope_store_kernel|kvq\w*kernel)", n)
     return m.group(1) if m else n
 
 
+def count(body):
+    return sum(not t.endswith(":") for t in body)
+
+
 old, new = bodies(sys.argv[1]), bodies(sys.argv[2])
+mo, mn = meta(sys.argv[1]), meta(sys.argv[2])
 pool = list(new)
 same = diff = 0
 for n, b in old:
@@ -42,7 +69,9 @@ for n, b in old:
     hit = next((i for i in cands if pool[i][1] == b), None)
     if hit is None:
         diff += 1
-        print(f"DIFFERENT  {base(n)}  ({n[:60]}...): {len(b)} instructions, candidates {[len(pool[i][1]) for i in cands]}")
+        print(f"DIFFERENT  {base(n)}  ({n[:60]}...): {count(b)} instructions, candidates {[count(pool[i][1]) for i in cands]}")
+        for i in cands:
+            print("           " + "  ".join(f"{f} {mo[n][f]} -> {mn[pool[i][0]][f]}" for f in META))
     else:
         same += 1
         print(f"identical  {base(n)}: {len(b)} lines")

@@ -1,4 +1,4 @@
-"""MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows_mx.hip) against the fp8 and bf16 forms
+"""MXFP4 on the row-batched decode path (weight_quant="mxfp4", mxfp4_row_batch=True; csrc/vv_gemv_rows.hip) against the fp8 and bf16 forms
 of the 3..8-row matrix-core GEMV and against MXFP4 on the lanes; writes profiles/mxfp4_rows.txt.
 
   1. per-launch us of the m = 8 rows GEMV on the LLM and head matrices of 1.5B and 7B, fragment-major bf16 / fp8 / mxfp4 in one process: per
@@ -11,7 +11,7 @@ of the 3..8-row matrix-core GEMV and against MXFP4 on the lanes; writes profiles
      audio-sec/s as p50 (min - max), device weight bytes, and the two mxfp4 waveforms against each other.  `rotate` turns the list of modes by
      that many places for the order the models are built in AND the order they are timed in (each model keeps its engines' HIP streams for the
      run, so a mode's place in the building order decides which streams it gets): a figure that is the kernel's holds under every rotation;
-  3. (needs hipcc, no GPU) VGPRs, scratch, occupancy and LDS of every gemv_rows_mx kernel from -Rpass-analysis=kernel-resource-usage.
+  3. (needs hipcc, no GPU) VGPRs, scratch, occupancy and LDS of every MXFP4 kernel of the rows GEMV from -Rpass-analysis=kernel-resource-usage.
     python tools/mb_mxfp4_rows.py [sections=123] [frames=60] [runs=5] [presets=1.5b,7b] [out=profiles/mxfp4_rows.txt] [rounds=5] [batches=4,8] [rotate=0]
 A section is appended to `out`; section 1 starts the file."""
 import ctypes as C
@@ -51,15 +51,15 @@ def p50(v):
 
 def section_3():
     from vibevoice_rocm_amd import build as vb
-    src = os.path.join(vb.HERE, "csrc", "vv_gemv_rows_mx.hip")
+    src = os.path.join(vb.HERE, "csrc", "vv_gemv_rows.hip")
     cmd = [vb.find_hipcc(), *vb.FLAGS, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(vb.HERE, "csrc"), "--cuda-device-only", "-S",
            "-Rpass-analysis=kernel-resource-usage", src, "-o", os.devnull]
     err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    say("# 3. build checks of csrc/vv_gemv_rows_mx.hip (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage)")
-    say("# gemv_rows_mx_kernel instantiations: DUAL NW KS PERS | VGPRs scratch(B/lane) occupancy(waves/SIMD) static LDS(B/block) + dynamic LDS (the A fragments)")
+    say("# 3. build checks of csrc/vv_gemv_rows.hip, weight format 2 = MXFP4 (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage)")
+    say("# gemv_rows_kernel<DUAL, NW, KS, PERS, 2> instantiations: DUAL NW KS PERS | VGPRs scratch(B/lane) occupancy(waves/SIMD) static LDS(B/block) + dynamic LDS (the A fragments)")
     rows = []
     for blk in re.split(r"remark: [^\n]*Function Name: ", err)[1:]:
-        m = re.match(r"\S*gemv_rows_mx_kernelILb([01])ELi(\d)ELi(\d)ELb([01])E", blk)
+        m = re.match(r"\S*gemv_rows_kernelILb([01])ELi(\d)ELi(\d)ELb([01])ELi2E", blk)
         if not m:
             continue
         g = lambda key: int(re.search(re.escape(key) + r": (\d+)", blk).group(1))

@@ -62,12 +62,14 @@ int vv_conv_hot_gemv_covers(const vv_lin_args& a);                // index of th
 int vv_launch_conv_hot_gemv(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_conv_hot_gemv_covers: 1 = launched
 int vv_launch_conv_hot_row(const vv_block& B, const float* x, float* y, float* hidden, float* hist_new, int C, float eps, hipStream_t s);
 void vv_conv_hot_set(int mask);                                   // tuning hook "conv_hot"
-// vv_gemv_rows.hip: 3..8 activation rows on the matrix cores; 1 launched, 0 not covered, < 0 error.  part / tickets: split-K workspace
-// (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry, left zero) or null
+// vv_gemv_rows.hip: 3..8 activation rows on the matrix cores, on bf16, fragment-major fp8 or VV_MXFP4_FRAG weights (vv_hip.h); 1 launched, 0 not
+// covered, < 0 error.  part / tickets: split-K workspace (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry,
+// left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
-// the same, decision apart from launch: gemv_rows_kernel<dual, nw, ks, pers, f8> on (gx, ksplit) blocks, spw weight loads per wave; atomic: the K
-// slices add into out.  have_ws: the caller has a partials workspace and tickets (their sizes follow); kind 1 = covered
-struct vv_rows_route { int kind, dual, nw, ks, pers, f8, ksplit, spw, atomic, n_groups, gx; };
+// the same, decision apart from launch: gemv_rows_kernel<dual, nw, ks, pers, wf> on (gx, ksplit) blocks, spw weight loads per wave (wf: the weight
+// format, 0 = bf16, 1 = fp8, 2 = MXFP4: 32-, 64-, 128-wide loads); atomic: the K slices add into out.  have_ws: the caller has a partials workspace
+// and tickets (their sizes follow); kind 1 = covered
+struct vv_rows_route { int kind, dual, nw, ks, pers, wf, ksplit, spw, atomic, n_groups, gx; };
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
 int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
 int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap);
@@ -75,14 +77,6 @@ size_t vv_gemv_rows_part_floats(int n, int dual);
 size_t vv_gemv_rows_tickets(int n);
 int vv_gemv_rows_init();
 void vv_gemv_rows_set(int on, int blocks, int pers);            // tuning hooks (negative / zero: keep)
-// vv_gemv_rows_mx.hip: gemv_rows_mx_kernel<dual, nw, ks, pers> - the same GEMV on VV_MXFP4_FRAG weights (vv_hip.h); ks / spw count 128-wide weight
-// loads per wave, the route's f8 field is 0.  Workspace, tickets and return values as above; the tune hooks of vv_gemv_rows.hip are mirrored here
-vv_rows_route vv_gemv_rows_mx_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
-int vv_launch_gemv_rows_mx_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
-int vv_launch_gemv_rows_mx(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
-int vv_gemv_rows_mx_route_name(const vv_rows_route& r, char* name, int cap);
-int vv_gemv_rows_mx_init();
-void vv_gemv_rows_mx_set(int on, int blocks, int pers, int atomic);   // negative (blocks / pers: zero too): keep
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets,
                  vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr, bool frag4 = false);
                  // vv_kernels.hip: f1 / f2 = fragment-major copies of a->w / a->w2 or null; with fp8 companions q1 / q2 (q != NULL) of the fp8 codes;

@@ -18,8 +18,20 @@
 //                       codes are decoded to bf16 in registers with the lane's row scale folded in (v_cvt_scalef32_pk_bf16_fp8; a power of two, so
 //                       code * scale is exact in bf16) and meet the same hi / lo activation fragments on the same bf16 MFMA: the products and their
 //                       summation order are those of the bf16 kernel on the effective matrix code * scale, bit for bit.
+//   MXFP4 weights       (VV_MXFP4_FRAG, weight-only OCP MXFP4: the row-batched decode step and the serving sessions of a weight_quant="mxfp4" model)
+//                       codes [N / 16][K / 128][64 lanes][16 B]: dword h of lane 16 c + n of 128-wide step J of row group g holds
+//                       W[16 g + n][128 J + 32 h + 8 c + i] in nibble i (bits 4 i .. 4 i + 3) - the B fragment of 32-wide k step 4 J + h in the lane
+//                       assignment of the bf16 fragment-major layout, so one 1 KB wave load carries FOUR MFMA steps.
+//     scales            bytes [N / 16][K / 128][16 rows][4 B]: byte h of the dword at ((g * K/128 + J) * 16 + n) * 4 is the E8M0 byte of block 4 J + h of
+//                       row 16 g + n.  An MX block (32 consecutive k of a row) is exactly one MFMA k step: one scale per B fragment, one 4-byte load
+//                       per lane per weight load, no table, no LDS on the decode path.
+//     decode            per dword h: s = 2^(e_h - 127) built as __uint_as_float(e_h << 23); four v_cvt_scalef32_pk_bf16_fp4 (byte select 0 .. 3) give
+//                       the bf16x8 B fragment; value(code) * s is exact in bf16, so the products and their summation order are those of the bf16 kernel
+//                       on the effective matrix wherever both cut K alike.
+//     KS                128-wide weight loads per wave: 4 KS A fragments (16 KS VGPRs) against 4 KS VGPRs of codes - a 4-bit weight needs four times
+//                       the activation registers and LDS per weight byte the bf16 form needs, which is what bounds KS (<= 4) and the K slice.
 //   workgroup (g, s)    = 16 weight rows (row group g)  x  K slice s of `ksplit`;  its NW waves split the slice into `spw` weight loads each (32-wide
-//                       k steps; 64-wide for fp8)
+//                       k steps; 64-wide for fp8, 128-wide for MXFP4)
 //   prologue            the block's x slice [8, K / ksplit] is fetched once (fp32), RMSNorm statistics over the block's columns, norm weight and
 //                       adaLN shift / scale applied, split into hi / lo and laid out in LDS in fragment order; every wave then holds its A
 //                       fragments in registers.  All of it is REQUESTED before the weights (loads return in order) and computed while the
@@ -60,10 +72,10 @@ struct RowsAux {
   int atomic;        // ksplit > 1 with a linear epilogue whose residual already sits in `out` (res == out): every K slice adds gate * (partial [+ bias])
                      // to out with fp32 atomics - no partial tiles, no ticket, nothing to wait for (the summation ORDER of the slices then varies from
                      // run to run: results reproduce to fp32 rounding, ~1e-7, not bit for bit; vv_tune("gemv_rows_atomic", 0) keeps the ticket)
-  int dbg;           // timing experiments (wrong results): 2 = no ticket merge, 4 = no activation loads
+  int dbg;           // timing experiments (wrong results; bf16 and fp8 only): 2 = no ticket merge, 4 = no activation loads
   float* part;       // [n_groups][ksplit][PST] partial tiles (ksplit > 1)
   int* tickets;      // [n_groups], zero on entry, left zero
-  int ksplit, spw;   // K slices per row group; weight loads per wave (32-wide k steps, 64-wide for fp8)
+  int ksplit, spw;   // K slices per row group; weight loads per wave (32-wide k steps, 64-wide for fp8, 128-wide for MXFP4)
   int n_groups;
 };
 
@@ -83,11 +95,30 @@ __device__ __forceinline__ void fp8_frags(const u32x4 w, float s, bf16x8& b0, bf
   b1 = bf16x8{p[4][0], p[4][1], p[5][0], p[5][1], p[6][0], p[6][1], p[7][0], p[7][1]};
 }
 
-// F8: fp8 fragment-major weights, KS 64-wide weight loads per wave (KA = 2 KS activation fragments); else bf16, KS = KA 32-wide loads
-template <bool DUAL, int NW, int KS, bool PERS, bool F8>
+// 8 e2m1 codes (one dword of a lane's MXFP4 load) under scale byte e -> the bf16 B fragment of one 32-wide k step
+__device__ __forceinline__ bf16x8 mx_frag(unsigned codes, unsigned e) {
+  const float s = __uint_as_float(e << 23);
+  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 0);
+  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 1);
+  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 2);
+  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+// The weight format WF (vv_rows_route.wf) owns the width of a weight load, the addresses `issue` computes, the decode in front of the MFMA and the
+// scale registers of the persistent walk - nothing else: prologue, LDS layout, fold, atomic form and epilogue are one text for all three.
+constexpr int WF_BF16 = 0;      // row-major or fragment-major bf16: a load is one 32-wide k step
+constexpr int WF_FP8 = 1;       // fragment-major e4m3fn codes, a row scale: a load is two 32-wide k steps
+constexpr int WF_MXFP4 = 2;     // fragment-major e2m1 codes, a scale dword beside each load: a load is four 32-wide k steps
+constexpr int rows_fpl(int wf) { return 1 << wf; }    // 32-wide A fragments per weight load
+
+// KS weight loads per wave against KA = rows_fpl(WF) * KS activation fragments
+template <bool DUAL, int NW, int KS, bool PERS, int WF>
 __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a, const RowsAux x) {
+  constexpr bool F8 = WF == WF_FP8, MX = WF == WF_MXFP4;
   constexpr int T = NW * 64;
-  constexpr int KA = F8 ? 2 * KS : KS;              // 32-wide A fragments per wave
+  constexpr int FPL = rows_fpl(WF);
+  constexpr int KA = FPL * KS;                      // 32-wide A fragments per wave
   constexpr int NCH = (KA + 7) / 8;                 // 4-column chunks per thread per activation row
   constexpr int NM = DUAL ? 2 : 1;
   constexpr int PST = 128 * NM + 8;                 // floats per partial tile: [NM][8][16] sums + 8 partial sums of squares
@@ -103,14 +134,14 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   const int ks = blockIdx.y;
   const int K = a.k, N = a.n, mr = a.m;
   const int spw = x.spw, ksplit = x.ksplit, n_groups = x.n_groups;
-  const int spa = F8 ? 2 * spw : spw;               // 32-wide k steps per wave
-  const int steps_total = K >> 5;
-  const int wsteps_total = F8 ? K >> 6 : steps_total;
+  const int dbg = MX ? 0 : x.dbg;
+  const int spa = FPL * spw;                        // 32-wide k steps per wave
+  const int wsteps_total = K >> (MX ? 7 : F8 ? 6 : 5);
   const int step0 = ks * NW * spa;                  // first 32-wide k step of this block
   const int k0 = step0 << 5;
   const bool rms = a.pro == VV_PRO_RMSNORM;
   const bool has_nw = rms && a.norm_w != nullptr, has_mod = MOD_OK && a.mod_scale != nullptr;
-  const bool frag = (a.flags & VV_LIN_W_FRAG) != 0;
+  const bool frag = MX || (a.flags & VV_LIN_W_FRAG) != 0;
   const bool reused = (a.flags & VV_LIN_W_REUSED) != 0;
 
   // ---- requests, oldest first: activations, norm weight, modulation, epilogue operands, then the weights ----------------------------------
@@ -120,7 +151,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   for (int cc = 0; cc < NCH; ++cc) {
     const int q = tid + cc * T;
     cval[cc] = q < NW * spa * 8 && (k0 + 4 * q) < K;
-    const int kk = (cval[cc] && !(x.dbg & 4)) ? k0 + 4 * q : 4 * (tid & 7);
+    const int kk = (cval[cc] && !(dbg & 4)) ? k0 + 4 * q : 4 * (tid & 7);
 #pragma unroll
     for (int m = 0; m < 8; ++m) xv[m][cc] = *reinterpret_cast<const float4*>(a.x + (int64_t)(m < mr ? m : mr - 1) * a.ldx + kk);
     if (has_nw) nv[cc] = *reinterpret_cast<const float4*>(a.norm_w + kk);
@@ -140,7 +171,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   const int emr = em < mr ? em : mr - 1;
   auto load_eo = [&](int grp) {
     EpiOps e;
-    const int egn = min(min(grp, n_groups - 1) * 16 + en, N - 1);
+    int egn = min(grp, n_groups - 1) * 16 + en;
+    if constexpr (!MX) egn = min(egn, N - 1);       // MXFP4: N % 16 == 0, in bounds as it is
     const float* pb = a.bias ? a.bias + egn : a.x;
     const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)emr * a.gate_ld + egn : (int64_t)egn) : a.x;
     const float* pr = a.res ? a.res + (int64_t)emr * a.ldres + egn : a.x;
@@ -148,29 +180,48 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
     return e;
   };
   const int sb = step0 + wave * spa;                // this wave's first 32-wide k step
-  const int sbw = F8 ? sb >> 1 : sb;                // ... and its first weight load
+  const int sbw = MX ? ks * NW * spw + wave * spw : F8 ? sb >> 1 : sb;      // ... and its first weight load
   const bf16_t* __restrict__ W = reinterpret_cast<const bf16_t*>(a.w);
   const bf16_t* __restrict__ W2 = reinterpret_cast<const bf16_t*>(a.w2);
+  const unsigned char* __restrict__ WB = reinterpret_cast<const unsigned char*>(a.w);          // MXFP4: codes and scale bytes
+  const unsigned char* __restrict__ WB2 = reinterpret_cast<const unsigned char*>(a.w2);
+  const unsigned char* __restrict__ S = reinterpret_cast<const unsigned char*>(a.wscale);
+  const unsigned char* __restrict__ S2 = reinterpret_cast<const unsigned char*>(a.w2scale);
   // fp8: the row scale of this lane's weight row (n) in row group grp; N % 16 == 0, so the clamped group is in bounds
   auto wscale_of = [&](const float* sc, int grp) { return F8 ? sc[min(grp, n_groups - 1) * 16 + n] : 1.0f; };
-  auto issue = [&](u32x4 (&w)[KS], u32x4 (&w2)[DUAL ? KS : 1], int grp) {
+  // a load that is not live (past the row's end, past the last row group, j >= spw) reads the first load of the matrix: a valid address
+  auto issue = [&](u32x4 (&w)[KS], unsigned (&e)[MX ? KS : 1], u32x4 (&w2)[DUAL ? KS : 1], unsigned (&e2)[(MX && DUAL) ? KS : 1], int grp) {
     const bool glive = grp < n_groups;
-    int64_t base;                                   // in bf16 elements (fp8: two codes per element)
-    if (frag) base = ((int64_t)grp * wsteps_total) * 512 + lane * 8;
-    else base = (int64_t)min(grp * 16 + n, N - 1) * K + c * 8;
+    int64_t base = 0;                               // in bf16 elements (fp8: two codes per element)
+    if constexpr (!MX) {
+      if (frag) base = ((int64_t)grp * wsteps_total) * 512 + lane * 8;
+      else base = (int64_t)min(grp * 16 + n, N - 1) * K + c * 8;
+    }
     const int64_t sstep = frag ? 512 : 32;
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
       const bool live = glive && j < spw && sbw + j < wsteps_total;
-      const int64_t off = live ? base + (int64_t)(sbw + j) * sstep : 0;
-      const u32x4* p1 = reinterpret_cast<const u32x4*>(W + off);
-      const u32x4* p2 = reinterpret_cast<const u32x4*>(W2 + off);
+      const u32x4 *p1, *p2;
+      const unsigned *q1 = nullptr, *q2 = nullptr;  // MXFP4: the load's scale dword, 4 bytes per weight row
+      if constexpr (MX) {
+        const int64_t ld = live ? (int64_t)grp * wsteps_total + (sbw + j) : 0;
+        p1 = reinterpret_cast<const u32x4*>(WB + (ld * 64 + lane) * 16);
+        q1 = reinterpret_cast<const unsigned*>(S + (ld * 16 + n) * 4);
+        p2 = reinterpret_cast<const u32x4*>(WB2 + (ld * 64 + lane) * 16);
+        q2 = reinterpret_cast<const unsigned*>(S2 + (ld * 16 + n) * 4);
+      } else {
+        const int64_t off = live ? base + (int64_t)(sbw + j) * sstep : 0;
+        p1 = reinterpret_cast<const u32x4*>(W + off);
+        p2 = reinterpret_cast<const u32x4*>(W2 + off);
+      }
       if (reused) {
         w[j] = *p1;
-        if (DUAL) w2[j] = *p2;
+        if constexpr (MX) e[j] = *q1;
+        if (DUAL) { w2[j] = *p2; if constexpr (MX) e2[j] = *q2; }
       } else {
         w[j] = __builtin_nontemporal_load(p1);
-        if (DUAL) w2[j] = __builtin_nontemporal_load(p2);
+        if constexpr (MX) e[j] = __builtin_nontemporal_load(q1);
+        if (DUAL) { w2[j] = __builtin_nontemporal_load(p2); if constexpr (MX) e2[j] = __builtin_nontemporal_load(q2); }
       }
     }
   };
@@ -178,14 +229,16 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
   int g = blockIdx.x;
   u32x4 wc[KS], wc2[DUAL ? KS : 1];
   u32x4 wn[PERS ? KS : 1], wn2[(PERS && DUAL) ? KS : 1];
+  unsigned ec[MX ? KS : 1], ec2[(MX && DUAL) ? KS : 1];                       // MXFP4: the loads' scale dwords
+  unsigned en_[(MX && PERS) ? KS : 1], en2[(MX && PERS && DUAL) ? KS : 1];
   EpiOps eo = load_eo(g), eo_n = eo;
-  float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;
+  float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;                         // fp8: the row scales
   if constexpr (F8) { sc = wscale_of(a.wscale, g); if (DUAL) sc2 = wscale_of(a.w2scale, g); }
-  issue(wc, wc2, g);
+  issue(wc, ec, wc2, ec2, g);
   if constexpr (PERS) {
     eo_n = load_eo(g + gstride);
     if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-    issue(wn, wn2, g + gstride);
+    issue(wn, en_, wn2, en2, g + gstride);
   }
   __builtin_amdgcn_sched_barrier(0);
 #define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
@@ -287,6 +340,16 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
             acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j]), b0, acc2, 0, 0, 0);
             acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j + 1]), b1, acc2, 0, 0, 0);
           }
+        } else if constexpr (MX) {       // the four 32-wide steps of the load in k order: the summation order of the bf16 kernel
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            const bf16x8 b = mx_frag(wc[j][h], (ec[j] >> (8 * h)) & 0xffu);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[4 * j + h]), b, acc, 0, 0, 0);
+            if (DUAL) {
+              const bf16x8 b2 = mx_frag(wc2[j][h], (ec2[j] >> (8 * h)) & 0xffu);
+              acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[4 * j + h]), b2, acc2, 0, 0, 0);
+            }
+          }
         } else {
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc[j]), acc, 0, 0, 0);
           if (DUAL) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc2[j]), acc2, 0, 0, 0);
@@ -321,7 +384,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
       }
       return;
     }
-    if (!PERS && ksplit > 1 && !(x.dbg & 2)) {
+    if (!PERS && ksplit > 1 && !(dbg & 2)) {
       // partial tile out (write-through), ticket, the last block of the row group folds
       float* pp = x.part + ((int64_t)g * ksplit + ks) * PST;
       if (tid < 128) {
@@ -376,11 +439,14 @@ __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a,
       eo = eo_n;
       sc = sn; sc2 = sn2;
 #pragma unroll
-      for (int j = 0; j < KS; ++j) { wc[j] = wn[j]; if (DUAL) wc2[j] = wn2[j]; }
+      for (int j = 0; j < KS; ++j) {
+        wc[j] = wn[j]; if (DUAL) wc2[j] = wn2[j];
+        if constexpr (MX) { ec[j] = en_[j]; if (DUAL) ec2[j] = en2[j]; }
+      }
       if (g + gstride < n_groups) {
         eo_n = load_eo(g + gstride);
         if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-        issue(wn, wn2, g + gstride);
+        issue(wn, en_, wn2, en2, g + gstride);
       }
     }
   }
@@ -393,16 +459,29 @@ int g_rows_pers = 192;      // persistent blocks of the whole-row SwiGLU kernels
 int g_rows_dbg = 0;
 int g_rows_atomic = 1;      // tuning hook "gemv_rows_atomic": 0 = always fold K slices through the ticket (deterministic summation order)
 
-template <bool DUAL, int NW, int KS, bool PERS, bool F8 = false>
+template <bool DUAL, int NW, int KS, bool PERS, int WF>
 int launch_cfg(const vv_lin_args& a, const RowsAux& x, int gx, hipStream_t s) {
-  const size_t lds = (size_t)NW * (F8 ? 2 * KS : KS) * 64 * 16;   // the LDS limit of every instantiation is raised in vv_gemv_rows_init (not capturable)
-  hipLaunchKernelGGL((gemv_rows_kernel<DUAL, NW, KS, PERS, F8>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
+  const size_t lds = (size_t)NW * rows_fpl(WF) * KS * 64 * 16;    // the LDS limit of every instantiation is raised in vv_gemv_rows_init (not capturable)
+  hipLaunchKernelGGL((gemv_rows_kernel<DUAL, NW, KS, PERS, WF>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
   return 1;
 }
 
-// the decision's template choice: gemv_rows_kernel<dual, nw, ks, pers, f8> and its grid
-void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int f8) {
-  r.dual = dual; r.nw = nw; r.ks = ks; r.pers = pers; r.f8 = f8;
+// Every kernel of this file, as (dual, nw, ks, pers, wf) - exactly what vv_gemv_rows_decide can choose: per format the whole-row kernels (8 waves;
+// SwiGLU also persistent), the SwiGLU K split (the same one-shot kernels) and the single-matrix K split (4 waves)
+#define VV_ROWS_ALL(X)                                                                                                         \
+  X(0, 8, 4, 0, WF_BF16) X(0, 8, 6, 0, WF_BF16) X(0, 8, 8, 0, WF_BF16)                                                         \
+  X(1, 8, 4, 0, WF_BF16) X(1, 8, 6, 0, WF_BF16) X(1, 8, 8, 0, WF_BF16) X(1, 8, 4, 1, WF_BF16) X(1, 8, 6, 1, WF_BF16)           \
+  X(0, 4, 3, 0, WF_BF16) X(0, 4, 6, 0, WF_BF16) X(0, 4, 9, 0, WF_BF16) X(0, 4, 12, 0, WF_BF16)                                 \
+  X(0, 8, 2, 0, WF_FP8) X(0, 8, 4, 0, WF_FP8)                                                                                  \
+  X(1, 8, 2, 0, WF_FP8) X(1, 8, 4, 0, WF_FP8) X(1, 8, 2, 1, WF_FP8) X(1, 8, 4, 1, WF_FP8)                                      \
+  X(0, 4, 2, 0, WF_FP8) X(0, 4, 4, 0, WF_FP8) X(0, 4, 6, 0, WF_FP8) X(0, 4, 8, 0, WF_FP8)                                      \
+  X(0, 8, 1, 0, WF_MXFP4) X(0, 8, 2, 0, WF_MXFP4)                                                                              \
+  X(1, 8, 1, 0, WF_MXFP4) X(1, 8, 2, 0, WF_MXFP4) X(1, 8, 1, 1, WF_MXFP4) X(1, 8, 2, 1, WF_MXFP4)                              \
+  X(0, 4, 1, 0, WF_MXFP4) X(0, 4, 2, 0, WF_MXFP4) X(0, 4, 3, 0, WF_MXFP4) X(0, 4, 4, 0, WF_MXFP4)
+
+// the decision's template choice: gemv_rows_kernel<dual, nw, ks, pers, wf> and its grid
+void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int wf) {
+  r.dual = dual; r.nw = nw; r.ks = ks; r.pers = pers; r.wf = wf;
   r.gx = r.n_groups;
   if (pers && r.gx > g_rows_pers) {                     // the same number of row groups for every block
     const int per = (r.n_groups + g_rows_pers - 1) / g_rows_pers;
@@ -411,39 +490,36 @@ void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int f8) {
   r.kind = 1;
 }
 
-// fp8 fragment-major weights.  A 64-wide weight load costs 4 VGPRs per matrix (8 in flight per persistent buffer pair) and its two activation
-// fragments 8: KS = 4 holds the whole K <= 2048 row in 8 waves and leaves the persistent dual form 64 weight + 32 fragment VGPRs, so fp8 runs
-// persistent at every whole-row width; the single-matrix split-K form goes up to 8 loads (8 KB in flight per wave, as the bf16 form's 8 - 12).
-void decide_fp8(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets, vv_rows_route& r) {
+// The K split of a long row (`steps` weight loads, NW waves per block), for every format: the first split whose waves take <= kscap loads and that
+// gives g_rows_blocks workgroups (or leaves <= `few` loads per wave), else the first with <= ksmax loads.  Sets r.ksplit, r.spw and r.atomic;
+// false = no split within MAXSPLIT, or the fold needs a workspace that is not there.
+bool rows_split(const vv_lin_args& a, int steps, int n_groups, int NW, int kscap, int ksmax, int few, bool have_ws, size_t part_floats,
+                size_t n_tickets, vv_rows_route& r) {
   const bool dual = a.w2 != nullptr;
-  const int steps = a.k / 64, n_groups = a.n / 16;
-  r.n_groups = n_groups; r.atomic = 0;
-  if (steps <= 32) {                                  // K <= 2048: whole rows per block
-    r.ksplit = 1;
-    r.spw = (steps + 7) / 8;
-    if (dual) rows_cfg(r, 1, 8, r.spw <= 2 ? 2 : 4, n_groups > g_rows_pers, 1);
-    else rows_cfg(r, 0, 8, r.spw <= 2 ? 2 : 4, 0, 1);
-    return;
-  }
-  if (a.mod_scale) return;
-  const int NW = dual ? 8 : 4, kscap = dual ? 4 : 6, ksmax = dual ? 4 : 8;
   int ksplit = 0, spw = 0;
   for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
     const int w = (steps + sp * NW - 1) / (sp * NW);
-    if (w <= kscap && ((long)n_groups * sp >= g_rows_blocks || w <= 2)) { ksplit = sp; spw = w; }
+    if (w <= kscap && ((long)n_groups * sp >= g_rows_blocks || w <= few)) { ksplit = sp; spw = w; }
   }
   for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
     const int w = (steps + sp * NW - 1) / (sp * NW);
     if (w <= ksmax) { ksplit = sp; spw = w; }
   }
-  if (!ksplit) return;
-  while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;
+  if (!ksplit) return false;
+  while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;     // drop K slices that would start past the end
   const size_t pst = dual ? 264 : 136;
   r.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
-  if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return;
+  if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return false;
   r.ksplit = ksplit; r.spw = spw;
-  if (dual) rows_cfg(r, 1, 8, spw <= 2 ? 2 : 4, 0, 1);
-  else rows_cfg(r, 0, 4, spw <= 2 ? 2 : spw <= 4 ? 4 : spw <= 6 ? 6 : 8, 0, 1);
+  return true;
+}
+
+// The smallest built KS that holds spw loads per wave.  wide: the 8-wave kernels (whole rows, SwiGLU K split); else the 4-wave single-matrix K split.
+int rows_ks(int wf, bool wide, int spw) {
+  if (wf == WF_MXFP4) return spw;                       // every KS the decision can ask for is built
+  if (wf == WF_FP8) return spw <= 2 ? 2 : spw <= 4 || wide ? 4 : spw <= 6 ? 6 : 8;
+  if (wide) return spw <= 4 ? 4 : spw <= 6 ? 6 : 8;
+  return spw <= 3 ? 3 : spw <= 6 ? 6 : spw <= 9 ? 9 : 12;
 }
 
 }  // namespace
@@ -462,71 +538,61 @@ size_t vv_gemv_rows_tickets(int n) { return (size_t)((n + 15) / 16); }
 
 // every kernel's LDS attribute is set before any graph capture (hipFuncSetAttribute is not capturable)
 int vv_gemv_rows_init() {
-#define VV_ROWS_ATTR_F(D, NW, KS, P, F8)                                                                                                  \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<D, NW, KS, P, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                          NW * (F8 ? 2 * KS : KS) * 64 * 16) != hipSuccess)                                                              \
+#define VV_ROWS_ATTR(D, NW, KS, P, WF)                                                                                                       \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<(D != 0), NW, KS, (P != 0), WF>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                          NW * rows_fpl(WF) * KS * 64 * 16) != hipSuccess)                                                                \
     return vv_set_error(VV_E_HIP, "gemv_rows: cannot raise the dynamic LDS limit");
-#define VV_ROWS_ATTR(D, NW, KS, P) VV_ROWS_ATTR_F(D, NW, KS, P, false)
-  VV_ROWS_ATTR(false, 4, 3, false) VV_ROWS_ATTR(false, 4, 6, false) VV_ROWS_ATTR(false, 4, 9, false) VV_ROWS_ATTR(false, 4, 12, false)
-  VV_ROWS_ATTR(false, 8, 4, false) VV_ROWS_ATTR(false, 8, 6, false) VV_ROWS_ATTR(false, 8, 8, false)
-  VV_ROWS_ATTR(true, 8, 4, false) VV_ROWS_ATTR(true, 8, 6, false) VV_ROWS_ATTR(true, 8, 8, false)
-  VV_ROWS_ATTR(true, 8, 4, true) VV_ROWS_ATTR(true, 8, 6, true)
-  VV_ROWS_ATTR_F(false, 8, 2, false, true) VV_ROWS_ATTR_F(false, 8, 4, false, true)
-  VV_ROWS_ATTR_F(true, 8, 2, false, true) VV_ROWS_ATTR_F(true, 8, 4, false, true) VV_ROWS_ATTR_F(true, 8, 2, true, true) VV_ROWS_ATTR_F(true, 8, 4, true, true)
-  VV_ROWS_ATTR_F(false, 4, 2, false, true) VV_ROWS_ATTR_F(false, 4, 4, false, true) VV_ROWS_ATTR_F(false, 4, 6, false, true) VV_ROWS_ATTR_F(false, 4, 8, false, true)
+  VV_ROWS_ALL(VV_ROWS_ATTR)
 #undef VV_ROWS_ATTR
-#undef VV_ROWS_ATTR_F
   return 0;
 }
 
 // The decision: which instantiation the call takes, its K split and grid; kind 0 = not covered (the caller falls back).  have_ws: a split-K
 // workspace of part_floats floats and n_tickets tickets exists (without one only shapes that need no K split, or the atomic form, are taken).
-// fp8 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
+// fp8 and MXFP4 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
+//
+// The three formats share the pattern and differ in the width of a weight load (32, 64, 128 k) and in what a load costs in registers:
+//   bf16    4 VGPRs per load and matrix, 4 of activation fragment: 8 loads hold the whole K <= 2048 row in 8 waves; the single-matrix split-K
+//           form goes up to 12 loads per wave.
+//   fp8     a 64-wide load costs 4 VGPRs per matrix (8 in flight per persistent buffer pair) and its two activation fragments 8: KS = 4 holds the
+//           whole row and leaves the persistent dual form 64 weight + 32 fragment VGPRs, so fp8 runs persistent at every whole-row width; the
+//           single-matrix split-K form goes up to 8 loads (8 KB in flight per wave, as the bf16 form's 8 - 12).
+//   MXFP4   a 128-wide load costs 4 VGPRs of codes + 1 of scale bytes per matrix and 16 of activation fragments, and 4 KB of LDS per wave: two loads
+//           hold the whole row (one chunk per thread: the adaLN prologue fits), the single-matrix split-K form goes up to 4 loads per wave
+//           (64 fragment VGPRs, 64 KB of LDS per block).
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets) {
   vv_rows_route r = {};
-  const bool f8 = a.wdt == VV_FP8;
-  if (!g_rows_on || (a.wdt != VV_BF16 && !f8) || a.m < 3 || a.m > 8 || a.k % 32 || a.k < 32) return r;
+  const int wf = a.wdt == VV_BF16 ? WF_BF16 : a.wdt == VV_FP8 ? WF_FP8 : a.wdt == VV_MXFP4_FRAG ? WF_MXFP4 : -1;
+  if (!g_rows_on || wf < 0 || a.m < 3 || a.m > 8) return r;
+  const int kw = 32 * rows_fpl(wf);                   // k per weight load
+  if (a.k % kw || a.k < kw) return r;
   if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return r;
   if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16 || a.ldx % 4) return r;
   if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
   if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return r;
-  if (f8) {
-    if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale)) return r;
-    decide_fp8(a, have_ws, part_floats, n_tickets, r);
-    return r;
-  }
-  if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return r;
+  if (wf == WF_BF16) {
+    if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return r;
+  } else if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || !a.wscale || (a.w2 && !a.w2scale)) return r;
+  if (wf == WF_MXFP4 && (a.n < 16 || (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4))) return r;
   const bool dual = a.w2 != nullptr;
-  const int steps = a.k / 32, n_groups = (a.n + 15) / 16;
+  const int steps = a.k / kw, n_groups = (a.n + 15) / 16;
   r.n_groups = n_groups; r.atomic = 0;
-  // whole rows per block when K <= 2048 (8 waves x <= 8 steps): no cross-block reduction at all
-  if (steps <= 64) {
+  // whole rows per block when K <= 2048 (8 waves x <= 8 bf16 loads): no cross-block reduction at all
+  if (a.k <= 2048) {
     r.ksplit = 1;
     r.spw = (steps + 7) / 8;
-    const bool pers = dual && n_groups > g_rows_pers && r.spw <= 6;      // 8 steps x 2 matrices x 2 buffers do not fit the registers
-    rows_cfg(r, dual, 8, r.spw <= 4 ? 4 : r.spw <= 6 ? 6 : 8, pers, 0);
+    // persistent when the row groups outnumber the blocks aimed for; bf16: 8 steps x 2 matrices x 2 buffers do not fit the registers
+    const bool pers = dual && n_groups > g_rows_pers && (wf != WF_BF16 || r.spw <= 6);
+    rows_cfg(r, dual, 8, rows_ks(wf, true, r.spw), pers, wf);
     return r;
   }
   // long rows: K slices across blocks, folded by the last arriver
   if (a.mod_scale) return r;                          // the modulated prologue needs the whole row's statistic up front
-  const int NW = dual ? 8 : 4, kscap = dual ? 8 : 9, ksmax = dual ? 8 : 12;
-  int ksplit = 0, spw = 0;
-  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
-    const int w = (steps + sp * NW - 1) / (sp * NW);
-    if (w <= kscap && ((long)n_groups * sp >= g_rows_blocks || w <= 3)) { ksplit = sp; spw = w; }
-  }
-  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
-    const int w = (steps + sp * NW - 1) / (sp * NW);
-    if (w <= ksmax) { ksplit = sp; spw = w; }
-  }
-  if (!ksplit) return r;
-  while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;     // drop K slices that would start past the end
-  const size_t pst = dual ? 264 : 136;
-  r.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
-  if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return r;
-  r.ksplit = ksplit; r.spw = spw;
-  if (dual) rows_cfg(r, 1, 8, spw <= 4 ? 4 : spw <= 6 ? 6 : 8, 0, 0);
-  else rows_cfg(r, 0, 4, spw <= 3 ? 3 : spw <= 6 ? 6 : spw <= 9 ? 9 : 12, 0, 0);
+  // loads per wave the split aims for and accepts at most, [format][dual], and the few loads below which more blocks are not worth another slice
+  static const int KSCAP[3][2] = {{9, 8}, {6, 4}, {3, 2}}, KSMAX[3][2] = {{12, 8}, {8, 4}, {4, 2}}, FEW[3] = {3, 2, 1};
+  const int NW = dual ? 8 : 4;
+  if (!rows_split(a, steps, n_groups, NW, KSCAP[wf][dual], KSMAX[wf][dual], FEW[wf], have_ws, part_floats, n_tickets, r)) return r;
+  rows_cfg(r, dual, NW, rows_ks(wf, dual, r.spw), 0, wf);
   return r;
 }
 
@@ -536,22 +602,18 @@ int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, floa
   if (r.kind != 1) return 0;
   RowsAux x;
   x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = r.n_groups; x.atomic = r.atomic; x.ksplit = r.ksplit; x.spw = r.spw;
-#define VV_ROWS_CASE(D, NW, KS, P, F8) \
-  if (r.dual == D && r.nw == NW && r.ks == KS && r.pers == P && r.f8 == F8) return launch_cfg<(D != 0), NW, KS, (P != 0), (F8 != 0)>(a, x, r.gx, s);
-  VV_ROWS_CASE(0, 4, 3, 0, 0) VV_ROWS_CASE(0, 4, 6, 0, 0) VV_ROWS_CASE(0, 4, 9, 0, 0) VV_ROWS_CASE(0, 4, 12, 0, 0)
-  VV_ROWS_CASE(0, 8, 4, 0, 0) VV_ROWS_CASE(0, 8, 6, 0, 0) VV_ROWS_CASE(0, 8, 8, 0, 0)
-  VV_ROWS_CASE(1, 8, 4, 0, 0) VV_ROWS_CASE(1, 8, 6, 0, 0) VV_ROWS_CASE(1, 8, 8, 0, 0)
-  VV_ROWS_CASE(1, 8, 4, 1, 0) VV_ROWS_CASE(1, 8, 6, 1, 0)
-  VV_ROWS_CASE(0, 8, 2, 0, 1) VV_ROWS_CASE(0, 8, 4, 0, 1)
-  VV_ROWS_CASE(1, 8, 2, 0, 1) VV_ROWS_CASE(1, 8, 4, 0, 1) VV_ROWS_CASE(1, 8, 2, 1, 1) VV_ROWS_CASE(1, 8, 4, 1, 1)
-  VV_ROWS_CASE(0, 4, 2, 0, 1) VV_ROWS_CASE(0, 4, 4, 0, 1) VV_ROWS_CASE(0, 4, 6, 0, 1) VV_ROWS_CASE(0, 4, 8, 0, 1)
+#define VV_ROWS_CASE(D, NW, KS, P, WF) \
+  if (r.dual == D && r.nw == NW && r.ks == KS && r.pers == P && r.wf == WF) return launch_cfg<(D != 0), NW, KS, (P != 0), WF>(a, x, r.gx, s);
+  VV_ROWS_ALL(VV_ROWS_CASE)
 #undef VV_ROWS_CASE
   return 0;
 }
 
 // the name vv_linear_route reports for this file's route: spelled here and nowhere else
 int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap) {
-  return snprintf(name, (size_t)cap, "gemv_rows<dual=%d,nw=%d,ks=%d,pers=%d,f8=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.f8, r.ksplit, r.atomic);
+  if (r.wf == WF_MXFP4)
+    return snprintf(name, (size_t)cap, "gemv_rows_mx<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
+  return snprintf(name, (size_t)cap, "gemv_rows<dual=%d,nw=%d,ks=%d,pers=%d,f8=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.wf, r.ksplit, r.atomic);
 }
 
 // decide + launch: 1 launched, 0 not covered (the caller falls back), < 0 error

@@ -37,7 +37,6 @@ extern "C" int vv_init(void) {
   VV_TRY(vv_block1d_init());
   VV_TRY(vv_convffn_init());
   VV_TRY(vv_gemv_rows_init());
-  VV_TRY(vv_gemv_rows_mx_init());
   return vv_fused_init();
 }
 // process-wide split-K scratch of the 3..8-row matrix-core GEMV for PUBLIC vv_linear calls (micro-benchmarks and tests only, switched on by
@@ -80,12 +79,12 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
   if (key && !strcmp(key, "gemv_blocks")) { vv_gemv_stream_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_mx_blocks")) { vv_gemv_mx_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_waves")) { vv_gemv_stream_set_waves(value); return 0; }
-  if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); vv_gemv_rows_mx_set(value, 0, -1, -1); return 0; }
-  if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); vv_gemv_rows_mx_set(-1, value, -1, -1); return 0; }
-  if (key && !strcmp(key, "gemv_rows_pers")) { vv_gemv_rows_set(-1, 0, value); vv_gemv_rows_mx_set(-1, 0, value, -1); return 0; }
+  if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); return 0; }
+  if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); return 0; }
+  if (key && !strcmp(key, "gemv_rows_pers")) { vv_gemv_rows_set(-1, 0, value); return 0; }
   if (key && !strcmp(key, "gemv_rows_scratch")) return rows_scratch(value);
   if (key && !strcmp(key, "gemv_rows_dbg")) { vv_gemv_rows_set_dbg(value); return 0; }
-  if (key && !strcmp(key, "gemv_rows_atomic")) { vv_gemv_rows_set_atomic(value); vv_gemv_rows_mx_set(-1, 0, -1, value != 0); return 0; }
+  if (key && !strcmp(key, "gemv_rows_atomic")) { vv_gemv_rows_set_atomic(value); return 0; }
   if (key && !strcmp(key, "gemv_opt")) { vv_gemv_stream_set_opt(value); return 0; }
   if (key && !strcmp(key, "gemv_dual_rw")) { vv_gemv_stream_set_dual_rw(value); return 0; }
   if (key && !strcmp(key, "gemv_small_rw")) { vv_gemv_stream_set_small_rw(value); return 0; }
@@ -501,10 +500,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
 // The m <= 8 family's decision (vv_linear launches it, vv_linear_route prints it): the 3..8-row matrix-core GEMV when the process-wide scratch is
 // on, the weight-streaming GEMV (or a hot kernel), two streaming passes of 4 + rest rows, the LDS-staged gemv_kernel<WT, M, DUAL, KS, NP> or the
 // generic kernel.  Plain values only: no pointer is followed, nothing is launched; the thresholds live here and in the two deciders it calls.
-enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX, GEMV_ROWS_MX };
+enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX };
 struct gemv_route {
   int kind;
-  vv_rows_route rows;                // GEMV_ROWS, or GEMV_ROWS_MX: the same GEMV on VV_MXFP4_FRAG weights (vv_gemv_rows_mx.hip)
+  vv_rows_route rows;                // GEMV_ROWS
   vv_stream_route st, st2;          // GEMV_SPLIT: rows 0..3 and the rest
   vv_mx_route mx;                   // GEMV_MX: the MXFP4 streaming GEMV (vv_gemv_mx.hip)
   int m, dual, ks, np, kc, blocks;  // GEMV_LDS: gemv_kernel<WT, m, dual, ks, np> staging kc columns at a time; GEMV_GENERIC: blocks
@@ -562,9 +561,9 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)", a.m, a.n, a.k);
   }
   if (a.wdt == VV_MXFP4_FRAG) {
-    // fragment-major MXFP4: the 3..8-row matrix-core GEMV of vv_gemv_rows_mx.hip and nothing else (process-wide split-K scratch as for bf16)
-    g->rows = vv_gemv_rows_mx_decide(a, g_rows_part != nullptr, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
-    if (g->rows.kind) { g->kind = GEMV_ROWS_MX; return 0; }
+    // fragment-major MXFP4: the 3..8-row matrix-core GEMV and nothing else (process-wide split-K scratch as for bf16)
+    g->rows = vv_gemv_rows_decide(a, g_rows_part != nullptr, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
+    if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights need VV_LIN_W_FRAG, 3..8 rows, n %% 16 == 0, k %% 128 == 0, scale bytes, 16-byte aligned codes "
                         "and activations, 4-byte aligned scales, fp32 activations and outputs, and split-K scratch for k > 2048 (m=%d n=%d k=%d flags=%d)",
                         a.m, a.n, a.k, a.flags);
@@ -618,7 +617,6 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
 static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* name, int cap) {
   const char* w = a.wdt == VV_F32 ? "f32" : "bf16";
   if (g.kind == GEMV_ROWS) vv_gemv_rows_route_name(g.rows, name, cap);
-  else if (g.kind == GEMV_ROWS_MX) vv_gemv_rows_mx_route_name(g.rows, name, cap);
   else if (g.kind == GEMV_STREAM) vv_gemv_stream_route_name(g.st, name, cap);
   else if (g.kind == GEMV_MX) vv_gemv_mx_route_name(g.mx, name, cap);
   else if (g.kind == GEMV_SPLIT) {
@@ -669,7 +667,6 @@ template <typename WT>
 static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStream_t s) {
   switch (g.kind) {
     case GEMV_ROWS: return vv_launch_gemv_rows_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: rows GEMV declined its own route");
-    case GEMV_ROWS_MX: return vv_launch_gemv_rows_mx_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP4 rows GEMV declined its own route");
     case GEMV_STREAM: return vv_launch_gemv_stream_route(a, g.st, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: streaming GEMV declined its own route");
     case GEMV_MX: return vv_launch_gemv_mx_route(a, g.mx, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP4 GEMV declined its own route");
     case GEMV_SPLIT: {
@@ -875,7 +872,7 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 // vv_linear for the composites of a row-batched step: 3..8 rows go to the matrix-core GEMV with the caller's split-K workspace, on the
 // fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices.
 // q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*).
-// frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form (codes, scale bytes behind them) and go to vv_gemv_rows_mx.hip; a matrix without
+// frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form (codes, scale bytes behind them) for the same kernel; a matrix without
 // such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
                  const vv_w8* q1, const vv_w8* q2, bool frag4) {
@@ -900,8 +897,7 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
       if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
       (void)hipEventRecord(pr.e0, (hipStream_t)stream);
     }
-    const int rc = mx ? vv_launch_gemv_rows_mx(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream)
-                      : vv_launch_gemv_rows(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream);
+    const int rc = vv_launch_gemv_rows(b, part, part_floats, tickets, n_tickets, (hipStream_t)stream);
     if (prof) {
       if (rc == 1) { (void)hipEventRecord(pr.e1, (hipStream_t)stream); prof_keep(pr); }
       else { (void)hipEventDestroy(pr.e0); (void)hipEventDestroy(pr.e1); }

@@ -669,7 +669,7 @@ class VibeVoiceForConditionalGenerationInference:
                 raise ValueError(f"a pre-quantized bitsandbytes NF4 checkpoint runs as weight_quant='nf4', not {weight_quant!r}")
             weight_quant, torch_dtype = "nf4", torch.bfloat16
         # mxfp4_row_batch=True (weight_quant="mxfp4" only): batches of row_batch_min..16 dialogues and serving sessions run the row-batched path on
-        # fragment-major copies of the MXFP4 codes and scale bytes (csrc/vv_gemv_rows_mx.hip; +0.53 B per copied weight).
+        # fragment-major copies of the MXFP4 codes and scale bytes (csrc/vv_gemv_rows.hip; +0.53 B per copied weight).
         # Off by default: the batch then runs on the lanes and open_session refuses the mode, as before
         if mxfp4_row_batch and weight_quant != "mxfp4":
             raise ValueError(f"mxfp4_row_batch=True needs weight_quant='mxfp4', not {weight_quant!r}")

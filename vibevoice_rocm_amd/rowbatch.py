@@ -6,7 +6,7 @@ B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in on
   graph A   Qwen2 decode step with R = 2 B rows (dialogue b = rows {2 b: positive, 2 b + 1: negative} of x, lens and one KV cache with 2 B
             rows): every weight matrix is read once for all dialogues (4..8 rows: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
             fragment-major weight copies - of the e4m3 codes with weight_quant="fp8", of the MXFP4 codes and scale bytes with weight_quant="mxfp4" and
-            mxfp4_row_batch=True (csrc/vv_gemv_rows_mx.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
+            mxfp4_row_batch=True (csrc/vv_gemv_rows.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
             bookkeeping per dialogue.  With do_sample it splits as Engine.step_decode does: A1 = the decode step and the constrained logits
             (no position bookkeeping), one host read-back of every row batch's logits, the tokens drawn on the host, A2 = the bookkeeping with
             those tokens as forced tokens;

@@ -149,7 +149,7 @@ def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict
 MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 MXFP4_BLOCK = 32
 MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
-# limits of the MX rows kernel's decision (csrc/vv_gemv_rows_mx.hip, vv_gemv_rows_mx_decide) that the host acts on: the adaLN-modulated prologue
+# limits of the MX rows kernel's decision (csrc/vv_gemv_rows.hip, vv_gemv_rows_decide) that the host acts on: the adaLN-modulated prologue
 # is served on whole rows only (K <= 2048); the SwiGLU pair splits K two ways at most inside the row-batched step's partials workspace
 # (csrc/vv_model.hip, rows_part_floats), 2 slices x 8 waves x 2 loads x 128 = 4096
 MXFP4_ROWS_MOD_K, MXFP4_ROWS_MAX_HIDDEN = 2048, 4096
