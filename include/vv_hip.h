@@ -83,7 +83,8 @@ enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
  * prologue on a bf16 x), a hint that the weights are re-read soon (keep them cacheable instead of streaming them
  * non-temporally: the diffusion head's matrices are reused by every one of the N solver steps of a frame), and
  * VV_LIN_W_FRAG: w / w2 point at the fragment-major copies of the matrices (vv_llm_layer.f_*; 3..8 rows, n % 16 == 0, bf16 with k % 32 == 0 or
- * fp8 codes with k % 64 == 0 and wscale (w2scale) - any other call with this flag is an error) */
+ * fp8 codes with k % 64 == 0 and wscale (w2scale); bf16 copies also at 9..16 rows, the 16-row form of the same GEMV - any other call with this
+ * flag is an error) */
 enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8 };
 
 const char* vv_last_error(void);
@@ -142,6 +143,7 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)
  *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
  *   "gemv_rows_mx<dual=0,nw=4,ks=3,pers=0> ksplit=6 atomic=0"              the same on VV_MXFP4_FRAG weights (ks: 128-wide weight loads per wave)
+ *   "gemv_rows16<dual=0,nw=4,ks=3,pers=0> ksplit=5 atomic=0"               9..16 rows on VV_LIN_W_FRAG bf16 weights: two row tiles per weight load (same condition)
  *   "gemv_hot<3>", "conv_hot_gemv<0>"                                      hot kernels, by table index
  *   "gemv_stream<m=4,...> + gemv_stream<m=2,...>"                          5..8 rows as two streaming passes of 4 + rest rows
  *   "gemv_lds<w=f32,m=3,dual=0,ks=4,np=2>", "gemv_generic<w=bf16>"         the LDS-staged and the generic fall-back
@@ -281,7 +283,7 @@ typedef struct vv_llm_layer {
   const void* wdown; /* [hidden, inter] */
   vv_w8 q_qkv, q_o, q_gate, q_up, q_down;
   /* optional fragment-major copies of the five matrices (NULL: none) for a row-batched decode step (4..8 rows = {positive, negative} x 2..4
-   * dialogues, vv_gemv_rows.hip).
+   * dialogues; with bf16 copies in every layer also 10..16 rows = 5..8 dialogues; vv_gemv_rows.hip).
    *   bf16 (the matrix has no fp8 companion, q_*.q == NULL): [N / 16][K / 32][4][16][8] bf16, i.e. element (16 g + n, 32 j + 8 c + e) of the
    *   row-major matrix at ((g * K/32 + j) * 64 + 16 c + n) * 8 + e - one matrix-core B fragment per 1 KB of contiguous memory.  N % 16 == 0,
    *   K % 32 == 0.
@@ -316,7 +318,7 @@ int vv_llm_tail(const vv_llm* m, const float* h, int64_t ldh, int R, float* out,
                 float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion, int* frame_counter,
                 vv_stream_t stream);
 
-/* One decode step for B dialogues batched into the row dimension: vv_llm_forward with R = 2 B rows (dialogue b = rows 2 b, 2 b + 1 of x, lens and
+/* One decode step for B <= 8 dialogues batched into the row dimension: vv_llm_forward with R = 2 B rows (dialogue b = rows 2 b, 2 b + 1 of x, lens and
  * of a KV cache with rows >= 2 B) streams the weights once for all of them; vv_llm_tail_batch then does for every dialogue what vv_llm_tail does
  * for one: h = the un-normalised rows at the start of the LLM workspace, out[2 B, hidden], logits_out[B][8], token_out[B], forced_token[B] or NULL,
  * lens[2 B], frame_counter[B]; active[B] (or NULL = all): a dialogue with active == 0 has finished - its rows are computed and dropped, its
@@ -421,7 +423,7 @@ int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const 
                    const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, void* ws,
                    const float* sde_noise /* [n_steps, latent] per-step variance noise of the SDE solver (dpm_solver.py:993-998) or NULL */,
                    vv_stream_t stream);
-/* sample_speech_tokens for B utterances at once (B <= 4; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights, with
+/* sample_speech_tokens for B utterances at once (B <= 8; 5..8 - 10..16 rows - on the bf16 matrices and their bf16 fragment-major copies alone; the ODE solver on the fused boundary - SDE coefficients return VV_E_UNSUPPORTED; bf16 weights, with
  * their fp8 companions' fragment-major codes where the layers carry them, or - VV_WQ_FRAG4 - the VV_MXFP4_FRAG form of their MXFP4 companions): cond[2 B, cond_dim] = rows
  * {positive, negative} of utterance b at 2 b, 2 b + 1; noise[b * ld_noise ..], latent_out[b * ld_latent ..].  Every head matrix is streamed once
  * per solver step for all utterances.  ws: vv_head_ws_bytes_batch(h, n_steps, B) bytes. */

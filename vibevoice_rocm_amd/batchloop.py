@@ -3,7 +3,7 @@ helpers the batch-of-one path shares with it (valid ids, limits, output packing)
 
 `run` is host bookkeeping only - limits, the token state machine, the batch coupling, which frames may be speculated, the reference-order
 noise draws, chunk collection and streaming.  It makes no torch.cuda call and knows no Engine, RowBatch or stream: all of that sits behind a
-driver (modeling._LaneDriver: one Engine lane per dialogue; modeling._RowDriver: RowBatch groups of 2..4 dialogues), so the loop runs under
+driver (modeling._LaneDriver: one Engine lane per dialogue; modeling._RowDriver: RowBatch groups of 2..4 dialogues, 2..8 at row_batch_width=8), so the loop runs under
 a recording fake on a machine without a GPU (tests/test_host_cpu.py).  A driver has the attributes `sde`, `n_steps` and the methods
 
   begin(prompts, voices, max_steps, valid)   fresh sequences; prompt embeddings with the voice rows `(mask, rows)` scattered in

@@ -13,6 +13,7 @@ SRC = [os.path.join(HERE, "csrc", f) for f in ("vv_kernels.hip", "vv_gemv_stream
                                                "vv_fused.hip", "vv_attn_decode.hip", "vv_attn_prefill.hip", "vv_model.hip",
                                                "vv_nf4_import.hip", "vv_kv_copy.hip", "vv_noise.hip")]
 HDR = [os.path.join(ROOT, "include", "vv_hip.h"), os.path.join(HERE, "csrc", "vv_common.h"), os.path.join(HERE, "csrc", "vv_head_boundary.inc"),
+       os.path.join(HERE, "csrc", "vv_gemv_rows_body.inc"), os.path.join(HERE, "csrc", "vv_gemv_rows_tile.inc"),
        os.path.join(HERE, "csrc", "vv_llm_tail.inc"), os.path.join(HERE, "csrc", "vv_llm_tail_fast.inc")]
 OUT = os.path.join(HERE, "libvv_hip.so")
 OBJDIR = os.path.join(HERE, "csrc", "build")

@@ -62,14 +62,15 @@ int vv_conv_hot_gemv_covers(const vv_lin_args& a);                // index of th
 int vv_launch_conv_hot_gemv(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_conv_hot_gemv_covers: 1 = launched
 int vv_launch_conv_hot_row(const vv_block& B, const float* x, float* y, float* hidden, float* hist_new, int C, float eps, hipStream_t s);
 void vv_conv_hot_set(int mask);                                   // tuning hook "conv_hot"
-// vv_gemv_rows.hip: 3..8 activation rows on the matrix cores, on bf16, fragment-major fp8 or VV_MXFP4_FRAG weights (vv_hip.h); 1 launched, 0 not
+// vv_gemv_rows.hip: 3..8 activation rows on the matrix cores, on bf16, fragment-major fp8 or VV_MXFP4_FRAG weights (vv_hip.h), and 9..16 rows on
+// fragment-major bf16 weights (gemv_rows16_kernel: two row tiles against every weight load); 1 launched, 0 not
 // covered, < 0 error.  part / tickets: split-K workspace (vv_gemv_rows_part_floats / vv_gemv_rows_tickets give the sizes; tickets zero on entry,
 // left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
 // the same, decision apart from launch: gemv_rows_kernel<dual, nw, ks, pers, wf> on (gx, ksplit) blocks, spw weight loads per wave (wf: the weight
 // format, 0 = bf16, 1 = fp8, 2 = MXFP4: 32-, 64-, 128-wide loads); atomic: the K slices add into out.  have_ws: the caller has a partials workspace
 // and tickets (their sizes follow); kind 1 = covered
-struct vv_rows_route { int kind, dual, nw, ks, pers, wf, ksplit, spw, atomic, n_groups, gx; };
+struct vv_rows_route { int kind, dual, nw, ks, pers, wf, ksplit, spw, atomic, n_groups, gx, rt; };   // rt: row tiles of 8 (2 = gemv_rows16_kernel)
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
 int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
 int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap);

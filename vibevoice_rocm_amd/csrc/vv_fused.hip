@@ -744,7 +744,7 @@ extern "C" int vv_llm_tail_batch(const vv_llm* m, const float* h, int64_t ldh, i
                                  float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
                                  int* frame_counter, const int* active, vv_stream_t stream) {
   if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch: null pointer");
-  if (B <= 0 || B > 4 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch: B=%d (1..4) nv=%d (<= 8)", B, nv);
+  if (B <= 0 || B > 8 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch: B=%d (1..8) nv=%d (<= 8)", B, nv);
   return llm_tail_batch_launch("vv_llm_tail_batch", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start, tok_diffusion,
                                frame_counter, active, nullptr, nullptr, (hipStream_t)stream);
 }
@@ -753,7 +753,7 @@ extern "C" int vv_llm_tail_batch_sample(const vv_llm* m, const float* h, int64_t
                                         float* logits_out, int* token_out, const int* forced_token, int* lens, int tok_start, int tok_diffusion,
                                         int* frame_counter, const int* active, const vv_sampler* sampler, const float* q, vv_stream_t stream) {
   if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample: null pointer");
-  if (B <= 0 || B > 4 || nv <= 0) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample: B=%d (1..4) nv=%d", B, nv);
+  if (B <= 0 || B > 8 || nv <= 0) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample: B=%d (1..8) nv=%d", B, nv);
   VV_TRY(check_sampler("vv_llm_tail_batch_sample", sampler, q, nv));
   return llm_tail_batch_launch("vv_llm_tail_batch_sample", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start,
                                tok_diffusion, frame_counter, active, sampler, q, (hipStream_t)stream);
@@ -776,7 +776,7 @@ extern "C" int vv_llm_tail_batch_sample_rows(const vv_llm* m, const float* h, in
                                              int tok_diffusion, int* frame_counter, const int* active, const vv_sampler* samplers, const uint64_t* seeds,
                                              vv_stream_t stream) {
   if (!m || !h || !out || !w_valid || !ids || !logits_out || !token_out) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: null pointer");
-  if (B <= 0 || B > 4 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: B=%d (1..4) nv=%d (<= 8)", B, nv);
+  if (B <= 0 || B > 8 || nv <= 0 || nv > 8) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: B=%d (1..8) nv=%d (<= 8)", B, nv);
   if (!lens || !samplers || !seeds) return vv_set_error(VV_E_ARG, "vv_llm_tail_batch_sample_rows: null lens / samplers / seeds");
   return llm_tail_batch_launch("vv_llm_tail_batch_sample_rows", m, h, ldh, B, out, ldo, w_valid, nv, ids, logits_out, token_out, forced_token, lens, tok_start,
                                tok_diffusion, frame_counter, active, nullptr, nullptr, (hipStream_t)stream, samplers, seeds);

@@ -1,5 +1,5 @@
 // vv_gemv_rows.hip — the weight-streaming GEMV for 3 .. 8 activation rows (dialogues batched into the row dimension: rows = {positive,
-// negative} x 2 .. 4 dialogues), on the matrix cores.
+// negative} x 2 .. 4 dialogues), on the matrix cores; and its 9 .. 16-row form (5 .. 8 dialogues) on the fragment-major bf16 copy, gemv_rows16_kernel.
 //
 // Roofline: HBM.  The VALU GEMV (vv_gemv_stream.hip) keeps M x K/wave activations in registers and spends M FMAs per weight: its time grows
 // 1.2 - 1.6 us per row and M = 8 does not fit its registers at all for K > 1024.  Here one v_mfma_f32_16x16x32_bf16 consumes a wave's 1 KB
@@ -112,344 +112,25 @@ constexpr int WF_FP8 = 1;       // fragment-major e4m3fn codes, a row scale: a l
 constexpr int WF_MXFP4 = 2;     // fragment-major e2m1 codes, a scale dword beside each load: a load is four 32-wide k steps
 constexpr int rows_fpl(int wf) { return 1 << wf; }    // 32-wide A fragments per weight load
 
-// KS weight loads per wave against KA = rows_fpl(WF) * KS activation fragments
+// The text of both kernels below (vv_gemv_rows_body.inc): KS weight loads per wave against KA = rows_fpl(WF) * KS activation fragments per row tile.  RT row tiles of 8
+// activation rows each: every B fragment meets RT A fragments (tile t = the hi / lo parts of rows 8 t .. 8 t + 7), RT MFMAs per weight load.
+//   RT == 1   gemv_rows_kernel, 3 .. 8 rows
+//   RT == 2   gemv_rows16_kernel, 9 .. 16 rows: twice the fragments (LDS, registers), accumulators, epilogue threads (256) and partial tile; the
+//             adaLN rows of tile 1 are requested once tile 0 is laid out (their registers are tile 0's), behind the weights; a wave adds the hi
+//             and lo accumulator rows across its lane halves before they go to LDS (the same sum, in the same order, as the 8-row reduction
+//             reads: the tile's 16 x 16 floats become 8 x 16), which keeps the widest instantiation inside one CU's LDS
+// 3 .. 8 activation rows: one row tile
 template <bool DUAL, int NW, int KS, bool PERS, int WF>
 __global__ __launch_bounds__(NW * 64) void gemv_rows_kernel(const vv_lin_args a, const RowsAux x) {
-  constexpr bool F8 = WF == WF_FP8, MX = WF == WF_MXFP4;
-  constexpr int T = NW * 64;
-  constexpr int FPL = rows_fpl(WF);
-  constexpr int KA = FPL * KS;                      // 32-wide A fragments per wave
-  constexpr int NCH = (KA + 7) / 8;                 // 4-column chunks per thread per activation row
-  constexpr int NM = DUAL ? 2 : 1;
-  constexpr int PST = 128 * NM + 8;                 // floats per partial tile: [NM][8][16] sums + 8 partial sums of squares
-  constexpr bool MOD_OK = NCH == 1;                 // adaLN shift / scale rows: only the instantiations whose slice is one chunk per thread (registers)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* xa = reinterpret_cast<u32x4*>(smem);       // [NW][KA][64] A fragments (16 B per lane)
-  __shared__ float red[PERS ? 2 : 1][NW][NM][256];  // per wave: the 16 x 16 accumulator tile(s); ping-pong when the block walks row groups
-  __shared__ float ssr[NW][8];
-  __shared__ float s_tot[8];
-  __shared__ int s_last;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = lane & 15, c = lane >> 4;
-  const int ks = blockIdx.y;
-  const int K = a.k, N = a.n, mr = a.m;
-  const int spw = x.spw, ksplit = x.ksplit, n_groups = x.n_groups;
-  const int dbg = MX ? 0 : x.dbg;
-  const int spa = FPL * spw;                        // 32-wide k steps per wave
-  const int wsteps_total = K >> (MX ? 7 : F8 ? 6 : 5);
-  const int step0 = ks * NW * spa;                  // first 32-wide k step of this block
-  const int k0 = step0 << 5;
-  const bool rms = a.pro == VV_PRO_RMSNORM;
-  const bool has_nw = rms && a.norm_w != nullptr, has_mod = MOD_OK && a.mod_scale != nullptr;
-  const bool frag = MX || (a.flags & VV_LIN_W_FRAG) != 0;
-  const bool reused = (a.flags & VV_LIN_W_REUSED) != 0;
+  constexpr int RT = 1;
+#include "vv_gemv_rows_body.inc"
+}
 
-  // ---- requests, oldest first: activations, norm weight, modulation, epilogue operands, then the weights ----------------------------------
-  float4 xv[8][NCH], nv[NCH], sv[8][MOD_OK ? NCH : 1], cv[8][MOD_OK ? NCH : 1];
-  bool cval[NCH];
-#pragma unroll
-  for (int cc = 0; cc < NCH; ++cc) {
-    const int q = tid + cc * T;
-    cval[cc] = q < NW * spa * 8 && (k0 + 4 * q) < K;
-    const int kk = (cval[cc] && !(dbg & 4)) ? k0 + 4 * q : 4 * (tid & 7);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) xv[m][cc] = *reinterpret_cast<const float4*>(a.x + (int64_t)(m < mr ? m : mr - 1) * a.ldx + kk);
-    if (has_nw) nv[cc] = *reinterpret_cast<const float4*>(a.norm_w + kk);
-    if constexpr (MOD_OK) {
-      if (has_mod) {
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-          const int64_t mo = (int64_t)(m < mr ? m : mr - 1) * a.ld_mod + kk;
-          sv[m][cc] = *reinterpret_cast<const float4*>(a.mod_shift + mo);
-          cv[m][cc] = *reinterpret_cast<const float4*>(a.mod_scale + mo);
-        }
-      }
-    }
-  }
-  // epilogue operands of output (em, en) of a row group = thread tid < 128; absent operands read x[0] (a valid address), ignored at use
-  const int em = (tid >> 4) & 7, en = tid & 15;
-  const int emr = em < mr ? em : mr - 1;
-  auto load_eo = [&](int grp) {
-    EpiOps e;
-    int egn = min(grp, n_groups - 1) * 16 + en;
-    if constexpr (!MX) egn = min(egn, N - 1);       // MXFP4: N % 16 == 0, in bounds as it is
-    const float* pb = a.bias ? a.bias + egn : a.x;
-    const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)emr * a.gate_ld + egn : (int64_t)egn) : a.x;
-    const float* pr = a.res ? a.res + (int64_t)emr * a.ldres + egn : a.x;
-    e.b = *pb; e.g = *pg; e.r = *pr;
-    return e;
-  };
-  const int sb = step0 + wave * spa;                // this wave's first 32-wide k step
-  const int sbw = MX ? ks * NW * spw + wave * spw : F8 ? sb >> 1 : sb;      // ... and its first weight load
-  const bf16_t* __restrict__ W = reinterpret_cast<const bf16_t*>(a.w);
-  const bf16_t* __restrict__ W2 = reinterpret_cast<const bf16_t*>(a.w2);
-  const unsigned char* __restrict__ WB = reinterpret_cast<const unsigned char*>(a.w);          // MXFP4: codes and scale bytes
-  const unsigned char* __restrict__ WB2 = reinterpret_cast<const unsigned char*>(a.w2);
-  const unsigned char* __restrict__ S = reinterpret_cast<const unsigned char*>(a.wscale);
-  const unsigned char* __restrict__ S2 = reinterpret_cast<const unsigned char*>(a.w2scale);
-  // fp8: the row scale of this lane's weight row (n) in row group grp; N % 16 == 0, so the clamped group is in bounds
-  auto wscale_of = [&](const float* sc, int grp) { return F8 ? sc[min(grp, n_groups - 1) * 16 + n] : 1.0f; };
-  // a load that is not live (past the row's end, past the last row group, j >= spw) reads the first load of the matrix: a valid address
-  auto issue = [&](u32x4 (&w)[KS], unsigned (&e)[MX ? KS : 1], u32x4 (&w2)[DUAL ? KS : 1], unsigned (&e2)[(MX && DUAL) ? KS : 1], int grp) {
-    const bool glive = grp < n_groups;
-    int64_t base = 0;                               // in bf16 elements (fp8: two codes per element)
-    if constexpr (!MX) {
-      if (frag) base = ((int64_t)grp * wsteps_total) * 512 + lane * 8;
-      else base = (int64_t)min(grp * 16 + n, N - 1) * K + c * 8;
-    }
-    const int64_t sstep = frag ? 512 : 32;
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-      const bool live = glive && j < spw && sbw + j < wsteps_total;
-      const u32x4 *p1, *p2;
-      const unsigned *q1 = nullptr, *q2 = nullptr;  // MXFP4: the load's scale dword, 4 bytes per weight row
-      if constexpr (MX) {
-        const int64_t ld = live ? (int64_t)grp * wsteps_total + (sbw + j) : 0;
-        p1 = reinterpret_cast<const u32x4*>(WB + (ld * 64 + lane) * 16);
-        q1 = reinterpret_cast<const unsigned*>(S + (ld * 16 + n) * 4);
-        p2 = reinterpret_cast<const u32x4*>(WB2 + (ld * 64 + lane) * 16);
-        q2 = reinterpret_cast<const unsigned*>(S2 + (ld * 16 + n) * 4);
-      } else {
-        const int64_t off = live ? base + (int64_t)(sbw + j) * sstep : 0;
-        p1 = reinterpret_cast<const u32x4*>(W + off);
-        p2 = reinterpret_cast<const u32x4*>(W2 + off);
-      }
-      if (reused) {
-        w[j] = *p1;
-        if constexpr (MX) e[j] = *q1;
-        if (DUAL) { w2[j] = *p2; if constexpr (MX) e2[j] = *q2; }
-      } else {
-        w[j] = __builtin_nontemporal_load(p1);
-        if constexpr (MX) e[j] = __builtin_nontemporal_load(q1);
-        if (DUAL) { w2[j] = __builtin_nontemporal_load(p2); if constexpr (MX) e2[j] = __builtin_nontemporal_load(q2); }
-      }
-    }
-  };
-  const int gstride = gridDim.x;
-  int g = blockIdx.x;
-  u32x4 wc[KS], wc2[DUAL ? KS : 1];
-  u32x4 wn[PERS ? KS : 1], wn2[(PERS && DUAL) ? KS : 1];
-  unsigned ec[MX ? KS : 1], ec2[(MX && DUAL) ? KS : 1];                       // MXFP4: the loads' scale dwords
-  unsigned en_[(MX && PERS) ? KS : 1], en2[(MX && PERS && DUAL) ? KS : 1];
-  EpiOps eo = load_eo(g), eo_n = eo;
-  float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;                         // fp8: the row scales
-  if constexpr (F8) { sc = wscale_of(a.wscale, g); if (DUAL) sc2 = wscale_of(a.w2scale, g); }
-  issue(wc, ec, wc2, ec2, g);
-  if constexpr (PERS) {
-    eo_n = load_eo(g + gstride);
-    if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-    issue(wn, en_, wn2, en2, g + gstride);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
-#pragma unroll
-  for (int cc = 0; cc < NCH; ++cc) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) VV_FENCE4(xv[m][cc]);
-    if (has_nw) VV_FENCE4(nv[cc]);
-    if constexpr (MOD_OK) {
-      if (has_mod) {
-#pragma unroll
-        for (int m = 0; m < 8; ++m) { VV_FENCE4(sv[m][cc]); VV_FENCE4(cv[m][cc]); }
-      }
-    }
-  }
-#undef VV_FENCE4
-
-  // ---- activation prologue -------------------------------------------------------------------------------------------------------------
-  float rstd[8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m) rstd[m] = 1.0f;
-  if (rms) {
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      float s1 = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < NCH; ++cc) {
-        const float4 v = xv[m][cc];
-        s1 += cval[cc] ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
-      }
-      s1 = vv_wave_sum(s1);
-      if (lane == 0) ssr[wave][m] = s1;
-    }
-    __syncthreads();
-    if (tid < 8) {
-      float tot = 0.f;
-#pragma unroll
-      for (int w4 = 0; w4 < NW; ++w4) tot += ssr[w4][tid];          // fixed order: deterministic
-      s_tot[tid] = tot;
-    }
-    __syncthreads();
-    if (ksplit == 1) {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) rstd[m] = rsqrtf(s_tot[m] / (float)K + a.eps);
-    }
-  }
-#pragma unroll
-  for (int cc = 0; cc < NCH; ++cc) {
-    const int q = tid + cc * T;
-    if (q >= NW * KA * 8) continue;
-    const int js = q >> 3, wv = js / spa, j = js - wv * spa;        // block-relative k step -> (wave, step of the wave)
-    if (wv >= NW) continue;
-    const int cq = (q & 7) >> 1, half = q & 1;
-    unsigned char* base = smem + ((size_t)((wv * KA + j) * 64 + cq * 16) * 16 + half * 8);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      float4 v = xv[m][cc];
-      if (rms) {
-        const float r = rstd[m];
-        v.x *= r; v.y *= r; v.z *= r; v.w *= r;
-        if (has_nw) { v.x *= nv[cc].x; v.y *= nv[cc].y; v.z *= nv[cc].z; v.w *= nv[cc].w; }
-        if constexpr (MOD_OK) {
-          if (has_mod) {
-            v.x = v.x * (1.0f + cv[m][cc].x) + sv[m][cc].x; v.y = v.y * (1.0f + cv[m][cc].y) + sv[m][cc].y;
-            v.z = v.z * (1.0f + cv[m][cc].z) + sv[m][cc].z; v.w = v.w * (1.0f + cv[m][cc].w) + sv[m][cc].w;
-          }
-        }
-      }
-      if (!cval[cc] || m >= mr) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const unsigned h0 = bf_bits(v.x), h1 = bf_bits(v.y), h2 = bf_bits(v.z), h3 = bf_bits(v.w);
-      const float l0 = v.x - __uint_as_float(h0 << 16), l1 = v.y - __uint_as_float(h1 << 16);
-      const float l2 = v.z - __uint_as_float(h2 << 16), l3 = v.w - __uint_as_float(h3 << 16);
-      u32x2 hi, lo;
-      hi.x = h0 | (h1 << 16); hi.y = h2 | (h3 << 16);
-      lo.x = bf_bits(l0) | (bf_bits(l1) << 16); lo.y = bf_bits(l2) | (bf_bits(l3) << 16);
-      *reinterpret_cast<u32x2*>(base + (size_t)m * 16) = hi;               // fragment row m: high parts
-      *reinterpret_cast<u32x2*>(base + (size_t)(m + 8) * 16) = lo;         // fragment row m + 8: low parts
-    }
-  }
-  __syncthreads();
-  u32x4 af[KA];
-#pragma unroll
-  for (int j = 0; j < KA; ++j) af[j] = xa[(wave * KA + j) * 64 + lane];
-
-  // ---- the weights meet the fragments: one row group per pass -------------------------------------------------------------------------
-  int pp_ = 0;
-  while (g < n_groups) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-      if (j < spw && sbw + j < wsteps_total) {
-        if constexpr (F8) {              // the two 32-wide halves in k order: the summation order of the bf16 kernel
-          bf16x8 b0, b1;
-          fp8_frags(wc[j], sc, b0, b1);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j]), b0, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j + 1]), b1, acc, 0, 0, 0);
-          if (DUAL) {
-            fp8_frags(wc2[j], sc2, b0, b1);
-            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j]), b0, acc2, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[2 * j + 1]), b1, acc2, 0, 0, 0);
-          }
-        } else if constexpr (MX) {       // the four 32-wide steps of the load in k order: the summation order of the bf16 kernel
-#pragma unroll
-          for (int h = 0; h < 4; ++h) {
-            const bf16x8 b = mx_frag(wc[j][h], (ec[j] >> (8 * h)) & 0xffu);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[4 * j + h]), b, acc, 0, 0, 0);
-            if (DUAL) {
-              const bf16x8 b2 = mx_frag(wc2[j][h], (ec2[j] >> (8 * h)) & 0xffu);
-              acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[4 * j + h]), b2, acc2, 0, 0, 0);
-            }
-          }
-        } else {
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc[j]), acc, 0, 0, 0);
-          if (DUAL) acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[j]), __builtin_bit_cast(bf16x8, wc2[j]), acc2, 0, 0, 0);
-        }
-      }
-    }
-    // accumulator: lane (n, c) holds fragment rows 4 c + i of weight row n
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      red[pp_][wave][0][(4 * c + i) * 16 + n] = acc[i];
-      if (DUAL) red[pp_][wave][NM - 1][(4 * c + i) * 16 + n] = acc2[i];
-    }
-    __syncthreads();
-    float s = 0.f, s2 = 0.f;
-    if (tid < 128) {
-#pragma unroll
-      for (int w4 = 0; w4 < NW; ++w4) {
-        s += red[pp_][w4][0][tid] + red[pp_][w4][0][tid + 128];               // high-part row + low-part row
-        if (DUAL) s2 += red[pp_][w4][NM - 1][tid] + red[pp_][w4][NM - 1][tid + 128];
-      }
-    }
-    float rs = 1.0f;
-    if (!PERS && ksplit > 1 && x.atomic) {
-      if (tid < 128) {
-        const int gn = g * 16 + en;
-        if (em < mr && gn < N) {
-          float v = s;
-          if (a.bias && ks == 0) v += eo.b;
-          if (a.gate) v *= eo.g;
-          atomicAdd(a.out + (int64_t)em * a.ldo + gn, v);
-        }
-      }
-      return;
-    }
-    if (!PERS && ksplit > 1 && !(dbg & 2)) {
-      // partial tile out (write-through), ticket, the last block of the row group folds
-      float* pp = x.part + ((int64_t)g * ksplit + ks) * PST;
-      if (tid < 128) {
-        __hip_atomic_store(pp + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (DUAL) __hip_atomic_store(pp + 128 + tid, s2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (tid < 8) __hip_atomic_store(pp + 128 * NM + tid, rms ? s_tot[tid] : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const int tk = __hip_atomic_fetch_add(&x.tickets[g], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (tk == ksplit - 1);
-        if (s_last) __hip_atomic_store(&x.tickets[g], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-      }
-      __syncthreads();
-      if (!s_last) return;
-      if (tid >= 128) return;
-      const float* p0 = x.part + (int64_t)g * ksplit * PST;
-      float pv[MAXSPLIT], pv2[DUAL ? MAXSPLIT : 1], pq[MAXSPLIT];
-#pragma unroll
-      for (int i = 0; i < MAXSPLIT; ++i) {                            // every partial requested before the first is used
-        const int ii = i < ksplit ? i : 0;
-        pv[i] = __hip_atomic_load(p0 + (int64_t)ii * PST + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (DUAL) pv2[i] = __hip_atomic_load(p0 + (int64_t)ii * PST + 128 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        pq[i] = __hip_atomic_load(p0 + (int64_t)ii * PST + 128 * NM + em, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      s = 0.f; s2 = 0.f;
-      float q2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < MAXSPLIT; ++i) {
-        if (i < ksplit) { s += pv[i]; if (DUAL) s2 += pv2[i]; q2 += pq[i]; }
-      }
-      if (rms) rs = rsqrtf(q2 / (float)K + a.eps);
-    }
-    if (tid < 128) {
-      const int gn = g * 16 + en;
-      if (em < mr && gn < N) {
-        float v = s * rs, v2 = s2 * rs;
-        if (a.bias) v += eo.b;
-        if (a.act == VV_ACT_GELU) v = gelu1(v);
-        else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
-        if (a.gate) v *= eo.g;
-        if (a.res) v += eo.r;
-        a.out[(int64_t)em * a.ldo + gn] = v;
-      }
-    }
-    if constexpr (!PERS) {
-      break;
-    } else {
-      g += gstride;
-      pp_ ^= 1;                                        // ping-pong: one barrier per row group is enough
-      eo = eo_n;
-      sc = sn; sc2 = sn2;
-#pragma unroll
-      for (int j = 0; j < KS; ++j) {
-        wc[j] = wn[j]; if (DUAL) wc2[j] = wn2[j];
-        if constexpr (MX) { ec[j] = en_[j]; if (DUAL) ec2[j] = en2[j]; }
-      }
-      if (g + gstride < n_groups) {
-        eo_n = load_eo(g + gstride);
-        if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-        issue(wn, en_, wn2, en2, g + gstride);
-      }
-    }
-  }
+// 9 .. 16 activation rows on the fragment-major bf16 copy: two row tiles, two MFMAs per weight load, one pass over the weights
+template <bool DUAL, int NW, int KS, bool PERS>
+__global__ __launch_bounds__(NW * 64) void gemv_rows16_kernel(const vv_lin_args a, const RowsAux x) {
+  constexpr int RT = 2, WF = WF_BF16;
+#include "vv_gemv_rows_body.inc"
 }
 
 int g_rows_on = 1;          // tuning hook "gemv_rows": 0 = never take this path
@@ -466,6 +147,13 @@ int launch_cfg(const vv_lin_args& a, const RowsAux& x, int gx, hipStream_t s) {
   return 1;
 }
 
+template <bool DUAL, int NW, int KS, bool PERS>
+int launch_cfg16(const vv_lin_args& a, const RowsAux& x, int gx, hipStream_t s) {
+  const size_t lds = (size_t)2 * NW * KS * 64 * 16;               // two row tiles of fragments; raised in vv_gemv_rows_init as well
+  hipLaunchKernelGGL((gemv_rows16_kernel<DUAL, NW, KS, PERS>), dim3(gx, x.ksplit), dim3(NW * 64), lds, s, a, x);
+  return 1;
+}
+
 // Every kernel of this file, as (dual, nw, ks, pers, wf) - exactly what vv_gemv_rows_decide can choose: per format the whole-row kernels (8 waves;
 // SwiGLU also persistent), the SwiGLU K split (the same one-shot kernels) and the single-matrix K split (4 waves)
 #define VV_ROWS_ALL(X)                                                                                                         \
@@ -479,7 +167,13 @@ int launch_cfg(const vv_lin_args& a, const RowsAux& x, int gx, hipStream_t s) {
   X(1, 8, 1, 0, WF_MXFP4) X(1, 8, 2, 0, WF_MXFP4) X(1, 8, 1, 1, WF_MXFP4) X(1, 8, 2, 1, WF_MXFP4)                              \
   X(0, 4, 1, 0, WF_MXFP4) X(0, 4, 2, 0, WF_MXFP4) X(0, 4, 3, 0, WF_MXFP4) X(0, 4, 4, 0, WF_MXFP4)
 
-// the decision's template choice: gemv_rows_kernel<dual, nw, ks, pers, wf> and its grid
+// Every gemv_rows16_kernel, as (dual, nw, ks, pers): the bf16 forms of the list above, chosen by the same rules
+#define VV_ROWS16_ALL(X)                                                                       \
+  X(0, 8, 4, 0) X(0, 8, 6, 0) X(0, 8, 8, 0)                                                    \
+  X(1, 8, 4, 0) X(1, 8, 6, 0) X(1, 8, 8, 0) X(1, 8, 4, 1) X(1, 8, 6, 1)                        \
+  X(0, 4, 3, 0) X(0, 4, 6, 0) X(0, 4, 9, 0) X(0, 4, 12, 0)
+
+// the decision's template choice: gemv_rows_kernel<dual, nw, ks, pers, wf> (r.rt == 2: gemv_rows16_kernel<dual, nw, ks, pers>) and its grid
 void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int wf) {
   r.dual = dual; r.nw = nw; r.ks = ks; r.pers = pers; r.wf = wf;
   r.gx = r.n_groups;
@@ -496,18 +190,19 @@ void rows_cfg(vv_rows_route& r, int dual, int nw, int ks, int pers, int wf) {
 bool rows_split(const vv_lin_args& a, int steps, int n_groups, int NW, int kscap, int ksmax, int few, bool have_ws, size_t part_floats,
                 size_t n_tickets, vv_rows_route& r) {
   const bool dual = a.w2 != nullptr;
+  const int maxsplit = MAXSPLIT / r.rt;               // two row tiles: partial tiles twice the size, half as many of them
   int ksplit = 0, spw = 0;
-  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
+  for (int sp = 2; sp <= maxsplit && !ksplit; ++sp) {
     const int w = (steps + sp * NW - 1) / (sp * NW);
     if (w <= kscap && ((long)n_groups * sp >= g_rows_blocks || w <= few)) { ksplit = sp; spw = w; }
   }
-  for (int sp = 2; sp <= MAXSPLIT && !ksplit; ++sp) {
+  for (int sp = 2; sp <= maxsplit && !ksplit; ++sp) {
     const int w = (steps + sp * NW - 1) / (sp * NW);
     if (w <= ksmax) { ksplit = sp; spw = w; }
   }
   if (!ksplit) return false;
   while (ksplit > 1 && (ksplit - 1) * NW * spw >= steps) --ksplit;     // drop K slices that would start past the end
-  const size_t pst = dual ? 264 : 136;
+  const size_t pst = (size_t)(dual ? 264 : 136) * r.rt;
   r.atomic = g_rows_atomic && !dual && a.pro == VV_PRO_NONE && a.act == VV_ACT_NONE && a.res && a.res == a.out && a.ldres == a.ldo;
   if (!r.atomic && (!have_ws || (size_t)n_groups * ksplit * pst > part_floats || (size_t)n_groups > n_tickets)) return false;
   r.ksplit = ksplit; r.spw = spw;
@@ -532,7 +227,8 @@ void vv_gemv_rows_set(int on, int blocks, int pers) {
   if (pers > 0) g_rows_pers = pers;
 }
 
-// floats of partials workspace a launch on (n, k, dual) may need (upper bound over the launcher's rules), and ticket ints
+// floats of partials workspace a launch on (n, k, dual) may need (upper bound over the launcher's rules), and ticket ints.  The 16-row kernel
+// needs no more: its partial tiles are twice the 8-row kernel's and it splits K at most MAXSPLIT / 2 ways
 size_t vv_gemv_rows_part_floats(int n, int dual) { return (size_t)((n + 15) / 16) * MAXSPLIT * (dual ? 264 : 136); }
 size_t vv_gemv_rows_tickets(int n) { return (size_t)((n + 15) / 16); }
 
@@ -544,6 +240,12 @@ int vv_gemv_rows_init() {
     return vv_set_error(VV_E_HIP, "gemv_rows: cannot raise the dynamic LDS limit");
   VV_ROWS_ALL(VV_ROWS_ATTR)
 #undef VV_ROWS_ATTR
+#define VV_ROWS16_ATTR(D, NW, KS, P)                                                                                                         \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows16_kernel<(D != 0), NW, KS, (P != 0)>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                          2 * NW * KS * 64 * 16) != hipSuccess)                                                                           \
+    return vv_set_error(VV_E_HIP, "gemv_rows16: cannot raise the dynamic LDS limit");
+  VV_ROWS16_ALL(VV_ROWS16_ATTR)
+#undef VV_ROWS16_ATTR
   return 0;
 }
 
@@ -563,7 +265,9 @@ int vv_gemv_rows_init() {
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets) {
   vv_rows_route r = {};
   const int wf = a.wdt == VV_BF16 ? WF_BF16 : a.wdt == VV_FP8 ? WF_FP8 : a.wdt == VV_MXFP4_FRAG ? WF_MXFP4 : -1;
-  if (!g_rows_on || wf < 0 || a.m < 3 || a.m > 8) return r;
+  if (!g_rows_on || wf < 0 || a.m < 3 || a.m > 16) return r;
+  r.rt = a.m > 8 ? 2 : 1;                             // 9 .. 16 rows: gemv_rows16_kernel, on the fragment-major bf16 copy only
+  if (r.rt == 2 && (wf != WF_BF16 || !(a.flags & VV_LIN_W_FRAG))) return r;
   const int kw = 32 * rows_fpl(wf);                   // k per weight load
   if (a.k % kw || a.k < kw) return r;
   if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return r;
@@ -602,6 +306,13 @@ int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, floa
   if (r.kind != 1) return 0;
   RowsAux x;
   x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = r.n_groups; x.atomic = r.atomic; x.ksplit = r.ksplit; x.spw = r.spw;
+  if (r.rt == 2) {
+#define VV_ROWS16_CASE(D, NW, KS, P) \
+    if (r.dual == D && r.nw == NW && r.ks == KS && r.pers == P && r.wf == WF_BF16) return launch_cfg16<(D != 0), NW, KS, (P != 0)>(a, x, r.gx, s);
+    VV_ROWS16_ALL(VV_ROWS16_CASE)
+#undef VV_ROWS16_CASE
+    return 0;
+  }
 #define VV_ROWS_CASE(D, NW, KS, P, WF) \
   if (r.dual == D && r.nw == NW && r.ks == KS && r.pers == P && r.wf == WF) return launch_cfg<(D != 0), NW, KS, (P != 0), WF>(a, x, r.gx, s);
   VV_ROWS_ALL(VV_ROWS_CASE)
@@ -611,6 +322,8 @@ int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, floa
 
 // the name vv_linear_route reports for this file's route: spelled here and nowhere else
 int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap) {
+  if (r.rt == 2)
+    return snprintf(name, (size_t)cap, "gemv_rows16<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
   if (r.wf == WF_MXFP4)
     return snprintf(name, (size_t)cap, "gemv_rows_mx<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
   return snprintf(name, (size_t)cap, "gemv_rows<dual=%d,nw=%d,ks=%d,pers=%d,f8=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.wf, r.ksplit, r.atomic);

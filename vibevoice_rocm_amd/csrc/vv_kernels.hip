@@ -39,7 +39,7 @@ extern "C" int vv_init(void) {
   VV_TRY(vv_gemv_rows_init());
   return vv_fused_init();
 }
-// process-wide split-K scratch of the 3..8-row matrix-core GEMV for PUBLIC vv_linear calls (micro-benchmarks and tests only, switched on by
+// process-wide split-K scratch of the 3..8-row (and 9..16-row) matrix-core GEMV for PUBLIC vv_linear calls (micro-benchmarks and tests only, switched on by
 // vv_tune("gemv_rows_scratch", 1): one stream at a time).  The composites hand vv_linear_ws their own workspace instead.
 static float* g_rows_part = nullptr;
 static int* g_rows_tk = nullptr;
@@ -510,15 +510,15 @@ struct gemv_route {
   size_t lds;
 };
 
-// rows 4.. of a 5..8-row call as a call of its own (the second pass of GEMV_SPLIT): every per-row operand advances by 4 rows
-static vv_lin_args split_hi(const vv_lin_args& a) {
+// rows r.. of a call as a call of its own (r = 4: the second pass of GEMV_SPLIT on 5..8 rows): every per-row operand advances by r rows
+static vv_lin_args split_hi(const vv_lin_args& a, int r = 4) {
   vv_lin_args hi = a;
-  hi.m = a.m - 4;
-  hi.x = a.x + 4 * a.ldx;
-  hi.out = a.out + 4 * a.ldo;
-  if (a.res) hi.res = a.res + 4 * a.ldres;
-  if (a.gate && a.gate_ld) hi.gate = a.gate + 4 * a.gate_ld;
-  if (a.mod_scale) { hi.mod_scale = a.mod_scale + 4 * a.ld_mod; hi.mod_shift = a.mod_shift + 4 * a.ld_mod; }
+  hi.m = a.m - r;
+  hi.x = a.x + r * a.ldx;
+  hi.out = a.out + r * a.ldo;
+  if (a.res) hi.res = a.res + r * a.ldres;
+  if (a.gate && a.gate_ld) hi.gate = a.gate + r * a.gate_ld;
+  if (a.mod_scale) { hi.mod_scale = a.mod_scale + r * a.ld_mod; hi.mod_shift = a.mod_shift + r * a.ld_mod; }
   return hi;
 }
 
@@ -585,12 +585,13 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
   const bool dual = a.w2 != nullptr;
   const size_t wsz = a.wdt == VV_F32 ? sizeof(float) : sizeof(bf16_t);
   const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!dual || (uintptr_t)a.w2 % 16 == 0);
-  if (a.m > 2 && g_rows_part) {                               // 3..8 rows on the matrix cores (process-wide scratch: see rows_scratch)
+  if (a.m > 2 && g_rows_part) {                               // 3..8 rows (9..16 on VV_LIN_W_FRAG weights) on the matrix cores (process-wide scratch: see rows_scratch)
     g->rows = vv_gemv_rows_decide(a, true, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
     if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
   }
-  if (a.flags & VV_LIN_W_FRAG)                                // only the 3..8-row matrix-core GEMV reads the fragment-major layout
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_LIN_W_FRAG weights are read by the 3..8-row matrix-core GEMV only (m=%d n=%d k=%d not covered)", a.m, a.n, a.k);
+  if (a.flags & VV_LIN_W_FRAG)                                // only the 3..8-row matrix-core GEMV and its 9..16-row form read the fragment-major layout
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_LIN_W_FRAG weights are read by the 3..8-row matrix-core GEMV only, and by its 9..16-row form "
+                        "(m=%d n=%d k=%d not covered: no split-K scratch, or a shape outside both)", a.m, a.n, a.k);
   g->st = vv_gemv_stream_decide(a);                           // bf16 weight-streaming fast path (<= 4 rows; 5..8 rows when K splits to <= 2 units per wave)
   if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
   if (a.m > 4 && a.wdt == VV_BF16 && a.ldx != 0) {
@@ -686,7 +687,7 @@ static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStrea
 enum { LIN_FAM_SKINNY = 1, LIN_FAM_GEMV, LIN_FAM_MFMA, LIN_FAM_GEMM_F32 };
 static int linear_family(const vv_lin_args& a, vv_mfma_route* r) {
   if (vv_skinny_covers(a)) return LIN_FAM_SKINNY;                // a few rows x K = 512..2560, plain epilogue: the resampling convs (vv_convffn.hip)
-  if (a.m <= 8) return LIN_FAM_GEMV;
+  if (a.m <= 8 || ((a.flags & VV_LIN_W_FRAG) && a.m <= 16)) return LIN_FAM_GEMV;     // 9..16 rows on the fragment-major copy: the 16-row matrix-core GEMV or nothing
   *r = vv_mfma_decide(a);                                        // bf16 weights: matrix-core path
   if (r->kind < 0) return r->kind;
   if (r->kind > 0) return LIN_FAM_MFMA;
@@ -813,10 +814,12 @@ static int linear_check_args(const vv_lin_args* a) {
                                   !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights exist for the 3..8-row matrix-core GEMV alone: VV_LIN_W_FRAG, 3 <= m <= 8, n %% 16 == 0, "
                         "k %% 128 == 0, wscale (w2scale), no bf16 hand-off (m=%d n=%d k=%d flags=%d)", a->m, a->n, a->k, a->flags);
-  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && a->wdt != VV_MXFP4_FRAG && (a->wdt != VV_BF16 || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 32))
-    return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..8 rows, n %% 16 == 0 and k %% 32 == 0");
+  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && a->wdt != VV_MXFP4_FRAG && (a->wdt != VV_BF16 || a->m < 3 || a->m > 16 || a->n % 16 || a->k % 32))
+    return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..16 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
     return vv_set_error(VV_E_ARG, "vv_linear: bf16 activation hand-off needs bf16 weights, m > 8 and k %% 16 == 0");
+  if ((a->flags & VV_LIN_W_FRAG) && (a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)))
+    return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG weights take fp32 activations and give fp32 outputs (no bf16 hand-off)");
   return 0;
 }
 
@@ -871,12 +874,14 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 
 // vv_linear for the composites of a row-batched step: 3..8 rows go to the matrix-core GEMV with the caller's split-K workspace, on the
 // fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices.
+// 9..16 rows: the 16-row form of that GEMV, on bf16 fragment-major copies only (no fp8 companions, no VV_WQ_FRAG4); else two passes of 5..8 rows.
 // q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*).
 // frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form (codes, scale bytes behind them) for the same kernel; a matrix without
 // such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
                  const vv_w8* q1, const vv_w8* q2, bool frag4) {
-  if (a && a->wdt == VV_BF16 && a->m > 2 && a->m <= 8 && a->x && a->w && a->out) {
+  const bool wide_ok = a && !frag4 && !(q1 && q1->q) && f1 && (!a->w2 || f2);
+  if (a && a->wdt == VV_BF16 && a->m > 2 && (a->m <= 8 || (a->m <= 16 && wide_ok)) && a->x && a->w && a->out) {
     vv_lin_args b = *a;
     const bool f8 = !frag4 && q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
     const bool mx = frag4 && f1 && (!b.w2 || f2);
@@ -904,6 +909,16 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
     }
     if (rc < 0) return rc;
     if (rc == 1) { VV_CHECK_LAUNCH("vv_linear(rows)"); return 0; }
+  }
+  if (a && a->wdt == VV_BF16 && a->m > 8 && a->m <= 16 && a->ldx != 0 && !(a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && a->x && a->w && a->out) {
+    // 9..16 rows the 16-row GEMV does not take (no bf16 fragment-major copy, a K it does not cover): two passes of 5..8 rows, each on the route
+    // the 8-row step takes for this matrix - vv_linear at these row counts would round the activations to bf16 once on the matrix-core GEMM
+    // (2^-9) where every <= 8-row route keeps fp32 or hi + lo (2^-17)
+    vv_lin_args lo = *a;
+    lo.m = a->m / 2;
+    const vv_lin_args hi = split_hi(*a, lo.m);
+    VV_TRY(vv_linear_ws(&lo, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, frag4));
+    return vv_linear_ws(&hi, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, frag4);
   }
   return vv_linear(a, stream);
 }

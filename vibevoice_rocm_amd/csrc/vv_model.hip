@@ -56,6 +56,8 @@ static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q
 #define VV_PREFILL_ROWS 64
 // decode attention over long contexts splits the keys over up to this many blocks per (row, q head) (vv_attn_decode.hip)
 #define VV_ATT_ROWS 8
+// ... and for the 9..16-row decode step (two row tiles of the matrix-core GEMV): the partials and tickets of a call are sized by its rows
+static inline size_t att_rows(int R) { return (R > VV_ATT_ROWS && R <= 16) ? 16 : VV_ATT_ROWS; }
 #define VV_ATT_MAX_SPLIT 16        // per-head kernel
 #define VV_ATT_PART_SPLITS 128     // capacity of the partials workspace: the grouped kernel spreads long contexts over up to 128 splits per (row, KV head)
 
@@ -78,8 +80,8 @@ extern "C" size_t vv_llm_ws_bytes(const vv_llm* m, int R) {
   const size_t widest = (size_t)(m->inter > m->hidden ? m->inter : m->hidden);
   return al((size_t)R * m->hidden) + al((size_t)R * qkv) + al((size_t)R * m->heads * m->head_dim) + al((size_t)R * m->inter) +
          al((size_t)R * m->head_dim) + (R >= VV_PREFILL_ROWS ? al((size_t)R * widest / 2 + 64) : 0) +
-         al((size_t)VV_ATT_ROWS * m->heads * VV_ATT_PART_SPLITS * (m->head_dim + 2)) + al((size_t)VV_ATT_ROWS * m->heads) +   // split-key decode attention
-         ((R > 2 && R <= 8) ? al(rows_part_floats(m)) + al(rows_tickets(m)) : 0);                                            // split-K partials of the 3..8-row GEMV
+         al(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (m->head_dim + 2)) + al(att_rows(R) * m->heads) +                   // split-key decode attention
+         ((R > 2 && R <= 16) ? al(rows_part_floats(m)) + al(rows_tickets(m)) : 0);                                           // split-K partials of the 3..8-row and the 9..16-row GEMV
 }
 
 extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens,
@@ -103,20 +105,26 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
   VV_TRY(vv_rope_table(lens, m->inv_freq, R, d, rope, stream));
   const bool prefill = (R >= VV_PREFILL_ROWS) && m->wdt == VV_BF16 && H % 16 == 0 && m->inter % 16 == 0 && qd % 16 == 0;
   void* xb = prefill ? (void*)c.take((size_t)R * (m->inter > H ? m->inter : H) / 2 + 64) : nullptr;
-  float* att_part = c.take((size_t)VV_ATT_ROWS * m->heads * VV_ATT_PART_SPLITS * (d + 2));
-  int* att_tickets = reinterpret_cast<int*>(c.take((size_t)VV_ATT_ROWS * m->heads));
+  float* att_part = c.take(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (d + 2));
+  int* att_tickets = reinterpret_cast<int*>(c.take(att_rows(R) * m->heads));
   // contexts beyond ~1K keys: one block per (row, q head) would pull all of its K / V through a single CU (~95 GB/s: 8 us at S = 3000)
   const bool decode = (cache_rows == nullptr && R <= kv->rows);
+  // 9..16 rows: two row tiles of the same GEMV, when every layer has the bf16 fragment-major copies (no VV_WQ_FRAG4, whose copies are MXFP4 codes)
+  bool rows16 = decode && R > 8 && R <= 16 && m->wdt == VV_BF16 && !frag4;
+  for (int l = 0; rows16 && l < m->layers; ++l) {
+    const vv_llm_layer& L = m->layer[l];
+    rows16 = L.f_qkv && L.f_o && L.f_gate && L.f_up && L.f_down;
+  }
   int att_split = 1;
-  if (decode && R <= VV_ATT_ROWS && kv->s_max > 1024) {
+  if (decode && (R <= VV_ATT_ROWS || rows16) && kv->s_max > 1024) {
     att_split = (kv->s_max + 511) / 512;
     if (att_split > VV_ATT_MAX_SPLIT) att_split = VV_ATT_MAX_SPLIT;
-    hipError_t e = hipMemsetAsync(att_tickets, 0, (size_t)VV_ATT_ROWS * m->heads * sizeof(int), s);
+    hipError_t e = hipMemsetAsync(att_tickets, 0, att_rows(R) * m->heads * sizeof(int), s);
     if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_llm_forward: %s", hipGetErrorString(e));
   }
   void* xb2 = prefill ? (void*)act : nullptr;      // bf16 SwiGLU output [R, inter] lives in the (otherwise unused) fp32 act buffer
   // 3..8 rows (dialogues batched into the row dimension): the matrix-core GEMV with its split-K workspace, fragment-major weights when the model has them
-  const bool rows8 = decode && R > 2 && R <= 8 && m->wdt == VV_BF16;
+  const bool rows8 = (decode && R > 2 && R <= 8 && m->wdt == VV_BF16) || rows16;      // from here on "rows8" is either
   float* rpart = nullptr;
   int* rtick = nullptr;
   size_t rpart_n = 0, rtick_n = 0;
@@ -367,11 +375,12 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
 
 // B utterances per call: rows [2 B] everywhere the single-utterance sampler has 2; conditioning rows laid out [step][2 B]
 extern "C" size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B) {
-  if (!h || n_steps <= 0 || B <= 0 || B > 4) return 0;
+  if (!h || n_steps <= 0 || B <= 0 || B > 8) return 0;
   VV_WQ_STRIP(vv_head, h);
   const size_t R = (size_t)2 * B * n_steps, D = h->D;
-  return al(8 * D) /*c0*/ + al(R * D) /*c (bf16 rows fit)*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + 2 * al(8 * D) /*hidden rows x 2*/ +
-         al(8 * (size_t)h->ffn) + 2 * al((size_t)B * (D + h->latent)) /*solver state X, M*/ +
+  const size_t HR = B <= 4 ? 8 : (size_t)2 * B;       // hidden / act / c0 rows: 8 as ever up to 4 utterances, 2 B beyond
+  return al(HR * D) /*c0*/ + al(R * D) /*c (bf16 rows fit)*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + 2 * al(HR * D) /*hidden rows x 2*/ +
+         al(HR * (size_t)h->ffn) + 2 * al((size_t)B * (D + h->latent)) /*solver state X, M*/ +
          al(vv_gemv_rows_part_floats(h->D, 0)) + al(vv_gemv_rows_tickets(h->ffn));
 }
 
@@ -390,7 +399,7 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
                              const float* sde_noise, int64_t ld_sde, vv_stream_t stream, const float* cfg_rows = nullptr) {
   const char* fn = sde_fn ? sde_fn : "vv_head_sample_batch";
   if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
-  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 4) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..4)", fn, n_steps, h->layers, B);
+  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 8) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..8)", fn, n_steps, h->layers, B);
   VV_WQ_STRIP(vv_head, h);
   const bool f8q = wq == VV_FP8;                  // NF4 companions: the bf16 matrices (and their bf16 fragment-major copies) serve these rows
   if (!sde_fn)
@@ -405,14 +414,15 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
   hipStream_t s = (hipStream_t)stream;
   const int D = h->D, R2 = 2 * B;
   const size_t R = (size_t)R2 * n_steps;
+  const size_t HR = B <= 4 ? 8 : (size_t)R2;          // as vv_head_ws_bytes_batch
   Carver cv(ws);
-  float* c0 = cv.take(8 * (size_t)D);
+  float* c0 = cv.take(HR * D);
   float* c = cv.take(R * D);
   float* mod[16];
   for (int l = 0; l < h->layers; ++l) mod[l] = cv.take(R * 3 * D);
   float* modf = cv.take(R * 2 * D);
-  float* hb[2] = {cv.take(8 * (size_t)D), cv.take(8 * (size_t)D)};
-  float* act = cv.take(8 * (size_t)h->ffn);
+  float* hb[2] = {cv.take(HR * D), cv.take(HR * D)};
+  float* act = cv.take(HR * (size_t)h->ffn);
   const int64_t sst = D + h->latent;
   float* Xs = cv.take((size_t)B * sst);
   float* Ms = cv.take((size_t)B * sst);

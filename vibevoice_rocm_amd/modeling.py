@@ -331,17 +331,42 @@ class _LaneDriver:
             self.pool.shutdown()
 
 
+ROW_BATCH_WIDTHS = (4, 8)      # dialogues per row batch at most: 8 rows (csrc gemv_rows_kernel) or 16 (gemv_rows16_kernel, bf16 weights only)
+
+
+def check_row_batch_width(width, torch_dtype, weight_quant, kv_cache_dtype):
+    """ValueError unless width is 4, or 8 on what the 16-row matrix-core GEMV serves: bf16 weights without companions, a bf16 KV cache"""
+    if isinstance(width, bool) or width not in ROW_BATCH_WIDTHS:
+        raise ValueError(f"row_batch_width={width!r}: 4 (row batches of up to 4 dialogues, 8 rows) or 8 (up to 8 dialogues, 16 rows)")
+    if width == 8:
+        if weight_quant is not None:
+            raise ValueError(f"row_batch_width=8 serves bf16 weights only: the 16-row matrix-core GEMV has no weight_quant={weight_quant!r} form")
+        if torch_dtype != torch.bfloat16:
+            raise ValueError(f"row_batch_width=8 needs torch_dtype=torch.bfloat16, not {torch_dtype}")
+        if kv_cache_dtype == "fp8":
+            raise ValueError("row_batch_width=8 needs a bf16 KV cache: the row-batched decode step has no kv_cache_dtype='fp8' form")
+    return int(width)
+
+
+def row_partition(B: int, width: int = 4) -> List[int]:
+    """Sizes of the row batches B dialogues run as: ceil(B / width) groups, balanced, the larger ones first (6 at width 4: [3, 3]; at 8: [6])"""
+    n_groups = -(-B // width)
+    return [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]
+
+
 class _RowDriver:
     """batchloop driver: the B dialogues batched into the ROW dimension of the weight-heavy half of a frame (rowbatch.RowBatch: one Qwen2
     decode step with 2 B rows, one diffusion sampling with 2 B rows; the conv tokenizers stay per dialogue on their lanes' streams).  5..16
-    dialogues run as ceil(B / 4) row batches, all on the main stream: each step enqueues A and H of every batch, then the conv tails - a
+    dialogues run as ceil(B / 4) row batches (row_batch_width=8: 5..8 as one, 9..16 as two), all on the main stream: each step enqueues A and H of every batch, then the conv tails - a
     batch's tails overlap the other batches' A and H.  With do_sample every row batch's logits are read back once per step and the tokens
     drawn in ascending dialogue order, so a seeded call draws what the lanes draw; results agree with the lanes to the rounding of the
     matrix-core GEMV (activations as bf16 hi + lo, ~2e-6 relative per product)."""
 
-    def __init__(self, model, B: int, cfg_scale, ST: int, SD: int):
+    def __init__(self, model, B: int, cfg_scale, ST: int, SD: int, width: Optional[int] = None):
         """cfg_scale: a number (the scale is a launch argument of graph H and part of its key), or B of them: every row batch keeps its
-        dialogues' scales on the device and runs the graph H that reads them there (RowBatch.begin(cfg_rows=))"""
+        dialogues' scales on the device and runs the graph H that reads them there (RowBatch.begin(cfg_rows=)).  width: dialogues per row
+        batch at most (default: the model's row_batch_width)"""
+        self.width = int(getattr(model, "row_batch_width", 4) if width is None else width)
         self.cfg_rows = _cfg_scales(cfg_scale, B)
         self.model, self.main, self.cfg_scale, self.ST, self.SD = model, model.engine, (1.0 if self.cfg_rows else float(cfg_scale)), ST, SD
         if B > 4:
@@ -358,8 +383,7 @@ class _RowDriver:
     def begin(self, prompts, voices, max_steps, valid):
         from .rowbatch import RowBatch
         model, lanes, B, off = self.model, self.lanes, len(self.lanes), 0
-        n_groups = -(-B // 4)                                                                       # row batches of <= 4 dialogues, sizes balanced
-        for n in [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]:
+        for n in row_partition(B, self.width):                                                      # row batches of <= width dialogues, sizes balanced
             idxs = list(range(off, off + n))
             key = (n, off) if lanes[0] is model._lanes[0] else (n, off, "side")
             rb = model._rowbatch.get(key)
@@ -503,8 +527,7 @@ class _SessionDriver(_RowDriver):
     def open(self, max_context: int, valid):
         from .rowbatch import RowBatch
         model, lanes, B, off = self.model, self.lanes, len(self.lanes), 0
-        n_groups = -(-B // 4)                                                                       # as _RowDriver.begin partitions a batch
-        for n in [B // n_groups + (1 if g < B % n_groups else 0) for g in range(n_groups)]:
+        for n in row_partition(B, self.width):                                                      # as _RowDriver.begin partitions a batch
             idxs = list(range(off, off + n))
             key = (n, off, "session") if lanes[0] is model._lanes[0] else (n, off, "session", "side")
             rb = model._rowbatch.get(key)
@@ -653,7 +676,12 @@ class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
                  kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
-                 seeded_tokens: bool = False):
+                 seeded_tokens: bool = False, row_batch_width: int = 4):
+        # row_batch_width: dialogues per row batch at most.  4 (default): 5..16 dialogues run as ceil(B / 4) row batches of up to 8 rows.  8: as
+        # ceil(B / 8) row batches of up to 16 rows - one pass over the LLM and head weights for up to 8 dialogues (csrc gemv_rows16_kernel; bf16
+        # weights and KV cache only; DESIGN.md section 5m says for which batch sizes that is faster).  generate(row_batch_width=) overrides it per call
+        self.row_batch_width = check_row_batch_width(row_batch_width, torch.bfloat16 if prequant else torch_dtype, "nf4" if prequant else weight_quant,
+                                                     kv_cache_dtype)
         # kv_cache_dtype: None / "bf16" = the KV cache in the compute dtype; "fp8" = e4m3 bytes with one power-of-two scale per (layer, KV head)
         # for the decode steps (bf16 arithmetic, head_dim 128; the prompt is prefilled on a bf16 staging cache and converted, engine.py); combines
         # with any weight_quant.  Checked first: a bad value raises ValueError before any weight is touched
@@ -758,7 +786,8 @@ class VibeVoiceForConditionalGenerationInference:
         return cls(cfg, sd, device=device, torch_dtype=torch_dtype, attn_implementation=attn_implementation or "hip_gfx950",
                    use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
                    device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False),
-                   mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False))
+                   mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False),
+                   row_batch_width=kw.get("row_batch_width", 4))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -978,7 +1007,10 @@ class VibeVoiceForConditionalGenerationInference:
             # dialogues batched into the row dimension of the LLM / diffusion-head weight passes (rowbatch.py), or one engine lane each
             rows = kwargs.get("row_batch", self.row_batch) and self.row_batch_min <= B <= 16 and self.dtype == torch.bfloat16 and \
                 self._rows_quant_ok() and self.kv_cache_dtype != "fp8"      # fp8 KV: on the lanes (RowBatch needs a bf16 cache)
-            driver = (_RowDriver if rows else _LaneDriver)(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"])
+            if "row_batch_width" in kwargs:      # per call, like row_batch=: the same checks as at construction
+                check_row_batch_width(kwargs["row_batch_width"], self.dtype, self.weight_quant, self.kv_cache_dtype)
+            driver = (_RowDriver(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"], width=kwargs.get("row_batch_width")) if rows
+                      else _LaneDriver(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"]))
             if vps is not None:
                 driver.prefixes = vps
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,

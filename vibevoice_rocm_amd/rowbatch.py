@@ -1,10 +1,10 @@
 """Row-batched decode for the dialogues of ONE generate() call (reference: the batched loop of modeling_vibevoice_inference.py:430-673).
 
 `Engine` lanes run B dialogues as B independent launch chains that each stream every LLM and diffusion-head weight once per frame.  Here the
-B dialogues (2 <= B <= 4 per RowBatch; generate() runs 5..8 as two of them in one loop) share ONE chain for the two weight-heavy parts of a frame:
+B dialogues (2 <= B <= 4 per RowBatch, up to 8 on a row_batch_width=8 model; generate() runs more as several of them in one loop) share ONE chain for the two weight-heavy parts of a frame:
 
   graph A   Qwen2 decode step with R = 2 B rows (dialogue b = rows {2 b: positive, 2 b + 1: negative} of x, lens and one KV cache with 2 B
-            rows): every weight matrix is read once for all dialogues (4..8 rows: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
+            rows): every weight matrix is read once for all dialogues (4..8 rows, and 10..16 on bf16 weights: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
             fragment-major weight copies - of the e4m3 codes with weight_quant="fp8", of the MXFP4 codes and scale bytes with weight_quant="mxfp4" and
             mxfp4_row_batch=True (csrc/vv_gemv_rows.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
             bookkeeping per dialogue.  With do_sample it splits as Engine.step_decode does: A1 = the decode step and the constrained logits
@@ -58,8 +58,8 @@ class RowBatch:
         a lane whose stream IS that stream runs its conv tail inline behind H, the others fork / join through events."""
         self.lanes = lanes
         self.B = B = len(lanes)
-        if not 2 <= B <= 4:
-            raise L.VVError("row batching serves 2..4 dialogues per call")
+        if not 2 <= B <= 8:
+            raise L.VVError("row batching serves 2..8 dialogues per row batch")
         eng = self.main = lanes[0]
         self.lib, self.cfg, self.device, self.stream = eng.lib, eng.cfg, eng.device, (stream or eng.stream)
         self._on_main = [e.stream.cuda_stream == self.stream.cuda_stream for e in lanes]
@@ -67,6 +67,8 @@ class RowBatch:
                 not (eng.w.quant in (None, "fp8") or (eng.w.quant == "mxfp4" and eng.w.mxfp4_row_batch)):
             raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions, or MXFP4 ones with mxfp4_row_batch=True) and a bf16 KV cache "
                             "(kv_cache_dtype='fp8' batches run on the lanes: the row-batched decode step has no fp8-KV form)")
+        if B > 4 and eng.w.quant is not None:
+            raise L.VVError("row batches of 5..8 dialogues (10..16 rows) need bf16 weights without companions: the 16-row matrix-core GEMV has no quantized form")
         self.uid = next(_UID)
         cfg, H = self.cfg, self.cfg.hidden
         f32 = dict(dtype=torch.float32, device=self.device)
