@@ -43,7 +43,7 @@ enum { VV_NF4 = 3 };
  * vv_llm_forward with R in 3..8, vv_head_sample_batch(_sde), vv_llm_tail_batch) uses the bf16 matrices (row-major or their bf16 fragment-major
  * f_* copies), which hold the same effective values. */
 enum { VV_WQ_NF4 = 0x100 };
-/* VV_MXFP4: weight-only OCP Microscaling (MX v1.0) FP4, streaming GEMV only (csrc/vv_gemv_mx.hip): m <= 2, k % 32 == 0, no VV_LIN_W_FRAG, no bf16
+/* VV_MXFP4: weight-only OCP Microscaling (MX v1.0) FP4, streaming GEMV only (csrc/vv_gemv_stream.hip, weight format 3): m <= 2, k % 32 == 0, no VV_LIN_W_FRAG, no bf16
  * hand-off.  A block is 32 consecutive k of one row with one E8M0 scale byte e worth 2^(e - 127); elements are e2m1 codes - codes 0..7 mean
  * +0, 0.5, 1, 1.5, 2, 3, 4, 6 and codes 8..15 the same values negated.  Effective weight W[n][k] = value(code) * 2^(e - 127): exact in bf16.
  * Valid scale bytes are 2 <= e <= 252 (every non-zero effective weight is then a normal, finite fp32); the entry points do not read the bytes.

@@ -971,12 +971,13 @@ def test_built_library_holds_exactly_the_enumerated_kernels(tmp_path):
     """What is compiled is what can be launched: the gfx950 code objects of the three units hold one kernel per entry of ALL_INSTANTIATIONS and no
     other instantiation of the four templates (CPU only: reads the symbol tables of the object files build() left).  The device side is read
     because the host side proves nothing: launch stubs behind a dead branch vanish while their kernels are still generated.  gemv_rows_kernel's
-    weight format 2 (MXFP4) is the other list's: ALL_ROWS_MX of tests/test_host_rowbatch_mxfp4.py, held to exactly that set there."""
+    weight format 2 (MXFP4) is the other list's: ALL_ROWS_MX of tests/test_host_rowbatch_mxfp4.py, held to exactly that set there; so is
+    gemv_stream_kernel's weight format 3 (MXFP4): ALL_MX of tests/test_hip_mxfp4.py."""
     names = {"gemv_stream_kernel": lambda m, dual, ksplit, ku, rw, wq: _stream(m, dual, ksplit, ku, rw, WQS[wq]),
              "gemv_rows_kernel": _rows, "gemv_kernel": _lds, "gemv_generic_kernel": lambda w: f"gemv_generic<w={w}>"}
     got = set()
     for unit in ("vv_gemv_stream.hip", "vv_gemv_rows.hip", "vv_kernels.hip"):
-        got |= instantiations_of([(k, args) for k, args in built_kernels(unit, tmp_path) if (k, args[-1]) != ("gemv_rows_kernel", "2")], names)
+        got |= instantiations_of([(k, args) for k, args in built_kernels(unit, tmp_path) if (k, args[-1]) not in (("gemv_rows_kernel", "2"), ("gemv_stream_kernel", "3"))], names)
     assert got == set(ALL_INSTANTIATIONS), sorted(got ^ set(ALL_INSTANTIATIONS))
 
 

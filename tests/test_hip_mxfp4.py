@@ -1,4 +1,5 @@
-"""Weight-only OCP MXFP4 (weight_quant="mxfp4", vv_linear's VV_MXFP4 form, csrc/vv_gemv_mx.hip) on the MI355X.
+"""Weight-only OCP MXFP4 (weight_quant="mxfp4", vv_linear's VV_MXFP4 form: gemv_stream_kernel's weight format 3, csrc/vv_gemv_stream.hip) on
+the MI355X.
 
 1. `test_decode_is_exact`: one matrix with all 16 codes in every nibble position of a dword, rows 0..4 (two 4-row groups), two 512-wide K
    units, scale bytes {2, 64, 120..134, 200, 252}; one-hot activations read every weight back.  Every output is value(code) * 2^(e - 127)
@@ -8,12 +9,12 @@
    selects it (whole units and ragged ends alternating), against a torch fp64 reference on the effective weights - the walk of
    tests/test_hip_gemv.py (whose case class, operand sets, layout with NaN gaps and guard rows, and three figures are imported): n in
    {1, 3, 4, 5, ...}, m in {1, 2}, broadcast rows, pitches wider than the rows, every prologue and epilogue, in-place residual, two runs
-   bit-identical with every input bit-unchanged.  Cases with the "gemv_mx_blocks" hook make one wave walk three and more row groups.
+   bit-identical with every input bit-unchanged.  Cases with the "gemv_blocks" hook make one wave walk three and more row groups.
    Bars: that file's rule, checked on the CPU for every case here (`test_bars_sit_between_floor_and_dropped_chunk`): at least 8 x the error of
    an fp32 stand-in against fp64, at most a tenth of what one dropped 8-column chunk costs an element.  The rule admits the project's 3e-4 for
    every case, so BAR is that file's.  The effective weights are exact in fp32 and in the reference, as every other weight type's.
-3. `test_built_unit_holds_exactly_the_enumerated_kernels` (CPU: reads the object file build() left): the gfx950 code object of vv_gemv_mx.hip
-   holds exactly the 40 enumerated kernels.
+3. `test_built_unit_holds_exactly_the_enumerated_kernels` (CPU: reads the object file build() left): the gfx950 code object of
+   vv_gemv_stream.hip holds exactly the 40 enumerated kernels of weight format 3.
 4. `test_refusals`: each refused argument set returns VV_E_UNSUPPORTED from vv_linear_route and from vv_linear, and nothing is written.
 5. the engine: generate() against the oracle on mxfp4_effective_state_dict (bar 2e-2, the project's bar for this comparison in fp8 and nf4
    modes) and more than that bar from bf16, graphs equal eager, the decode step's recorded weight types, a batch of 3 on the lanes, and the
@@ -47,7 +48,7 @@ gpu = pytest.mark.gpu
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the launch ladder's rules, restated (vv_gemv_mx.hip: mx_exists, vv_gemv_mx_decide)
+# the launch ladder's rules for weight format 3, restated (vv_gemv_stream.hip: stream_built_mx, vv_gemv_stream_decide)
 # ---------------------------------------------------------------------------------------------------------------
 def _mx(m, dual, ksplit, ku):
     return f"gemv_mx<m={m},dual={dual},ksplit={ksplit},ku={ku}>"
@@ -124,7 +125,7 @@ def _cases():
     # a persistent grid: one block of 4 waves (or one K-split block) walks 3 and more row groups, the last one partial
     for i, (k, dual, n, blocks) in enumerate(((1024, 0, 61, 1), (1536, 1, 45, 1), (3072, 0, 27, 2), (2560, 1, 18, 1), (10752, 0, 13, 1))):
         o = ops(dual, i + 3)
-        cs.append(Case(f"mx_pers_d{dual}_k{k}_n{n}_{tag(o)}", mx_decide(2, k, dual), 2, n, k, wq="mxfp4", hooks={"gemv_mx_blocks": blocks}, **o))
+        cs.append(Case(f"mx_pers_d{dual}_k{k}_n{n}_{tag(o)}", mx_decide(2, k, dual), 2, n, k, wq="mxfp4", hooks={"gemv_blocks": blocks}, **o))
     return cs
 
 
@@ -232,8 +233,14 @@ def test_cases_reach_every_compiled_instantiation():
 
 def test_built_unit_holds_exactly_the_enumerated_kernels(tmp_path):
     """What is compiled is what can launch (CPU only: reads the symbol table of the object file build() left): the gfx950 code object of
-    vv_gemv_mx.hip holds one gemv_mx_kernel per entry of ALL_MX and no other instantiation of the template."""
-    got = instantiations_of(built_kernels("vv_gemv_mx.hip", tmp_path), {"gemv_mx_kernel": _mx})
+    vv_gemv_stream.hip holds one gemv_stream_kernel<m, dual, ksplit, ku, 4, 3> (weight format 3 = MXFP4, four rows per step) per entry of ALL_MX
+    and no other instantiation of the template with that format.  The formats 0 / 1 / 2 are the other list's: ALL_INSTANTIATIONS of
+    tests/test_hip_gemv.py, held to exactly that set there."""
+    def name(m, dual, ksplit, ku, rw, wq):
+        assert (rw, wq) == (4, 3)
+        return _mx(m, dual, ksplit, ku)
+    got = instantiations_of([(k, args) for k, args in built_kernels("vv_gemv_stream.hip", tmp_path) if (k, args[-1]) == ("gemv_stream_kernel", "3")],
+                            {"gemv_stream_kernel": name})
     assert got == set(ALL_MX), sorted(got ^ set(ALL_MX))
 
 
@@ -245,7 +252,7 @@ _FAKE = {name: 0x10000000 * (i + 1) for i, name in enumerate(("x", "w", "w2", "n
 
 
 class _tuned:
-    """sets the case's vv_tune keys (only "gemv_mx_blocks" here) and puts them back at 0 = the built-in rule on the way out"""
+    """sets the case's vv_tune keys (only "gemv_blocks" here) and puts them back at 0 = the built-in rule on the way out"""
 
     def __init__(self, hooks):
         self.hooks = hooks
@@ -253,7 +260,7 @@ class _tuned:
     def __enter__(self):
         L, l = _lib()[:2]
         for key, v in self.hooks.items():
-            assert key == "gemv_mx_blocks"
+            assert key == "gemv_blocks"
             L.check(l.vv_tune(key.encode(), v), f"vv_tune {key}")
 
     def __exit__(self, *exc):

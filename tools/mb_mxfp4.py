@@ -8,7 +8,7 @@
   2. generate() per preset (1.5B, 7B), 1 dialogue, forced bench schedule (`frames` speech frames), injected noise, 20 steps: the four models
      are built side by side, warmed, and timed in alternation, `runs` >= 5 runs each (host clock around a call that ends in a device
      synchronise); audio-sec/s as p50 (min - max), and each quantised waveform's relative RMS against the bf16 one of the same process;
-  3. (needs hipcc, no GPU) VGPRs, scratch, occupancy and LDS of every gemv_mx kernel from -Rpass-analysis=kernel-resource-usage.
+  3. (needs hipcc, no GPU) VGPRs, scratch, occupancy and LDS of every MXFP4 (weight format 3) gemv_stream_kernel from -Rpass-analysis=kernel-resource-usage.
     python tools/mb_mxfp4.py [sections=123] [frames=60] [runs=5] [presets=1.5b,7b] [out=profiles/mxfp4_gemv.txt] [rounds=5]
 A section is appended to `out`; section 1 starts the file."""
 import ctypes as C
@@ -45,16 +45,16 @@ def p50(v):
 
 def section_3():
     from vibevoice_rocm_amd import build as vb
-    src = os.path.join(vb.HERE, "csrc", "vv_gemv_mx.hip")
+    src = os.path.join(vb.HERE, "csrc", "vv_gemv_stream.hip")
     cmd = [vb.find_hipcc(), *vb.FLAGS, "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(vb.HERE, "csrc"), "--cuda-device-only", "-S",
            "-Rpass-analysis=kernel-resource-usage", src, "-o", os.devnull]
     err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    say("# 3. build checks of csrc/vv_gemv_mx.hip (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage)")
-    say("# gemv_mx_kernel instantiations: M DUAL KSPLIT KU | VGPRs scratch(B/lane) occupancy(waves/SIMD) LDS(B/block); LDS = the RMSNorm / split-K")
+    say("# 3. build checks of the MXFP4 kernels of csrc/vv_gemv_stream.hip (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage)")
+    say("# gemv_stream_kernel<M, DUAL, KSPLIT, KU, 4, 3> instantiations: M DUAL KSPLIT KU | VGPRs scratch(B/lane) occupancy(waves/SIMD) LDS(B/block); LDS = the RMSNorm / split-K")
     say("# reduction slots only: the decode path has no table and no LDS")
     rows = []
     for blk in re.split(r"remark: [^\n]*Function Name: ", err)[1:]:
-        m = re.match(r"\S*gemv_mx_kernelILi(\d)ELb([01])ELi(\d+)ELi(\d)E", blk)
+        m = re.match(r"\S*gemv_stream_kernelILi(\d)ELb([01])ELi(\d+)ELi(\d)ELi4ELi3EE", blk)
         if not m:
             continue
         g = lambda key: int(re.search(re.escape(key) + r": (\d+)", blk).group(1))

@@ -37,17 +37,12 @@ struct vv_kv_args8 : vv_kv_args {
 // followed, no HIP call, the only copy of the thresholds - and a LAUNCH of that struct; vv_linear_route prints the same struct, so the name it
 // reports is the kernel vv_linear starts.  kind 0 = not covered (the caller falls back).
 enum { VV_GEMV_STREAM = 1, VV_GEMV_HOT = 2, VV_GEMV_CONV_HOT = 3 };
-// vv_gemv_stream.hip: gemv_stream_kernel<m, dual, ksplit, ku, rw, wq> (wq: 0 bf16, 1 fp8, 2 NF4) on blocks x threads, or a hot kernel (table entry idx)
+// vv_gemv_stream.hip: gemv_stream_kernel<m, dual, ksplit, ku, rw, wq> (wq: 0 bf16, 1 fp8, 2 NF4, 3 MXFP4: the VV_MXFP4 weights' streaming GEMV,
+// m <= 2, named gemv_mx<m, dual, ksplit, ku>) on blocks x threads, or a hot kernel (table entry idx)
 struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, blocks, threads; };
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
 int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
-// vv_gemv_mx.hip: gemv_mx_kernel<m, dual, ksplit, ku> on blocks x threads - the streaming GEMV on VV_MXFP4 weights (m <= 2); kind 1 = covered, 0 = refused
-struct vv_mx_route { int kind, m, dual, ksplit, ku, n_groups, blocks, threads; };
-vv_mx_route vv_gemv_mx_decide(const vv_lin_args& a);
-int vv_launch_gemv_mx_route(const vv_lin_args& a, const vv_mx_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
-int vv_gemv_mx_route_name(const vv_mx_route& r, char* name, int cap);
-void vv_gemv_mx_set_blocks(int b);                                // tuning hook "gemv_mx_blocks": persistent blocks of the MXFP4 GEMV (0 = the built-in rule)
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
 // template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.

@@ -6,11 +6,12 @@
 // workgroups are persistent: each wave walks its row groups with the next group's loads already in flight while
 // it reduces the current one (register double buffering), so the memory pipe never drains between rows.
 // Row sums use DPP row reductions (vv_wave_sum), every output's epilogue (bias / GELU / SwiGLU / gate / residual) runs in its own
-// lane on operands fetched one row group ahead, M <= 2 has an fp8 (e4m3fn codes + row scale) and an NF4 (4-bit codes + per-64 block
-// scale, see below) instantiation, M = 8 covers the T = 8 conv stage when K splits to <= 2 units per wave.
+// lane on operands fetched one row group ahead, M <= 2 has an fp8 (e4m3fn codes + row scale), an NF4 (4-bit codes + per-64 block
+// scale, see below) and an MXFP4 (OCP e2m1 codes + one E8M0 scale byte per 32 k of a row, see below) instantiation, M = 8 covers the T = 8
+// conv stage when K splits to <= 2 units per wave.
 //   KSPLIT == 1        a wave owns RW whole weight rows per step (block = 4 independent waves)        K <= 2560
 //   KSPLIT == 4/8/16   the block's 4/8/16 waves split K (interleaved 512-element units) and combine through LDS
-//                      in a fixed order (long K: 1.5B down-projections, every 7B matrix)
+//                      in a fixed order (long K: 1.5B down-projections, every 7B matrix); MXFP4: 4 / 8 waves, K <= 2560 whole (SwiGLU: 2048)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -47,23 +48,28 @@ __device__ __forceinline__ void unpack8_f8(const u32x4 v, float (&o)[8]) {
 // they are loaded one row group ahead, in front of the weight loads that follow them in the queue (loads return in order: an
 // operand load issued at epilogue time would sit behind two row groups of prefetched weights)
 typedef float vf2 __attribute__((ext_vector_type(2)));
-struct EpiOp { float b, g, r, s, s2; };   // bias, gate, residual, fp8 row scales (raw loads; absent operands are ignored at use)
-__device__ __forceinline__ EpiOp epi_load(const vv_lin_args& a, int m, int n) {
+// ROWSC: the instantiation can meet fp8 row scales at all (every format but MXFP4).  For the others the fp8 loads and multiplies hang on the
+// run-time test a.wdt == VV_FP8; the MXFP4 kernels carry none of them: their EpiOp is b, g, r.
+template <bool ROWSC> struct EpiOp { float b, g, r, s, s2; };   // bias, gate, residual, fp8 row scales (raw loads; absent operands are ignored at use)
+template <> struct EpiOp<false> { float b, g, r; };
+template <bool ROWSC>
+__device__ __forceinline__ EpiOp<ROWSC> epi_load(const vv_lin_args& a, int m, int n) {
   // straight-line and use-free: an absent operand reads x[0] (always a valid address), the values are only looked at in epi_pre.
   // With a select per operand here the compiler waited for each dword right away - draining every load issued before it - and a
   // uniform branch per operand cut the issue sequence into blocks it then reordered.
-  EpiOp e;
-  const bool f8s = a.wdt == VV_FP8, f8d = f8s && a.w2;
+  EpiOp<ROWSC> e;
+  const bool f8s = ROWSC && a.wdt == VV_FP8, f8d = f8s && a.w2;
   const float* pb = a.bias ? a.bias + n : a.x;
   const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)m * a.gate_ld + n : (int64_t)n) : a.x;
   const float* pr = a.res ? a.res + (int64_t)m * a.ldres + n : a.x;
   const float* ps = f8s ? a.wscale + n : a.x;
   const float* ps2 = f8d ? a.w2scale + n : a.x;
-  e.b = *pb; e.g = *pg; e.r = *pr; e.s = *ps; e.s2 = *ps2;
+  e.b = *pb; e.g = *pg; e.r = *pr;
+  if constexpr (ROWSC) { e.s = *ps; e.s2 = *ps2; }
   return e;
 }
-__device__ __forceinline__ EpiOp epi_load_cond(const vv_lin_args& a, int m, int n) {   // one uniform branch per operand (owner lanes only)
-  EpiOp e;
+__device__ __forceinline__ EpiOp<true> epi_load_cond(const vv_lin_args& a, int m, int n) {   // one uniform branch per operand (owner lanes only)
+  EpiOp<true> e;
   e.b = a.bias ? a.bias[n] : 0.f;
   e.g = a.gate ? (a.gate_ld ? a.gate[(int64_t)m * a.gate_ld + n] : a.gate[n]) : 1.f;
   e.r = a.res ? a.res[(int64_t)m * a.ldres + n] : 0.f;
@@ -71,8 +77,11 @@ __device__ __forceinline__ EpiOp epi_load_cond(const vv_lin_args& a, int m, int 
   e.s2 = (a.wdt == VV_FP8 && a.w2) ? a.w2scale[n] : 1.f;
   return e;
 }
-__device__ __forceinline__ void epi_pre(const vv_lin_args& a, int m, int n, float v, float v2, const EpiOp& e) {
-  if (a.wdt == VV_FP8) { v *= e.s; if (a.w2) v2 *= e.s2; }      // fp8 codes carry a row scale
+template <bool ROWSC>
+__device__ __forceinline__ void epi_pre(const vv_lin_args& a, int m, int n, float v, float v2, const EpiOp<ROWSC>& e) {
+  if constexpr (ROWSC) {
+    if (a.wdt == VV_FP8) { v *= e.s; if (a.w2) v2 *= e.s2; }      // fp8 codes carry a row scale
+  }
   if (a.bias) v += e.b;
   if (a.act == VV_ACT_GELU) v = gelu1(v);
   else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
@@ -102,14 +111,35 @@ __device__ __forceinline__ void nf4_build_lut(float s, unsigned int* dst) {   //
   *reinterpret_cast<u32x4*>(dst + 4) = u32x4{e[4], e[5], e[6], e[7]};
 }
 
+// MXFP4 (VV_MXFP4, weight-only OCP Microscaling FP4): the NF4 geometry - a row group is FOUR weight rows, a lane's 16-byte load carries the 32
+// codes of its own 8-wide k slice of one 512-wide unit in each of the 4 rows (layout: include/vv_hip.h) - and one 4-byte load per unit carries
+// the four rows' scale bytes of the lane's 32-block.  Decode is the vector ALU's own: v_cvt_scalef32_pk_f32_fp4 turns one byte (two codes) and
+// the block scale 2^(e - 127), built as __uint_as_float(e << 23), into two scaled fp32 weights - four per dword of codes, no table, no LDS.
+
+// The 8 weights of one dword of codes (nibble i = k0 + i) under scale byte e: byte b of the dword holds k0 + 2 b (low nibble) and k0 + 2 b + 1
+__device__ __forceinline__ void unpack8_mx(unsigned int c, unsigned int e, vf2 (&w)[4]) {
+  const float s = __uint_as_float(e << 23);
+  w[0] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c, s, 0);
+  w[1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c, s, 1);
+  w[2] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c, s, 2);
+  w[3] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(c, s, 3);
+}
+// The MXFP4 kernels were written against one setting of the "gemv_opt" tune word and never read it: batched prologue for RMSNorm (bit 0) and
+// for no prologue (bit 1), straight-line epilogue-operand loads (bit 2); no block-staged prologue (bit 3: their dual whole-row kernels take
+// the per-wave paths, so no staging buffer sits in their LDS) and no forced cacheable loads (bit 4).  Their registers and grids were sized
+// under that policy, so it is a compile-time constant for them; note that it is NOT the library default (13) the other formats run under.
+constexpr int MX_OPT = 7;
+
 int g_blocks_override = 0;   // tuning hook (vv_tune)
 int g_waves_override = 0;    // tuning hook "gemv_waves": waves per block of the whole-row (KSPLIT == 1) kernels, 3 .. 8
 int g_opt = 13;              // tuning hook "gemv_opt": bit 0 / 1 = batched prologue for RMSNorm / no prologue, bit 2 = straight-line epilogue-operand loads, bit 3 = block-staged RMSNorm prologue (KSPLIT == 1)
 int g_long_cap = 512;        // persistent blocks for K-split launches with K > 6144 (tuning hook)
 int g_long_ku = 5;           // K units per wave allowed for rows longer than 12 units (tuning hook: 3 -> 8 waves split K)
 
-template <int M, bool DUAL, int KSPLIT, int KU, int RW, int WQ>   // WQ: 0 bf16, 1 fp8, 2 NF4 (RW == 4)
-__global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_kernel(const vv_lin_args a, const int n_groups, const int opt) {
+template <int M, bool DUAL, int KSPLIT, int KU, int RW, int WQ>   // WQ: 0 bf16, 1 fp8, 2 NF4 (RW == 4), 3 MXFP4 (RW == 4)
+__global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_kernel(const vv_lin_args a, const int n_groups, const int tune_opt) {
+  constexpr bool mx = WQ == 3;
+  const int opt = mx ? MX_OPT : tune_opt;            // MXFP4: the fixed policy above, the argument is never read
   constexpr int NW = (KSPLIT == 1) ? 8 : KSPLIT;     // waves per block (KSPLIT == 1: at most; the launcher picks 3 .. 8 so that the row groups divide evenly)
   __shared__ float red[NW * M];
   __shared__ float part[2][NW][RW * M * 2];
@@ -119,6 +149,10 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
   const int K = a.k, N = a.n, mr = a.m;          // mr <= M real rows
   const bf16_t* __restrict__ W = reinterpret_cast<const bf16_t*>(a.w);
   const bf16_t* __restrict__ W2 = reinterpret_cast<const bf16_t*>(a.w2);
+  const unsigned char* __restrict__ C1 = reinterpret_cast<const unsigned char*>(a.w);         // MXFP4: codes and scale bytes
+  const unsigned char* __restrict__ C2 = reinterpret_cast<const unsigned char*>(a.w2);
+  const unsigned char* __restrict__ S1 = reinterpret_cast<const unsigned char*>(a.wscale);
+  const unsigned char* __restrict__ S2 = reinterpret_cast<const unsigned char*>(a.w2scale);
 
   // ---- this lane's k offsets and activation fragment (kept in registers for the whole kernel) -------------------
   int koff[KU];
@@ -133,17 +167,39 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
   const bool reused = (a.flags & VV_LIN_W_REUSED) != 0 || (opt & 16);    // opt bit 4 (tuning): every matrix with cacheable loads
   constexpr bool f8 = WQ == 1;                   // weight-only fp8 / NF4 are instantiations of their own: the bf16 kernels carry none of it
   constexpr bool nf4 = WQ == 2;
-  static_assert(!nf4 || (RW == 4 && M <= 2), "NF4: 4 rows per 16-byte code load, decode rows only");
-  const int units_k = (K + 511) >> 9;            // NF4: 512-wide units per row in the packed layout
+  static_assert(!(nf4 || mx) || (RW == 4 && M <= 2), "NF4, MXFP4: 4 rows per 16-byte code load, decode rows only");
+  const int units_k = (K + 511) >> 9;            // NF4, MXFP4: 512-wide units per row in the packed layout
   // the first row group's weight loads are issued before the activation prologue so both latencies overlap
   const int gstride = (KSPLIT == 1) ? gridDim.x * nwv : gridDim.x;
   int g = (KSPLIT == 1) ? blockIdx.x * nwv + wave : blockIdx.x;
-  u32x4 cur[RW][KU], cur2[DUAL ? RW : 1][KU];
-  u32x4 nxt[RW][KU], nxt2[DUAL ? RW : 1][KU];
-  auto issue = [&](u32x4 (&b)[RW][KU], u32x4 (&b2)[DUAL ? RW : 1][KU], int grp) {
+  // MXFP4: slot 0 holds the four rows' codes, and a unit's scale dword (byte r = row r) travels beside them in a register of its own (as a lane
+  // of a 16-byte slot it pinned all four registers of the slot in both buffers); the other formats never touch the scale arrays
+  constexpr int NB = mx ? 1 : RW, NB2 = (DUAL && !mx) ? RW : 1;     // 16-byte slots per unit in a buffer
+  constexpr int NS = mx ? KU : 1, NS2 = (mx && DUAL) ? KU : 1;
+  u32x4 cur[NB][KU], cur2[NB2][KU];
+  u32x4 nxt[NB][KU], nxt2[NB2][KU];
+  unsigned int ws[NS], ws2[NS2], nws[NS], nws2[NS2];
+  auto issue = [&](u32x4 (&b)[NB][KU], u32x4 (&b2)[NB2][KU], unsigned int (&s)[NS], unsigned int (&s2)[NS2], int grp) {
     // a group past the end (the unconditional second issue of a wave that owns a single group) degenerates to one 16-byte
     // line per instruction: every lane reads element 0 of the matrix
     const bool live = grp < n_groups;
+    if constexpr (mx) {        // unit u: 16 B of codes (dword r = row r) in b[0][u], the scale dword in s[u]
+      // a group past the end and a unit past the row's end read offset 0 of the matrix: always inside it
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+        const int unit = (KSPLIT == 1) ? u : (wave + NW * u);
+        const bool ok = live && unit < units_k;
+        const int64_t gu = ok ? (int64_t)grp * units_k + unit : 0;
+        const int64_t co = ok ? (gu * 64 + lane) * 16 : 0;
+        const int64_t so = ok ? (gu * 16 + (lane >> 2)) * 4 : 0;
+        const u32x4* p1 = reinterpret_cast<const u32x4*>(C1 + co);
+        const u32x4* p2 = reinterpret_cast<const u32x4*>(C2 + co);
+        if (reused) { b[0][u] = *p1; if constexpr (DUAL) b2[0][u] = *p2; }
+        else { b[0][u] = __builtin_nontemporal_load(p1); if constexpr (DUAL) b2[0][u] = __builtin_nontemporal_load(p2); }
+        s[u] = *reinterpret_cast<const unsigned int*>(S1 + so);
+        if constexpr (DUAL) s2[u] = *reinterpret_cast<const unsigned int*>(S2 + so);
+      }
+    } else {
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
       const int n = min(grp * RW + r, N - 1);
@@ -187,23 +243,32 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
         }
       }
     }
+    }
   };
   // epilogue: output (r, m) of a row group belongs to lane / thread  r * M + m  (KSPLIT == 1: lane of the wave that owns the
   // group; K split: thread of the block), so activations like GELU run once per output in parallel lanes instead of RW x M
   // times in lane 0, and each owner fetches its own operands one group ahead
   constexpr int NE = 1;
-  const bool has_eo = a.bias || a.gate || a.res || a.wdt == VV_FP8;
+  const bool has_eo = a.bias || a.gate || a.res || (!mx && a.wdt == VV_FP8);
   const int eid = (KSPLIT == 1) ? lane : tid;
-  EpiOp eo_cur[NE], eo_nxt[NE];
+  EpiOp<!mx> eo_cur[NE], eo_nxt[NE];
   const int eo_id = eid < RW * M ? eid : 0;       // lanes that own no output fetch output 0's operands: no divergent branch around the loads
   const int eo_r = eo_id / M, eo_m = (eo_id - eo_r * M) < mr ? (eo_id - eo_r * M) : mr - 1;
-  auto load_eo = [&](EpiOp (&e)[NE], int grp) {
+  auto load_eo = [&](EpiOp<!mx> (&e)[NE], int grp) {
     if (!has_eo) return;
-    if (opt & 4) { e[0] = epi_load(a, eo_m, min((grp < n_groups ? grp : n_groups - 1) * RW + eo_r, N - 1)); return; }
-    if (grp < n_groups && eid < RW * M) e[0] = epi_load_cond(a, eo_m, min(grp * RW + eo_r, N - 1));
+    if (opt & 4) { e[0] = epi_load<!mx>(a, eo_m, min((grp < n_groups ? grp : n_groups - 1) * RW + eo_r, N - 1)); return; }
+    if constexpr (!mx) {
+      if (grp < n_groups && eid < RW * M) e[0] = epi_load_cond(a, eo_m, min(grp * RW + eo_r, N - 1));
+    }
   };
+  // (MXFP4 sets and moves its one record without the one-trip loop: the loop form gave its kernels another register assignment than they had
+  // as a unit of their own, and dropping the loop does the same to the other formats' - profiles/stream_mx_fold.txt)
+  if constexpr (mx) {
+    eo_cur[0].b = 0.f; eo_cur[0].g = 1.f; eo_cur[0].r = 0.f; eo_nxt[0] = eo_cur[0];
+  } else {
 #pragma unroll
-  for (int i = 0; i < NE; ++i) { eo_cur[i].b = 0.f; eo_cur[i].g = 1.f; eo_cur[i].r = 0.f; eo_cur[i].s = 1.f; eo_cur[i].s2 = 1.f; eo_nxt[i] = eo_cur[i]; }
+    for (int i = 0; i < NE; ++i) { eo_cur[i].b = 0.f; eo_cur[i].g = 1.f; eo_cur[i].r = 0.f; eo_cur[i].s = 1.f; eo_cur[i].s2 = 1.f; eo_nxt[i] = eo_cur[i]; }
+  }
   float xr[M][KU][8];
   // Activation side.  BATCHED (the per-frame shapes: M * KU <= 8, no SiLU prologue): every load the prologue needs - x rows, norm
   // weight, adaLN shift / scale - is issued in ONE batch AHEAD of the weight loads.  Loads return in order: these are L2 hits and
@@ -212,7 +277,8 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
   // started once the first weights had landed: +2 us on every kernel with a prologue, +4 us on the dual one.)
   // the SwiGLU (dual) kernels take the block-staged prologue, the others the per-wave batched one: one fast path per instantiation
   // keeps the register allocation of each kernel at what its own path needs
-  constexpr bool CAN_STAGE = KSPLIT == 1 && (DUAL || M == 8);    // M = 8 (the T = 8 conv stage): 32 KB of activations per WAVE otherwise
+  // (MXFP4: never block-staged, see MX_OPT)
+  constexpr bool CAN_STAGE = KSPLIT == 1 && (DUAL || M == 8) && !mx;    // M = 8 (the T = 8 conv stage): 32 KB of activations per WAVE otherwise
   constexpr bool BATCHED = (M * KU <= 8) && !CAN_STAGE;
   // adaLN-modulated rows on a non-dual kernel (the head's 64-row final linear) keep the legacy path: the batch would pin 96 more registers
   const bool batched = BATCHED && ((a.pro == VV_PRO_RMSNORM && !a.mod_scale && (opt & 1)) || (a.pro == VV_PRO_NONE && (opt & 2)));
@@ -246,9 +312,9 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
       }
     }
     load_eo(eo_cur, g);
-    issue(cur, cur2, g);
+    issue(cur, cur2, ws, ws2, g);
     load_eo(eo_nxt, g + gstride);
-    issue(nxt, nxt2, g + gstride);
+    issue(nxt, nxt2, nws, nws2, g + gstride);
     __builtin_amdgcn_sched_barrier(0);
 #define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 #pragma unroll
@@ -329,9 +395,9 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     // the first two row groups go out unconditionally (a group past the end costs one 16-byte line per load instruction) so that
     // no branch separates them from the loads above, and nothing below is scheduled ahead of them
     load_eo(eo_cur, g);
-    issue(cur, cur2, g);
+    issue(cur, cur2, ws, ws2, g);
     load_eo(eo_nxt, g + gstride);
-    issue(nxt, nxt2, g + gstride);
+    issue(nxt, nxt2, nws, nws2, g + gstride);
     __builtin_amdgcn_sched_barrier(0);
     // everything the prologue computes with is made opaque HERE, behind the weight loads: hipcc otherwise hoists pieces of the
     // arithmetic (and the waits they need) into the blocks above, in front of the weight issue
@@ -388,8 +454,8 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
       }
     }
   } else {
-  if (g < n_groups) { load_eo(eo_cur, g); issue(cur, cur2, g); }
-  if (g + gstride < n_groups) { load_eo(eo_nxt, g + gstride); issue(nxt, nxt2, g + gstride); }   // two row groups in flight before the prologue even starts
+  if (g < n_groups) { load_eo(eo_cur, g); issue(cur, cur2, ws, ws2, g); }
+  if (g + gstride < n_groups) { load_eo(eo_nxt, g + gstride); issue(nxt, nxt2, nws, nws2, g + gstride); }   // two row groups in flight before the prologue even starts
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const float* xrow = a.x + (int64_t)(m < mr ? m : mr - 1) * a.ldx;
@@ -500,6 +566,26 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
         }
         __builtin_amdgcn_wave_barrier();         // the next pair's tables overwrite these only after every read above was issued
       }
+    } else if constexpr (mx) {
+      // the conversion delivers (k, k + 1) as a register pair, which is the packed FMA's operand as it stands
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+          vf2 w[4], w2[4];
+          unpack8_mx(cur[0][u][r], (ws[u] >> (8 * r)) & 0xffu, w);
+          if constexpr (DUAL) unpack8_mx(cur2[0][u][r], (ws2[u] >> (8 * r)) & 0xffu, w2);
+#pragma unroll
+          for (int m = 0; m < M; ++m) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const vf2 xp = {xr[m][u][2 * j], xr[m][u][2 * j + 1]};
+              pacc[r][m] = __builtin_elementwise_fma(w[j], xp, pacc[r][m]);
+              if constexpr (DUAL) pacc2[r][m] = __builtin_elementwise_fma(w2[j], xp, pacc2[r][m]);
+            }
+          }
+        }
+      }
     } else {
 #pragma unroll
     for (int u = 0; u < KU; ++u) {
@@ -538,7 +624,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
             if (lane == r * M + m) { v = acc[r][m]; if (DUAL) v2 = acc2[r][m]; }
         const int r = lane / M, m = lane - r * M;
         const int n = g * RW + r;
-        if (n < N && m < mr) epi_pre(a, m, n, v, v2, eo_cur[0]);
+        if (n < N && m < mr) epi_pre<!mx>(a, m, n, v, v2, eo_cur[0]);
       }
     } else {
       if (lane == 0) {
@@ -558,19 +644,31 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
           float s = 0.f, s2 = 0.f;
 #pragma unroll
           for (int w4 = 0; w4 < NW; ++w4) { s += part[parity][w4][tid * 2]; s2 += part[parity][w4][tid * 2 + 1]; }
-          epi_pre(a, m, n, s, s2, eo_cur[0]);
+          epi_pre<!mx>(a, m, n, s, s2, eo_cur[0]);
         }
       }
       parity ^= 1;                                 // ping-pong: one barrier per group is enough
     }
+    if constexpr (mx) {
+      eo_cur[0] = eo_nxt[0];
+    } else {
 #pragma unroll
-    for (int i = 0; i < NE; ++i) eo_cur[i] = eo_nxt[i];
+      for (int i = 0; i < NE; ++i) eo_cur[i] = eo_nxt[i];
+    }
+    if constexpr (mx) {                            // one slot per unit, its scale dword beside it: one loop, unit by unit
+#pragma unroll
+      for (int u = 0; u < KU; ++u) {
+        cur[0][u] = nxt[0][u]; ws[u] = nws[u];
+        if constexpr (DUAL) { cur2[0][u] = nxt2[0][u]; ws2[u] = nws2[u]; }
+      }
+    } else {
 #pragma unroll
     for (int r = 0; r < RW; ++r)
 #pragma unroll
       for (int u = 0; u < KU; ++u) { cur[r][u] = nxt[r][u]; if (DUAL) cur2[r][u] = nxt2[r][u]; }
+    }
     g = gn;
-    if (g + gstride < n_groups) { load_eo(eo_nxt, g + gstride); issue(nxt, nxt2, g + gstride); }   // keep two groups in flight
+    if (g + gstride < n_groups) { load_eo(eo_nxt, g + gstride); issue(nxt, nxt2, nws, nws2, g + gstride); }   // keep two groups in flight
   }
 }
 
@@ -588,18 +686,29 @@ constexpr bool stream_built(bool dual, int ksplit, int ku) {
 }
 // NF4: <= 2 rows, <= 8 waves (LDS), the dual kernel at <= 4 units per wave (registers)
 constexpr bool stream_built_nf4(int m, bool dual, int ksplit, int ku) { return stream_built(dual, ksplit, ku) && m <= 2 && ksplit <= 8 && !(dual && ku > 4); }
+// MXFP4, a rule of its own (not NF4's): <= 2 rows; whole rows at 1..5 units, the SwiGLU kernel (two code streams) at 1..4; 4 waves splitting K at
+// 2..5 units per wave, 8 waves at 3..5 (2 units x 8 waves is already served by 4 waves x 4 units); SwiGLU with K split: 2..3 units per wave on 4 or
+// 8 waves; never 16 waves
+constexpr bool stream_built_mx(int m, bool dual, int ksplit, int ku) {
+  if (m != 1 && m != 2) return false;
+  if (ksplit == 1) return ku >= 1 && ku <= (dual ? 4 : 5);
+  if (ksplit != 4 && ksplit != 8) return false;
+  if (dual) return ku == 2 || ku == 3;
+  return ku >= (ksplit == 4 ? 2 : 3) && ku <= 5;
+}
 // 5..8 rows: the fragment is 8 rows x KU x 8 floats, so K is split until KU <= 2 (16 waves x 8 rows does not fit the 128-VGPR budget of a 1024-thread block)
 constexpr bool stream_built_m8(int ksplit, int ku, int rw) { return (ksplit == 1 && (ku == 1 || ku == 2) && rw == 1) || ((ksplit == 4 || ksplit == 8) && ku == 2 && rw == 2); }
 // Every kernel of this file that exists, as (m, dual, ksplit, ku, rw, wq): the launch ladder instantiates under this predicate and nothing else, and
 // the decision checks its finished route against it, so neither can name a kernel the other does not have.
 //   m = 8      bf16 only, one weight stream
-//   NF4        rw = 4 (four rows per 16-byte code load), and no other weight type has rw = 4
+//   NF4, MXFP4 rw = 4 (four rows per 16-byte code load), and no other weight type has rw = 4
 //   bf16, fp8  rw = 1 or 2; fp8 for decode rows (m <= 2) only; rw = 1 for the dual kernels (gemv_dual_rw) and the whole-row ones (gemv_small_rw):
 //              a non-dual K-split kernel is always rw = 2
 constexpr bool stream_exists(int m, bool dual, int ksplit, int ku, int rw, int wq) {
   if (m == 8) return wq == 0 && !dual && stream_built_m8(ksplit, ku, rw);
   if (m != 1 && m != 2 && m != 4) return false;
   if (wq == 2) return rw == 4 && stream_built_nf4(m, dual, ksplit, ku);
+  if (wq == 3) return rw == 4 && stream_built_mx(m, dual, ksplit, ku);
   if (wq != 0 && !(wq == 1 && m <= 2)) return false;
   if (rw != 1 && rw != 2) return false;
   if (rw == 1 && !dual && ksplit != 1) return false;
@@ -617,7 +726,8 @@ void stream_grid(const vv_lin_args& a, vv_stream_route& r) {
   const int work = (KSPLIT == 1) ? (n_groups + waves - 1) / waves : n_groups;       // blocks if each wave did exactly one group
   // K split: every block reads all of x (M x K fp32 from L2); beyond ~6K columns that traffic rivals the weights, so long
   // rows use fewer, persistent blocks (n=1536 k=8960: 10.4 us at 768 blocks, 9.1 us at 512)
-  const int cap = (KSPLIT == 1) ? (DUAL ? (RW == 1 ? 512 : 448) : 512) : (a.k > 6144 ? g_long_cap : 1024);
+  // (whole rows, dual: 448 at two and four rows per step - bf16 / fp8 under gemv_dual_rw = 2, NF4 - except MXFP4, whose every whole-row cap is 512)
+  const int cap = (KSPLIT == 1) ? (DUAL ? ((RW == 1 || r.wq == 3) ? 512 : 448) : 512) : (a.k > 6144 ? g_long_cap : 1024);
   int blocks = work < cap ? work : cap;
   if (g_blocks_override > 0) blocks = g_blocks_override < work ? g_blocks_override : work;
   r.n_groups = n_groups;
@@ -644,6 +754,7 @@ bool launch_wq(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s) {
     case 0: return launch_one<M, DUAL, KSPLIT, KU, RW, 0>(a, r, s);
     case 1: return launch_one<M, DUAL, KSPLIT, KU, RW, 1>(a, r, s);
     case 2: return launch_one<M, DUAL, KSPLIT, KU, RW, 2>(a, r, s);   // never a bf16 read of codes
+    case 3: return launch_one<M, DUAL, KSPLIT, KU, RW, 3>(a, r, s);
   }
   return false;
 }
@@ -699,13 +810,19 @@ void vv_gemv_stream_set_small_rw(int r) { g_small_rw = r; }
 // (the caller falls back).  Reads the arguments' values and alignments and the tune state only.
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
   vv_stream_route r = {};
-  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4) || a.m > 8 || a.k % 8) return r;
+  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4 && a.wdt != VV_MXFP4) || a.m > 8 || a.k % 8) return r;
   // NF4: decode rows only, whole 64-blocks, scales for every matrix, 16-byte aligned codes (vv_hip.h)
   if (a.wdt == VV_NF4 && (a.m > 2 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) ||
                           (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4) || (a.flags & VV_LIN_W_FRAG)))
     return r;
   if (a.wdt == VV_FP8 && (a.m > 2 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 8 || (a.w2 && (uintptr_t)a.w2 % 8))) return r;
-  r.wq = a.wdt == VV_NF4 ? 2 : a.wdt == VV_FP8 ? 1 : 0;
+  // MXFP4 (vv_hip.h): decode rows only, whole 32-blocks, a scale array for every matrix, 16-byte aligned codes and scales, no fragment-major flag,
+  // no bf16 hand-off; rows longer than the kernels reach (40 units, SwiGLU 24) find no kernel below
+  if (a.wdt == VV_MXFP4 && (a.m < 1 || a.m > 2 || a.k % 32 || !a.wscale || (a.w2 && !a.w2scale) ||
+                            (a.flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || (uintptr_t)a.w % 16 || (uintptr_t)a.wscale % 16 ||
+                            (a.w2 && ((uintptr_t)a.w2 % 16 || (uintptr_t)a.w2scale % 16))))
+    return r;
+  r.wq = a.wdt == VV_MXFP4 ? 3 : a.wdt == VV_NF4 ? 2 : a.wdt == VV_FP8 ? 1 : 0;
   if (a.m > 4) {
     if (a.w2 || a.wdt != VV_BF16) return r;
     if ((uintptr_t)a.w % 16 || (uintptr_t)a.x % 16 || a.ldx % 4) return r;
@@ -742,7 +859,7 @@ vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
   // smallest wave count whose per-wave slice fits the register-resident activation fragment (KU <= 5 units; <= 3 for the
   // dual kernel when K is split, its registers hold two weight streams)
   int ksplit = 1, ku = units;
-  if (units > ((a.wdt == VV_NF4 && dual) ? 4 : 5)) {   // the NF4 SwiGLU kernel holds two code streams and their tables: <= 4 units
+  if (units > ((r.wq >= 2 && dual) ? 4 : 5)) {   // the NF4 SwiGLU kernel holds two code streams and their tables, the MXFP4 one two code streams: <= 4 units
     const int kumax = dual ? 3 : (units > 12 ? g_long_ku : 5);
     ksplit = 0;
     for (int w : {4, 8, 16}) {
@@ -753,10 +870,10 @@ vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
   }
   r.m = a.m == 1 ? 1 : a.m == 2 ? 2 : 4;
   r.dual = dual; r.ksplit = ksplit; r.ku = ku;
-  if (r.wq == 2) r.rw = 4;                       // NF4: 4 rows per 16-byte code load
+  if (r.wq >= 2) r.rw = 4;                       // NF4, MXFP4: 4 rows per 16-byte code load
   else if (dual) r.rw = g_dual_rw == 1 ? 1 : 2;
   else r.rw = (ksplit == 1 && a.n <= 4096 && g_small_rw == 1) ? 1 : 2;
-  if (!stream_exists(r.m, dual, ksplit, ku, r.rw, r.wq)) return r;   // no such kernel (NF4: 16 waves of table slots would not fit the block's LDS)
+  if (!stream_exists(r.m, dual, ksplit, ku, r.rw, r.wq)) return r;   // no such kernel (NF4: 16 waves of table slots would not fit the block's LDS; MXFP4 has no 16-wave form)
   stream_grid(a, r);
   r.kind = VV_GEMV_STREAM;
   return r;
@@ -779,6 +896,7 @@ int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, 
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap) {
   if (r.kind == VV_GEMV_HOT) return snprintf(name, (size_t)cap, "gemv_hot<%d>", r.idx);
   if (r.kind == VV_GEMV_CONV_HOT) return snprintf(name, (size_t)cap, "conv_hot_gemv<%d>", r.idx);
+  if (r.wq == 3) return snprintf(name, (size_t)cap, "gemv_mx<m=%d,dual=%d,ksplit=%d,ku=%d>", r.m, r.dual, r.ksplit, r.ku);   // the MXFP4 routes' documented name (vv_hip.h)
   return snprintf(name, (size_t)cap, "gemv_stream<m=%d,dual=%d,ksplit=%d,ku=%d,rw=%d,wq=%s>", r.m, r.dual, r.ksplit, r.ku, r.rw,
                   r.wq == 2 ? "nf4" : r.wq == 1 ? "fp8" : "bf16");
 }

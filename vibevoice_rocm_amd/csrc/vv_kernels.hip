@@ -77,7 +77,6 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
   if (key && !strcmp(key, "gemv_long_cap")) { vv_gemv_stream_set_long(value, 0); return 0; }
   if (key && !strcmp(key, "gemv_long_ku")) { vv_gemv_stream_set_long(0, value); return 0; }
   if (key && !strcmp(key, "gemv_blocks")) { vv_gemv_stream_set_blocks(value); return 0; }
-  if (key && !strcmp(key, "gemv_mx_blocks")) { vv_gemv_mx_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_waves")) { vv_gemv_stream_set_waves(value); return 0; }
   if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); return 0; }
   if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); return 0; }
@@ -500,12 +499,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
 // The m <= 8 family's decision (vv_linear launches it, vv_linear_route prints it): the 3..8-row matrix-core GEMV when the process-wide scratch is
 // on, the weight-streaming GEMV (or a hot kernel), two streaming passes of 4 + rest rows, the LDS-staged gemv_kernel<WT, M, DUAL, KS, NP> or the
 // generic kernel.  Plain values only: no pointer is followed, nothing is launched; the thresholds live here and in the two deciders it calls.
-enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX };
+enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC };
 struct gemv_route {
   int kind;
   vv_rows_route rows;                // GEMV_ROWS
   vv_stream_route st, st2;          // GEMV_SPLIT: rows 0..3 and the rest
-  vv_mx_route mx;                   // GEMV_MX: the MXFP4 streaming GEMV (vv_gemv_mx.hip)
   int m, dual, ks, np, kc, blocks;  // GEMV_LDS: gemv_kernel<WT, m, dual, ks, np> staging kc columns at a time; GEMV_GENERIC: blocks
   size_t lds;
 };
@@ -569,9 +567,9 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
                         a.m, a.n, a.k, a.flags);
   }
   if (a.wdt == VV_MXFP4) {
-    // weight-only MXFP4 has a streaming GEMV of its own (<= 2 rows, vv_gemv_mx.hip) and nothing else
-    g->mx = vv_gemv_mx_decide(a);
-    if (g->mx.kind) { g->kind = GEMV_MX; return 0; }
+    // weight-only MXFP4 has the weight-streaming GEMV (<= 2 rows, gemv_stream_kernel's format 3) and nothing else
+    g->st = vv_gemv_stream_decide(a);
+    if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights need m <= 2, k %% 32 == 0 (at most 40 units of 512, SwiGLU 24), scale bytes and 16-byte aligned "
                         "codes, scales and activations (m=%d k=%d)", a.m, a.k);
   }
@@ -619,7 +617,6 @@ static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* nam
   const char* w = a.wdt == VV_F32 ? "f32" : "bf16";
   if (g.kind == GEMV_ROWS) vv_gemv_rows_route_name(g.rows, name, cap);
   else if (g.kind == GEMV_STREAM) vv_gemv_stream_route_name(g.st, name, cap);
-  else if (g.kind == GEMV_MX) vv_gemv_mx_route_name(g.mx, name, cap);
   else if (g.kind == GEMV_SPLIT) {
     char lo[96], hi[96];
     vv_gemv_stream_route_name(g.st, lo, sizeof(lo));
@@ -669,7 +666,6 @@ static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStrea
   switch (g.kind) {
     case GEMV_ROWS: return vv_launch_gemv_rows_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: rows GEMV declined its own route");
     case GEMV_STREAM: return vv_launch_gemv_stream_route(a, g.st, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: streaming GEMV declined its own route");
-    case GEMV_MX: return vv_launch_gemv_mx_route(a, g.mx, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP4 GEMV declined its own route");
     case GEMV_SPLIT: {
       vv_lin_args lo = a;
       lo.m = 4;
