@@ -84,8 +84,12 @@ enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
  * non-temporally: the diffusion head's matrices are reused by every one of the N solver steps of a frame), and
  * VV_LIN_W_FRAG: w / w2 point at the fragment-major copies of the matrices (vv_llm_layer.f_*; 3..8 rows, n % 16 == 0, bf16 with k % 32 == 0 or
  * fp8 codes with k % 64 == 0 and wscale (w2scale); bf16 copies also at 9..16 rows, the 16-row form of the same GEMV - any other call with this
- * flag is an error) */
-enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8 };
+ * flag is an error).
+ * VV_LIN_PACKED: the call belongs to a packed prompt prefill (hundreds to thousands of rows).  With bf16 weights, VV_LIN_X_BF16, no prologue,
+ * n % 128 == 0, k % 64 == 0, ldx % 8 == 0, 16-byte aligned operands, an epilogue of bias / residual / VV_ACT_SWIGLU (+ VV_LIN_OUT_BF16) and
+ * m >= vv_tune("gemm_packed_rows") (0 = never) it runs on the LDS-DMA tile GEMM of csrc/vv_gemm_packed.hip; any other call routes exactly as
+ * without the flag */
+enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8, VV_LIN_PACKED = 16 };
 
 const char* vv_last_error(void);
 int vv_abi_version(void);
@@ -137,7 +141,8 @@ typedef struct vv_lin_args {
 int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
- * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>"; "skinny" or "gemm_f32"; and for the
+ * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>", or "gemm_packed<dual=0,obf=0>" for
+ * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16); "skinny" or "gemm_f32"; and for the
  * m <= 8 family (fp8, NF4 and MXFP4 weights included) the kernel itself:
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)
@@ -309,6 +314,15 @@ size_t vv_llm_ws_bytes(const vv_llm* m, int R);
  * pass; modeling_vibevoice_inference.py:478-480 and :581-583) and the prompt prefill (R = L0; :478 at step 0). */
 int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens,
                    const int* cache_rows, float* out, int64_t ldo, void* ws, vv_stream_t stream);
+/* The prompt prefill for the rows of SEVERAL prompts in one weight pass: vv_llm_forward's prefill (R >= 64 rows of a bf16 model; fewer rows run
+ * as vv_llm_forward runs them) with VV_LIN_PACKED on its matrix-core linears.  Row r sits at position lens[r] of cache row cache_rows[r]
+ * (both device int[R], both required) and reads and writes that (cache row, position) alone: rows of one cache row must be in ascending
+ * position order, rows of different cache rows may follow each other in any order.  The final RMSNorm runs on the nsel rows sel[i] only
+ * (device int[nsel], each in [0, R)): out is [nsel, hidden].  Workspace: vv_llm_prefill_packed_ws_bytes(m, R).  VV_E_ARG for a null pointer
+ * or nsel <= 0, VV_E_UNSUPPORTED for an fp8 cache; no allocation, no synchronisation. */
+size_t vv_llm_prefill_packed_ws_bytes(const vv_llm* m, int R);
+int vv_llm_prefill_packed(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens, const int* cache_rows,
+                          const int* sel, int nsel, float* out, int64_t ldo, void* ws, vv_stream_t stream);
 /* out == NULL: the final RMSNorm is left to the caller; the un-normalised last hidden rows then stay at the START of ws as [R, hidden] fp32.
  * vv_llm_tail finishes a decode step in one launch: out[R, hidden] = final RMSNorm(h) (the {condition, negative condition} of the
  * diffusion head), logits[nv] = w_valid[nv, hidden] . out[0] (the constrained vocabulary rows of lm_head, VibeVoiceTokenConstraintProcessor

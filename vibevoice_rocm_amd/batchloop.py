@@ -402,7 +402,7 @@ class Session:
 
     def __init__(self, driver, slots: int, special: dict, pad_id: int, max_pos: int, latent: int, max_context: int, device_noise: bool = True,
                  sample_fn=None, sampler: Optional[tuple] = None, speculate: bool = True, verbose: bool = False, on_close=None,
-                 seeded_tokens: bool = False):
+                 seeded_tokens: bool = False, packed_prefill: bool = False):
         if not isinstance(slots, int) or not 2 <= slots <= 16:
             raise ValueError(f"Session: slots={slots!r} (2..16)")
         if max_context is None or int(max_context) <= 0:
@@ -412,6 +412,7 @@ class Session:
         if seeded_tokens and sample_fn is not None:
             raise ValueError("Session: seeded_tokens draws the tokens on the device: it excludes sample_fn (the host sampler)")
         self.seeded_tokens = bool(seeded_tokens)
+        self.packed_prefill = bool(packed_prefill)      # _admit: every queued request that finds a slot, then ONE first_tokens call for them all
         self.default_row = (tuple(sampler) if sampler is not None else GREEDY_ROW) if self.seeded_tokens else None
         if self.seeded_tokens:
             sampler = None                # no session-wide warpers on the driver, no q: every request's row travels with its admission
@@ -579,8 +580,45 @@ class Session:
                     d.reach = d.reach or d.step < d.max_steps
                     self._retire(b, d)
 
+    def _admit_packed(self) -> List[int]:
+        """_admit with packed_prefill: every queued request that finds a free slot is admitted (FIFO, lowest free slot first, driver.admit for
+        each as ever), ONE driver.first_tokens call prefills them - the driver packs a row batch's newcomers into one weight pass - and their
+        tokens are handled together in slot order, as a decode step's are.  A first token that retires its dialogue frees the slot for whoever still waits: the stages repeat.
+        admission_ms holds one entry per such wave (what the running dialogues waited), admissions one per request."""
+        drv, new = self.driver, []
+        while self.queue and len(self.live) < self.slots:
+            t0, wave = time.perf_counter(), []
+            while self.queue and len(self.live) < self.slots:
+                h = self.queue.pop(0)
+                r = h.request
+                max_length, max_steps = self.limits_of(int(r.prompt.shape[0]), r.max_new_tokens, r.max_length_times)
+                d = _Dialogue(h, max_length, max_steps)
+                if self._stopped(d) or max_steps <= 0:
+                    self._retire(None, d)
+                    continue
+                b = min(set(range(self.slots)) - set(self.live))
+                self.admissions.append((b, sorted(self.live)))
+                h.slot = b
+                self.live[b] = d
+                drv.admit(b, r)
+                wave.append(b)
+            if not wave:
+                continue
+            wave.sort()
+            forced = {b: self._forced(self.live[b]) for b in wave}
+            kw = {} if self.sampler is None else dict(q={b: draw_q(self.nv) for b in wave if forced[b] is None})
+            toks = drv.first_tokens(wave, forced, self.sample_fn, **kw)
+            self.admission_ms.append((time.perf_counter() - t0) * 1e3)
+            # one _handle for the wave, as a decode step's tokens are handled: slot order, and ONE driver.speech for its diffusing dialogues - a
+            # diffusion sampling per newcomer would rewrite every dialogue's latent while the previous newcomer's conv tail still reads its own
+            self._handle({b: toks[b] for b in wave}, set())
+            new += wave
+        return new
+
     def _admit(self) -> List[int]:
         """returns the slots it filled"""
+        if self.packed_prefill:
+            return self._admit_packed()
         drv, new = self.driver, []
         while self.queue and len(self.live) < self.slots:
             h = self.queue.pop(0)

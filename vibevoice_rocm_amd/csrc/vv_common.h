@@ -86,6 +86,13 @@ vv_mfma_route vv_mfma_decide(const vv_lin_args& a);
 int vv_launch_mfma_route(const vv_lin_args& a, const vv_mfma_route& r, hipStream_t s);   // 1 launched, < 0 error
 int vv_mfma_route_name(const vv_mfma_route& r, char* name, int cap);
 int vv_mfma_gemm_init();
+// vv_gemm_packed.hip: the LDS-DMA 128 x 128 tile GEMM of the packed prompt prefill (gemm_packed_kernel<dual, obf>), taken by VV_LIN_PACKED calls alone.
+// vv_gemm_packed_covers is the only copy of what it takes (no launch, no pointer followed); the launch of a covered call returns 0
+bool vv_gemm_packed_covers(const vv_lin_args& a);
+int vv_launch_gemm_packed(const vv_lin_args& a, hipStream_t s);
+int vv_gemm_packed_route_name(const vv_lin_args& a, char* name, int cap);
+void vv_gemm_packed_set_rows(int rows);                          // tuning hook "gemm_packed_rows" (0 = never, < 0 = the default)
+int vv_gemm_packed_init();
 // vv_attn_decode.hip: bf16 KV cache, head_dim 128; part / tickets = split-key workspace ([R, heads, nsplit, 130] floats, [R, heads] zeroed ints) or null
 // part_cap: splits the partials workspace has room for (>= nsplit); the grouped kernel may use more splits than the per-head kernel's nsplit
 int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float2* rope, const int* lens, float* out,
@@ -135,7 +142,8 @@ bool vv_convffn_prefers(int wdt, int T, int C);
 int vv_launch_skinny(const vv_lin_args& a, hipStream_t s);       // resampling convs of a streaming frame: 1 launched, 0 not covered
 bool vv_skinny_covers(const vv_lin_args& a);                      // what vv_launch_skinny would launch (the same predicate, no launch)
 void vv_skinny_set(int on, int min_m, int max_m);
-int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s);
+int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s,
+                    const int* sel = nullptr);                    // sel (device int[rows]) or null: output row r normalises input row sel[r]
 
 #ifdef __HIPCC__
 // fp32 -> e4m3fn code, round to nearest even, saturating at +-448 (never the NaN code 0x7f; a NaN input gives +-448): the KV cache's codes

@@ -34,6 +34,7 @@ int vv_mixer_init();
 extern "C" int vv_init(void) {
   VV_TRY(vv_mixer_init());
   VV_TRY(vv_mfma_gemm_init());
+  VV_TRY(vv_gemm_packed_init());
   VV_TRY(vv_block1d_init());
   VV_TRY(vv_convffn_init());
   VV_TRY(vv_gemv_rows_init());
@@ -111,6 +112,7 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
   if (key && !strcmp(key, "mfma_tiled_small_dual")) { vv_mfma_set_tiled_small_dual(value); return 0; }
   if (key && !strcmp(key, "mfma_tiled_small")) { vv_mfma_set_tiled_small(value); return 0; }
   if (key && !strcmp(key, "mfma_tiled_rows")) { vv_mfma_set_tiled_rows(value); return 0; }
+  if (key && !strcmp(key, "gemm_packed_rows")) { vv_gemm_packed_set_rows(value); return 0; }
   if (key && !strcmp(key, "mfma_mt")) { vv_mfma_set_mt(value); return 0; }
   if (key && !strcmp(key, "mfma_mt_prefill")) { vv_mfma_set_mt_prefill(value); return 0; }
   return vv_set_error(VV_E_ARG, "vv_tune: unknown key");
@@ -680,8 +682,9 @@ static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStrea
 }
 
 // The kernel family a bf16 / fp32-weight vv_linear call takes: decided here for the launch below and for vv_linear_route alike.  < 0 = error.
-enum { LIN_FAM_SKINNY = 1, LIN_FAM_GEMV, LIN_FAM_MFMA, LIN_FAM_GEMM_F32 };
+enum { LIN_FAM_SKINNY = 1, LIN_FAM_GEMV, LIN_FAM_MFMA, LIN_FAM_GEMM_F32, LIN_FAM_PACKED };
 static int linear_family(const vv_lin_args& a, vv_mfma_route* r) {
+  if (vv_gemm_packed_covers(a)) return LIN_FAM_PACKED;           // VV_LIN_PACKED at packed-prefill row counts (vv_gemm_packed.hip); else the flag changes nothing
   if (vv_skinny_covers(a)) return LIN_FAM_SKINNY;                // a few rows x K = 512..2560, plain epilogue: the resampling convs (vv_convffn.hip)
   if (a.m <= 8 || ((a.flags & VV_LIN_W_FRAG) && a.m <= 16)) return LIN_FAM_GEMV;     // 9..16 rows on the fragment-major copy: the 16-row matrix-core GEMV or nothing
   *r = vv_mfma_decide(a);                                        // bf16 weights: matrix-core path
@@ -698,6 +701,7 @@ static int launch_linear(const vv_lin_args& a, hipStream_t s) {
   vv_mfma_route route = {};
   const int fam = linear_family(a, &route);
   if (fam < 0) return fam;
+  if (fam == LIN_FAM_PACKED) return vv_launch_gemm_packed(a, s);
   if (fam == LIN_FAM_SKINNY) return vv_launch_skinny(a, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: skinny GEMM declined its own route");
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
@@ -832,6 +836,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     fam = linear_family(*a, &route);
     if (fam < 0) return fam;
     if (fam == LIN_FAM_MFMA) vv_mfma_route_name(route, name, cap);
+    else if (fam == LIN_FAM_PACKED) vv_gemm_packed_route_name(*a, name, cap);
     else if (fam != LIN_FAM_GEMV) snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : "gemm_f32");
   }
   else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
@@ -2087,10 +2092,11 @@ extern "C" int vv_copy_rows(const float* x, int64_t ldx, float* out, int64_t ldo
 }
 
 // rows of RMSNorm (final LLM norm): out = x * rsqrt(mean x^2 + eps) * w
-__global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int64_t ldx, const float* w, float eps, int n, float* out, int64_t ldo) {
+// sel (or null): output row r normalises input row sel[r]
+__global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int64_t ldx, const float* w, float eps, int n, float* out, int64_t ldo, const int* sel) {
   __shared__ float red[4];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* xr = x + (int64_t)r * ldx;
+  const float* xr = x + (int64_t)(sel ? sel[r] : r) * ldx;
   float s = 0.f;
   for (int c = tid; c < n; c += blockDim.x) s += xr[c] * xr[c];
   s = wave_sum_dpp(s);
@@ -2099,8 +2105,8 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int64
   const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)n + eps);
   for (int c = tid; c < n; c += blockDim.x) out[(int64_t)r * ldo + c] = xr[c] * rstd * (w ? w[c] : 1.f);
 }
-int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s) {
-  hipLaunchKernelGGL(rmsnorm_rows_kernel, dim3(rows), dim3(256), 0, s, x, ldx, w, eps, n, out, ldo);
+int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s, const int* sel) {
+  hipLaunchKernelGGL(rmsnorm_rows_kernel, dim3(rows), dim3(256), 0, s, x, ldx, w, eps, n, out, ldo, sel);
   VV_CHECK_LAUNCH("vv_rmsnorm_rows");
   return 0;
 }

@@ -84,12 +84,14 @@ extern "C" size_t vv_llm_ws_bytes(const vv_llm* m, int R) {
          ((R > 2 && R <= 16) ? al(rows_part_floats(m)) + al(rows_tickets(m)) : 0);                                           // split-K partials of the 3..8-row and the 9..16-row GEMV
 }
 
-extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens,
-                              const int* cache_rows, float* out, int64_t ldo, void* ws, vv_stream_t stream) {
-  if (!m || !kv || !x || !lens || !ws || !m->layer) return vv_set_error(VV_E_ARG, "vv_llm_forward: null pointer");
-  if (R <= 0) return vv_set_error(VV_E_ARG, "vv_llm_forward: R=%d", R);
+// vv_llm_forward and vv_llm_prefill_packed: one layer loop.  lin_flags: ORed into the flags of the prefill branch's matrix-core linears
+// (VV_LIN_PACKED or 0); sel (device int[nsel]) or null: the final norm runs on rows sel[i] alone, out is [nsel, hidden]
+static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens,
+                       const int* cache_rows, float* out, int64_t ldo, void* ws, vv_stream_t stream, int lin_flags, const int* sel, int nsel) {
+  if (!m || !kv || !x || !lens || !ws || !m->layer) return vv_set_error(VV_E_ARG, "%s: null pointer", who);
+  if (R <= 0) return vv_set_error(VV_E_ARG, "%s: R=%d", who, R);
   if (kv->layers != m->layers || kv->kv_heads != m->kv_heads || kv->head_dim != m->head_dim)
-    return vv_set_error(VV_E_ARG, "vv_llm_forward: kv cache shape does not match the model");
+    return vv_set_error(VV_E_ARG, "%s: kv cache shape does not match the model", who);
   VV_WQ_STRIP(vv_llm, m);
   hipStream_t s = (hipStream_t)stream;
   const int H = m->hidden, d = m->head_dim, qd = m->heads * d, qkvd = (m->heads + 2 * m->kv_heads) * d;
@@ -120,7 +122,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     att_split = (kv->s_max + 511) / 512;
     if (att_split > VV_ATT_MAX_SPLIT) att_split = VV_ATT_MAX_SPLIT;
     hipError_t e = hipMemsetAsync(att_tickets, 0, att_rows(R) * m->heads * sizeof(int), s);
-    if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_llm_forward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   void* xb2 = prefill ? (void*)act : nullptr;      // bf16 SwiGLU output [R, inter] lives in the (otherwise unused) fp32 act buffer
   // 3..8 rows (dialogues batched into the row dimension): the matrix-core GEMV with its split-K workspace, fragment-major weights when the model has them
@@ -133,7 +135,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     rpart = c.take(rpart_n);
     rtick = reinterpret_cast<int*>(c.take(rtick_n));
     hipError_t e = hipMemsetAsync(rtick, 0, rtick_n * sizeof(int), s);
-    if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_llm_forward: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   if (rows8) {      // the residual stream lives in h from the start: the split-K projections then accumulate into it in place (vv_gemv_rows.hip)
     VV_TRY(vv_copy_rows(x, ldx, h, H, R, H, stream));
@@ -152,7 +154,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     if (prefill) {
       VV_TRY(vv_cast_rows_bf16(hin, ldh, R, H, VV_PRO_RMSNORM, L.ln1, m->rms_eps, xb, H, stream));
       a = lin_base((const float*)xb, H, R, L.wqkv, qkvd, H, m->wdt, qkv, qkvd);
-      a.flags = VV_LIN_X_BF16; a.bias = L.bqkv;
+      a.flags = VV_LIN_X_BF16 | lin_flags; a.bias = L.bqkv;
     } else {
       a = lin_base(hin, ldh, R, L.wqkv, qkvd, H, m->wdt, qkv, qkvd);
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln1; a.eps = m->rms_eps; a.bias = L.bqkv;
@@ -168,7 +170,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     if (prefill) {
       VV_TRY(vv_cast_rows_bf16(att, qd, R, qd, VV_PRO_NONE, nullptr, 0.f, xb, qd, stream));
       a = lin_base((const float*)xb, qd, R, L.wo, H, qd, m->wdt, h, H);
-      a.flags = VV_LIN_X_BF16;
+      a.flags = VV_LIN_X_BF16 | lin_flags;
     } else {
       a = lin_base(att, qd, R, L.wo, H, qd, m->wdt, h, H);
       if (!rows8) use_w8(a, wq, L.q_o);
@@ -179,7 +181,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     if (prefill) {
       VV_TRY(vv_cast_rows_bf16(h, H, R, H, VV_PRO_RMSNORM, L.ln2, m->rms_eps, xb, H, stream));
       a = lin_base((const float*)xb, H, R, L.wgate, m->inter, H, m->wdt, act, m->inter);
-      a.flags = VV_LIN_X_BF16;
+      a.flags = VV_LIN_X_BF16 | lin_flags;
     } else {
       a = lin_base(h, H, R, L.wgate, m->inter, H, m->wdt, act, m->inter);
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln2; a.eps = m->rms_eps;
@@ -192,7 +194,7 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     VV_TRY(lin(a, L.f_gate, L.f_up, &L.q_gate, &L.q_up));
     if (prefill) {
       a = lin_base((const float*)xb2, m->inter, R, L.wdown, H, m->inter, m->wdt, h, H);
-      a.flags = VV_LIN_X_BF16;
+      a.flags = VV_LIN_X_BF16 | lin_flags;
     } else {
       a = lin_base(act, m->inter, R, L.wdown, H, m->inter, m->wdt, h, H);
       if (!rows8) use_w8(a, wq, L.q_down);
@@ -201,7 +203,24 @@ extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, 
     VV_TRY(lin(a, L.f_down, nullptr, &L.q_down));
   }
   if (!out) return 0;       // the caller runs the final norm itself (vv_llm_tail: norm + logits + token + bookkeeping in one launch)
-  return vv_rmsnorm_rows(h, H, m->final_norm, m->rms_eps, R, H, out, ldo, s);
+  return vv_rmsnorm_rows(h, H, m->final_norm, m->rms_eps, sel ? nsel : R, H, out, ldo, s, sel);
+}
+
+extern "C" int vv_llm_forward(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens,
+                              const int* cache_rows, float* out, int64_t ldo, void* ws, vv_stream_t stream) {
+  return llm_forward("vv_llm_forward", m, kv, x, ldx, R, lens, cache_rows, out, ldo, ws, stream, 0, nullptr, 0);
+}
+
+extern "C" size_t vv_llm_prefill_packed_ws_bytes(const vv_llm* m, int R) { return vv_llm_ws_bytes(m, R); }
+
+// Several prompts' rows in one pass: vv_llm_forward's prefill with VV_LIN_PACKED on its matrix-core linears and the final norm on the selected
+// rows only.  Every row reads and writes its own (cache row, position) alone, so the rows of a pass may belong to any mix of cache rows
+extern "C" int vv_llm_prefill_packed(const vv_llm* m, const vv_kv* kv, const float* x, int64_t ldx, int R, const int* lens, const int* cache_rows,
+                                     const int* sel, int nsel, float* out, int64_t ldo, void* ws, vv_stream_t stream) {
+  if (!cache_rows || !sel || !out) return vv_set_error(VV_E_ARG, "vv_llm_prefill_packed: null pointer");
+  if (nsel <= 0) return vv_set_error(VV_E_ARG, "vv_llm_prefill_packed: nsel=%d", nsel);
+  if (kv && kv->kvdt == VV_FP8) return vv_set_error(VV_E_UNSUPPORTED, "vv_llm_prefill_packed: an fp8 KV cache takes no prompt rows (prefill a bf16 cache, then vv_kv_quantize)");
+  return llm_forward("vv_llm_prefill_packed", m, kv, x, ldx, R, lens, cache_rows, out, ldo, ws, stream, VV_LIN_PACKED, sel, nsel);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

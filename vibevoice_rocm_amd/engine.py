@@ -154,6 +154,7 @@ class Engine:
         self._kv_t = None
         self._llm_ws = None
         self._llm_ws_rows = 0
+        self.prefill_passes = 0         # vv_llm_prefill_packed calls so far (prefill(packed=True))
         self._graphs: Dict[str, int] = {}
         self._graph_key = None
         self.valid_ids: List[int] = []
@@ -293,8 +294,16 @@ class Engine:
                                          L.ptr(cache_rows), out.data_ptr(), out.stride(0), self._llm_ws.data_ptr(), self.sp),
                  "vv_llm_forward")
 
+    def llm_prefill_packed(self, x: torch.Tensor, lens: torch.Tensor, cache_rows: torch.Tensor, sel: torch.Tensor, out: torch.Tensor, kv=None):
+        """vv_llm_prefill_packed: the prefill pass whose matrix-core linears carry VV_LIN_PACKED; out [len(sel), H] = the selected rows' states"""
+        R = x.shape[0]
+        self._ensure_llm_ws(R)
+        self._ck(self.lib.vv_llm_prefill_packed(C.byref(self.w.llm), C.byref(kv or self.kv), x.data_ptr(), x.stride(0), R, lens.data_ptr(),
+                                                cache_rows.data_ptr(), sel.data_ptr(), sel.shape[0], out.data_ptr(), out.stride(0),
+                                                self._llm_ws.data_ptr(), self.sp), "vv_llm_prefill_packed")
+
     def prefill(self, embeds: torch.Tensor, row: int = 0, pos0: int = 0, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None,
-                prefix=None, keep_staging: bool = False):
+                prefix=None, keep_staging: bool = False, packed: bool = False):
         """Prompt prefill on cache row `row`: embeds [L0, H] fp32 -> self.hidden2[row] = last hidden state; lens[row] = pos0+L0.
         Prompts longer than `chunk` rows run as ceil(L0 / chunk) EQUAL chunks (rounded up to 32 rows): a short trailing chunk would stream
         every weight matrix once more for a handful of rows (1 040 tokens as 1 024 + 16 cost 18.5 ms, as 2 x 520 they cost 12).
@@ -305,7 +314,9 @@ class Engine:
         after the prefix only - are prefilled at position P (pos0 must be 0: the prefix implies it).  On an fp8 KV cache the restore goes into the
         staging cache, sized for P + L0, and the scales are derived from all P + L0 slots, as without a prefix.
         keep_staging (fp8 KV cache): skip the conversion and return the staging cache (vv_kv, its tensors) - how save_prefix gets at the prompt's
-        bf16 K / V; the byte cache is left alone and the engine is not ready to decode."""
+        bf16 K / V; the byte cache is left alone and the engine is not ready to decode.
+        packed (packed_prefill): every chunk runs through vv_llm_prefill_packed - one segment plus the negative row - so its GEMMs may take the
+        packed-prefill tile kernel, and only the rows whose state is kept are final-normed; `chunk` is then the rows per pass."""
         L0 = embeds.shape[0]
         P = 0
         if prefix is not None:
@@ -340,6 +351,12 @@ class Engine:
                     lens[-1] = 0
                     rows[-1] = 1
                     x = torch.cat([x, neg_embed.to(x.dtype).reshape(1, -1)])
+                if packed:
+                    sel = torch.arange(n - 1, n + (1 if last else 0), dtype=torch.int32, device=self.device)      # the segment's last row (, the negative row)
+                    out = torch.empty(sel.shape[0], self.cfg.hidden, dtype=torch.float32, device=self.device)
+                    self.llm_prefill_packed(x, lens, rows, sel, out, kv=kv)
+                    self.prefill_passes += 1
+                    continue
                 out = torch.empty(x.shape[0], self.cfg.hidden, dtype=torch.float32, device=self.device)
                 self.llm_forward(x, lens, rows, out, kv=kv)
             if stage is not None and not keep_staging:

@@ -207,6 +207,15 @@ def _embed_prompt(eng: Engine, ids: torch.Tensor, voice, after: Optional[torch.c
     return x0
 
 
+PACKED_PREFILL_ROWS = 4096      # rows per packed prefill pass (packed_prefill_rows=): eight headline prompts, their negative rows included, are one pass
+
+
+def check_packed_rows(rows) -> int:
+    if isinstance(rows, bool) or not isinstance(rows, int) or rows < 64:
+        raise ValueError(f"packed_prefill_rows={rows!r}: an int >= 64 (rows per packed prefill pass)")
+    return rows
+
+
 class _LaneDriver:
     """batchloop driver: one Engine lane per dialogue (own HIP stream, KV cache and conv state).  Phase A of every live sample is enqueued
     before any token is awaited, so the B dependent chains fill each other's bubbles on the GPU; a sample is the same computation as in a
@@ -218,6 +227,7 @@ class _LaneDriver:
         self.model, self.cfg_scale, self.ST, self.SD = model, (rows or [float(cfg_scale)] * B), ST, SD
         self.lanes = [model._lane(b) for b in range(B)]
         self.prefixes = [None] * B          # generate(voice_prefix=): dialogue -> VoicePrefix or None
+        self.packed = None                  # packed_prefill: rows per pass - every lane's prompt then runs through vv_llm_prefill_packed (Engine.prefill)
         for e in self.lanes[1:]:
             e.sync_in()
         self.sde, self.n_steps = self.lanes[0].sde, self.lanes[0].n_steps
@@ -253,8 +263,8 @@ class _LaneDriver:
     def first_tokens(self, live, forced, sample_fn, q=None):
         lanes, toks = self.lanes, {}
         for b in live:
-            lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])),
-                             prefix=self.prefixes[b])
+            lanes[b].prefill(self.x0[b], row=0, pos0=0, chunk=self.packed or getattr(self.model, "_prefill_chunk", 1024),
+                             neg_embed=lanes[b].embed_ids(torch.tensor([self.ST])), prefix=self.prefixes[b], packed=self.packed is not None)
         for b in live:
             toks[b] = lanes[b].first_token(self.ST, self.SD, forced[b], sample_fn, q=(q or {}).get(b))
             if toks[b] == self.SD:
@@ -379,6 +389,7 @@ class _RowDriver:
         self.groups, self.at = [], {}          # (row batch, its dialogues); dialogue -> (row batch, index in it)
         self.dn = False                        # set_noise_seeds: `eligible` / `speech` rows are (frame index, None), graph H draws the noise
         self.prefixes = [None] * B             # generate(voice_prefix=): dialogue -> VoicePrefix or None
+        self.packed = None                     # packed_prefill: rows per pass - first_tokens prefills a row batch's dialogues in one weight pass
 
     def begin(self, prompts, voices, max_steps, valid):
         from .rowbatch import RowBatch
@@ -416,8 +427,14 @@ class _RowDriver:
     def first_tokens(self, live, forced, sample_fn, q=None):
         at, toks = self.at, {}
         st_embed = self.main.embed_ids(torch.tensor([self.ST]))
-        for b in live:
-            at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed, prefix=self.prefixes[b])
+        if self.packed is not None:
+            for rb, idxs in self.groups:       # one packed prefill per row batch: its live dialogues' prompts (and negative rows) share the weight passes
+                mine = [b for b in idxs if b in live]
+                if mine:
+                    rb.prefill_packed([(at[b][1], self.x0[b], self.prefixes[b]) for b in mine], chunk_rows=self.packed, neg_embed=st_embed)
+        else:
+            for b in live:
+                at[b][0].prefill(at[b][1], self.x0[b], chunk=getattr(self.model, "_prefill_chunk", 1024), neg_embed=st_embed, prefix=self.prefixes[b])
         for b in live:
             rb, loc = at[b]
             toks[b] = rb.first_token(loc, forced[b], sample_fn, q=(q or {}).get(b))
@@ -519,8 +536,9 @@ class _SessionDriver(_RowDriver):
     for max_context tokens per dialogue, cache keys of their own in model._rowbatch) and refilled slot by slot (`admit`).  Every row batch keeps its
     slots' guidance scales on the device, so one graph H serves whatever scales its occupants bring."""
 
-    def __init__(self, model, slots: int, ST: int, SD: int, device_noise: bool):
+    def __init__(self, model, slots: int, ST: int, SD: int, device_noise: bool, packed: Optional[int] = None):
         super().__init__(model, slots, [1.0] * slots, ST, SD)
+        self.packed = packed
         self.dn = bool(device_noise)
         self.x0 = [None] * slots
 
@@ -564,9 +582,11 @@ class VibeVoiceSession:
     """An open serving session of one model (model.open_session): dialogues are submitted one by one, each with its own guidance scale, limits,
     schedule, noise seed and streamer; `step()` admits queued dialogues into free row-batch slots and advances every live one by a token.  Each
     dialogue is served as generate() serves it alone (batchloop.Session).  The sampler (generation_config, device_sampling) and the solver are
-    the session's - opened with seeded_tokens=True, every request may bring its own generation_config and token_seed instead (submit) -; admission is synchronous (a newcomer's prefill runs between two steps on the main stream)."""
+    the session's - opened with seeded_tokens=True, every request may bring its own generation_config and token_seed instead (submit) -; admission is synchronous (a newcomer's prefill runs between two steps on the main stream;
+    opened with packed_prefill=True, the requests queued at a step are admitted together and their prompts prefilled in one weight pass per row batch)."""
 
-    def __init__(self, model, tokenizer, slots, max_context, generation_config, device_noise, device_sampling, seeded_tokens=False):
+    def __init__(self, model, tokenizer, slots, max_context, generation_config, device_noise, device_sampling, seeded_tokens=False,
+                 packed_prefill=False):
         self.model, cfg = model, model.config
         gen_cfg = dict(generation_config or {})
         do_sample = bool(gen_cfg.get("do_sample", False))
@@ -583,14 +603,15 @@ class VibeVoiceSession:
         self.special = dict(speech_start=tokenizer.speech_start_id, speech_end=tokenizer.speech_end_id, speech_diffusion=tokenizer.speech_diffusion_id,
                             eos=tokenizer.eos_token_id, bos=getattr(tokenizer, "bos_token_id", None))
         pad_id = getattr(tokenizer, "pad_id", None)
-        self.driver = _SessionDriver(model, slots, self.special["speech_start"], self.special["speech_diffusion"], device_noise)
+        self.driver = _SessionDriver(model, slots, self.special["speech_start"], self.special["speech_diffusion"], device_noise,
+                                     packed=model.packed_prefill_rows if packed_prefill else None)
         model.engine.sync_in()
         with torch.cuda.stream(model.engine.stream):
             self.driver.open(int(max_context), batchloop.valid_token_ids(self.special))
             self._s = batchloop.Session(self.driver, slots, self.special, self.special["eos"] if pad_id is None else pad_id, cfg.max_pos, cfg.latent,
                                         max_context, device_noise=device_noise, sample_fn=sample_fn, sampler=sampler,
                                         speculate=model.speculative_frames and model._use_graphs, on_close=self._closed,
-                                        seeded_tokens=self.seeded_tokens)
+                                        seeded_tokens=self.seeded_tokens, packed_prefill=bool(packed_prefill))
 
     slots = property(lambda self: self._s.slots)
     admission_ms = property(lambda self: self._s.admission_ms)      # host time of every admission (prefill + first token, synchronous): the stall of the running dialogues
@@ -676,7 +697,13 @@ class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
                  kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
-                 seeded_tokens: bool = False, row_batch_width: int = 4):
+                 seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS):
+        # packed_prefill: the prompts of a row batch's dialogues are prefilled in ONE weight pass (RowBatch.prefill_packed, vv_llm_prefill_packed)
+        # instead of one pass per dialogue, in passes of at most packed_prefill_rows rows; a single dialogue and the lanes take the same entry
+        # for their one prompt.  Off by default; generate(packed_prefill=, packed_prefill_rows=) overrides per call, open_session(packed_prefill=)
+        # per session
+        self.packed_prefill = bool(packed_prefill)
+        self.packed_prefill_rows = check_packed_rows(packed_prefill_rows)
         # row_batch_width: dialogues per row batch at most.  4 (default): 5..16 dialogues run as ceil(B / 4) row batches of up to 8 rows.  8: as
         # ceil(B / 8) row batches of up to 16 rows - one pass over the LLM and head weights for up to 8 dialogues (csrc gemv_rows16_kernel; bf16
         # weights and KV cache only; DESIGN.md section 5m says for which batch sizes that is faster).  generate(row_batch_width=) overrides it per call
@@ -787,7 +814,8 @@ class VibeVoiceForConditionalGenerationInference:
                    use_graphs=kw.get("use_graphs", True), weight_quant=wq, prequant=prequant or None, kv_cache_dtype=kw.get("kv_cache_dtype"),
                    device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False),
                    mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False),
-                   row_batch_width=kw.get("row_batch_width", 4))
+                   row_batch_width=kw.get("row_batch_width", 4), packed_prefill=kw.get("packed_prefill", False),
+                   packed_prefill_rows=kw.get("packed_prefill_rows", PACKED_PREFILL_ROWS))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -897,13 +925,15 @@ class VibeVoiceForConditionalGenerationInference:
 
     # ---- serving sessions ---------------------------------------------------------------------------------------
     def open_session(self, tokenizer=None, slots: int = 8, max_context: Optional[int] = None, generation_config=None, device_noise: bool = True,
-                     device_sampling: Optional[bool] = None, seeded_tokens: bool = False) -> "VibeVoiceSession":
+                     device_sampling: Optional[bool] = None, seeded_tokens: bool = False, packed_prefill: bool = False) -> "VibeVoiceSession":
         """Open a serving session: `slots` (2..16) row-batch slots - ceil(slots / 4) row batches, as a batched generate() partitions them - whose
         KV caches are sized once for `max_context` tokens per dialogue (required).  Dialogues are submitted to the session one by one and a
         finished one frees its slot for the next between two steps (VibeVoiceSession, batchloop.Session).  Needs what row batching needs -
         bf16, weight_quant None or "fp8" (or "mxfp4" on a model built with mxfp4_row_batch=True), a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
         per model; generate() raises RuntimeError until it is closed.  seeded_tokens=True: every request may bring its own generation_config and token_seed
-        (submit), greedy and sampled requests share the one graph A, and a dialogue's tokens do not depend on who shares the session."""
+        (submit), greedy and sampled requests share the one graph A, and a dialogue's tokens do not depend on who shares the session.
+        packed_prefill=True: the requests queued when a step begins are admitted together and prefilled in one weight pass per row batch
+        (passes of the model's packed_prefill_rows rows) instead of one pass each."""
         if getattr(self, "_session", None) is not None:
             raise RuntimeError("open_session(): this model already has an open session (one per model); close() it first")
         if tokenizer is None:
@@ -923,7 +953,8 @@ class VibeVoiceForConditionalGenerationInference:
             why = "use_graphs=False (the session replays captured graphs)"
         if why is not None:
             raise ValueError(f"open_session(): a session runs on the row-batched decode path, which this model cannot take: {why}")
-        sess = VibeVoiceSession(self, tokenizer, slots, int(max_context), generation_config, bool(device_noise), device_sampling, bool(seeded_tokens))
+        sess = VibeVoiceSession(self, tokenizer, slots, int(max_context), generation_config, bool(device_noise), device_sampling, bool(seeded_tokens),
+                                packed_prefill=bool(packed_prefill))
         self._session = sess
         return sess
 
@@ -961,6 +992,8 @@ class VibeVoiceForConditionalGenerationInference:
         max_length_times = kwargs.get("max_length_times", 2)
         refresh_negative = bool(kwargs.get("refresh_negative", True))     # False: reference :501-515 (no caller of the reference uses it)
         self._prefill_chunk = int(kwargs.get("prefill_chunk", 1024))   # extension: rows per prefill launch sequence (cfg 5: 512-token chunks)
+        # extension: packed prompt prefill for this call (None: off), rows per pass
+        packed = check_packed_rows(kwargs.get("packed_prefill_rows", self.packed_prefill_rows)) if kwargs.get("packed_prefill", self.packed_prefill) else None
         forced_tokens = kwargs.get("forced_tokens")          # extension: bench / fixtures drive the token schedule
         noise = kwargs.get("noise")                          # extension: injected diffusion noise [F, latent]
         speech_noise = kwargs.get("speech_noise")            # extension: (std_noise [S], eps_noise [S, F, 64])
@@ -1013,6 +1046,7 @@ class VibeVoiceForConditionalGenerationInference:
                       else _LaneDriver(self, B, cfg_scale, special["speech_start"], special["speech_diffusion"]))
             if vps is not None:
                 driver.prefixes = vps
+            driver.packed = packed
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,
@@ -1032,7 +1066,7 @@ class VibeVoiceForConditionalGenerationInference:
         r = self._generate_one(ids, sp, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens, noise, audio_streamer,
                                stop_check_fn, 0, verbose, sample_fn, sde_noise, refresh_negative=refresh_negative, sampler=sampler,
                                prefix=None if vps is None else vps[0], noise_seed=None if noise_seeds is None else noise_seeds[0],
-                               token_sampling=None if token_sampling is None else (token_sampling[0][0], token_sampling[1][0]))
+                               token_sampling=None if token_sampling is None else (token_sampling[0][0], token_sampling[1][0]), packed=packed)
         if audio_streamer is not None:
             audio_streamer.end()
         return batchloop.pack_output([torch.cat([input_ids[0][~keep], r["sequence"]])], [r["audio"]], [r["reach_max"]], pad_id, in_dev, return_speech)
@@ -1134,7 +1168,8 @@ class VibeVoiceForConditionalGenerationInference:
 
     def _generate_one(self, ids: torch.Tensor, sp_mask, conn, special, cfg_scale, max_new_tokens, max_length_times, forced_tokens,
                       noise, audio_streamer, stop_check_fn, sample_idx, verbose, sample_fn=None, sde_noise=None, refresh_negative=True, sampler=None,
-                      prefix: Optional[VoicePrefix] = None, noise_seed: Optional[int] = None, token_sampling: Optional[tuple] = None):
+                      prefix: Optional[VoicePrefix] = None, noise_seed: Optional[int] = None, token_sampling: Optional[tuple] = None,
+                      packed: Optional[int] = None):
         eng, cfg = self.engine, self.config
         dn = noise_seed is not None         # device noise: the engine draws frame f's noise from (noise_seed, f); draw / pending_nz / rewind are not used
         nv = len(set(batchloop.valid_token_ids(special)))
@@ -1205,7 +1240,8 @@ class VibeVoiceForConditionalGenerationInference:
             q = batchloop.draw_q(nv) if (sampler is not None and forced is None) else None     # where the host sampler's multinomial draws
             if step == 0:
                 # the negative branch's prompt, a single speech_start (:377-381), is one more row of the prompt prefill (cache row 1, position 0)
-                eng.prefill(x0, row=0, pos0=0, chunk=getattr(self, "_prefill_chunk", 1024), neg_embed=eng.embed_ids(torch.tensor([ST])), prefix=prefix)
+                eng.prefill(x0, row=0, pos0=0, chunk=packed or getattr(self, "_prefill_chunk", 1024), neg_embed=eng.embed_ids(torch.tensor([ST])), prefix=prefix,
+                            packed=packed is not None)
                 tok = eng.first_token(ST_dev, SD, forced, sample_fn, q=q)
                 if tok == SD or not refresh_negative:
                     eng.commit_negative_prompt()         # the branch is in use from step 0 on (otherwise the row is overwritten by the next speech_start)

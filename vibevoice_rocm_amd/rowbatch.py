@@ -95,6 +95,8 @@ class RowBatch:
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
         self._pf_ws = None
         self._pf_rows = 0
+        self.prefill_passes = 0         # vv_llm_prefill_packed calls so far (prefill_packed)
+        self._pk_host = None
         self.token_host = torch.zeros(B, dtype=torch.int32).pin_memory()
         self.forced_host = torch.full((B,), -1, dtype=torch.int32).pin_memory()
         self.active_host = torch.ones(B, dtype=torch.int32).pin_memory()
@@ -326,6 +328,83 @@ class RowBatch:
             else:
                 self.hidden[row].copy_(out[-1])
             self.lens[row] = P + L0
+
+    def prefill_packed(self, items, chunk_rows: int = 4096, neg_embed: Optional[torch.Tensor] = None):
+        """Prompt prefill of SEVERAL dialogues in one weight pass (vv_llm_prefill_packed).  items: [(dialogue b, embeds [L_b, H] of the rows to
+        prefill, its VoicePrefix or None)].  Prefixes are restored with vv_kv_copy as `prefill` restores them; the dialogues' rows are packed
+        back to back in ascending b - dialogue b on cache row 2 b at positions P_b + i - and cut into passes of at most chunk_rows rows (a cut
+        inside a dialogue: its later rows run in the next pass at their own positions, as a chunked prefill's do).  neg_embed [1, H]: every
+        dialogue's one-token negative prompt (cache row 2 b + 1, position 0) rides on the last pass; `commit_negative` puts it in use.  Positions,
+        cache rows and the selected rows (each dialogue's last, the negatives) are built on the host and uploaded once per pass.  Then hidden[2 b],
+        hidden[2 b + 1] and lens[2 b] are what `prefill` leaves.  Counts its passes in self.prefill_passes."""
+        items = sorted(items, key=lambda it: it[0])
+        if not items or len({it[0] for it in items}) != len(items) or not all(0 <= it[0] < self.B for it in items):
+            raise L.VVError("RowBatch.prefill_packed: one entry per dialogue of this row batch")
+        chunk_rows, H, nb = max(1, int(chunk_rows)), self.cfg.hidden, len(items)
+        pos, row, end = [], [], {}                 # per packed row: position, cache row; index of a dialogue's last row -> its hidden row
+        for b, emb, prefix in items:
+            P = 0 if prefix is None else int(prefix.P)
+            n = int(emb.shape[0])
+            if n < 1:
+                raise L.VVError("RowBatch.prefill_packed: a dialogue without rows")
+            pos += range(P, P + n)
+            row += [2 * b] * n
+            end[len(pos) - 1] = 2 * b
+        T = len(pos)
+        cuts = list(range(0, T, chunk_rows))
+        if neg_embed is not None:
+            pos += [0] * nb
+            row += [2 * b + 1 for b, _, _ in items]
+            end.update({T + i: 2 * b + 1 for i, (b, _, _) in enumerate(items)})
+        passes = [(c0, min(T, c0 + chunk_rows) if i + 1 < len(cuts) else len(pos)) for i, c0 in enumerate(cuts)]
+        cap = max(c1 - c0 for c0, c1 in passes)
+        # one pinned int32 image per pass: positions | cache rows | selected rows, then (hidden row of each selected row); the last image
+        # carries the dialogues' new lens entries behind it: (2 b, P_b + L_b)
+        width = 3 * cap + 2 * self.B + 2 * nb
+        if self._pk_host is None or self._pk_host.shape[0] < len(passes) or self._pk_host.shape[1] < width:
+            self._pk_host = torch.zeros(max(len(passes), 4), width, dtype=torch.int32).pin_memory()
+            self._pk_event = torch.cuda.Event()
+        else:
+            self._pk_event.synchronize()          # the previous call's uploads have left the buffer
+        with torch.cuda.stream(self.stream):
+            xs = [emb.to(torch.float32) for _, emb, _ in items]
+            if neg_embed is not None:
+                xs += [neg_embed.to(torch.float32).reshape(1, H)] * nb
+            x = torch.cat(xs) if len(xs) > 1 else xs[0].contiguous()
+            if cap > self._pf_rows:              # one workspace for `prefill` and the packed passes: the two size functions agree
+                self._pf_rows = max(cap, 64)
+                self._pf_ws = torch.empty(self.lib.vv_llm_prefill_packed_ws_bytes(C.byref(self.main.w.llm), self._pf_rows), dtype=torch.uint8, device=self.device)
+            for b, _, prefix in items:
+                if prefix is not None:
+                    self._ck(self.lib.vv_kv_copy(C.byref(prefix.kv), 0, C.byref(self.kv), 2 * b, int(prefix.P), self.sp), "vv_kv_copy")
+            for p, (c0, c1) in enumerate(passes):
+                n = c1 - c0
+                sel = [i for i in range(c0, c1) if i in end]
+                dst = [end[i] for i in sel]
+                if not sel:
+                    sel = [c1 - 1]                 # a pass that ends no dialogue: the entry wants a row; its state is dropped
+                img = self._pk_host[p]
+                img[:n] = torch.tensor(pos[c0:c1], dtype=torch.int32)
+                img[cap: cap + n] = torch.tensor(row[c0:c1], dtype=torch.int32)
+                img[2 * cap: 2 * cap + len(sel)] = torch.tensor([i - c0 for i in sel], dtype=torch.int32)
+                used = 3 * cap + len(dst)
+                if dst:
+                    img[3 * cap: used] = torch.tensor(dst, dtype=torch.int32)
+                last = p + 1 == len(passes)
+                if last:
+                    img[used: used + 2 * nb] = torch.tensor([2 * b for b, _, _ in items] + [(0 if pf is None else int(pf.P)) + int(emb.shape[0]) for _, emb, pf in items],
+                                                            dtype=torch.int32)
+                meta = img[: used + (2 * nb if last else 0)].to(self.device, non_blocking=True)
+                out = torch.empty(len(sel), H, dtype=torch.float32, device=self.device)
+                self._ck(self.lib.vv_llm_prefill_packed(C.byref(self.main.w.llm), C.byref(self.kv), x[c0:c1].data_ptr(), x.stride(0), n, meta.data_ptr(),
+                                                        meta[cap:].data_ptr(), meta[2 * cap:].data_ptr(), len(sel), out.data_ptr(), out.stride(0),
+                                                        self._pf_ws.data_ptr(), self.sp), "vv_llm_prefill_packed")
+                self.prefill_passes += 1
+                if dst:
+                    self.hidden.index_copy_(0, meta[3 * cap: used].long(), out[: len(dst)])
+                if last:
+                    self.lens.index_copy_(0, meta[used: used + nb].long(), meta[used + nb: used + 2 * nb])
+            self._pk_event.record(self.stream)
 
     def commit_negative(self, b: int):
         with torch.cuda.stream(self.stream):
