@@ -542,6 +542,38 @@ int vv_connector_pair(const vv_connector* ac, const vv_connector* sem, const flo
                       int rows_out, float* ws, vv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Row-batched conv tails: the one-row stage (C = 2048, one row per frame) of both streaming tokenizers for the B dialogues of a row batch in
+ * ONE pass over its weights (csrc/vv_conv_rows.hip), every dialogue on its own streaming state.
+ *   nets:    (host) array of B nets that are forks of one net - the same weight pointers, every state pointer moved by one offset per dialogue
+ *            (DeviceWeights.fork) - anything else is VV_E_ARG
+ *   active:  device int[B]; a dialogue with active == 0 rides along: its rows are computed from whatever the buffers hold and dropped - no
+ *            store reaches its state or its output row
+ * Covered: bf16 weights without companions, a streaming net whose one-row stage is C = 2048 with hs / dw_last on every block, 2 <= B <= 8;
+ * anything else is VV_E_UNSUPPORTED, bad arguments VV_E_ARG, both before any launch.  No allocation, no synchronisation, capturable.
+ *   vv_decoder_front_rows     context gather, stem conv, the one-row blocks, the transposed hand-over conv 2048 -> 8 x 1024: row b of mid
+ *                             (pitch ld_mid >= 8192) = dialogue b's input of the C = 1024 stage; latent row b at latent + b * ld_latent
+ *   vv_decoder_forward_from   the remaining stages and the head conv of ONE dialogue and one frame from its mid row, with their state: wav.
+ *                             vv_decoder_front_rows then vv_decoder_forward_from leave dialogue b's state and waveform as vv_decoder_forward does
+ *   vv_encoder_forward_until  ONE dialogue: stem up to and including the C = 1024 stage; mid = its [T / hop x 8, 1024] rows
+ *   vv_encoder_back_rows      each dialogue's hand-over conv context, the hand-over conv 16 x 1024 -> 2048, the one-row blocks, the head conv:
+ *                             feat[b * ld_feat ..] = dialogue b's feature.  vv_encoder_forward_until then vv_encoder_back_rows = vv_encoder_forward
+ *   vv_connector_pair_rows    vv_connector_pair for B dialogues: out rows b * rows_out .. + rows_out - 1 (pitch ld_out) for the active ones;
+ *                             ws: 2 * B * hidden floats
+ * Workspaces: vv_conv_rows_ws_bytes(net, B, decoder) for the two *_rows composites (0: not covered), vv_convnet_ws_bytes(net, T, decoder) for
+ * vv_decoder_forward_from (T = 1) and vv_encoder_forward_until.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t vv_conv_rows_ws_bytes(const vv_convnet* net, int B, int decoder);
+int vv_decoder_front_rows(const vv_convnet* const* nets, int B, const int* active, const float* latent, int64_t ld_latent,
+                          float pre_scale, float pre_bias, float* mid, int64_t ld_mid, void* ws, vv_stream_t stream);
+int vv_decoder_forward_from(const vv_convnet* net, const float* mid, float* wav, void* ws, vv_stream_t stream);
+int vv_encoder_forward_until(const vv_convnet* net, const float* wav, int64_t T, float* mid, void* ws, vv_stream_t stream);
+int vv_encoder_back_rows(const vv_convnet* const* nets, int B, const int* active, const float* mid, int64_t ld_mid,
+                         float* feat, int64_t ld_feat, void* ws, vv_stream_t stream);
+int vv_connector_pair_rows(const vv_connector* ac, const vv_connector* sem, const float* latent, int64_t ld_latent,
+                           const float* semfeat, int64_t ld_feat, const int* active, float* out, int64_t ld_out,
+                           int rows_out, int B, float* ws, vv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * hipGraph capture of whatever the caller enqueues between begin/end on `stream`.
  * ------------------------------------------------------------------------------------------------------------ */
 int vv_graph_begin(vv_stream_t stream);

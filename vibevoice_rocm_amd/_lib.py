@@ -181,6 +181,12 @@ PROTOTYPES = {
     "vv_convnet_reset": (C.c_int, [C.POINTER(ConvNet), vp]),
     "vv_connector_forward": (C.c_int, [C.POINTER(Connector), vp, C.c_int, vp, C.c_int, vp, vp]),
     "vv_connector_pair": (C.c_int, [C.POINTER(Connector), C.POINTER(Connector), vp, vp, vp, i64, C.c_int, vp, vp]),
+    "vv_conv_rows_ws_bytes": (C.c_size_t, [C.POINTER(ConvNet), C.c_int, C.c_int]),
+    "vv_decoder_front_rows": (C.c_int, [C.POINTER(C.POINTER(ConvNet)), C.c_int, vp, vp, i64, C.c_float, C.c_float, vp, i64, vp, vp]),
+    "vv_decoder_forward_from": (C.c_int, [C.POINTER(ConvNet), vp, vp, vp, vp]),
+    "vv_encoder_forward_until": (C.c_int, [C.POINTER(ConvNet), vp, i64, vp, vp, vp]),
+    "vv_encoder_back_rows": (C.c_int, [C.POINTER(C.POINTER(ConvNet)), C.c_int, vp, vp, i64, vp, i64, vp, vp]),
+    "vv_connector_pair_rows": (C.c_int, [C.POINTER(Connector), C.POINTER(Connector), vp, i64, vp, i64, vp, vp, i64, C.c_int, C.c_int, vp, vp]),
     "vv_graph_begin": (C.c_int, [vp]),
     "vv_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "vv_graph_launch": (C.c_int, [vp, vp]),

@@ -124,6 +124,20 @@ int vv_launch_connector_pair(const vv_connector* ac, const vv_connector* sem, co
 int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, float* const* mod, float* modf, hipStream_t s);   // 1 launched, 0 not covered
 struct vv_conv_ctx_item { float* pad; float* state; int ctx, T, C; const float* dw_w; float* hs; int affine; float scale, bias; };   // dw_w / hs (scatter only): also hs[c] = sum_k<6 dw_w[c, k] * new state[k, c]; affine (gather only): pad = state * scale + bias (the net's input rides along)
 int vv_conv_ctx_batch(const vv_conv_ctx_item* items, int n, int scatter, hipStream_t s);   // scatter 0: pad[0:ctx] <- state; 1: state <- pad[T : T + ctx]
+// vv_conv_rows.hip: the one-row stage of the conv tokenizers for the 2..8 dialogues of a row batch in one weight pass.  The dialogues' nets are
+// forks of one net: dialogue b's streaming state sits at dialogue 0's address + d[b] floats.  Every launcher: 0 = enqueued, < 0 error
+struct vv_rows_delta { int64_t d[8]; };
+enum { VV_ROWS_W2 = 0, VV_ROWS_DEC = 1, VV_ROWS_SEM = 2 };       // the three GEMV shapes: block W2 2048 x 8192, hand-overs 8192 x 4096 and 2048 x 16384
+int vv_launch_row_in_rows(const vv_block& B, int nb, const float* x, float* y, float* hidden, float* hist_new, const vv_rows_delta& dl, const int* active,
+                          float eps, hipStream_t s);             // x / y [nb, 2048], hidden [nb, 8192], hist_new [nb][6, 2048] scratch (active dialogues)
+int vv_launch_rows_gemv(int shape, int nb, const float* x, int64_t ldx, const void* w, const float* bias, const float* gate, const float* res,
+                        int64_t ldres, float* out, int64_t ldo, const int* active, hipStream_t s);   // active != NULL: only active dialogues' rows are stored
+// one move of a gather (buf_b <- other_b [* scale + bias], every dialogue) or a scatter (other_b <- buf_b, active dialogues; with hs also the block
+// history's hs_b from the rows stored): buf_b = buf + b * ld_buf, other_b = other + d[b] (relocate: a state pointer of dialogue 0) or + b * ld_other
+struct vv_rows_item { float* buf; int64_t ld_buf; float* other; int64_t ld_other; int relocate, n, C; const float* dw_w; float* hs; int affine; float scale, bias; };
+#define VV_ROWS_ITEMS 24
+int vv_launch_rows_ctx(const vv_rows_item* items, int n, int nb, const vv_rows_delta& dl, const int* active, int scatter, hipStream_t s);
+int vv_launch_rows_bcast(const float* src, int64_t ld_src, float* out, int64_t ldo, int rows_out, int n, int nb, const int* active, hipStream_t s);
 int vv_block1d_init();                                            // vv_block1d.hip
 int vv_launch_block1d(const vv_block& B, int wdt, const float* x, float* out, int T, int C, float eps, hipStream_t s);   // 1 launched, 0 not covered
 void vv_block1d_set_fused(int on);

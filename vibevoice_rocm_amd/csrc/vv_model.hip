@@ -671,11 +671,14 @@ static int conv_left_ctx(const vv_conv& cv, float* pad, int64_t T, vv_stream_t s
   return 0;
 }
 
-extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, int T0, float pre_scale, float pre_bias, float* wav,
-                                  void* ws, vv_stream_t stream) {
-  if (!net || !latent || !wav || !ws) return vv_set_error(VV_E_ARG, "vv_decoder_forward: null pointer");
-  if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "vv_decoder_forward: bad T/stages");
+// vv_decoder_forward, and - mid != NULL - vv_decoder_forward_from: the frame enters behind the hand-over conv (sample[1]) with mid = that conv's
+// output [stride, cout]; stage 0, the hand-over conv and their streaming state are the caller's (vv_decoder_front_rows)
+static int decoder_run(const char* who, const vv_convnet* net, const float* latent, int T0, float pre_scale, float pre_bias, float* wav,
+                       void* ws, vv_stream_t stream, const float* mid) {
+  if (!net || (!latent && !mid) || !wav || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", who);
+  if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "%s: bad T/stages", who);
   VV_WQ_STRIP(vv_convnet, net);
+  const int first = mid ? 1 : 0;                  // the first stage this call runs
   size_t ael, hel;
   convnet_sizes(net, T0, 1, &ael, &hel);
   Carver cvr(ws);
@@ -685,10 +688,12 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
   int64_t T = T0;
   // stem input: padded [6 + T, vae] in A
   const vv_conv& stem = net->sample[0];
-  if (stem.transposed || stem.stride != 1) return vv_set_error(VV_E_ARG, "vv_decoder_forward: stem must be a stride-1 conv");
+  if (stem.transposed || stem.stride != 1) return vv_set_error(VV_E_ARG, "%s: stem must be a stride-1 conv", who);
   // streaming: every conv reads its own padded-input region; all left contexts are placed by ONE launch up front and collected by
   // ONE launch at the end (they were one dependent launch per conv: 8 per frame and net)
   const bool streaming = convnet_streaming(net);
+  if (mid && (!streaming || net->n_stages < 2 || !net->sample[1].transposed))
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: needs a streaming net whose second conv is the transposed hand-over", who);
   size_t poff[VV_MAX_STAGES + 1];
   float* pads = nullptr;
   vv_conv_ctx_item items[VV_CTX_ITEMS];
@@ -700,26 +705,33 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
     int64_t Ti = T0;
     for (int i = 0; i <= net->n_stages; ++i) {
       const vv_conv& cv = (i == net->n_stages) ? net->head : net->sample[i];
-      if (conv_ctx_of(cv) > 0) items[n_items++] = vv_conv_ctx_item{pads + poff[i], cv.state, conv_ctx_of(cv), (int)Ti, cv.cin};
+      if (conv_ctx_of(cv) > 0 && (!mid || i > 1)) items[n_items++] = vv_conv_ctx_item{pads + poff[i], cv.state, conv_ctx_of(cv), (int)Ti, cv.cin};
       if (cv.transposed) Ti *= cv.stride;
     }
     // the scaled latent frame rides along with the context gather: one launch instead of two in front of the stem conv
     vv_conv_ctx_item gi[VV_MAX_STAGES + 2];
     for (int i = 0; i < n_items; ++i) gi[i] = items[i];
-    gi[n_items] = vv_conv_ctx_item{pads + poff[0] + (size_t)conv_ctx_of(stem) * stem.cin, const_cast<float*>(latent), (int)T, 0, stem.cin, nullptr, nullptr, 1,
-                                   pre_scale, pre_bias};
-    VV_TRY(vv_conv_ctx_batch(gi, n_items + 1, 0, (hipStream_t)stream));
+    int n_gather = n_items;
+    if (!mid)
+      gi[n_gather++] = vv_conv_ctx_item{pads + poff[0] + (size_t)conv_ctx_of(stem) * stem.cin, const_cast<float*>(latent), (int)T, 0, stem.cin, nullptr, nullptr, 1,
+                                        pre_scale, pre_bias};
+    VV_TRY(vv_conv_ctx_batch(gi, n_gather, 0, (hipStream_t)stream));
   }
   float* pad = streaming ? pads + poff[0] : A;
   if (!streaming) VV_TRY(vv_affine(latent, pre_scale, pre_bias, pad + (size_t)conv_ctx_of(stem) * stem.cin, (int64_t)T * stem.cin, stream));
   float* cur = nullptr;     // current activation buffer, `pad` holds the next conv's input
   float* other = nullptr;
-  for (int i = 0; i < net->n_stages; ++i) {
+  for (int i = first; i < net->n_stages; ++i) {
     const vv_conv& cv = net->sample[i];
     if (!streaming) VV_TRY(conv_left_ctx(cv, pad, T, stream));
     float* outb = (pad == A) ? Bf : A;
     vv_lin_args a;
-    if (cv.transposed) {
+    if (mid && i == 1) {        // the hand-over conv ran in the caller: its output rows become this stage's input (the blocks ping-pong on A / Bf)
+      outb = A;
+      T *= cv.stride;
+      hipError_t e = hipMemcpyAsync(outb, mid, (size_t)T * cv.cout * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    } else if (cv.transposed) {
       a = lin_base(pad, cv.cin, (int)T, cv.w, cv.stride * cv.cout, 2 * cv.cin, net->wdt, outb, (int64_t)cv.stride * cv.cout);
       a.bias = cv.b;
       VV_TRY(vv_linear(&a, stream));
@@ -743,7 +755,7 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
     } else {
       float* dstb = next_pad ? next_pad : other;
       hipError_t e = hipMemcpyAsync(dstb + (size_t)nctx * C, cur, (size_t)T * C * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_decoder_forward: %s", hipGetErrorString(e));
+      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
       pad = dstb;
     }
   }
@@ -756,10 +768,25 @@ extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, in
   return 0;
 }
 
-extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64_t T0, float* feat, void* ws, vv_stream_t stream) {
-  if (!net || !wav || !feat || !ws) return vv_set_error(VV_E_ARG, "vv_encoder_forward: null pointer");
-  if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "vv_encoder_forward: bad T/stages");
+extern "C" int vv_decoder_forward(const vv_convnet* net, const float* latent, int T0, float pre_scale, float pre_bias, float* wav,
+                                  void* ws, vv_stream_t stream) {
+  if (!latent) return vv_set_error(VV_E_ARG, "vv_decoder_forward: null pointer");
+  return decoder_run("vv_decoder_forward", net, latent, T0, pre_scale, pre_bias, wav, ws, stream, nullptr);
+}
+
+extern "C" int vv_decoder_forward_from(const vv_convnet* net, const float* mid, float* wav, void* ws, vv_stream_t stream) {
+  if (!mid) return vv_set_error(VV_E_ARG, "vv_decoder_forward_from: null pointer");
+  return decoder_run("vv_decoder_forward_from", net, nullptr, 1, 0.f, 0.f, wav, ws, stream, mid);
+}
+
+// vv_encoder_forward, and - mid_out != NULL - vv_encoder_forward_until: the frame leaves behind the blocks of the last stage but one, whose result
+// goes to mid_out [T, C] instead of the hand-over conv's padded input; that conv, the last stage, the head and their state are the caller's
+// (vv_encoder_back_rows)
+static int encoder_run(const char* who, const vv_convnet* net, const float* wav, int64_t T0, float* feat, void* ws, vv_stream_t stream, float* mid_out) {
+  if (!net || !wav || (!feat && !mid_out) || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", who);
+  if (T0 <= 0 || net->n_stages < 1 || net->n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_ARG, "%s: bad T/stages", who);
   VV_WQ_STRIP(vv_convnet, net);
+  const int last_i = mid_out ? net->n_stages - 2 : net->n_stages;      // the last conv this call runs (n_stages: the head)
   hipStream_t s = (hipStream_t)stream;
   size_t ael, hel;
   convnet_sizes(net, T0, 0, &ael, &hel);
@@ -776,6 +803,7 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
     int64_t Ti = T0;
     for (int i = 0; i < net->n_stages && streaming; ++i) { if (Ti % net->sample[i].stride) streaming = false; Ti /= net->sample[i].stride; }
   }
+  if (mid_out && (!streaming || net->n_stages < 2)) return vv_set_error(VV_E_UNSUPPORTED, "%s: needs a streaming frame of a net with two stages or more", who);
   size_t poff[VV_MAX_STAGES + 1];
   float* pads = nullptr;
   vv_conv_ctx_item items[VV_CTX_ITEMS];
@@ -787,7 +815,7 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
     int64_t Ti = T0;
     for (int i = 0; i <= net->n_stages; ++i) {
       const vv_conv& cv = (i == net->n_stages) ? net->head : net->sample[i];
-      if (conv_ctx_of(cv) > 0) items[n_items++] = vv_conv_ctx_item{pads + poff[i], cv.state, conv_ctx_of(cv), (int)Ti, cv.cin};
+      if (conv_ctx_of(cv) > 0 && i <= last_i) items[n_items++] = vv_conv_ctx_item{pads + poff[i], cv.state, conv_ctx_of(cv), (int)Ti, cv.cin};
       Ti = (Ti + cv.stride - 1) / cv.stride;
     }
     // the waveform chunk rides along with the context gather (no separate copy in front of the stem conv)
@@ -799,13 +827,13 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
   float* pad = streaming ? pads + poff[0] : A;
   hipError_t e = hipSuccess;
   if (!streaming) e = hipMemcpyAsync(pad + (size_t)conv_ctx_of(stem) * stem.cin, wav, (size_t)T * stem.cin * 4, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_encoder_forward: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
   float* cur = nullptr;
   float* other = nullptr;
-  for (int i = 0; i <= net->n_stages; ++i) {
+  for (int i = 0; i <= last_i; ++i) {
     const bool is_head = (i == net->n_stages);
     const vv_conv& cv = is_head ? net->head : net->sample[i];
-    if (cv.transposed) return vv_set_error(VV_E_ARG, "vv_encoder_forward: transposed conv in an encoder");
+    if (cv.transposed) return vv_set_error(VV_E_ARG, "%s: transposed conv in an encoder", who);
     const int ctx = conv_ctx_of(cv);
     if (!streaming) VV_TRY(conv_left_ctx(cv, pad, T, stream));
     // output length as the reference's non-streaming padding rule gives it (modular_vibevoice_tokenizer.py:127-133);
@@ -815,7 +843,7 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
     const int64_t have = ctx + T;
     if (need > have) {
       e = hipMemsetAsync(pad + (size_t)have * cv.cin, 0, (size_t)(need - have) * cv.cin * 4, s);
-      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_encoder_forward: %s", hipGetErrorString(e));
+      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     float* outb = is_head ? feat : ((pad == A) ? Bf : A);
     vv_lin_args a = lin_base(pad, (int64_t)cv.stride * cv.cin, (int)Tout, cv.w, cv.cout, cv.kk * cv.cin, net->wdt, outb, cv.cout);
@@ -842,19 +870,30 @@ extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64
     other = (cur == A) ? Bf : A;
     const int C = cv.cout;
     const vv_conv& nxt = (i + 1 < net->n_stages) ? net->sample[i + 1] : net->head;
-    const int nctx = conv_ctx_of(nxt);
-    float* next_pad = streaming ? pads + poff[i + 1] : nullptr;
+    const bool leave = mid_out && i == last_i;                      // this stage's result is the call's output
+    const int nctx = leave ? 0 : conv_ctx_of(nxt);
+    float* next_pad = leave ? mid_out : streaming ? pads + poff[i + 1] : nullptr;
     if (net->n_blocks[i] > 0) {
       VV_TRY(run_blocks(net, wq, i, T, C, cur, other, hid, nctx, &pad, stream, next_pad, row_hist, items, &n_items, &row_stage));
     } else {
       float* dstb = next_pad ? next_pad : other;
       e = hipMemcpyAsync(dstb + (size_t)nctx * C, cur, (size_t)T * C * 4, hipMemcpyDeviceToDevice, s);
-      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_encoder_forward: %s", hipGetErrorString(e));
+      if (e != hipSuccess) return vv_set_error(VV_E_HIP, "%s: %s", who, hipGetErrorString(e));
       pad = dstb;
     }
   }
   if (streaming) VV_TRY(vv_conv_ctx_batch(items, n_items, 1, s));
   return 0;
+}
+
+extern "C" int vv_encoder_forward(const vv_convnet* net, const float* wav, int64_t T0, float* feat, void* ws, vv_stream_t stream) {
+  if (!feat) return vv_set_error(VV_E_ARG, "vv_encoder_forward: null pointer");
+  return encoder_run("vv_encoder_forward", net, wav, T0, feat, ws, stream, nullptr);
+}
+
+extern "C" int vv_encoder_forward_until(const vv_convnet* net, const float* wav, int64_t T, float* mid, void* ws, vv_stream_t stream) {
+  if (!mid) return vv_set_error(VV_E_ARG, "vv_encoder_forward_until: null pointer");
+  return encoder_run("vv_encoder_forward_until", net, wav, T, nullptr, ws, stream, mid);
 }
 
 extern "C" int vv_convnet_reset(const vv_convnet* net, vv_stream_t stream) {
@@ -885,6 +924,212 @@ extern "C" int vv_convnet_reset(const vv_convnet* net, vv_stream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the one-row stage (C = 2048, one row per frame) of both tokenizers for the B dialogues of a row batch: one pass over its weights
+// (kernels: vv_conv_rows.hip).  The dialogues' nets are forks of one net - same weights, every state pointer moved by one offset per dialogue.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct RowsPlan {
+  vv_convnet net;          // dialogue 0's net, wdt stripped
+  vv_rows_delta dl;        // dialogue b's state = dialogue 0's + dl.d[b] floats
+  int rs;                  // the one-row stage
+  int nb;                  // its blocks
+  const vv_conv* ho;       // the hand-over conv between it and the C = 1024 stage
+  int ctx0, P0;            // decoder: the stem's left context rows and the pitch of a dialogue's padded stem input
+  int ctxh, Kh;            // the hand-over conv's left context rows and its K (= pitch of a dialogue's padded input)
+  int ctxd, PH;            // encoder: the head conv's left context rows and the pitch of a dialogue's padded head input
+};
+
+inline int r64(size_t n) { return (int)((n + 63) & ~(size_t)63); }
+
+// the shape part of the coverage: net alone (vv_conv_rows_ws_bytes asks with one net)
+int rows_shape(const char* who, const vv_convnet* net0, int decoder, RowsPlan* p) {
+  p->net = *net0;
+  vv_convnet& n = p->net;
+  if (n.wdt & (VV_WQ_NF4 | VV_WQ_MXFP4 | VV_WQ_FRAG4)) return vv_set_error(VV_E_UNSUPPORTED, "%s: quantised companions are not served", who);
+  if (n.wdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "%s: bf16 weights only", who);
+  if (n.n_stages < 2 || n.n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_UNSUPPORTED, "%s: %d stages", who, n.n_stages);
+  if (!convnet_streaming(&n)) return vv_set_error(VV_E_UNSUPPORTED, "%s: a streaming net (every conv with its state) only", who);
+  p->rs = decoder ? 0 : n.n_stages - 1;
+  p->nb = n.n_blocks[p->rs];
+  p->ho = decoder ? &n.sample[1] : &n.sample[n.n_stages - 1];
+  const vv_conv& ho = *p->ho;
+  if (n.sample[p->rs].cout != 2048 || p->nb < 1 || p->nb > VV_ROW_BLOCKS || p->nb + 4 > VV_ROWS_ITEMS)
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: the one-row stage must be C = 2048 with 1..%d blocks (C = %d, %d blocks)", who, VV_ROW_BLOCKS, n.sample[p->rs].cout, p->nb);
+  for (int j = 0; j < p->nb; ++j) {
+    const vv_block& b = n.blocks[p->rs][j];
+    if (b.q_w1.q || b.q_w2.q) return vv_set_error(VV_E_UNSUPPORTED, "%s: fp8 companions are not served", who);
+    if (!b.hist || !b.hs || !b.dw_last) return vv_set_error(VV_E_UNSUPPORTED, "%s: the one-row blocks need hist, hs and dw_last", who);
+  }
+  if (decoder) {
+    const vv_conv& stem = n.sample[0];
+    if (stem.transposed || stem.stride != 1 || !ho.transposed || ho.cin != 2048 || ho.stride * ho.cout != 8192)
+      return vv_set_error(VV_E_UNSUPPORTED, "%s: needs a stride-1 stem and the transposed hand-over 2048 -> 8 x 1024", who);
+    p->ctx0 = conv_ctx_of(stem); p->P0 = r64((size_t)(p->ctx0 + 3) * stem.cin);
+    p->ctxh = 1; p->Kh = 2 * ho.cin;
+    p->ctxd = 0; p->PH = 0;
+  } else {
+    const vv_conv& hd = n.head;
+    if (ho.transposed || ho.kk * ho.cin != 16384 || ho.cout != 2048 || ho.kk <= ho.stride || hd.transposed || hd.stride != 1 || hd.cin != 2048)
+      return vv_set_error(VV_E_UNSUPPORTED, "%s: needs the strided hand-over with K = 16384 into C = 2048 and a stride-1 head", who);
+    p->ctx0 = 0; p->P0 = 0;
+    p->ctxh = conv_ctx_of(ho); p->Kh = ho.kk * ho.cin;
+    p->ctxd = conv_ctx_of(hd); p->PH = r64((size_t)(p->ctxd + 3) * hd.cin);
+  }
+  return 0;
+}
+
+// nets[0 .. B): forks of one net?  Same weights (VV_E_ARG otherwise), every state pointer of the part these calls run moved by ONE offset per dialogue
+int rows_plan(const char* who, const vv_convnet* const* nets, int B, int decoder, RowsPlan* p) {
+  if (B < 2 || B > 8) return vv_set_error(VV_E_UNSUPPORTED, "%s: B=%d (2..8 dialogues)", who, B);
+  for (int b = 0; b < B; ++b)
+    if (!nets[b]) return vv_set_error(VV_E_ARG, "%s: null net", who);
+  VV_TRY(rows_shape(who, nets[0], decoder, p));
+  const vv_convnet& n0 = p->net;
+  const int rs = p->rs, hoi = decoder ? 1 : n0.n_stages - 1;
+  const float* base0 = n0.blocks[rs][0].hist;
+  p->dl.d[0] = 0;
+  for (int b = 1; b < 8; ++b) p->dl.d[b] = 0;
+  for (int b = 1; b < B; ++b) {
+    const vv_convnet& n = *nets[b];
+    if (n.wdt != nets[0]->wdt || n.n_stages != n0.n_stages || n.eps != n0.eps || n.n_blocks[rs] != p->nb || !n.blocks[rs])
+      return vv_set_error(VV_E_ARG, "%s: net %d is not a fork of net 0", who, b);
+    const int64_t d = n.blocks[rs][0].hist - base0;
+    for (int c = 0; c < b; ++c)
+      if (d == p->dl.d[c]) return vv_set_error(VV_E_ARG, "%s: nets %d and %d share their streaming state", who, c, b);
+    p->dl.d[b] = d;
+    auto conv_ok = [&](const vv_conv& a, const vv_conv& f) {
+      return a.w == f.w && a.b == f.b && a.cin == f.cin && a.cout == f.cout && a.kk == f.kk && a.stride == f.stride && a.transposed == f.transposed &&
+             (a.state ? f.state == a.state + d : !f.state);
+    };
+    bool ok = conv_ok(n0.sample[rs], n.sample[rs]) && conv_ok(n0.sample[hoi], n.sample[hoi]) && (decoder || conv_ok(n0.head, n.head));
+    for (int j = 0; ok && j < p->nb; ++j) {
+      const vv_block& a = n0.blocks[rs][j];
+      const vv_block& f = n.blocks[rs][j];
+      ok = a.gamma == f.gamma && a.ffn_gamma == f.ffn_gamma && a.norm_w == f.norm_w && a.ffn_norm_w == f.ffn_norm_w && a.dw_w == f.dw_w && a.dw_b == f.dw_b &&
+           a.w1 == f.w1 && a.b1 == f.b1 && a.w2 == f.w2 && a.b2 == f.b2 && a.dw_last == f.dw_last && !f.q_w1.q && !f.q_w2.q && f.hist == a.hist + d &&
+           f.hs == a.hs + d;
+    }
+    if (!ok) return vv_set_error(VV_E_ARG, "%s: net %d is not a fork of net 0 (same weights, state moved by one offset)", who, b);
+  }
+  return 0;
+}
+
+struct RowsWs { float *X, *Y, *hid, *hn, *pad0, *hpad, *hdpad, *feat; };
+
+size_t rows_carve(const RowsPlan& p, int B, int decoder, void* ws, RowsWs* w) {
+  const size_t C = 2048;
+  Carver cv(ws);
+  char* base = cv.p;
+  float* X = cv.take(B * C);
+  float* Y = cv.take(B * C);
+  float* hid = cv.take(B * 4 * C);
+  float* hn = cv.take((size_t)p.nb * B * 6 * C);
+  float* pad0 = decoder ? cv.take((size_t)B * p.P0) : nullptr;
+  float* hpad = cv.take((size_t)B * p.Kh);
+  float* hdpad = decoder ? nullptr : cv.take((size_t)B * p.PH);
+  float* feat = decoder ? nullptr : cv.take((size_t)B * p.net.head.cout);
+  if (w) *w = RowsWs{X, Y, hid, hn, pad0, hpad, hdpad, feat};
+  return (size_t)(cv.p - base);
+}
+
+// the stage's blocks on x = w.X: row_in_rows + the W2 GEMV per block; the last block's result goes to row b of (dst, ld_dst)
+// and the blocks' history moves join the call's closing scatter
+int rows_blocks(const RowsPlan& p, int B, const RowsWs& w, const int* active, float* dst, int64_t ld_dst, vv_rows_item* items, int* n_items, hipStream_t s) {
+  const int C = 2048;
+  float* cur = w.X;
+  float* other = w.Y;
+  for (int j = 0; j < p.nb; ++j) {
+    const vv_block& blk = p.net.blocks[p.rs][j];
+    const bool last = j == p.nb - 1;
+    float* hn = w.hn + (size_t)j * B * 6 * C;
+    VV_TRY(vv_launch_row_in_rows(blk, B, cur, other, w.hid, hn, p.dl, active, p.net.eps, s));
+    items[(*n_items)++] = vv_rows_item{hn, (int64_t)6 * C, blk.hist, 0, 1, 6 * C, C, blk.dw_w, blk.hs, 0, 0.f, 0.f};
+    // out = y + ffn_gamma (W2 hidden + b2): y sits in `other`, the result replaces it (each element is read and written by one thread)
+    VV_TRY(vv_launch_rows_gemv(VV_ROWS_W2, B, w.hid, 4 * C, blk.w2, blk.b2, blk.ffn_gamma, other, C, last ? dst : other, last ? ld_dst : C, nullptr, s));
+    float* t = cur; cur = other; other = t;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t vv_conv_rows_ws_bytes(const vv_convnet* net, int B, int decoder) {
+  if (!net || B < 2 || B > 8) return 0;
+  RowsPlan p;
+  if (rows_shape("vv_conv_rows_ws_bytes", net, decoder, &p)) return 0;
+  return rows_carve(p, B, decoder, nullptr, nullptr);
+}
+
+extern "C" int vv_decoder_front_rows(const vv_convnet* const* nets, int B, const int* active, const float* latent, int64_t ld_latent, float pre_scale,
+                                     float pre_bias, float* mid, int64_t ld_mid, void* ws, vv_stream_t stream) {
+  const char* who = "vv_decoder_front_rows";
+  if (!nets || !active || !latent || !mid || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", who);
+  RowsPlan p;
+  VV_TRY(rows_plan(who, nets, B, 1, &p));
+  const vv_conv& stem = p.net.sample[0];
+  const vv_conv& ho = *p.ho;
+  if (ld_latent < stem.cin || ld_mid < (int64_t)ho.stride * ho.cout || ld_mid % 4 || ((uintptr_t)mid % 16))
+    return vv_set_error(VV_E_ARG, "%s: ld_latent=%lld ld_mid=%lld", who, (long long)ld_latent, (long long)ld_mid);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = 2048;
+  RowsWs w;
+  rows_carve(p, B, 1, ws, &w);
+  const int nin = p.ctx0 * stem.cin;
+  vv_rows_item items[VV_ROWS_ITEMS];
+  int n = 0;
+  // every dialogue's left contexts and its scaled latent frame into place: one launch
+  items[n++] = vv_rows_item{w.pad0, p.P0, stem.state, 0, 1, nin, stem.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  items[n++] = vv_rows_item{w.pad0 + nin, p.P0, const_cast<float*>(latent), ld_latent, 0, stem.cin, stem.cin, nullptr, nullptr, 1, pre_scale, pre_bias};
+  items[n++] = vv_rows_item{w.hpad, p.Kh, ho.state, 0, 1, ho.cin, ho.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  VV_TRY(vv_launch_rows_ctx(items, n, B, p.dl, active, 0, s));
+  // the stem conv (K = 7 x latent, 1.8 MB) per dialogue as vv_decoder_forward runs it: the one-row blocks' histories then match it bit for bit
+  for (int b = 0; b < B; ++b) {
+    vv_lin_args a = lin_base(w.pad0 + (size_t)b * p.P0, (int64_t)stem.stride * stem.cin, 1, stem.w, stem.cout, stem.kk * stem.cin, p.net.wdt, w.X + (size_t)b * C, C);
+    a.bias = stem.b;
+    VV_TRY(vv_linear(&a, stream));
+  }
+  n = 0;
+  items[n++] = vv_rows_item{w.pad0 + stem.cin, p.P0, stem.state, 0, 1, nin, stem.cin, nullptr, nullptr, 0, 0.f, 0.f};          // rows [T, T + ctx), T = 1
+  items[n++] = vv_rows_item{w.hpad + ho.cin, p.Kh, ho.state, 0, 1, ho.cin, ho.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  VV_TRY(rows_blocks(p, B, w, active, w.hpad + ho.cin, p.Kh, items, &n, s));
+  VV_TRY(vv_launch_rows_gemv(VV_ROWS_DEC, B, w.hpad, p.Kh, ho.w, ho.b, nullptr, nullptr, 0, mid, ld_mid, active, s));
+  return vv_launch_rows_ctx(items, n, B, p.dl, active, 1, s);
+}
+
+extern "C" int vv_encoder_back_rows(const vv_convnet* const* nets, int B, const int* active, const float* mid, int64_t ld_mid, float* feat, int64_t ld_feat,
+                                    void* ws, vv_stream_t stream) {
+  const char* who = "vv_encoder_back_rows";
+  if (!nets || !active || !mid || !feat || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", who);
+  RowsPlan p;
+  VV_TRY(rows_plan(who, nets, B, 0, &p));
+  const vv_conv& ho = *p.ho;
+  const vv_conv& hd = p.net.head;
+  const int nmid = ho.stride * ho.cin, nctxh = p.ctxh * ho.cin, nctxd = p.ctxd * hd.cin;
+  if (ld_mid < nmid || ld_feat < hd.cout) return vv_set_error(VV_E_ARG, "%s: ld_mid=%lld ld_feat=%lld", who, (long long)ld_mid, (long long)ld_feat);
+  hipStream_t s = (hipStream_t)stream;
+  RowsWs w;
+  rows_carve(p, B, 0, ws, &w);
+  vv_rows_item items[VV_ROWS_ITEMS];
+  int n = 0;
+  items[n++] = vv_rows_item{w.hpad, p.Kh, ho.state, 0, 1, nctxh, ho.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  items[n++] = vv_rows_item{w.hpad + nctxh, p.Kh, const_cast<float*>(mid), ld_mid, 0, nmid, ho.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  if (nctxd > 0) items[n++] = vv_rows_item{w.hdpad, p.PH, hd.state, 0, 1, nctxd, hd.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  VV_TRY(vv_launch_rows_ctx(items, n, B, p.dl, active, 0, s));
+  VV_TRY(vv_launch_rows_gemv(VV_ROWS_SEM, B, w.hpad, p.Kh, ho.w, ho.b, nullptr, nullptr, 0, w.X, 2048, nullptr, s));
+  n = 0;
+  items[n++] = vv_rows_item{w.hpad + nmid, p.Kh, ho.state, 0, 1, nctxh, ho.cin, nullptr, nullptr, 0, 0.f, 0.f};                // rows [T, T + ctx), T = stride
+  if (nctxd > 0) items[n++] = vv_rows_item{w.hdpad + hd.cin, p.PH, hd.state, 0, 1, nctxd, hd.cin, nullptr, nullptr, 0, 0.f, 0.f};
+  VV_TRY(rows_blocks(p, B, w, active, w.hdpad + nctxd, p.PH, items, &n, s));
+  // the head conv (sem_dim outputs, K = kk x 2048): all dialogues' rows in one call, into scratch; the scatter stores the active ones
+  vv_lin_args a = lin_base(w.hdpad, p.PH, B, hd.w, hd.cout, hd.kk * hd.cin, p.net.wdt, w.feat, hd.cout);
+  a.bias = hd.b;
+  VV_TRY(vv_linear(&a, stream));
+  items[n++] = vv_rows_item{w.feat, hd.cout, feat, ld_feat, 0, hd.cout, hd.cout, nullptr, nullptr, 0, 0.f, 0.f};
+  return vv_launch_rows_ctx(items, n, B, p.dl, active, 1, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // SpeechConnector
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int vv_connector_forward(const vv_connector* c, const float* x, int R, float* out, int accumulate, float* ws, vv_stream_t stream) {
@@ -909,6 +1154,33 @@ extern "C" int vv_connector_pair(const vv_connector* ac, const vv_connector* sem
   VV_TRY(vv_connector_forward(sem, semfeat, 1, out, 1, ws, stream));
   for (int r = 1; r < rows_out; ++r) VV_TRY(vv_copy_rows(out, 0, out + r * ldo, ldo, 1, ac->hidden, stream));
   return 0;
+}
+
+// Both connectors for the B dialogues of a row batch: every matrix is read once for all rows; the sums of the ACTIVE dialogues go to rows
+// b * rows_out .. + rows_out - 1 of out.  ws: 2 * B * hidden floats
+extern "C" int vv_connector_pair_rows(const vv_connector* ac, const vv_connector* sem, const float* latent, int64_t ld_latent, const float* semfeat,
+                                      int64_t ld_feat, const int* active, float* out, int64_t ld_out, int rows_out, int B, float* ws, vv_stream_t stream) {
+  if (!ac || !sem || !latent || !semfeat || !active || !out || !ws || rows_out < 1) return vv_set_error(VV_E_ARG, "vv_connector_pair_rows: bad args");
+  if (B < 2 || B > 8) return vv_set_error(VV_E_UNSUPPORTED, "vv_connector_pair_rows: B=%d (2..8 dialogues)", B);
+  if (ac->hidden != sem->hidden || ld_latent < ac->din || ld_feat < sem->din || ld_out < ac->hidden)
+    return vv_set_error(VV_E_ARG, "vv_connector_pair_rows: shapes");
+  const int H = ac->hidden;
+  float* t = ws;
+  float* sum = ws + (size_t)B * H;
+  const vv_connector* cs[2] = {ac, sem};
+  const float* xs[2] = {latent, semfeat};
+  const int64_t lds[2] = {ld_latent, ld_feat};
+  for (int i = 0; i < 2; ++i) {
+    const vv_connector* c = cs[i];
+    vv_lin_args a = lin_base(xs[i], lds[i], B, c->fc1, H, c->din, c->wdt, t, H);
+    a.bias = c->b1;
+    VV_TRY(vv_linear(&a, stream));
+    a = lin_base(t, H, B, c->fc2, H, H, c->wdt, sum, H);
+    a.pro = VV_PRO_RMSNORM; a.norm_w = c->norm_w; a.eps = 1e-6f; a.bias = c->b2;
+    if (i) { a.res = sum; a.ldres = H; }
+    VV_TRY(vv_linear(&a, stream));
+  }
+  return vv_launch_rows_bcast(sum, H, out, ld_out, rows_out, H, B, active, (hipStream_t)stream);
 }
 
 extern "C" size_t vv_sizeof(const char* name) {

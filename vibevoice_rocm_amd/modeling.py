@@ -358,6 +358,21 @@ def check_row_batch_width(width, torch_dtype, weight_quant, kv_cache_dtype):
     return int(width)
 
 
+def check_batched_conv_rows(flag, torch_dtype, weight_quant, config):
+    """ValueError unless the row-batched conv tails (batched_conv_rows=True, csrc/vv_conv_rows.hip) serve the model: bf16 weights without
+    companions and tokenizers whose one-row stage is C = 2048 (32 filters, six ratios)"""
+    if not flag:
+        return False
+    if weight_quant is not None:
+        raise ValueError(f"batched_conv_rows=True serves bf16 weights only: the row-batched one-row stage has no weight_quant={weight_quant!r} form")
+    if torch_dtype != torch.bfloat16:
+        raise ValueError(f"batched_conv_rows=True needs torch_dtype=torch.bfloat16, not {torch_dtype}")
+    for what, filt, ratios in (("acoustic decoder", config.ac_dec_filters, config.ac_ratios), ("semantic encoder", config.sem_filters, config.sem_ratios)):
+        if filt != 32 or filt * 2 ** len(ratios) != 2048:
+            raise ValueError(f"batched_conv_rows=True needs tokenizers whose one-row stage is C = 2048 (n_filters = 32): the {what} has n_filters = {filt}")
+    return True
+
+
 def row_partition(B: int, width: int = 4) -> List[int]:
     """Sizes of the row batches B dialogues run as: ceil(B / width) groups, balanced, the larger ones first (6 at width 4: [3, 3]; at 8: [6])"""
     n_groups = -(-B // width)
@@ -390,6 +405,8 @@ class _RowDriver:
         self.dn = False                        # set_noise_seeds: `eligible` / `speech` rows are (frame index, None), graph H draws the noise
         self.prefixes = [None] * B             # generate(voice_prefix=): dialogue -> VoicePrefix or None
         self.packed = None                     # packed_prefill: rows per pass - first_tokens prefills a row batch's dialogues in one weight pass
+        # batched_conv_rows: every row batch runs the one-row stage of both tokenizers once for its dialogues (RowBatch.enable_conv_rows)
+        self.conv_rows = bool(getattr(model, "batched_conv_rows", False))
 
     def begin(self, prompts, voices, max_steps, valid):
         from .rowbatch import RowBatch
@@ -397,9 +414,13 @@ class _RowDriver:
         for n in row_partition(B, self.width):                                                      # row batches of <= width dialogues, sizes balanced
             idxs = list(range(off, off + n))
             key = (n, off) if lanes[0] is model._lanes[0] else (n, off, "side")
+            if self.conv_rows:
+                key += ("conv_rows",)
             rb = model._rowbatch.get(key)
             if rb is None:
                 rb = model._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.main.stream)
+                if self.conv_rows:
+                    rb.enable_conv_rows()
             rb.begin(max(len(prompts[b]) for b in idxs) + max(max_steps, 1) + 8, valid, self.cfg_scale,
                      cfg_rows=[self.cfg_rows[b] for b in idxs] if self.cfg_rows else None)
             self.groups.append((rb, idxs))
@@ -548,9 +569,13 @@ class _SessionDriver(_RowDriver):
         for n in row_partition(B, self.width):                                                      # as _RowDriver.begin partitions a batch
             idxs = list(range(off, off + n))
             key = (n, off, "session") if lanes[0] is model._lanes[0] else (n, off, "session", "side")
+            if self.conv_rows:
+                key += ("conv_rows",)
             rb = model._rowbatch.get(key)
             if rb is None:
                 rb = model._rowbatch[key] = RowBatch([lanes[b] for b in idxs], stream=self.main.stream)
+                if self.conv_rows:
+                    rb.enable_conv_rows()
             rb.begin(max_context, valid, 1.0, cfg_rows=[1.0] * n)
             for loc in range(n):
                 rb.set_active(loc, False)              # a free slot's rows are computed and dropped; its positions stay
@@ -697,7 +722,14 @@ class VibeVoiceForConditionalGenerationInference:
     def __init__(self, config: VVConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", torch_dtype=torch.bfloat16,
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
                  kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
-                 seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS):
+                 seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS,
+                 batched_conv_rows: bool = False):
+        # batched_conv_rows: a row batch runs the one-row stage (C = 2048) of the acoustic decoder and the semantic encoder, and the connectors,
+        # once for all its dialogues - one pass over 78 % of the tokenizers' weights instead of one per dialogue (csrc/vv_conv_rows.hip, DESIGN.md
+        # section 5o).  bf16 weights without companions only.  Off by default; generate(batched_conv_rows=) overrides it per call, a session
+        # inherits it; one dialogue and the lanes ignore it.  Checked first: a bad combination raises ValueError before any weight is touched
+        self.batched_conv_rows = check_batched_conv_rows(batched_conv_rows, torch.bfloat16 if prequant else torch_dtype,
+                                                         "nf4" if prequant else weight_quant, config)
         # packed_prefill: the prompts of a row batch's dialogues are prefilled in ONE weight pass (RowBatch.prefill_packed, vv_llm_prefill_packed)
         # instead of one pass per dialogue, in passes of at most packed_prefill_rows rows; a single dialogue and the lanes take the same entry
         # for their one prompt.  Off by default; generate(packed_prefill=, packed_prefill_rows=) overrides per call, open_session(packed_prefill=)
@@ -815,7 +847,7 @@ class VibeVoiceForConditionalGenerationInference:
                    device_sampling=kw.get("device_sampling", False), device_noise=kw.get("device_noise", False),
                    mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False),
                    row_batch_width=kw.get("row_batch_width", 4), packed_prefill=kw.get("packed_prefill", False),
-                   packed_prefill_rows=kw.get("packed_prefill_rows", PACKED_PREFILL_ROWS))
+                   packed_prefill_rows=kw.get("packed_prefill_rows", PACKED_PREFILL_ROWS), batched_conv_rows=kw.get("batched_conv_rows", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -1047,6 +1079,8 @@ class VibeVoiceForConditionalGenerationInference:
             if vps is not None:
                 driver.prefixes = vps
             driver.packed = packed
+            if "batched_conv_rows" in kwargs:      # per call, like row_batch_width=: the same checks as at construction
+                driver.conv_rows = check_batched_conv_rows(kwargs["batched_conv_rows"], self.dtype, self.weight_quant, self.config)
             call = batchloop.BatchCall(special=special, pad_id=pad_id, max_pos=self.config.max_pos, latent=self.config.latent,
                                        max_new_tokens=max_new_tokens, max_length_times=max_length_times, forced_tokens=forced_tokens, noise=noise,
                                        sde_noise=sde_noise, audio_streamer=audio_streamer, stop_check_fn=stop_check_fn, verbose=verbose,

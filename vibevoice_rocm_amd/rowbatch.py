@@ -52,6 +52,50 @@ def _wait_all_jobs():
         _JOBS.pop(0).result()
 
 
+class ConvRowsBook:
+    """Host bookkeeping of the row-batched conv tails (batched_conv_rows): which dialogues owe a "back" - semantic encoder back end and
+    connectors into their rows of x - and which mask every call uploads.  No device work: RowBatch asks it, tests drive it alone.
+    A step may run several fronts (speculated dialogues first, the rest later); the back runs once, in front of the next graph A, over the
+    union of the dialogues that still owe one; a rolled-back frame owes nothing."""
+
+    def __init__(self, B: int):
+        self.B = int(B)
+        self.owed: set = set()
+        self.log: List[tuple] = []          # ("front" | "back", mask) per uploaded mask, in order
+
+    def _mask(self, which) -> List[int]:
+        w = set(int(b) for b in which)
+        if not w <= set(range(self.B)):
+            raise ValueError(f"dialogues {sorted(w)} of a row batch of {self.B}")
+        return [1 if b in w else 0 for b in range(self.B)]
+
+    def front(self, which) -> List[int]:
+        """a speech call for `which`: its front's mask; they now owe a back"""
+        m = self._mask(which)
+        if not any(m):
+            raise ValueError("a front without a dialogue")
+        self.owed |= set(int(b) for b in which)
+        self.log.append(("front", tuple(m)))
+        return m
+
+    def rollback(self, b: int):
+        """dialogue b's frame was mis-speculated: its state is restored, it owes nothing"""
+        self.owed.discard(int(b))
+
+    def back(self) -> Optional[List[int]]:
+        """in front of graph A: the mask of the one back of this step, or None when nobody owes one"""
+        if not self.owed:
+            return None
+        m = self._mask(self.owed)
+        self.owed = set()
+        self.log.append(("back", tuple(m)))
+        return m
+
+    def restart(self):
+        """a fresh batch (RowBatch.begin): nobody owes anything"""
+        self.owed = set()
+
+
 class RowBatch:
     def __init__(self, lanes: List[Engine], stream: Optional[torch.cuda.Stream] = None):
         """lanes: one Engine per dialogue (conv state, conv graphs, its stream).  stream: the stream graphs A and H run on (default: lanes[0]'s);
@@ -93,6 +137,7 @@ class RowBatch:
             self.tok_seed_dev = torch.zeros(B, dtype=torch.int64, device=self.device)         # its block of the step tail (graph "Ar")
             self.cfg_dev = torch.ones(B, **f32)           # guidance per dialogue, read on the device (begin(cfg_rows=) / admit): graph "Hc"
             self._llm_ws = torch.empty(self.lib.vv_llm_ws_bytes(C.byref(eng.w.llm), 2 * B), dtype=torch.uint8, device=self.device)
+        self.conv_rows: Optional[ConvRowsBook] = None      # enable_conv_rows(): the one-row stage of both tokenizers runs once per row batch
         self._pf_ws = None
         self._pf_rows = 0
         self.prefill_passes = 0         # vv_llm_prefill_packed calls so far (prefill_packed)
@@ -249,6 +294,10 @@ class RowBatch:
             with torch.cuda.stream(e.stream):
                 e.reset_speech_caches()
         self._lane_dirty = [False] * B
+        if self.conv_rows is not None:
+            self.conv_rows.restart()
+            for b in range(B):          # a front on the main stream must see the resets of the lanes' streams
+                self._lane_done(b)
 
     def admit(self, b: int, cfg_scale: float, noise_seed: Optional[int] = None, sampler: Optional[tuple] = None, token_seed: Optional[int] = None):
         """Slot b starts afresh for a new dialogue while the other slots go on (sessions; begin(cfg_rows=) opened the batch): lane b's outstanding
@@ -288,6 +337,9 @@ class RowBatch:
         self.set_active(b, True)
         with torch.cuda.stream(e.stream):
             e.reset_speech_caches()
+            if self.conv_rows is not None:
+                self.conv_rows.rollback(b)      # (nothing is owed by a slot that finished; a front waits for the reset through the lane's event)
+                self._lane_done(b)
 
     def prefill(self, b: int, embeds: torch.Tensor, neg: bool = False, chunk: int = 1024, neg_embed: Optional[torch.Tensor] = None, prefix=None):
         """Prompt prefill of dialogue b on cache row 2 b (neg: 2 b + 1), on the main stream; hidden[row] = last hidden state.  neg_embed [1, H]:
@@ -617,6 +669,118 @@ class RowBatch:
         self._ck(lib.vv_connector_pair(C.byref(w.ac_conn), C.byref(w.sem_conn), lat, e.sem.data_ptr(), self.x[2 * b].data_ptr(), cfg.hidden, 2,
                                        e.conn_ws.data_ptr(), e.sp), "connectors")
 
+    # ---- batched_conv_rows: front (main stream) -> middles (lanes) -> back (main stream, in front of the next graph A) ----------------
+    def enable_conv_rows(self):
+        """Switch this row batch to the row-batched conv tails (vv_decoder_front_rows / vv_encoder_back_rows / vv_connector_pair_rows): the
+        one-row stage of both tokenizers reads its weights once for all dialogues.  Idempotent; the per-dialogue tail graphs are not touched."""
+        if self.conv_rows is not None:
+            return
+        eng, cfg, B, lib = self.main, self.cfg, self.B, self.lib
+        if eng.w.quant is not None or eng.dtype != torch.bfloat16:
+            raise L.VVError("batched_conv_rows needs bf16 weights without companions")
+        fb = lib.vv_conv_rows_ws_bytes(C.byref(eng.w.dec), B, 1)
+        bb = lib.vv_conv_rows_ws_bytes(C.byref(eng.w.sem), B, 0)
+        if not fb or not bb:
+            raise L.VVError("batched_conv_rows: the tokenizers' one-row stage is not C = 2048 (n_filters != 32)")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._cr_dec = (C.POINTER(L.ConvNet) * B)(*[C.pointer(e.w.dec) for e in self.lanes])
+        self._cr_sem = (C.POINTER(L.ConvNet) * B)(*[C.pointer(e.w.sem) for e in self.lanes])
+        with torch.cuda.stream(self.stream):
+            self._cr_mid = torch.zeros(B, 8192, **f32)         # front -> middle: the decoder's C = 1024 stage input of every dialogue
+            self._cr_mid2 = torch.zeros(B, 8192, **f32)        # middle -> back: the encoder's C = 1024 stage output
+            self._cr_feat = torch.zeros(B, cfg.sem_dim, **f32)
+            self._cr_lat = torch.zeros(B, cfg.latent, **f32)   # the latents of the dialogues that owe a back (a later graph H rewrites self.latent)
+            self._cr_front_ws = torch.empty(fb, dtype=torch.uint8, device=self.device)
+            self._cr_back_ws = torch.empty(bb, dtype=torch.uint8, device=self.device)
+            self._cr_conn_ws = torch.empty(2 * B * cfg.hidden, **f32)
+            self._cr_front_mask = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self._cr_back_mask = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._cr_mask_host = torch.zeros(8, B, dtype=torch.int32).pin_memory()     # a ring: a row is rewritten 8 uploads later
+        self._cr_mask_k = 0
+        self._front_event = torch.cuda.Event()
+        self.conv_rows = ConvRowsBook(B)
+
+    def _cr_upload(self, mask: List[int], dev: torch.Tensor):
+        self._cr_mask_k = (self._cr_mask_k + 1) % self._cr_mask_host.shape[0]
+        row = self._cr_mask_host[self._cr_mask_k]
+        for b, v in enumerate(mask):
+            row[b] = int(v)
+        dev.copy_(row, non_blocking=True)
+
+    def _seq_front(self):
+        w = self.main.w
+        self._ck(self.lib.vv_decoder_front_rows(self._cr_dec, self.B, self._cr_front_mask.data_ptr(), self.latent.data_ptr(), self.cfg.latent,
+                                                1.0 / w.speech_scale, -w.speech_bias, self._cr_mid.data_ptr(), self._cr_mid.stride(0),
+                                                self._cr_front_ws.data_ptr(), self.sp), "vv_decoder_front_rows")
+
+    def _seq_mid(self, b, uid):
+        """the stages below the one-row stage of dialogue b on ITS stream: decoder from its hand-over rows, encoder up to its hand-over rows"""
+        e, cfg, lib = self.lanes[b], self.cfg, self.lib
+        self._ck(lib.vv_decoder_forward_from(C.byref(e.w.dec), self._cr_mid[b].data_ptr(), e.wav.data_ptr(), e._dec_ws.data_ptr(), e.sp), "vv_decoder_forward_from")
+        self._ck(lib.vv_encoder_forward_until(C.byref(e.w.sem), e.wav.data_ptr(), cfg.hop, self._cr_mid2[b].data_ptr(), e._sem_ws.data_ptr(), e.sp),
+                 "vv_encoder_forward_until")
+
+    def _seq_back(self):
+        w, cfg = self.main.w, self.cfg
+        self._ck(self.lib.vv_encoder_back_rows(self._cr_sem, self.B, self._cr_back_mask.data_ptr(), self._cr_mid2.data_ptr(), self._cr_mid2.stride(0),
+                                               self._cr_feat.data_ptr(), cfg.sem_dim, self._cr_back_ws.data_ptr(), self.sp), "vv_encoder_back_rows")
+        self._ck(self.lib.vv_connector_pair_rows(C.byref(w.ac_conn), C.byref(w.sem_conn), self._cr_lat.data_ptr(), cfg.latent, self._cr_feat.data_ptr(),
+                                                 cfg.sem_dim, self._cr_back_mask.data_ptr(), self.x.data_ptr(), cfg.hidden, 2, self.B,
+                                                 self._cr_conn_ws.data_ptr(), self.sp), "vv_connector_pair_rows")
+
+    def _back_if_owed(self):
+        """on the main stream, after _join_lanes and in front of graph A: the one back of the step for the dialogues that owe one"""
+        if self.conv_rows is None:
+            return
+        mask = self.conv_rows.back()
+        if mask is None:
+            return
+        self._cr_upload(mask, self._cr_back_mask)
+        self._run("back", self._seq_back)
+
+    def _speech_tails_rows(self, which: List[int]):
+        """speech_tails with batched_conv_rows: snapshots + front on the main stream right behind H, then every dialogue's middle on its lane"""
+        late = self.late_tails
+        with torch.cuda.stream(self.stream):
+            self._join_lanes()          # reset_speech / rollback / embed ran on the lanes' streams: the front reads and writes their state
+            mask = self.conv_rows.front(which)
+            for b in which:             # the rollback snapshot of every active dialogue, before the front writes any state; and its latent
+                e = self.lanes[b]
+                blob = e.w.state_blob()
+                self._ck(self.lib.vv_copy_rows(blob.data_ptr(), blob.numel(), e._state_snap.data_ptr(), blob.numel(), 1, blob.numel(), self.sp), "snapshot")
+                self._ck(self.lib.vv_copy_rows(self.latent[b].data_ptr(), self.cfg.latent, self._cr_lat[b].data_ptr(), self.cfg.latent, 1, self.cfg.latent,
+                                               self.sp), "latent")
+            self._cr_upload(mask, self._cr_front_mask)
+            self._run("front", self._seq_front)
+            self._front_event.record(self.stream)
+
+        def mid(b):
+            e = self.lanes[b]
+            torch.cuda.set_device(self.device)
+            if late and not self._on_main[b]:
+                self._front_event.synchronize()     # the worker waits for the front as a late tail waits for H: no stream-side wait
+            with torch.cuda.stream(e.stream):
+                e._run("RBmid", self._seq_mid, b, self.uid)
+                self._lane_done(b)
+                if self._timing is not None and self._tcur is not None:
+                    ev = torch.cuda.Event(enable_timing=True)
+                    ev.record(e.stream)
+                    self._tcur["t"].append(ev)
+
+        inline = []
+        for b in which:
+            if self._on_main[b]:
+                inline.append(b)
+            else:
+                if not late:
+                    self.lanes[b].stream.wait_event(self._front_event)
+                _submit(self.lanes[b].stream, mid, b)
+        for b in inline:
+            e = self.lanes[b]
+            if e.use_graphs and ("RBmid", b, self.uid) not in e._graphs:
+                _wait_all_jobs()        # first use captures on the main stream: no worker may still be waiting on _front_event (recorded there)
+            mid(b)
+
     def _seq_embed(self, b, uid):
         e, cfg = self.lanes[b], self.cfg
         self._ck(self.lib.vv_embed_row(e.w.embed.data_ptr(), e.w.wdt, cfg.hidden, self.token_dev[b:].data_ptr(), self.x[2 * b].data_ptr(), e.sp), "embed")
@@ -640,6 +804,7 @@ class RowBatch:
         [nv]} (do_sample on the device): the sampling variant of graph A - a dialogue with a forced token keeps it, the others draw theirs."""
         with torch.cuda.stream(self.stream):
             self._join_lanes()
+            self._back_if_owed()
             self._set_forced(forced)
             if self._timing is not None:
                 self._tcur = dict(a0=torch.cuda.Event(enable_timing=True), a1=torch.cuda.Event(enable_timing=True), h1=None, t=[])
@@ -666,6 +831,7 @@ class RowBatch:
         every row batch of the step before it waits for any (`logits_end`), then hands the drawn tokens to `decode_commit`."""
         with torch.cuda.stream(self.stream):
             self._join_lanes()
+            self._back_if_owed()
             self._run("A1", self._seq_A1)
             self.logits_host.copy_(self.logits, non_blocking=True)
             self._tok_event.record(self.stream)
@@ -758,6 +924,8 @@ class RowBatch:
                     self._tcur["t"].append(ev)
 
         self._wait_jobs()       # another row batch's worker may still be feeding (first use: capturing on) one of these streams
+        if self.conv_rows is not None:
+            return self._speech_tails_rows(which)
         inline = []
         for b in which:
             if self._on_main[b]:
@@ -789,12 +957,17 @@ class RowBatch:
     def rollback(self, b: int):
         self._wait_jobs()
         self.lanes[b].rollback_speech_state()
+        if self.conv_rows is not None:
+            self.conv_rows.rollback(b)      # the mis-speculated frame owes no back; the next front waits for the restore through the lane's event
+            self._lane_done(b)
 
     def reset_speech(self, b: int):
         self._wait_jobs()
         e = self.lanes[b]
         with torch.cuda.stream(e.stream):
             e.reset_speech_caches()
+            if self.conv_rows is not None:
+                self._lane_done(b)
 
     def synchronize(self):
         self._wait_jobs()
