@@ -543,7 +543,7 @@ int vv_connector_pair(const vv_connector* ac, const vv_connector* sem, const flo
 
 /* ------------------------------------------------------------------------------------------------------------
  * Row-batched conv tails: the one-row stage (C = 2048, one row per frame) of both streaming tokenizers for the B dialogues of a row batch in
- * ONE pass over its weights (csrc/vv_conv_rows.hip), every dialogue on its own streaming state.
+ * ONE pass over its weights (csrc/vv_conv_hot.hip), every dialogue on its own streaming state.
  *   nets:    (host) array of B nets that are forks of one net - the same weight pointers, every state pointer moved by one offset per dialogue
  *            (DeviceWeights.fork) - anything else is VV_E_ARG
  *   active:  device int[B]; a dialogue with active == 0 rides along: its rows are computed from whatever the buffers hold and dropped - no

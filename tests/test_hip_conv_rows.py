@@ -1,4 +1,4 @@
-"""Row-batched conv tails (csrc/vv_conv_rows.hip; vv_decoder_front_rows, vv_decoder_forward_from, vv_encoder_forward_until,
+"""Row-batched conv tails (csrc/vv_conv_hot.hip; vv_decoder_front_rows, vv_decoder_forward_from, vv_encoder_forward_until,
 vv_encoder_back_rows, vv_connector_pair_rows) against the per-dialogue composites they replace.
 
 Component nets with the real widths and few blocks: the "mid" preset with 32 tokenizer filters, so the one-row stage is C = 2048 with two
@@ -6,9 +6,10 @@ blocks (depths 1, .., 1, 2) and both hand-over convs have their real shapes.  On
 set of forks, the per-dialogue composites on a twin set, both from zeroed state.
 
 Figures of a GPU run (MI355X), relative RMS, dialogue 0, frames 0..2: per-dialogue path vs oracle 4.0e-3 .. 4.1e-3 (waveform) and
-4.5e-3 .. 6.1e-3 (semantic feature); batched path vs oracle: the same figures, digit for digit; batched vs per-dialogue: 0 for waveform, semantic
-feature and state blob at B = 2, 3 and 8 (the stem conv runs per dialogue, row_in_rows_kernel and rows_gemv_kernel keep the one-row kernels'
-summation order), x rows 2.2e-7 at B = 2 and 3 and 1.1e-3 at B = 8: the connectors' B-row vv_linear calls take the m = B routes - another fp32
+4.5e-3 .. 6.1e-3 (semantic feature); batched path vs oracle: the same figures, digit for digit; batched vs per-dialogue: waveform, semantic
+feature and state blob are EQUAL, asserted with torch.equal at every B (the stem conv runs per dialogue; row_in_rows_kernel and rows_gemv_kernel
+are one template each, the per-dialogue path runs their one-row instances, so row b has the one-row kernel's arithmetic by construction);
+x rows 2.2e-7 at B = 2 and 3 and 1.1e-3 at B = 8: the connectors' B-row vv_linear calls take the m = B routes - another fp32
 summation order at 2..3 rows; from 5 rows on the semantic connector's fc1 (K = 128, plain epilogue) is a shape of the skinny matrix-core kernel
 (vv_skinny_covers, csrc/vv_convffn.hip), which rounds its activation rows to bf16 (2^-9 relative per element) - under the yardstick."""
 import ctypes as C
@@ -186,7 +187,7 @@ def _subset(B):
     return m
 
 
-@pytest.mark.parametrize("B", [2, 3, 8])
+@pytest.mark.parametrize("B", [2, 3, 6, 7, 8])       # 6, 7: the 2048 x 16384 hand-over in passes of 3 and of 2 rows, 7 with a partial last pass
 def test_rows_vs_per_dialogue_composites(env, oracle_d0, B):
     cfg = env["cfg"]
     rows, twin = Rig(env, env["root"], B), Rig(env, env["root"], B)
@@ -215,13 +216,15 @@ def test_rows_vs_per_dialogue_composites(env, oracle_d0, B):
                 for t in (rows.mid[b], rows.mid2[b], rows.wav[b], rows.feat[b], rows.x[2 * b: 2 * b + 2]):
                     assert torch.equal(t, torch.full_like(t, SENT)), f"inactive dialogue {b}: output row written"
                 continue
-            dw = rel_rms(rows.wav[b].cpu().numpy(), twin.wav[b].cpu().numpy(), what=f"batched vs per-dialogue wav B={B} f={f} b={b}")
-            ds = rel_rms(rows.feat[b].cpu().numpy(), twin.feat[b].cpu().numpy(), what=f"batched vs per-dialogue sem B={B} f={f} b={b}")
+            # one kernel template for one row and for B rows: waveform, semantic feature and state are the per-dialogue path's, bit for bit
+            assert torch.equal(rows.wav[b], twin.wav[b]), f"B={B} f={f} b={b}: waveform differs from the per-dialogue path"
+            assert torch.equal(rows.feat[b], twin.feat[b]), f"B={B} f={f} b={b}: semantic feature differs from the per-dialogue path"
+            assert torch.equal(after[b], tb[b]), f"B={B} f={f} b={b}: state blob differs from the per-dialogue path"
+            # the connector rows: another summation order at m = B (module docstring), under the yardstick
             dx = rel_rms(rows.x[2 * b: 2 * b + 2].cpu().numpy(), twin.x[2 * b: 2 * b + 2].cpu().numpy(), what=f"batched vs per-dialogue x B={B} f={f} b={b}")
-            dst = rel_rms(after[b].cpu().numpy(), tb[b].cpu().numpy(), what=f"batched vs per-dialogue state B={B} f={f} b={b}")
             if b == 0:
-                print(f"  dialogue 0 batched vs per-dialogue: wav {dw:.3e} sem {ds:.3e} x {dx:.3e} state {dst:.3e}")
-            assert dw < yw and ds < ys and dx < ys and dst < min(yw, ys), (b, dw, ds, dx, dst, yw, ys)
+                print(f"  dialogue 0 batched vs per-dialogue: wav, sem and state equal, x {dx:.3e}")
+            assert dx < ys, (b, dx, ys)
             assert torch.equal(rows.x[2 * b], rows.x[2 * b + 1])
 
 

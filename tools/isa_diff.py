@@ -3,7 +3,9 @@
 Kernels are matched by their demangled base name and template arguments' order of appearance; labels and symbol names are normalised, so a
 renamed parameter type does not count, while any changed instruction, operand or kernel-argument offset does.  The rows GEMV's kernels are
 matched by their template arguments, the weight format as a number (gemv_rows_kernel's bool F8 -> 0 / 1, a gemv_rows_mx_kernel -> 2), and so are
-the streaming GEMV's (gemv_stream_kernel by its six arguments, a gemv_mx_kernel<M, DUAL, KSPLIT, KU> -> <M, DUAL, KSPLIT, KU, 4, 3>): a kernel
+the streaming GEMV's (gemv_stream_kernel by its six arguments, a gemv_mx_kernel<M, DUAL, KSPLIT, KU> -> <M, DUAL, KSPLIT, KU, 4, 3>),
+and the conv tokenizers' row-in kernels by theirs with the row count in front (a row_in_kernel<NT> -> row_in_rows_kernel<1, NT>, the earlier
+row_in_rows_kernel<BT> -> <BT, 0>): a kernel
 whose stream differs is listed with the registers, LDS, scratch and spill counts of its metadata on both sides."""
 import re
 import sys
@@ -55,6 +57,10 @@ def base(n):
     if m:
         args = re.findall(r"L[bi](\d+)E", m.group(2)) + (["4", "3"] if m.group(1) == "mx" else [])
         return "gemv_stream_kernel<" + ",".join(args) + ">"
+    m = re.search(r"\d+row_in(_rows)?_kernelI((?:L[bi]\d+E)+)E", n)
+    if m:
+        args = re.findall(r"L[bi](\d+)E", m.group(2))
+        return "row_in_rows_kernel<" + ",".join((["1"] if not m.group(1) else []) + args + (["0"] if m.group(1) and len(args) == 1 else [])) + ">"
     m = re.search(r"\d+(attn\w*kernel|rope_store_kernel|kvq\w*kernel)", n)
     return m.group(1) if m else n
 

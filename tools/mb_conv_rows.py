@@ -1,4 +1,4 @@
-"""Row-batched conv tails (batched_conv_rows, csrc/vv_conv_rows.hip) against the per-dialogue tails, one process, alternating legs, p50 (min - max):
+"""Row-batched conv tails (batched_conv_rows, csrc/vv_conv_hot.hip) against the per-dialogue tails, one process, alternating legs, p50 (min - max):
   composites  on the real 1.5B nets, in a dependent hipGraph chain of 20 frames: vv_decoder_front_rows and vv_encoder_back_rows at B = 2, 4, 8
               against B times the same part of the per-dialogue composites (vv_decoder_forward minus vv_decoder_forward_from, vv_encoder_forward
               minus vv_encoder_forward_until); the routes of the vv_linear calls the new composites make (vv_linear_route)
@@ -99,7 +99,7 @@ if "composites" in what:
         print(f"         vv_encoder_back_rows  {p50(t['back'])} us   per dialogue: one-row part of vv_encoder_forward {p50(s1)} us (full {p50(t['sem_full'])}, "
               f"until {p50(t['sem_until'])}) -> x {B} = {B * statistics.median(s1):.1f} us", flush=True)
         del ws
-    print("routes of the vv_linear calls inside the new composites (the 18 big matrices run on rows_gemv_kernel / row_in_rows_kernel, csrc/vv_conv_rows.hip):")
+    print("routes of the vv_linear calls inside the new composites (the 18 big matrices run on rows_gemv_kernel / row_in_rows_kernel, csrc/vv_conv_hot.hip):")
     buf = C.create_string_buffer(128)
     dummy = torch.zeros(8, 16384, **f32)
     for name, mm, n, k, ldx in (("decoder stem conv, per dialogue", 1, 2048, 7 * cfg.ac_dim, cfg.ac_dim), ("encoder head conv, B rows", 8, cfg.sem_dim, 7 * 2048, 9 * 2048),

@@ -20,10 +20,10 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef unsigned int att_raw __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void unpack8(const att_raw v, float (&o)[8]) {

@@ -21,13 +21,10 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned pk2(float a, float b) {      // two floats -> packed bf16 pair, round to nearest even

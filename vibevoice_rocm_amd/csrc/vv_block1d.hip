@@ -16,13 +16,9 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // phase timing of workgroup 0 / thread 0, debug builds only (-DVV_CF_TIMING, tools/convffn_phase.py)
 #ifdef VV_CF_TIMING
@@ -36,10 +32,6 @@ constexpr int TR = 32;          // rows per workgroup (one MFMA tile)
 constexpr int HALO = 6;         // causal depthwise kernel 7
 
 __device__ __forceinline__ float gelu1(float v) { return vv_gelu_as(v); }   // result goes to bf16: see vv_common.h
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-  const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
-  return (unsigned int)(*reinterpret_cast<const bf16_t*>(&x)) | ((unsigned int)(*reinterpret_cast<const bf16_t*>(&y)) << 16);
-}
 
 // sum over an aligned group of G = 8 / 16 / 32 consecutive lanes (all lanes active)
 template <int G>

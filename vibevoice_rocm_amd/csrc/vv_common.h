@@ -52,7 +52,8 @@ int vv_gemv_hot_covers(const vv_lin_args& a);                     // index of th
 int vv_launch_gemv_hot(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_gemv_hot_covers: 1 = launched on that entry's kernel
 void vv_gemv_hot_set(int mask);                                   // tuning hook "gemv_hot"
 // vv_conv_hot.hip: the conv tokenizers' one-row stage and hand-over GEMVs on kernels of their own (table: vv_conv_hot_shapes, vv_hip.h); bit i of
-// vv_tune("conv_hot") switches entry i.  1 = launched, 0 = no enabled entry matches (the caller goes on to today's path)
+// vv_tune("conv_hot") switches entry i.  1 = launched, 0 = no enabled entry matches (the caller goes on to today's path).  The row-batched
+// launchers further down start the same kernel templates with 2..8 rows
 int vv_conv_hot_gemv_covers(const vv_lin_args& a);                // index of the enabled GEMV table entry the call equals, or -1 (no launch)
 int vv_launch_conv_hot_gemv(const vv_lin_args& a, int idx, hipStream_t s);   // idx from vv_conv_hot_gemv_covers: 1 = launched
 int vv_launch_conv_hot_row(const vv_block& B, const float* x, float* y, float* hidden, float* hist_new, int C, float eps, hipStream_t s);
@@ -124,7 +125,7 @@ int vv_launch_connector_pair(const vv_connector* ac, const vv_connector* sem, co
 int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, float* const* mod, float* modf, hipStream_t s);   // 1 launched, 0 not covered
 struct vv_conv_ctx_item { float* pad; float* state; int ctx, T, C; const float* dw_w; float* hs; int affine; float scale, bias; };   // dw_w / hs (scatter only): also hs[c] = sum_k<6 dw_w[c, k] * new state[k, c]; affine (gather only): pad = state * scale + bias (the net's input rides along)
 int vv_conv_ctx_batch(const vv_conv_ctx_item* items, int n, int scatter, hipStream_t s);   // scatter 0: pad[0:ctx] <- state; 1: state <- pad[T : T + ctx]
-// vv_conv_rows.hip: the one-row stage of the conv tokenizers for the 2..8 dialogues of a row batch in one weight pass.  The dialogues' nets are
+// vv_conv_hot.hip, row batches: the one-row stage of the conv tokenizers for the 2..8 dialogues of a row batch in one weight pass.  The dialogues' nets are
 // forks of one net: dialogue b's streaming state sits at dialogue 0's address + d[b] floats.  Every launcher: 0 = enqueued, < 0 error
 struct vv_rows_delta { int64_t d[8]; };
 enum { VV_ROWS_W2 = 0, VV_ROWS_DEC = 1, VV_ROWS_SEM = 2 };       // the three GEMV shapes: block W2 2048 x 8192, hand-overs 8192 x 4096 and 2048 x 16384

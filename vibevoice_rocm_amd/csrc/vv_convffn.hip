@@ -23,14 +23,11 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // phase timing of workgroup (0, 0) / thread 0, debug builds only (-DVV_CF_TIMING, tools/convffn_phase.py)
 #ifdef VV_CF_TIMING
@@ -43,10 +40,6 @@ __device__ unsigned long long g_cf_t[8];
 constexpr int TR2 = 16;         // rows per workgroup of ffn_out (one 16 x 16 MFMA tile)
 constexpr int HALO = 6;         // causal depthwise kernel 7
 
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-  const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
-  return (unsigned int)(*reinterpret_cast<const bf16_t*>(&x)) | ((unsigned int)(*reinterpret_cast<const bf16_t*>(&y)) << 16);
-}
 __device__ __forceinline__ float sq4(const float4 v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
 
 template <int C, int TRV, int NT = 256> struct InLay {    // TRV: sequence rows per workgroup (<= 32; the MFMA tile stays 32 wide); NT: threads

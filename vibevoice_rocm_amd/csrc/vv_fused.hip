@@ -19,10 +19,10 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
 __device__ __forceinline__ float ldw(const float* p) { return *p; }
 __device__ __forceinline__ float ldw(const bf16_t* p) { return bf2f(*p); }

@@ -17,13 +17,9 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PK_T = 128;                        // tile rows of every operand (and of the output, both ways)
 constexpr int PK_BK = 64;                        // K elements per slab: a row is 128 bytes = 8 pieces of 16

@@ -23,29 +23,13 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float vf2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
-  o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-  o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-  o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);
-  o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-// NT: streamed once per frame (LLM); otherwise the matrix is re-read by the next solver step (head) and stays cacheable
-template <bool NT>
-__device__ __forceinline__ u32x4 ldw(const bf16_t* p) {
-  const u32x4* q = reinterpret_cast<const u32x4*>(p);
-  if constexpr (NT) return __builtin_nontemporal_load(q);
-  else return *q;
-}
+// ldw<NT> (vv_device.h), NT: streamed once per frame (LLM); otherwise the matrix is re-read by the next solver step (head) and stays cacheable
 
 // one lane's 8 weights of one K unit against both activation rows: even / odd k accumulate separately (v_pk_fma_f32), j ascending
 __device__ __forceinline__ void fma_unit(const u32x4 wv, const float (&x0)[8], const float (&x1)[8], vf2& p0, vf2& p1) {
@@ -64,8 +48,6 @@ __device__ __forceinline__ float vv_hot_gate_res(float v, float g, float r) {
   const float t = v * g;
   return t + r;
 }
-
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // SwiGLU pair (gate / up), K = 1536: RMSNorm (MOD: adaLN shift / scale on top) staged once per block over 256 threads, one weight row
@@ -389,8 +371,6 @@ __global__ __launch_bounds__(256) void hot_down_kernel(const vv_lin_args a) {
     a.out[(int64_t)eo_m * a.ldo + eo_n] = v;
   }
 }
-
-#undef VV_FENCE4
 
 // table order == bit order of the "gemv_hot" tuning key
 constexpr int N_HOT = 6;

@@ -132,7 +132,6 @@
     issue(wn, en_, wn2, en2, g + gstride);
   }
   __builtin_amdgcn_sched_barrier(0);
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 #pragma unroll
   for (int cc = 0; cc < NCH; ++cc) {
 #pragma unroll
@@ -145,7 +144,6 @@
       }
     }
   }
-#undef VV_FENCE4
 
   // ---- activation prologue -------------------------------------------------------------------------------------------------------------
   float rstd[MR];

@@ -18,22 +18,13 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
-
-typedef unsigned short bf16_t;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wsum(float v) { return vv_wave_sum(v); }   // DPP row reduction, all 64 lanes active
 __device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
 __device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
-  o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-  o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-  o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);
-  o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
-}
 
 // 8 e4m3fn weights in the low 8 bytes of the tile register (fp8 weight-only mode: 8-byte loads per lane)
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -47,7 +38,6 @@ __device__ __forceinline__ void unpack8_f8(const u32x4 v, float (&o)[8]) {
 // epilogue operands (bias / adaLN gate / residual) of one output: their addresses are known before the dot product is, so
 // they are loaded one row group ahead, in front of the weight loads that follow them in the queue (loads return in order: an
 // operand load issued at epilogue time would sit behind two row groups of prefetched weights)
-typedef float vf2 __attribute__((ext_vector_type(2)));
 // ROWSC: the instantiation can meet fp8 row scales at all (every format but MXFP4).  For the others the fp8 loads and multiplies hang on the
 // run-time test a.wdt == VV_FP8; the MXFP4 kernels carry none of them: their EpiOp is b, g, r.
 template <bool ROWSC> struct EpiOp { float b, g, r, s, s2; };   // bias, gate, residual, fp8 row scales (raw loads; absent operands are ignored at use)
@@ -316,7 +306,6 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     load_eo(eo_nxt, g + gstride);
     issue(nxt, nxt2, nws, nws2, g + gstride);
     __builtin_amdgcn_sched_barrier(0);
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
 #pragma unroll
@@ -327,7 +316,6 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
         for (int m = 0; m < M; ++m) { VV_FENCE4(sv[m][c]); VV_FENCE4(cv[m][c]); }
       }
     }
-#undef VV_FENCE4
     float ss[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -401,14 +389,12 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     __builtin_amdgcn_sched_barrier(0);
     // everything the prologue computes with is made opaque HERE, behind the weight loads: hipcc otherwise hoists pieces of the
     // arithmetic (and the waits they need) into the blocks above, in front of the weight issue
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 #pragma unroll
     for (int u = 0; u < KU; ++u) {
 #pragma unroll
       for (int m = 0; m < M; ++m) { VV_FENCE4(xa[m][u]); VV_FENCE4(xb[m][u]); }
       if (has_nw) { VV_FENCE4(na[u]); VV_FENCE4(nb[u]); }
     }
-#undef VV_FENCE4
     float ss[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {

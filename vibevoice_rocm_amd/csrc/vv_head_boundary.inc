@@ -47,12 +47,10 @@
   if constexpr (SDE) nx_nxt = a.nx[g + gstride < N ? g + gstride : 0];
   issue(nxt, g + gstride);
   __builtin_amdgcn_sched_barrier(0);
-#define VV_FENCE4(v) asm volatile("" : "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w))
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
     for (int r = 0; r < 2; ++r) { VV_FENCE4(hv[r][c]); VV_FENCE4(sv[r][c]); VV_FENCE4(cv[r][c]); }
-#undef VV_FENCE4
   float ss[2];
 #pragma unroll
   for (int r = 0; r < 2; ++r) {

@@ -14,6 +14,7 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // error plumbing
@@ -121,8 +122,6 @@ extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks
 // ---------------------------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------------------------
-typedef unsigned short bf16_t;
-
 __device__ __forceinline__ float bf2f(unsigned int u16) { return __uint_as_float(u16 << 16); }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -21,13 +21,9 @@
 
 #include "vv_hip.h"
 #include "vv_common.h"
+#include "vv_device.h"
 
 namespace {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 int g_mt_override = 0;   // tuning hook (vv_tune "mfma_mt")
 int g_mt_prefill_xb = 4;   // bf16 activations streamed from global (no LDS chunks / barriers): 128-row strips
@@ -44,10 +40,6 @@ template <int MT> struct Tile {                 // MT 32-row tiles per workgroup
 
 __device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
 __device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-  const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
-  return (unsigned int)(*reinterpret_cast<const bf16_t*>(&x)) | ((unsigned int)(*reinterpret_cast<const bf16_t*>(&y)) << 16);
-}
 __device__ __forceinline__ void epi1(const vv_lin_args& a, int m, int n, float v, float v2) {
   if (a.bias) v += a.bias[n];
   if (a.act == VV_ACT_GELU) v = gelu1(v);

@@ -925,7 +925,7 @@ extern "C" int vv_convnet_reset(const vv_convnet* net, vv_stream_t stream) {
 
 // ---------------------------------------------------------------------------------------------------------------
 // the one-row stage (C = 2048, one row per frame) of both tokenizers for the B dialogues of a row batch: one pass over its weights
-// (kernels: vv_conv_rows.hip).  The dialogues' nets are forks of one net - same weights, every state pointer moved by one offset per dialogue.
+// (kernels: vv_conv_hot.hip).  The dialogues' nets are forks of one net - same weights, every state pointer moved by one offset per dialogue.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 

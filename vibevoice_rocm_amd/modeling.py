@@ -359,7 +359,7 @@ def check_row_batch_width(width, torch_dtype, weight_quant, kv_cache_dtype):
 
 
 def check_batched_conv_rows(flag, torch_dtype, weight_quant, config):
-    """ValueError unless the row-batched conv tails (batched_conv_rows=True, csrc/vv_conv_rows.hip) serve the model: bf16 weights without
+    """ValueError unless the row-batched conv tails (batched_conv_rows=True, csrc/vv_conv_hot.hip) serve the model: bf16 weights without
     companions and tokenizers whose one-row stage is C = 2048 (32 filters, six ratios)"""
     if not flag:
         return False
@@ -725,7 +725,7 @@ class VibeVoiceForConditionalGenerationInference:
                  seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS,
                  batched_conv_rows: bool = False):
         # batched_conv_rows: a row batch runs the one-row stage (C = 2048) of the acoustic decoder and the semantic encoder, and the connectors,
-        # once for all its dialogues - one pass over 78 % of the tokenizers' weights instead of one per dialogue (csrc/vv_conv_rows.hip, DESIGN.md
+        # once for all its dialogues - one pass over 78 % of the tokenizers' weights instead of one per dialogue (csrc/vv_conv_hot.hip, DESIGN.md
         # section 5o).  bf16 weights without companions only.  Off by default; generate(batched_conv_rows=) overrides it per call, a session
         # inherits it; one dialogue and the lanes ignore it.  Checked first: a bad combination raises ValueError before any weight is touched
         self.batched_conv_rows = check_batched_conv_rows(batched_conv_rows, torch.bfloat16 if prequant else torch_dtype,
