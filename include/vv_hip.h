@@ -238,6 +238,14 @@ int vv_kv_copy(const vv_kv* src, int src_row, const vv_kv* dst, int dst_row, int
  * ------------------------------------------------------------------------------------------------------------ */
 int vv_block_mixer(const float* x, float* out, int T, int C, const float* norm_w, float eps, const float* dw_w,
                    const float* dw_b, const float* gamma, float* hist, vv_stream_t stream);
+/* The kernel vv_block_mixer would launch for these arguments under the current vv_tune state, written to name[cap]: decided by the very code
+ * vv_block_mixer launches through, without a launch and without touching the device (pointers count for NULL, alignment and x == out only):
+ *   "mixer_sliced<tr=32,cs=64>"    block_mixer_kernel: workgroups of tr rows x cs channels (cs: power of two <= 64)
+ *   "mixer_rows<tr=8,colfix=1>"    mixer_rows_kernel (16 <= T <= 256, C = 256 .. 2048 in steps of 256, vv_tune "mixer_rows"): tr rows x all channels
+ *                                  per workgroup; colfix: C / 4 divides 256, the kernel keeps one column's parameters in registers
+ * Arguments vv_block_mixer refuses return the same error. */
+int vv_block_mixer_route(const float* x, const float* out, int T, int C, const float* norm_w, const float* dw_w, const float* dw_b,
+                         const float* gamma, const float* hist, char* name, int cap);
 
 /* Streaming context for the dense convs: pad[0:ctx] <- state; state <- last ctx rows of [state ; pad[ctx:ctx+T]].
  * (SConv1d :364-380 keeps the last ctx inputs; SConvTranspose1d :538-547 needs only the previous input, ctx=1.) */
@@ -493,13 +501,26 @@ typedef struct vv_block {
  * (out != x).  Covered: bf16 weights, C = 32 / 64 / 128, T >= 32; anything else returns VV_E_UNSUPPORTED (the composites then
  * run vv_block_mixer + two vv_linear).  b->hist (or NULL) is the streaming state, updated in place. */
 int vv_block1d(const struct vv_block* b, int wdt, const float* x, float* out, int T, int C, float eps, vv_stream_t stream);
+/* The kernel vv_block1d would launch, as vv_block_mixer_route: "block1d<c=128> grid=3" - grid workgroups of 32-row tiles; grid below
+ * ceil(T / 32) (C = 128 above vv_tune "block1d_blocks" tiles) is the persistent walk, workgroup g taking tiles g, g + grid, ...  Pointers (x, out,
+ * the block's arrays) count for NULL, alignment and overlap only.  Arguments vv_block1d refuses return the same error. */
+int vv_block1d_route(const struct vv_block* b, int wdt, const float* x, const float* out, int T, int C, char* name, int cap);
 
 /* The same Block1D for the middle stages of a streaming frame (bf16 weights; C = 256 / 512 with 3 <= T <= 256, C = 1024 with T <= 64,
  * C = 128 with T <= 1024) as two launches (mixer +
  * first FFN GEMM, second FFN GEMM): x[T, C] -> out[T, C] (out != x).  ws: vv_block_mid_ws_bytes(T, C) bytes of scratch, 16-byte aligned.
- * Other shapes return VV_E_UNSUPPORTED.  b->hist as above. */
+ * Other shapes return VV_E_UNSUPPORTED.  b->hist as above.
+ * After the call ws holds, from its start: y = the mixer output (the FFN's residual) as [T, C] fp32, then the hidden activation
+ * gelu(W1 RMSNorm(y) + b1) as [T, 4C] bf16; the rest (6 * C floats + padding) is scratch for the history hand-over.  out may be the start of ws
+ * (out == y: the second launch then adds the FFN branch to y in place - the form the convnet composites use for every middle block); any other
+ * overlap of out with ws, or of x with the first T * C floats of ws, is not allowed. */
 size_t vv_block_mid_ws_bytes(int T, int C);
 int vv_block_mid(const struct vv_block* b, int wdt, const float* x, float* out, void* ws, int T, int C, float eps, vv_stream_t stream);
+/* The two kernels vv_block_mid would launch, as vv_block_mixer_route: "ffn_in<c=512,trv=8,nt=512> + ffn_out<c=512,nw=4>" - trv: rows per
+ * workgroup of the first launch (vv_tune "convffn_rows512" / "convffn_rows256" / "convffn_rows128": 8 | 16 | 32, 16 | 32 at C = 128; C = 1024
+ * always 8), nt its threads, nw the waves that split K in the second.  Pointers count for NULL, alignment and overlap only.  Arguments
+ * vv_block_mid refuses return the same error. */
+int vv_block_mid_route(const struct vv_block* b, int wdt, const float* x, const float* out, const void* ws, int T, int C, char* name, int cap);
 
 typedef struct vv_conv {
   const void* w;      /* re-laid: SConv1d [cout, kk*cin] with k index = tap*cin + ci;

@@ -359,17 +359,18 @@ def _accumulate(P, skip=None, rs=slice(None), cs=slice(None)):
     return acc
 
 
-def tile_row_errors(got, ref):
-    """(worst rel RMS over aligned 32 x 32 tiles cut at the edges, its tile index, worst rel RMS over rows, its row) of got against ref (fp64)"""
+def tile_row_errors(got, ref, tm=32, tn=32):
+    """(worst rel RMS over aligned tm x tn tiles (32 x 32 unless given) cut at the edges, its tile index, worst rel RMS over rows, its row) of
+    got against ref (fp64)"""
     got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
     e2, r2 = (got - ref) ** 2, ref ** 2
     m, n = ref.shape
-    mp, npad = -(-m // 32) * 32, -(-n // 32) * 32
+    mp, npad = -(-m // tm) * tm, -(-n // tn) * tn
 
     def tiles(a):
         p = np.zeros((mp, npad))
         p[:m, :n] = a
-        return p.reshape(mp // 32, 32, npad // 32, 32).sum((1, 3))
+        return p.reshape(mp // tm, tm, npad // tn, tn).sum((1, 3))
 
     t = np.sqrt(tiles(e2) / (tiles(r2) + 1e-300))
     r = np.sqrt(e2.sum(1) / (r2.sum(1) + 1e-300))
@@ -465,10 +466,11 @@ def test_docstring_table_is_current():
     assert routes == set(ALL_INSTANTIATIONS) and len(ALL_INSTANTIATIONS) == 30, routes ^ set(ALL_INSTANTIATIONS)
 
 
-def built_kernels(unit, tmp_path):
+def built_kernels(unit, tmp_path, plain=False):
     """(kernel template, [template arguments]) of every kernel descriptor (*.kd) in the gfx950 code object of one translation unit's object file
     under build.OBJDIR - what the device compiler generated, whatever the host side still launches.  Symbol names only: the .hip_fatbin section is
-    copied out, the gfx950 bundle unpacked and its symbol table listed, with the LLVM tools that sit next to hipcc."""
+    copied out, the gfx950 bundle unpacked and its symbol table listed, with the LLVM tools that sit next to hipcc.  plain: kernels that are no
+    templates are listed too, as (name, [])."""
     from vibevoice_rocm_amd import build as vb
     obj = vb._obj(os.path.join(vb.HERE, "csrc", unit))
     assert os.path.exists(obj), f"{obj} is missing: build() leaves one object file per translation unit there"
@@ -490,6 +492,10 @@ def built_kernels(unit, tmp_path):
         hit = re.search(r"(\w+)<(.*)>\(.*\) \(\.kd\)$", line)
         if hit:
             out.append((hit.group(1), hit.group(2).split(", ")))
+        elif plain:
+            hit = re.search(r"(\w+)\([^<>]*\) \(\.kd\)$", line)
+            if hit:
+                out.append((hit.group(1), []))
     return out
 
 

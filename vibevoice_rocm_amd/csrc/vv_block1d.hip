@@ -317,12 +317,8 @@ __global__ __launch_bounds__(256) void block1d_kernel(const float* __restrict__ 
 int g_blocks = 256;           // persistent workgroups at C = 128 (1 per CU: 5.15 ms voice encode vs 5.18 at 512, 5.59 unbounded); tuning hook "block1d_blocks"
 
 template <int C>
-int launch_c(const float* x, float* out, int T, const vv_block& B, float eps, hipStream_t s) {
-  const int n_tiles = (T + TR - 1) / TR;
-  // C = 128: the weight set is 262 KB per workgroup - resident workgroups walk the tiles.  C = 64 / 32 (65 / 16 KB): one workgroup per tile
-  // is faster (144 vs 176 us on a 40 000-row sequence: more independent workgroups per CU beat the saved re-fetch)
-  const int cap = (C == 128) ? g_blocks : n_tiles;
-  hipLaunchKernelGGL((block1d_kernel<C>), dim3(n_tiles < cap ? n_tiles : cap), dim3(256), Lay<C>::LDS, s, x, out, T, B, eps);
+int launch_c(const float* x, float* out, int T, const vv_block& B, float eps, int grid, hipStream_t s) {
+  hipLaunchKernelGGL((block1d_kernel<C>), dim3(grid), dim3(256), Lay<C>::LDS, s, x, out, T, B, eps);
   return hipGetLastError() == hipSuccess ? 1 : vv_set_error(VV_E_HIP, "vv_block1d: launch failed");
 }
 
@@ -350,8 +346,9 @@ int vv_block1d_init() {
   return 0;
 }
 
-// 1 = the whole block was enqueued as one launch, 0 = not covered (caller runs mixer + two linears), < 0 = error
-int vv_launch_block1d(const vv_block& B, int wdt, const float* x, float* out, int T, int C, float eps, hipStream_t s) {
+// What vv_launch_block1d launches: decided here for the launch and for vv_block1d_route alike (host only, no pointer is followed).
+// 1 = covered (*grid: workgroups of block1d_kernel<C>), 0 = not covered
+static int block1d_decide(const vv_block& B, int wdt, const float* x, const float* out, int T, int C, int* grid) {
   if (!g_fused || wdt != VV_BF16 || T < 32) return 0;
   {   // row tiles read their input (and halo) while others already write: the two [T, C] ranges must be disjoint
     const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, bytes = (uintptr_t)T * C * 4;
@@ -362,15 +359,45 @@ int vv_launch_block1d(const vv_block& B, int wdt, const float* x, float* out, in
   if (!a16(B.w1) || !a16(B.w2) || !a16(B.b1) || !a16(B.b2) || !a16(B.gamma) || !a16(B.ffn_gamma) || !a16(B.norm_w) || !a16(B.ffn_norm_w) ||
       !a16(B.dw_b) || !a16(B.dw_w) || !a16(x) || !a16(out) || (B.hist && !a16(B.hist)))
     return 0;
-  if (C == 32) return launch_c<32>(x, out, T, B, eps, s);
-  if (C == 64) return launch_c<64>(x, out, T, B, eps, s);
-  return launch_c<128>(x, out, T, B, eps, s);
+  const int n_tiles = (T + TR - 1) / TR;
+  // C = 128: the weight set is 262 KB per workgroup - resident workgroups walk the tiles.  C = 64 / 32 (65 / 16 KB): one workgroup per tile
+  // is faster (144 vs 176 us on a 40 000-row sequence: more independent workgroups per CU beat the saved re-fetch)
+  const int cap = (C == 128) ? g_blocks : n_tiles;
+  *grid = n_tiles < cap ? n_tiles : cap;
+  return 1;
+}
+
+// 1 = the whole block was enqueued as one launch, 0 = not covered (caller runs mixer + two linears), < 0 = error
+int vv_launch_block1d(const vv_block& B, int wdt, const float* x, float* out, int T, int C, float eps, hipStream_t s) {
+  int grid = 0;
+  if (!block1d_decide(B, wdt, x, out, T, C, &grid)) return 0;
+  if (C == 32) return launch_c<32>(x, out, T, B, eps, grid, s);
+  if (C == 64) return launch_c<64>(x, out, T, B, eps, grid, s);
+  return launch_c<128>(x, out, T, B, eps, grid, s);
+}
+
+// vv_block1d's refusals, for the call and for vv_block1d_route alike.  0 = covered (*grid as block1d_decide), < 0 = the call's error
+static int block1d_check(const vv_block* b, int wdt, const float* x, const float* out, int T, int C, int* grid) {
+  if (!b || !x || !out || T <= 0) return vv_set_error(VV_E_ARG, "vv_block1d: bad args");
+  if (!block1d_decide(*b, wdt, x, out, T, C, grid))
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_block1d: shape not covered by the fused kernel (C=%d T=%d wdt=%d)", C, T, wdt);
+  return 0;
 }
 
 extern "C" int vv_block1d(const vv_block* b, int wdt, const float* x, float* out, int T, int C, float eps, vv_stream_t stream) {
-  if (!b || !x || !out || T <= 0) return vv_set_error(VV_E_ARG, "vv_block1d: bad args");
+  int grid = 0;
+  VV_TRY(block1d_check(b, wdt, x, out, T, C, &grid));
   const int rc = vv_launch_block1d(*b, wdt, x, out, T, C, eps, (hipStream_t)stream);
-  if (rc < 0) return rc;
-  if (rc == 0) return vv_set_error(VV_E_UNSUPPORTED, "vv_block1d: shape not covered by the fused kernel (C=%d T=%d wdt=%d)", C, T, wdt);
+  return rc < 0 ? rc : 0;
+}
+
+// The kernel vv_block1d would launch for these arguments under the current vv_tune state, by the same decision (block1d_check, block1d_decide):
+// nothing is launched.  grid < ceil(T / 32) means the persistent walk: a workgroup takes row tiles blockIdx.x, blockIdx.x + grid, ...
+extern "C" int vv_block1d_route(const vv_block* b, int wdt, const float* x, const float* out, int T, int C, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_block1d_route: no room for the name");
+  name[0] = 0;
+  int grid = 0;
+  VV_TRY(block1d_check(b, wdt, x, out, T, C, &grid));
+  snprintf(name, (size_t)cap, "block1d<c=%d> grid=%d", C, grid);
   return 0;
 }

@@ -521,7 +521,8 @@ int g_skinny = 1, g_skinny_min_m = 5, g_skinny_max_m = 2048;   // up to the T = 
 int g_on = 1;
 
 // threads of ffn_in per channel count: the mixer part is instruction-issue bound, so the wide stages spread it over 8 waves
-template <int C> constexpr int in_threads() { return (C == 512 || C == 1024) ? 512 : 256; }
+constexpr int in_threads_of(int c) { return (c == 512 || c == 1024) ? 512 : 256; }
+template <int C> constexpr int in_threads() { return in_threads_of(C); }
 
 template <int C, int TRV, int NW>
 int launch_c(const vv_block& B, const float* x, float* y, void* hidden, float* hist_new, float* out, int T, float eps, hipStream_t s) {
@@ -630,10 +631,10 @@ int vv_launch_ffn_in_row_hs(const vv_block& B, int wdt, const float* x, float* y
   return hipGetLastError() == hipSuccess ? 1 : vv_set_error(VV_E_HIP, "vv_convffn: launch failed");
 }
 
-// One Block1D of a middle stage: x[T, C] -> y[T, C] (mixer output, also the FFN residual) -> hidden (bf16 [T, 4C]) -> out[T, C]
-// (out may be y).  hist_new: 6 * C floats of scratch.  1 = enqueued, 0 = not covered (caller runs mixer + two linears), < 0 = error
-int vv_launch_convffn(const vv_block& B, int wdt, const float* x, float* y, void* hidden, float* hist_new, float* out, int T, int C, float eps,
-                      hipStream_t s) {
+// What vv_launch_convffn launches: decided here for the launch and for vv_block_mid_route alike (host only, no pointer is followed).
+// 1 = covered (ffn_in_kernel<C, trv, false, in_threads<C>()> + ffn_out_kernel<C, nw>), 0 = not covered
+static int convffn_decide(const vv_block& B, int wdt, const float* x, const float* y, const void* hidden, const float* hist_new, const float* out, int T,
+                          int C, int* trv, int* nw) {
   if (!g_on || wdt != VV_BF16 || T < 3 || (C != 128 && C != 256 && C != 512 && C != 1024) || (C == 1024 && T > 64)) return 0;
   if (C == 128 ? (!g_c128 || T > 1024) : T > 256) return 0;
   auto a16 = [](const void* q) { return q && ((uintptr_t)q % 16) == 0; };
@@ -644,32 +645,60 @@ int vv_launch_convffn(const vv_block& B, int wdt, const float* x, float* y, void
     const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y, bytes = (uintptr_t)T * C * 4;
     if (xa < ya + bytes && ya < xa + bytes) return 0;
   }
-  if (C == 128) {
-    if (g_trv128 == 16) return launch_c<128, 16, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-    return launch_c<128, 32, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-  }
-  if (C == 256) {
-    if (g_trv256 == 8) return launch_c<256, 8, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-    if (g_trv256 == 16) return launch_c<256, 16, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-    return launch_c<256, 32, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-  }
-  if (C == 512) {
-    if (g_trv512 == 8) return launch_c<512, 8, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-    if (g_trv512 == 16) return launch_c<512, 16, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-    return launch_c<512, 32, 4>(B, x, y, hidden, hist_new, out, T, eps, s);
-  }
-  return launch_c<1024, 8, 8>(B, x, y, hidden, hist_new, out, T, eps, s);     // T = 8 rows per frame: 8-row tiles, K = 4096 over 8 waves
+  *nw = 4;
+  if (C == 128) *trv = g_trv128 == 16 ? 16 : 32;
+  else if (C == 256) *trv = (g_trv256 == 8 || g_trv256 == 16) ? g_trv256 : 32;
+  else if (C == 512) *trv = (g_trv512 == 8 || g_trv512 == 16) ? g_trv512 : 32;
+  else { *trv = 8; *nw = 8; }                    // C = 1024, T = 8 rows per frame: 8-row tiles, K = 4096 over 8 waves
+  return 1;
+}
+
+// One Block1D of a middle stage: x[T, C] -> y[T, C] (mixer output, also the FFN residual) -> hidden (bf16 [T, 4C]) -> out[T, C]
+// (out may be y).  hist_new: 6 * C floats of scratch.  1 = enqueued, 0 = not covered (caller runs mixer + two linears), < 0 = error
+int vv_launch_convffn(const vv_block& B, int wdt, const float* x, float* y, void* hidden, float* hist_new, float* out, int T, int C, float eps,
+                      hipStream_t s) {
+  int trv = 0, nw = 0;
+  if (!convffn_decide(B, wdt, x, y, hidden, hist_new, out, T, C, &trv, &nw)) return 0;
+#define VV_CF_GO(CC, TT, NN) if (C == CC && trv == TT) return launch_c<CC, TT, NN>(B, x, y, hidden, hist_new, out, T, eps, s)
+  VV_CF_GO(128, 16, 4); VV_CF_GO(128, 32, 4);
+  VV_CF_GO(256, 8, 4); VV_CF_GO(256, 16, 4); VV_CF_GO(256, 32, 4);
+  VV_CF_GO(512, 8, 4); VV_CF_GO(512, 16, 4); VV_CF_GO(512, 32, 4);
+  VV_CF_GO(1024, 8, 8);
+#undef VV_CF_GO
+  return vv_set_error(VV_E_UNSUPPORTED, "vv_convffn: no kernel for C=%d with %d-row tiles", C, trv);
+}
+
+// vv_block_mid's refusals and its pieces of ws (the layout include/vv_hip.h documents), for the call and for vv_block_mid_route alike.
+// 0 = covered, < 0 = the call's error
+static int block_mid_decide(const vv_block* b, int wdt, const float* x, const float* out, void* ws, int T, int C, float** y, char** hidden, float** hn,
+                            int* trv, int* nw) {
+  if (!b || !x || !out || !ws || T <= 0) return vv_set_error(VV_E_ARG, "vv_block_mid: bad args");
+  *y = reinterpret_cast<float*>(ws);
+  *hidden = reinterpret_cast<char*>(ws) + (size_t)T * C * 4;
+  *hn = reinterpret_cast<float*>(*hidden + (size_t)T * 4 * C * 2);
+  if (!convffn_decide(*b, wdt, x, *y, *hidden, *hn, out, T, C, trv, nw))
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_block_mid: shape not covered (C=%d T=%d wdt=%d)", C, T, wdt);
+  return 0;
 }
 
 extern "C" size_t vv_block_mid_ws_bytes(int T, int C) { return (size_t)T * C * 4 + (size_t)T * 4 * C * 2 + (size_t)HALO * C * 4 + 64; }
 
 extern "C" int vv_block_mid(const vv_block* b, int wdt, const float* x, float* out, void* ws, int T, int C, float eps, vv_stream_t stream) {
-  if (!b || !x || !out || !ws || T <= 0) return vv_set_error(VV_E_ARG, "vv_block_mid: bad args");
-  float* y = reinterpret_cast<float*>(ws);
-  char* hidden = reinterpret_cast<char*>(ws) + (size_t)T * C * 4;
-  float* hn = reinterpret_cast<float*>(hidden + (size_t)T * 4 * C * 2);
+  float* y; char* hidden; float* hn;
+  int trv = 0, nw = 0;
+  VV_TRY(block_mid_decide(b, wdt, x, out, ws, T, C, &y, &hidden, &hn, &trv, &nw));
   const int rc = vv_launch_convffn(*b, wdt, x, y, hidden, hn, out, T, C, eps, (hipStream_t)stream);
-  if (rc < 0) return rc;
-  if (rc == 0) return vv_set_error(VV_E_UNSUPPORTED, "vv_block_mid: shape not covered (C=%d T=%d wdt=%d)", C, T, wdt);
+  return rc < 0 ? rc : 0;
+}
+
+// The two kernels vv_block_mid would launch for these arguments under the current vv_tune state, by the same decision (block_mid_decide,
+// convffn_decide): nothing is launched.  nt: threads of ffn_in_kernel, nw: waves of ffn_out_kernel.
+extern "C" int vv_block_mid_route(const vv_block* b, int wdt, const float* x, const float* out, const void* ws, int T, int C, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_block_mid_route: no room for the name");
+  name[0] = 0;
+  float* y; char* hidden; float* hn;
+  int trv = 0, nw = 0;
+  VV_TRY(block_mid_decide(b, wdt, x, out, const_cast<void*>(ws), T, C, &y, &hidden, &hn, &trv, &nw));
+  snprintf(name, (size_t)cap, "ffn_in<c=%d,trv=%d,nt=%d> + ffn_out<c=%d,nw=%d>", C, trv, in_threads_of(C), C, nw);
   return 0;
 }

@@ -1719,8 +1719,16 @@ int vv_mixer_init() {
 static int g_mixer_rows = 1;
 void vv_mixer_set_rows(int on) { g_mixer_rows = on; }
 
-extern "C" int vv_block_mixer(const float* x, float* out, int T, int C, const float* norm_w, float eps, const float* dw_w,
-                              const float* dw_b, const float* gamma, float* hist, vv_stream_t stream) {
+// The kernel a vv_block_mixer call takes and its launch shape: decided here for the launch below and for vv_block_mixer_route alike (host only,
+// no pointer is followed).  0 = decided, < 0 = the call's refusal.
+struct mixer_route {
+  int rows;          // 1: mixer_rows_kernel (tr rows per workgroup), 0: block_mixer_kernel (tr rows x cs channels per workgroup)
+  int tr, cs;
+  dim3 grid;
+  size_t lds;
+};
+static int mixer_decide(const float* x, const float* out, int T, int C, const float* norm_w, const float* dw_w, const float* dw_b, const float* gamma,
+                        const float* hist, mixer_route* r) {
   if (!x || !out || !norm_w || !dw_w || !dw_b || !gamma) return vv_set_error(VV_E_ARG, "vv_block_mixer: null pointer");
   if (x == out) return vv_set_error(VV_E_ARG, "vv_block_mixer: in-place not allowed (halo rows)");
   if (T <= 0 || C <= 0) return vv_set_error(VV_E_ARG, "vv_block_mixer: bad shape");
@@ -1732,10 +1740,9 @@ extern "C" int vv_block_mixer(const float* x, float* out, int T, int C, const fl
       int TRr = 8;
       while (TRr > 1 && ((TRr + 6) * (C / 4) > 256 * MIXR_NI || TRr / 2 >= T)) TRr >>= 1;
       if ((TRr + 6) * (C / 4) <= 256 * MIXR_NI && !(hist && T > TRr && TRr < 6)) {
-        const size_t ldsb = ((size_t)(TRr + 6) * C + (size_t)TRr * C + (size_t)(TRr + 6) * 8) * sizeof(float);
-        hipLaunchKernelGGL(mixer_rows_kernel, dim3((T + TRr - 1) / TRr), dim3(256), ldsb, (hipStream_t)stream, x, out, T, C, norm_w, eps,
-                           dw_w, dw_b, gamma, hist, TRr);
-        VV_CHECK_LAUNCH("vv_block_mixer");
+        r->rows = 1; r->tr = TRr; r->cs = C;
+        r->grid = dim3((T + TRr - 1) / TRr);
+        r->lds = ((size_t)(TRr + 6) * C + (size_t)TRr * C + (size_t)(TRr + 6) * 8) * sizeof(float);
         return 0;
       }
     }
@@ -1743,14 +1750,37 @@ extern "C" int vv_block_mixer(const float* x, float* out, int T, int C, const fl
   int CS = 64;                                   // channel slice: power of two <= 64 that covers narrow stages exactly
   while (CS > 1 && CS / 2 >= C) CS >>= 1;
   int TR = T < MIX_TR ? T : MIX_TR;
-  const size_t lds = (size_t)((TR + 6) * CS + (TR + 6)) * sizeof(float);
   if (hist && TR < 6 && T > TR)   // row tiles 1..5 would read hist while tile 0 rewrites it
     return vv_set_error(VV_E_UNSUPPORTED, "vv_block_mixer: streaming with C=%d needs T<=%d rows per call (got %d)", C, TR, T);
-  dim3 grid((T + TR - 1) / TR, (C + CS - 1) / CS);
-  if (grid.y > 65535u || grid.x > 2147483647u) return vv_set_error(VV_E_UNSUPPORTED, "vv_block_mixer: grid too large");
-  hipLaunchKernelGGL(block_mixer_kernel, grid, dim3(256), lds, (hipStream_t)stream, x, out, T, C, norm_w, eps,
-                     dw_w, dw_b, gamma, hist, TR, CS);
+  r->rows = 0; r->tr = TR; r->cs = CS;
+  r->lds = (size_t)((TR + 6) * CS + (TR + 6)) * sizeof(float);
+  r->grid = dim3((T + TR - 1) / TR, (C + CS - 1) / CS);
+  if (r->grid.y > 65535u || r->grid.x > 2147483647u) return vv_set_error(VV_E_UNSUPPORTED, "vv_block_mixer: grid too large");
+  return 0;
+}
+
+extern "C" int vv_block_mixer(const float* x, float* out, int T, int C, const float* norm_w, float eps, const float* dw_w,
+                              const float* dw_b, const float* gamma, float* hist, vv_stream_t stream) {
+  mixer_route r;
+  VV_TRY(mixer_decide(x, out, T, C, norm_w, dw_w, dw_b, gamma, hist, &r));
+  if (r.rows)
+    hipLaunchKernelGGL(mixer_rows_kernel, r.grid, dim3(256), r.lds, (hipStream_t)stream, x, out, T, C, norm_w, eps, dw_w, dw_b, gamma, hist, r.tr);
+  else
+    hipLaunchKernelGGL(block_mixer_kernel, r.grid, dim3(256), r.lds, (hipStream_t)stream, x, out, T, C, norm_w, eps, dw_w, dw_b, gamma, hist, r.tr, r.cs);
   VV_CHECK_LAUNCH("vv_block_mixer");
+  return 0;
+}
+
+// The kernel vv_block_mixer would launch for these arguments under the current vv_tune state, by the same decision (mixer_decide): nothing is
+// launched.  colfix is how mixer_rows_kernel itself reads C (a thread keeps one column in every pass: C / 4 divides 256).
+extern "C" int vv_block_mixer_route(const float* x, const float* out, int T, int C, const float* norm_w, const float* dw_w, const float* dw_b,
+                                    const float* gamma, const float* hist, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_block_mixer_route: no room for the name");
+  name[0] = 0;
+  mixer_route r;
+  VV_TRY(mixer_decide(x, out, T, C, norm_w, dw_w, dw_b, gamma, hist, &r));
+  if (r.rows) snprintf(name, (size_t)cap, "mixer_rows<tr=%d,colfix=%d>", r.tr, (256 % (C / 4)) == 0 ? 1 : 0);
+  else snprintf(name, (size_t)cap, "mixer_sliced<tr=%d,cs=%d>", r.tr, r.cs);
   return 0;
 }
 
