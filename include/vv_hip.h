@@ -53,11 +53,12 @@ enum { VV_WQ_NF4 = 0x100 };
  *                     i.e. the byte of row 4 q + r, block b of unit u (k = 512 u + 32 b .. + 31) at ((q * ceil(K/512) + u) * 16 + b) * 4 + r
  * Padding (rows past N, k past K) holds code 0 and scale byte 127.  Rows of at most 40 units of 512 k (SwiGLU, w2 != NULL: 24).  Any other
  * MXFP4 call (m > 2, k % 32, a missing scale pointer, a misaligned pointer, VV_LIN_W_FRAG, VV_LIN_X_BF16 / VV_LIN_OUT_BF16) returns
- * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike. */
+ * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike.  The one other reader of this layout is the matrix-core GEMM on the codes, which a
+ * call asks for with VV_LIN_W_MXGEMM (vv_lin_args.flags, below: m >= 3, bf16 x); without that bit nothing above changes. */
 enum { VV_MXFP4 = 4 };
 /* VV_WQ_MXFP4: as VV_WQ_NF4, for companions that hold MXFP4 (codes in q, the scale bytes' address in scale, the VV_MXFP4 layouts above).  The
  * 1..2-row GEMVs stream them; every 3..8-row path (unless VV_WQ_FRAG4, below) and the prefill use the bf16 matrices, which hold exactly the same
- * effective values. */
+ * effective values - unless the model is LEAN (below, after VV_WQ_FRAG4): its LLM has no bf16 matrices and runs those passes on the codes. */
 enum { VV_WQ_MXFP4 = 0x200 };
 /* VV_MXFP4_FRAG: the same OCP MXFP4 values (codes, E8M0 scale bytes 2..252, effective weight value(code) * 2^(e - 127)) in FRAGMENT-MAJOR order, for the
  * 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding occurs), fp32
@@ -76,6 +77,13 @@ enum { VV_MXFP4_FRAG = 5 };
  * for every matrix that has a copy; a matrix the form cannot take (N % 16, K % 128) keeps f_* = NULL and the bf16 row-major fallback.  The
  * prefill and the m <= 2 calls are unchanged.  No bf16 fragment copy may sit in f_* under this bit. */
 enum { VV_WQ_FRAG4 = 0x400 };
+/* A LEAN MXFP4 LLM (vv_llm with VV_WQ_MXFP4): every layer's five bf16 pointers (wqkv, wo, wgate, wup, wdown) are NULL beside present companions
+ * (q_*.q and q_*.scale) - no descriptor bit, the NULL pointers say it; all five of all layers or none (a mix is VV_E_ARG).  hidden, inter and
+ * heads * head_dim must be multiples of 128 and the qkv width a multiple of 16 (what VV_LIN_W_MXGEMM takes).  vv_llm_forward and
+ * vv_llm_prefill_packed then run every non-decode pass of R >= 3 rows as the prefill (activations cast to bf16 once per GEMM) on
+ * VV_LIN_W_MXGEMM; R <= 2 streams the companions as ever; a decode pass (cache_rows == NULL) of 3..8 rows runs on the VV_MXFP4_FRAG copies under
+ * VV_WQ_FRAG4.  A pass that would need a matrix that is not resident - a 3..8-row decode pass without those copies, a 9..16-row decode pass -
+ * returns VV_E_UNSUPPORTED naming the lean mode before anything is launched.  vv_llm_ws_bytes counts the bf16 staging buffer from R = 3 on. */
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
@@ -88,8 +96,15 @@ enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
  * VV_LIN_PACKED: the call belongs to a packed prompt prefill (hundreds to thousands of rows).  With bf16 weights, VV_LIN_X_BF16, no prologue,
  * n % 128 == 0, k % 64 == 0, ldx % 8 == 0, 16-byte aligned operands, an epilogue of bias / residual / VV_ACT_SWIGLU (+ VV_LIN_OUT_BF16) and
  * m >= vv_tune("gemm_packed_rows") (0 = never) it runs on the LDS-DMA tile GEMM of csrc/vv_gemm_packed.hip; any other call routes exactly as
- * without the flag */
-enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8, VV_LIN_PACKED = 16 };
+ * without the flag
+ * VV_LIN_W_MXGEMM: the matrix-core GEMM on MXFP4 CODES (csrc/vv_gemm_mx.hip) - w / w2 and wscale / w2scale are a VV_MXFP4 companion (wdt ==
+ * VV_MXFP4, the layout above, any row and K padding it carries), x is bf16 (VV_LIN_X_BF16, no prologue), m >= 3, n % 16 == 0, k % 128 == 0, the
+ * epilogue is bias / residual (its own array or out) / VV_ACT_SWIGLU with w2 (+ VV_LIN_OUT_BF16), no gate.  Codes, scale bytes, x, out, bias and
+ * res 16-byte aligned, ldx % 8 == 0, ldo % 4 == 0, ldres % 4 == 0.  The codes are decoded in registers; no bf16 copy of the matrix is read.  No
+ * atomics and one fixed K order: a row's result does not depend on the other rows of the call, bit for bit.  Any other call with the bit (another
+ * wdt, fp32 x, a prologue, m < 3, n % 16, k % 128, missing scales, a misaligned operand) returns VV_E_UNSUPPORTED from vv_linear and
+ * vv_linear_route alike, nothing launched; every VV_MXFP4 / VV_MXFP4_FRAG call without the bit is taken or refused exactly as before */
+enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8, VV_LIN_PACKED = 16, VV_LIN_W_MXGEMM = 32 };
 
 const char* vv_last_error(void);
 int vv_abi_version(void);
@@ -142,7 +157,8 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
  * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>", or "gemm_packed<dual=0,obf=0>" for
- * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16); "skinny" or "gemm_f32"; and for the
+ * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call; "skinny" or
+ * "gemm_f32"; and for the
  * m <= 8 family (fp8, NF4 and MXFP4 weights included) the kernel itself:
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)

@@ -18,7 +18,7 @@ VV_WQ_MXFP4 = 0x200    # likewise: the companions hold OCP MXFP4 (e2m1 codes, E8
 VV_WQ_FRAG4 = 0x400    # next to VV_WQ_MXFP4 on vv_llm / vv_head: the layers' f_* copies hold the VV_MXFP4_FRAG form (codes, then scale bytes)
 PRO_NONE, PRO_RMSNORM, PRO_SILU = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SWIGLU = 0, 1, 2
-LIN_X_BF16, LIN_OUT_BF16, LIN_W_REUSED, LIN_W_FRAG, LIN_PACKED = 1, 2, 4, 8, 16
+LIN_X_BF16, LIN_OUT_BF16, LIN_W_REUSED, LIN_W_FRAG, LIN_PACKED, LIN_W_MXGEMM = 1, 2, 4, 8, 16, 32
 VV_MAX_STAGES = 8
 KVQ_DERIVE_SCALES = 1  # vv_kv_quantize flags
 

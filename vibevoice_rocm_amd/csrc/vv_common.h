@@ -94,6 +94,11 @@ int vv_launch_gemm_packed(const vv_lin_args& a, hipStream_t s);
 int vv_gemm_packed_route_name(const vv_lin_args& a, char* name, int cap);
 void vv_gemm_packed_set_rows(int rows);                          // tuning hook "gemm_packed_rows" (0 = never, < 0 = the default)
 int vv_gemm_packed_init();
+// vv_gemm_mx.hip: the matrix-core GEMM on VV_MXFP4 codes (gemm_mx_kernel<dual, obf>), taken by VV_LIN_W_MXGEMM calls alone.  vv_gemm_mx_check is the
+// only copy of what it takes (no launch, no pointer followed): 0, or VV_E_UNSUPPORTED with the reason; the launch of a checked call returns 0
+int vv_gemm_mx_check(const vv_lin_args& a);
+int vv_launch_gemm_mx(const vv_lin_args& a, hipStream_t s);
+int vv_gemm_mx_route_name(const vv_lin_args& a, char* name, int cap);
 // vv_attn_decode.hip: bf16 KV cache, head_dim 128; part / tickets = split-key workspace ([R, heads, nsplit, 130] floats, [R, heads] zeroed ints) or null
 // part_cap: splits the partials workspace has room for (>= nsplit); the grouped kernel may use more splits than the per-head kernel's nsplit
 int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float2* rope, const int* lens, float* out,

@@ -803,6 +803,7 @@ static int linear_check_args(const vv_lin_args* a) {
       (a->m < 3 || a->m > 8 || a->n % 16 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_ARG, "vv_linear: fp8 VV_LIN_W_FRAG weights need 3..8 rows, n %% 16 == 0, k %% 64 == 0 and wscale (w2scale) (m=%d n=%d k=%d)",
                         a->m, a->n, a->k);
+  if (a->flags & VV_LIN_W_MXGEMM) return vv_gemm_mx_check(*a);      // the GEMM on MXFP4 codes: its own unit says what it takes, every other rule below is for calls without the bit
   if (a->wdt == VV_NF4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights exist for the streaming GEMV alone: m <= 2, k %% 64 == 0, wscale (w2scale), "
                         "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
@@ -839,6 +840,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     else if (fam != LIN_FAM_GEMV) snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : "gemm_f32");
   }
   else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  if (a->flags & VV_LIN_W_MXGEMM) { vv_gemm_mx_route_name(*a, name, cap); return 0; }      // linear_check_args has asked vv_gemm_mx_check
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
     VV_TRY(gemv_decide(*a, &g));
@@ -858,7 +860,8 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
     if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
     (void)hipEventRecord(pr.e0, s);
   }
-  if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
+  if (a->flags & VV_LIN_W_MXGEMM) rc = vv_launch_gemm_mx(*a, s);      // wdt == VV_MXFP4 and everything else the kernel needs: linear_check_args
+  else if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
   else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4 || a->wdt == VV_MXFP4_FRAG) {   // weight-only fp8 / NF4 / MXFP4: the rows or a streaming GEMV, or refused (gemv_decide)
     gemv_route g;
@@ -880,6 +883,17 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 // such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
                  const vv_w8* q1, const vv_w8* q2, bool frag4) {
+  // a lean MXFP4 model's matrix (vv_hip.h: w == NULL, for a SwiGLU pair w2 too): its VV_MXFP4_FRAG copy serves the call or nothing does
+  vv_lin_args lean_a;
+  const bool lean = a && !a->w && a->x && a->out;
+  if (lean) {
+    const bool dual = a->act == VV_ACT_SWIGLU;
+    if (!frag4 || !f1 || (dual && !f2) || a->m < 3 || a->m > 8 || a->wdt != VV_BF16)
+      return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean mxfp4 model (no bf16 matrix is resident): m=%d rows need the matrix's VV_MXFP4_FRAG copy and 3..8 rows", a->m);
+    lean_a = *a;
+    lean_a.w = f1; lean_a.w2 = dual ? f2 : nullptr;
+    a = &lean_a;
+  }
   const bool wide_ok = a && !frag4 && !(q1 && q1->q) && f1 && (!a->w2 || f2);
   if (a && a->wdt == VV_BF16 && a->m > 2 && (a->m <= 8 || (a->m <= 16 && wide_ok)) && a->x && a->w && a->out) {
     vv_lin_args b = *a;
@@ -910,6 +924,8 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
     if (rc < 0) return rc;
     if (rc == 1) { VV_CHECK_LAUNCH("vv_linear(rows)"); return 0; }
   }
+  if (lean)       // w stands in for a matrix that does not exist: no row-major route may read it
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean mxfp4 model (no bf16 matrix is resident): the MXFP4 rows kernel does not take m=%d n=%d k=%d", a->m, a->n, a->k);
   if (a && a->wdt == VV_BF16 && a->m > 8 && a->m <= 16 && a->ldx != 0 && !(a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && a->x && a->w && a->out) {
     // 9..16 rows the 16-row GEMV does not take (no bf16 fragment-major copy, a K it does not cover): two passes of 5..8 rows, each on the route
     // the 8-row step takes for this matrix - vv_linear at these row counts would round the activations to bf16 once on the matrix-core GEMM

@@ -74,12 +74,37 @@ static size_t rows_tickets(const vv_llm* m) {
   return vv_gemv_rows_tickets(n > m->hidden ? n : m->hidden);
 }
 
+// A lean MXFP4 LLM (vv_hip.h): the layers' bf16 pointers are NULL beside present MXFP4 companions.  1 = lean, 0 = every matrix resident, < 0 = a
+// descriptor that is neither (VV_E_ARG) or a lean one whose shapes the GEMM on the codes does not take (VV_E_UNSUPPORTED).  Host only
+static int llm_lean(const char* who, const vv_llm* m) {
+  if (!m->layer || m->layers <= 0) return 0;
+  int nul = 0;
+  for (int l = 0; l < m->layers; ++l) {
+    const vv_llm_layer& L = m->layer[l];
+    nul += !L.wqkv + !L.wo + !L.wgate + !L.wup + !L.wdown;
+  }
+  if (!nul) return 0;
+  if (nul != 5 * m->layers) return vv_set_error(VV_E_ARG, "%s: %d of %d LLM matrices are NULL: a lean mxfp4 model has none of them, any other model all", who, nul, 5 * m->layers);
+  if (!(m->wdt & VV_WQ_MXFP4) || (m->wdt & 0xff) != VV_BF16) return vv_set_error(VV_E_ARG, "%s: NULL LLM matrices (the lean mode) need VV_BF16 | VV_WQ_MXFP4", who);
+  for (int l = 0; l < m->layers; ++l) {
+    const vv_llm_layer& L = m->layer[l];
+    for (const vv_w8* q : {&L.q_qkv, &L.q_o, &L.q_gate, &L.q_up, &L.q_down})
+      if (!q->q || !q->scale) return vv_set_error(VV_E_ARG, "%s: lean mxfp4 model: layer %d has neither a bf16 matrix nor an MXFP4 companion", who, l);
+  }
+  const int qd = m->heads * m->head_dim, qkvd = (m->heads + 2 * m->kv_heads) * m->head_dim;
+  if (m->hidden % 128 || m->inter % 128 || qd % 128 || qkvd % 16)
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: lean mxfp4 model: hidden=%d inter=%d q width=%d must be multiples of 128 and the qkv width %d of 16 "
+                        "(the GEMM on the codes takes n %% 16 == 0, k %% 128 == 0)", who, m->hidden, m->inter, qd, qkvd);
+  return 1;
+}
+
 extern "C" size_t vv_llm_ws_bytes(const vv_llm* m, int R) {
   if (!m || R <= 0) return 0;
+  const bool stage3 = R >= 3 && R < VV_PREFILL_ROWS && llm_lean("vv_llm_ws_bytes", m) == 1;      // a lean model casts to bf16 from 3 rows on
   const size_t qkv = (size_t)(m->heads + 2 * m->kv_heads) * m->head_dim;
   const size_t widest = (size_t)(m->inter > m->hidden ? m->inter : m->hidden);
   return al((size_t)R * m->hidden) + al((size_t)R * qkv) + al((size_t)R * m->heads * m->head_dim) + al((size_t)R * m->inter) +
-         al((size_t)R * m->head_dim) + (R >= VV_PREFILL_ROWS ? al((size_t)R * widest / 2 + 64) : 0) +
+         al((size_t)R * m->head_dim) + (R >= VV_PREFILL_ROWS || stage3 ? al((size_t)R * widest / 2 + 64) : 0) +
          al(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (m->head_dim + 2)) + al(att_rows(R) * m->heads) +                   // split-key decode attention
          ((R > 2 && R <= 16) ? al(rows_part_floats(m)) + al(rows_tickets(m)) : 0);                                           // split-K partials of the 3..8-row and the 9..16-row GEMV
 }
@@ -92,9 +117,25 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   if (R <= 0) return vv_set_error(VV_E_ARG, "%s: R=%d", who, R);
   if (kv->layers != m->layers || kv->kv_heads != m->kv_heads || kv->head_dim != m->head_dim)
     return vv_set_error(VV_E_ARG, "%s: kv cache shape does not match the model", who);
+  const int lean_rc = llm_lean(who, m);
+  if (lean_rc < 0) return lean_rc;
+  const bool lean = lean_rc == 1;
   VV_WQ_STRIP(vv_llm, m);
   hipStream_t s = (hipStream_t)stream;
   const int H = m->hidden, d = m->head_dim, qd = m->heads * d, qkvd = (m->heads + 2 * m->kv_heads) * d;
+  const bool decode = (cache_rows == nullptr && R <= kv->rows);
+  if (lean && decode && R > 2 && R < VV_PREFILL_ROWS) {
+    // lean: no bf16 matrix is resident, so a 3..8-row decode pass runs on the VV_MXFP4_FRAG copies or not at all, and 9..16 rows not at all -
+    // said here, before the first launch
+    bool copies = frag4 && R <= 8;
+    for (int l = 0; copies && l < m->layers; ++l) {
+      const vv_llm_layer& L = m->layer[l];
+      copies = L.f_qkv && L.f_o && L.f_gate && L.f_up && L.f_down;
+    }
+    if (!copies)
+      return vv_set_error(VV_E_UNSUPPORTED, "%s: lean mxfp4 model (no bf16 LLM matrices): a decode pass of %d rows needs the VV_MXFP4_FRAG copies of every layer "
+                          "(VV_WQ_FRAG4, mxfp4_row_batch=True) and 3..8 rows; 9..16 rows need bf16 copies, which the lean mode does not keep", who, R);
+  }
   Carver c(ws);
   float* h = c.take((size_t)R * H);
   float* qkv = c.take((size_t)R * qkvd);
@@ -105,12 +146,12 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   const float* hin = x;
   int64_t ldh = ldx;
   VV_TRY(vv_rope_table(lens, m->inv_freq, R, d, rope, stream));
-  const bool prefill = (R >= VV_PREFILL_ROWS) && m->wdt == VV_BF16 && H % 16 == 0 && m->inter % 16 == 0 && qd % 16 == 0;
+  // a lean model casts from 3 rows on in every non-decode pass: its matrices exist as codes alone, which the GEMM of vv_gemm_mx.hip reads
+  const bool prefill = (R >= VV_PREFILL_ROWS || (lean && R > 2 && !decode)) && m->wdt == VV_BF16 && H % 16 == 0 && m->inter % 16 == 0 && qd % 16 == 0;
   void* xb = prefill ? (void*)c.take((size_t)R * (m->inter > H ? m->inter : H) / 2 + 64) : nullptr;
   float* att_part = c.take(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (d + 2));
   int* att_tickets = reinterpret_cast<int*>(c.take(att_rows(R) * m->heads));
   // contexts beyond ~1K keys: one block per (row, q head) would pull all of its K / V through a single CU (~95 GB/s: 8 us at S = 3000)
-  const bool decode = (cache_rows == nullptr && R <= kv->rows);
   // 9..16 rows: two row tiles of the same GEMV, when every layer has the bf16 fragment-major copies (no VV_WQ_FRAG4, whose copies are MXFP4 codes)
   bool rows16 = decode && R > 8 && R <= 16 && m->wdt == VV_BF16 && !frag4;
   for (int l = 0; rows16 && l < m->layers; ++l) {
@@ -148,6 +189,14 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
     // or, under VV_WQ_FRAG4, the VV_MXFP4_FRAG form of the MXFP4 companions
     return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr, frag4);
   };
+  // lean, outside the rows kernel: the matrix is its MXFP4 companion - under VV_LIN_W_MXGEMM in the prefill branch, as the streaming GEMV's
+  // operand at 1..2 rows (what use_w8 does for a model that has both)
+  auto lean_w = [&](vv_lin_args& a, const vv_w8& q, const vv_w8* q2 = nullptr) {
+    if (!lean || rows8) return;
+    a.w = q.q; a.wscale = q.scale; a.wdt = VV_MXFP4;
+    if (q2) { a.w2 = q2->q; a.w2scale = q2->scale; }
+    if (prefill) a.flags |= VV_LIN_W_MXGEMM;
+  };
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
     vv_lin_args a;
@@ -160,6 +209,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.ln1; a.eps = m->rms_eps; a.bias = L.bqkv;
       if (!rows8) use_w8(a, wq, L.q_qkv);
     }
+    lean_w(a, L.q_qkv);
     VV_TRY(lin(a, L.f_qkv, nullptr, &L.q_qkv));
     if (decode) {
       VV_TRY(vv_attn_decode_ws(qkv, qkvd, R, m->heads, kv, l, rope, lens, att, qd, att_part, att_tickets, att_split, VV_ATT_PART_SPLITS, stream));   // decode: RoPE + append fused
@@ -176,6 +226,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
       if (!rows8) use_w8(a, wq, L.q_o);
     }
     a.res = hin; a.ldres = ldh;
+    lean_w(a, L.q_o);
     VV_TRY(lin(a, L.f_o, nullptr, &L.q_o));
     hin = h; ldh = H;
     if (prefill) {
@@ -191,6 +242,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
     if (prefill) {            // the SwiGLU output is handed to the down projection in bf16: no separate cast pass
       a.out = reinterpret_cast<float*>(xb2); a.ldo = m->inter; a.flags |= VV_LIN_OUT_BF16;
     }
+    lean_w(a, L.q_gate, &L.q_up);
     VV_TRY(lin(a, L.f_gate, L.f_up, &L.q_gate, &L.q_up));
     if (prefill) {
       a = lin_base((const float*)xb2, m->inter, R, L.wdown, H, m->inter, m->wdt, h, H);
@@ -200,6 +252,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
       if (!rows8) use_w8(a, wq, L.q_down);
     }
     a.res = h; a.ldres = H;
+    lean_w(a, L.q_down);
     VV_TRY(lin(a, L.f_down, nullptr, &L.q_down));
   }
   if (!out) return 0;       // the caller runs the final norm itself (vv_llm_tail: norm + logits + token + bookkeeping in one launch)

@@ -226,10 +226,22 @@ class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
     def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None,
-                 prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False):
+                 prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False, mxfp4_lean: bool = False):
         """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
         are imported as they are (vv_nf4_import) and need quant="nf4".  mxfp4_row_batch (quant="mxfp4" only): the 3..8-row paths stream the
-        MXFP4 companions in fragment-major form (VV_WQ_FRAG4 on the LLM's and the head's descriptors; ensure_frag builds the copies)."""
+        MXFP4 companions in fragment-major form (VV_WQ_FRAG4 on the LLM's and the head's descriptors; ensure_frag builds the copies).
+        mxfp4_lean (quant="mxfp4" only): the LLM's matrices exist as MXFP4 codes alone - no bf16 copy is uploaded, their descriptor pointers are
+        NULL and every pass of 3 or more prompt rows runs the GEMM on the codes (csrc/vv_gemm_mx.hip; lean_report lists what was dropped).
+        Kept in bf16, because something still reads them in that form:
+          * matrices without a companion (embeddings / lm_head, the head's projections and adaLN, connectors, the tokenizers' convs);
+          * a companion-set matrix whose shape the GEMM refuses (N % 16, K % 128) - then none of the LLM's is dropped, a model is lean as a whole;
+          * the diffusion head's gate / up / down: vv_head_forward and the row-batched samplers read them row-major at more than two rows (with
+            mxfp4_row_batch the pair at K > MXFP4_ROWS_MOD_K has no fragment copy and runs on the bf16 matrix, ensure_frag);
+          * the tokenizers' one-row-stage FFN matrices: the same blocks run as GEMMs whenever a pass brings more than two rows."""
+        if mxfp4_lean and quant != "mxfp4":
+            raise ValueError(f"mxfp4_lean=True drops the bf16 copies of the MXFP4 matrices: it needs weight_quant='mxfp4', not {quant!r}")
+        self.mxfp4_lean = bool(mxfp4_lean)
+        self._lean_dropped: List[Dict[str, object]] = []      # lean_report(): {"name", "n", "k", "bytes"} per matrix that has no bf16 copy
         if mxfp4_row_batch and quant != "mxfp4":
             raise ValueError(f"mxfp4_row_batch=True serves the MXFP4 companions on the row-batched path: it needs weight_quant='mxfp4', not {quant!r}")
         if mxfp4_row_batch and cfg.hidden > MXFP4_ROWS_MAX_HIDDEN:
@@ -301,13 +313,13 @@ class DeviceWeights:
         from .bnb import import_nf4
         return import_nf4([r], self.device, companion=False)[0].view(r.shape)
 
-    def _mat_q_keys(self, keys: List[str], quantise: bool):
+    def _mat_q_keys(self, keys: List[str], quantise: bool, lean: Optional[str] = None):
         """_mat_q of the named matrices stacked along N (one key, or q / k / v for the fused [q|k|v] matrix).  Matrices that a pre-quantized
         checkpoint holds in bnb form are imported as they are - with the VV_NF4 companion when `quantise` and every part fits it exactly; a
         companion-set matrix that such a checkpoint holds unquantized runs bf16, without a companion (it is not quantised on the fly)."""
         if not self._pre:
             t = self._sd[keys[0]] if len(keys) == 1 else torch.cat([self._sd[k] for k in keys], dim=0)
-            return self._mat_q(t, quantise)
+            return self._mat_q(t, quantise, lean)
         w8 = L.W8()
         parts = [self._pre.get(k) for k in keys]
         if all(p is not None for p in parts):
@@ -321,11 +333,12 @@ class DeviceWeights:
         t = torch.cat([self._w(k).to(self.device, self.wdtype) for k in keys], dim=0)
         return self._mat(t), w8
 
-    def _mat_q(self, t: torch.Tensor, quantise: bool):
+    def _mat_q(self, t: torch.Tensor, quantise: bool, lean: Optional[str] = None):
         """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
         mode it holds the effective weights bf16(table[code] * absmax) and the companion the packed codes and block scales (pack_nf4).
         An NF4 matrix with K % 64 != 0 gets no companion.  In mxfp4 mode the bf16 copy holds value(code) * 2^(e - 127) (exact) and the
-        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion."""
+        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion.  lean (a name for
+        lean_report, mxfp4 only): the bf16 copy is not made - (None, companion); the effective matrix lives while the codes are packed."""
         w8 = L.W8()
         if self.quant == "nf4" and quantise and t.shape[1] % NF4_BLOCK == 0:
             codes, absmax, eff = quantize_nf4(t.to(device=self.device, dtype=torch.bfloat16))    # the bf16 weight, widened
@@ -340,6 +353,10 @@ class DeviceWeights:
             packed, sb = self._aligned(packed), self._aligned(sb)
             self._keep += [packed, sb]
             w8.q, w8.scale = L.ptr(packed), L.ptr(sb)          # vv_w8.scale carries the address of the scale BYTES (vv_hip.h, VV_MXFP4)
+            if lean is not None:
+                n, k = t.shape
+                self._lean_dropped.append({"name": lean, "n": int(n), "k": int(k), "bytes": 2 * int(n) * int(k)})
+                return None, w8
             return self._mat(eff), w8
         if not (quantise and self.quant == "fp8"):
             return self._mat(t), w8
@@ -507,6 +524,11 @@ class DeviceWeights:
         self._keep.append(t)
         return t
 
+    def lean_report(self) -> List[Dict[str, object]]:
+        """The matrices an mxfp4_lean model holds as MXFP4 codes alone: [{"name", "n", "k", "bytes"}], bytes = 2 n k = the bf16 copy that was not
+        uploaded (nbytes() of the same model without mxfp4_lean is larger by exactly their sum).  Empty without the mode."""
+        return [dict(d) for d in self._lean_dropped]
+
     def nbytes(self) -> int:
         ts = [t for t in self._keep if isinstance(t, torch.Tensor)] + list(self._frag_state["tensors"])
         return sum(t.numel() * t.element_size() for t in ts)
@@ -519,11 +541,15 @@ class DeviceWeights:
         has_head = "lm_head.weight" in sd or "lm_head.weight" in self._pre
         self.lm_head = self.embed if (cfg.tie or not has_head) else self._mat(self._w("lm_head.weight"))
         layers = (L.LlmLayer * cfg.layers)()
+        # lean: all of the LLM's matrices or none (csrc/vv_model.hip takes a model whose five pointers are NULL in every layer) - every one of
+        # them must be a shape the GEMM on the codes takes: N % 16 == 0, K % 128 == 0
+        qd, qkvd = cfg.heads * cfg.head_dim, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim
+        lean = self.mxfp4_lean and not (cfg.hidden % 128 or cfg.inter % 128 or qd % 128 or qkvd % 16)
         for l in range(cfg.layers):
             q = f"{p}layers.{l}."
             qz = self.quant is not None
             lay = layers[l]
-            wqkv, lay.q_qkv = self._mat_q_keys([q + f"self_attn.{n}_proj.weight" for n in "qkv"], qz)
+            wqkv, lay.q_qkv = self._mat_q_keys([q + f"self_attn.{n}_proj.weight" for n in "qkv"], qz, q + "self_attn.qkv_proj.weight" if lean else None)
             bqkv = self._vec(torch.cat([sd[q + "self_attn.q_proj.bias"], sd[q + "self_attn.k_proj.bias"],
                                         sd[q + "self_attn.v_proj.bias"]], dim=0))
             lay.ln1 = L.ptr(self._vec(sd[q + "input_layernorm.weight"]))
@@ -531,7 +557,7 @@ class DeviceWeights:
             lay.wqkv, lay.bqkv = L.ptr(wqkv), L.ptr(bqkv)
             for field, qf, key in (("wo", "q_o", "self_attn.o_proj.weight"), ("wgate", "q_gate", "mlp.gate_proj.weight"),
                                    ("wup", "q_up", "mlp.up_proj.weight"), ("wdown", "q_down", "mlp.down_proj.weight")):
-                wm, w8 = self._mat_q_keys([q + key], qz)
+                wm, w8 = self._mat_q_keys([q + key], qz, q + key if lean else None)
                 setattr(lay, field, L.ptr(wm))
                 setattr(lay, qf, w8)
         # Qwen2RotaryEmbedding.compute_default_rope_parameters, same fp32 ops as the reference stack
