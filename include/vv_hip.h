@@ -485,6 +485,39 @@ int vv_head_sample_batch_sde(const vv_head* h, const float* cond, int64_t ld_con
 int vv_head_sample_batch_cfg(const vv_head* h, const float* cond, int64_t ld_cond, const float* noise, int64_t ld_noise, const float* temb,
                              const vv_dpm_coef* coef, int n_steps, const float* cfg_rows /* device, [B] */, float* latent_out, int64_t ld_latent,
                              int B, void* ws, const float* sde_noise /* NULL: ODE */, int64_t ld_sde, vv_stream_t stream);
+/* vv_head_sample_route - the stage kernels a sampler call with these arguments takes, by the decisions the call itself makes (one copy of each
+ * condition, shared with the launch path); nothing is launched and no device pointer is followed (pointers count for NULL and alignment; coef,
+ * a host array, is read for coef[i].cn).  B = 0: vv_head_sample(h, cond, ld_cond, .., temb, coef, n_steps, .., ws, sde ? noise : NULL).
+ * B >= 1: the batched entry points - cfg_rows != NULL vv_head_sample_batch_cfg, else sde != 0 vv_head_sample_batch_sde, else
+ * vv_head_sample_batch; sde != 0 stands for a non-NULL sde_noise with a sufficient ld_sde.  noise and latent_out are taken as given.
+ * name (cap bytes) becomes "pre=<..> mod=<..> step=<..>":
+ *   pre   "head_pre<ku=K>"                         head_pre_kernel<K> (cond_dim = 512 K): cond_proj, the bf16 conditioning rows and the solver state
+ *         "linear+add_rows_silu_bf16+head_init<bf16>"   vv_linear, vv_add_rows_silu_bf16, head_init_kernel<bf16_t>: the batched samplers always, the
+ *                                                  single one where head_pre does not cover the call (cond_dim % 512, n_steps > 128, latent > 256, ..)
+ *         "linear+add_rows_silu+head_init<bf16|f32>"    fp32 conditioning rows (n_steps <= 4, D % 32, fp32 weights) in front of the fused boundary
+ *         "linear+add_rows_silu[_bf16]"            the same in front of the three-launch step (vv_dpm_proj initialises the state)
+ *         "...+head_sde_proj<bf16>"                batched with variance noise: head_sde_proj_kernel maps it into state space before the loop
+ *   mod   "adaln_lds<nst=12>" (D = 1536), "adaln_all<nst=28,nm=1>" (D = 3584): every adaLN matrix in one launch; "linear": one vv_linear each
+ *   step  "boundary<ku=K,sde=S,cfg=C>"             head_boundary_kernel<K, S> (C = 1: head_boundary_cfg_kernel<K, S>), K = ceil(D / 512); S = 1: the
+ *                                                  steps with coef[i].cn != 0 run the SDE instantiation, the others (and every step at S = 0) <K, false>
+ *         "dpm_proj"                               vv_dpm_proj + the FinalLayer vv_linear: fused_g NULL / unaligned, D % 8, D > 4096, or vv_head_sample
+ *                                                  with variance noise or a coef[i].cn != 0
+ * Arguments the sampler refuses return the sampler's error (VV_E_ARG / VV_E_UNSUPPORTED, vv_last_error names the entry point); VV_E_ARG also for
+ * name == NULL, cap <= 0, B < 0 and cfg_rows with B = 0. */
+int vv_head_sample_route(const vv_head* h, const float* cond, int64_t ld_cond, const float* temb, const vv_dpm_coef* coef, int n_steps, int B,
+                         int sde, const float* cfg_rows, const void* ws, char* name, int cap);
+/* vv_head_ws_layout - byte offsets of the regions the samplers carve out of ws, from the carving code they run (B = 0: vv_head_sample; B >= 1
+ * the batched samplers, sde != 0: with variance noise).  off[] in this order, -1 = the form has no such region; returns the number of entries
+ * written (layers + 10, + 5 for B = 0) or an error (VV_E_ARG: NULL h / off, n_steps <= 0, layers > 16, B outside 0..8, sde with B = 0, cap too small):
+ *   c0      fp32 [2 | 2 B rows, D] cond_proj output (not written where head_pre runs)
+ *   c       conditioning rows silu(c0 + temb_i), row (i * 2 B + r); bf16 [rows, D] packed, or fp32 [rows, D] where the route's pre says add_rows_silu
+ *   mod[l]  l < layers: fp32 [rows, 3 D] shift | scale | gate of layer l        modf    fp32 [rows, 2 D] shift | scale of the FinalLayer
+ *   h0, h1  the two hidden-row buffers [2 | 2 B rows, D]: step i's layers work in h(i & 1), its boundary writes h((i + 1) & 1)
+ *   act     [rows, ffn]        Xs, Ms   solver state [P x ; x] and previous x0 prediction, utterance b at b * (D + latent) floats
+ *   NX      SDE, batched: [B][n_steps][D + latent] variance noise in state space, else -1
+ *   B = 0 only - the three-launch form's v [2, latent], x double buffer (2 entries), x0-history double buffer (2 entries)
+ *   end     bytes carved = vv_head_ws_bytes / vv_head_ws_bytes_batch(_sde) */
+int vv_head_ws_layout(const vv_head* h, int n_steps, int B, int sde, int64_t* off, int cap);
 /* The samplers' Gaussian noise drawn on the device, one launch for B utterances: noise[b * ld_noise + e], e < n, is the initial latent (kind 0) and,
  * when sde_noise is given, sde_noise[b * ld_sde + s * n + e] the variance noise of solver step s < n_steps (kind 1 + s) - the buffers
  * vv_head_sample and vv_head_sample_batch(_sde) read.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85)

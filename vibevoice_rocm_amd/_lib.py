@@ -178,6 +178,8 @@ PROTOTYPES = {
     "vv_noise_normal": (C.c_int, [vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vv_head_sample": (C.c_int, [C.POINTER(Head), vp, i64, vp, vp, C.POINTER(DpmCoef), C.c_int, C.c_float, vp, vp, vp, vp]),
     "vv_head_forward": (C.c_int, [C.POINTER(Head), vp, vp, vp, C.c_int, vp, vp, vp]),
+    "vv_head_sample_route": (C.c_int, [C.POINTER(Head), vp, i64, vp, C.POINTER(DpmCoef), C.c_int, C.c_int, C.c_int, vp, vp, C.c_char_p, C.c_int]),
+    "vv_head_ws_layout": (C.c_int, [C.POINTER(Head), C.c_int, C.c_int, C.c_int, C.POINTER(i64), C.c_int]),
     "vv_convnet_ws_bytes": (C.c_size_t, [C.POINTER(ConvNet), i64, C.c_int]),
     "vv_decoder_forward": (C.c_int, [C.POINTER(ConvNet), vp, C.c_int, C.c_float, C.c_float, vp, vp, vp]),
     "vv_encoder_forward": (C.c_int, [C.POINTER(ConvNet), vp, i64, vp, vp, vp]),

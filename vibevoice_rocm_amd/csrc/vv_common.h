@@ -128,6 +128,11 @@ int vv_head_pre_fused(const vv_head* h, const float* cond2, int64_t ld_cond, con
 int vv_launch_connector_pair(const vv_connector* ac, const vv_connector* sem, const float* latent, const float* semfeat, float* out, int64_t ldo, int rows_out,
                              float* ws, hipStream_t s);   // 1 launched, 0 not covered
 int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, float* const* mod, float* modf, hipStream_t s);   // 1 launched, 0 not covered
+// what the three launchers above take, decided once for the launch and for vv_head_sample_route (host only, nothing launched): the kernel's
+// template argument (KU of head_pre_kernel / NST of the adaLN kernel: 12 adaln_lds, 28 adaln_all / KU of head_boundary_kernel), 0 = not covered
+int vv_head_pre_decide(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, int n_steps, const void* c_bf16);
+int vv_head_modulations_decide(const vv_head* h, const void* c_bf16, int rows);
+int vv_head_boundary_decide(const vv_head* h);
 struct vv_conv_ctx_item { float* pad; float* state; int ctx, T, C; const float* dw_w; float* hs; int affine; float scale, bias; };   // dw_w / hs (scatter only): also hs[c] = sum_k<6 dw_w[c, k] * new state[k, c]; affine (gather only): pad = state * scale + bias (the net's input rides along)
 int vv_conv_ctx_batch(const vv_conv_ctx_item* items, int n, int scatter, hipStream_t s);   // scatter 0: pad[0:ctx] <- state; 1: state <- pad[T : T + ctx]
 // vv_conv_hot.hip, row batches: the one-row stage of the conv tokenizers for the 2..8 dialogues of a row batch in one weight pass.  The dialogues' nets are

@@ -627,6 +627,13 @@ bool vv_head_boundary_supported(const vv_head* h) {
   return h->fused_g != nullptr && h->D % 8 == 0 && h->D <= 4096 && ((uintptr_t)h->fused_g % 16 == 0);
 }
 
+// KU of the head_boundary(_cfg)_kernel<KU, SDE> a supported head takes (K = D in chunks of 512, the last one partial), 0 = D outside 1..4096:
+// decided here for the launch and for vv_head_sample_route alike
+int vv_head_boundary_decide(const vv_head* h) {
+  const int ku = (h->D + 511) / 512;
+  return (h->D > 0 && ku <= 8) ? ku : 0;
+}
+
 int vv_head_boundary_fused(const vv_head* h, const float* hrows, int64_t ldh, const float* shift, const float* scale, int64_t ld_mod, float cfg,
                            const vv_dpm_coef* k, float* Xs, float* Ms, float* h_out, int64_t ldh_out, float* latent_out, hipStream_t s) {
   return vv_head_boundary_batch(h, hrows, ldh, shift, scale, ld_mod, cfg, k, Xs, Ms, 0, h_out, ldh_out, latent_out, 0, 1, s);
@@ -641,7 +648,7 @@ int vv_head_boundary_batch(const vv_head* h, const float* hrows, int64_t ldh, co
   a.nx = k->cn != 0.f ? nx : nullptr; a.nx_stride = nx_stride;     // cn == 0 (the ODE solver, the SDE solver's last step): the ODE instantiation
   a.G = h->fused_g; a.h = hrows; a.ldh = ldh; a.shift = shift; a.scale = scale; a.ld_mod = ld_mod; a.eps = h->eps; a.cfg = cfg; a.k = *k;
   a.Xs = Xs; a.Ms = Ms; a.h_out = h_out; a.ldh_out = ldh_out; a.latent_out = latent_out; a.D = h->D; a.latent = h->latent;
-  switch ((h->D + 511) / 512) {
+  switch (vv_head_boundary_decide(h)) {
     case 1: launch_boundary<1>(a, B, s, cfg_rows); break;
     case 2: launch_boundary<2>(a, B, s, cfg_rows); break;
     case 3: launch_boundary<3>(a, B, s, cfg_rows); break;
@@ -810,15 +817,26 @@ int vv_fused_init() {     // before any graph capture
   return 0;
 }
 
-// 1 = launched, 0 = not covered (caller runs one vv_linear per matrix)
-int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, float* const* mod, float* modf, hipStream_t s) {
+// Which kernel serves all adaLN modulations of `rows` bf16 conditioning rows in one launch - 12: adaln_lds_kernel<12> (D = 1536), 28:
+// adaln_all_kernel<28, 1> (D = 3584), 0: none (one vv_linear per matrix).  Host only, no pointer is followed but h->layer; decided here for the
+// launch and for vv_head_sample_route alike
+int vv_head_modulations_decide(const vv_head* h, const void* c_bf16, int rows) {
   const int D = h->D;
   if (h->wdt != VV_BF16 || h->layers > 16 || rows < 1 || ((uintptr_t)c_bf16 % 16) || ((uintptr_t)h->final_adaln % 16)) return 0;
   if (D != 4 * 32 * 12 && D != 4 * 32 * 28) return 0;
+  for (int l = 0; l < h->layers; ++l)
+    if ((uintptr_t)h->layer[l].adaln % 16) return 0;
+  return D == 4 * 32 * 12 ? 12 : 28;
+}
+
+// 1 = launched, 0 = not covered (caller runs one vv_linear per matrix)
+int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, float* const* mod, float* modf, hipStream_t s) {
+  const int D = h->D;
+  const int nst = vv_head_modulations_decide(h, c_bf16, rows);
+  if (!nst) return 0;
   AdaTab tab;
   int total = 0;
   for (int l = 0; l < h->layers; ++l) {
-    if ((uintptr_t)h->layer[l].adaln % 16) return 0;
     tab.w[l] = reinterpret_cast<const bf16_t*>(h->layer[l].adaln); tab.out[l] = mod[l]; tab.nblk[l] = 3 * D / 16; tab.ldo[l] = 3 * D;
     total += tab.nblk[l];
   }
@@ -828,7 +846,7 @@ int vv_head_modulations_fused(const vv_head* h, const void* c_bf16, int rows, fl
   tab.n = f + 1;
   for (int l = tab.n; l < 17; ++l) { tab.w[l] = nullptr; tab.out[l] = nullptr; tab.nblk[l] = 0; tab.ldo[l] = 0; }
   const bf16_t* c = reinterpret_cast<const bf16_t*>(c_bf16);
-  if (D == 4 * 32 * 12) hipLaunchKernelGGL((adaln_lds_kernel<12>), dim3(total < 256 ? total : 256, (rows + 39) / 40), dim3(256), ADA_LDS, s, c, rows, tab, total);
+  if (nst == 12) hipLaunchKernelGGL((adaln_lds_kernel<12>), dim3(total < 256 ? total : 256, (rows + 39) / 40), dim3(256), ADA_LDS, s, c, rows, tab, total);
   else hipLaunchKernelGGL((adaln_all_kernel<28, 1>), dim3(total, (rows + 15) / 16), dim3(256), 0, s, c, rows, D, tab);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vv_set_error(VV_E_HIP, "vv_head_modulations_fused: %s", hipGetErrorString(e));
@@ -859,19 +877,28 @@ int vv_launch_connector_pair(const vv_connector* ac, const vv_connector* sem, co
   return 1;
 }
 
+// KU of the head_pre_kernel<KU> these arguments take (cond_dim = 512 KU), 0 = not covered.  Host only, no pointer is followed; decided here for
+// the launch and for vv_head_sample_route alike
+int vv_head_pre_decide(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, int n_steps, const void* c_bf16) {
+  const int D = h->D, K = h->cond_dim;
+  if (h->wdt != VV_BF16 || K <= 0 || K % 512 || K / 512 > 7 || D % 2 || n_steps > 128 || h->latent > 256) return 0;
+  auto a16 = [](const void* q) { return q && ((uintptr_t)q % 16) == 0; };
+  if (!a16(h->cond_proj) || !a16(cond2) || (ld_cond % 4) || !a16(temb) || !a16(c_bf16) || !h->noisy_proj) return 0;
+  return K / 512;
+}
+
 // 1 = launched (cond_proj + silu row expansion + solver-state init), 0 = not covered
 int vv_head_pre_fused(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, int n_steps, void* c_bf16, const float* noise,
                       float* Xs, float* Ms, float* h0, int64_t ldh, hipStream_t s) {
   const int D = h->D, K = h->cond_dim;
-  if (h->wdt != VV_BF16 || K % 512 || K / 512 > 7 || D % 2 || n_steps > 128 || h->latent > 256) return 0;
-  auto a16 = [](const void* q) { return q && ((uintptr_t)q % 16) == 0; };
-  if (!a16(h->cond_proj) || !a16(cond2) || (ld_cond % 4) || !a16(temb) || !a16(c_bf16) || !h->noisy_proj) return 0;
+  const int ku = vv_head_pre_decide(h, cond2, ld_cond, temb, n_steps, c_bf16);
+  if (!ku) return 0;
   HeadPreArgs a;
   a.Wc = (const bf16_t*)h->cond_proj; a.cond = cond2; a.ld_cond = ld_cond; a.K = K; a.temb = temb; a.n_steps = n_steps; a.c_out = (bf16_t*)c_bf16;
   a.P = (const bf16_t*)h->noisy_proj; a.noise = noise; a.D = D; a.latent = h->latent; a.Xs = Xs; a.Ms = Ms; a.h0 = h0; a.ldh = ldh;
   a.gemv_blocks = 192;
   const int init_blocks = (D + h->latent + 255) / 256;
-  switch (K / 512) {
+  switch (ku) {
 #define VV_HP(KU) case KU: hipLaunchKernelGGL((head_pre_kernel<KU>), dim3(a.gemv_blocks + init_blocks), dim3(256), 0, s, a); break;
     VV_HP(1) VV_HP(2) VV_HP(3) VV_HP(4) VV_HP(5) VV_HP(6) VV_HP(7)
 #undef VV_HP

@@ -279,14 +279,68 @@ extern "C" int vv_llm_prefill_packed(const vv_llm* m, const vv_kv* kv, const flo
 // ---------------------------------------------------------------------------------------------------------------
 // diffusion head + DPM-Solver++ sampling
 // ---------------------------------------------------------------------------------------------------------------
+// ---- the samplers' workspace and stage choice: one copy each, for the launch path and for vv_head_ws_layout / vv_head_sample_route ----
+// byte offsets of the regions a sampler carves out of its workspace; none = the form has no such region
+struct HeadWs {
+  static constexpr size_t none = ~(size_t)0;
+  size_t c0, c, mod[16], modf, hb[2], act, Xs, Ms, NX, v, xb[2], mb[2], rpart, rtick, end;
+  size_t rpart_n, rtick_n;       // floats / ints of the rows GEMV's split-K partials and tickets (batched form)
+};
+struct OffCarver {               // Carver on offsets
+  size_t o = 0;
+  size_t take(size_t n_floats) { const size_t r = o; o += al(n_floats); return r; }
+};
+
+// vv_head_sample (h with the companion flags stripped)
+static HeadWs head_carve_single(const vv_head* h, int n_steps) {
+  const size_t D = h->D, R = 2 * (size_t)n_steps > 8 ? 2 * (size_t)n_steps : 8;
+  HeadWs o;
+  OffCarver cv;
+  o.c0 = cv.take(8 * D);
+  o.c = cv.take(R * D);
+  for (int l = 0; l < 16; ++l) o.mod[l] = l < h->layers ? cv.take(R * 3 * D) : HeadWs::none;
+  o.modf = cv.take(R * 2 * D);
+  o.hb[0] = cv.take(8 * D);
+  o.act = cv.take(8 * (size_t)h->ffn);
+  o.v = cv.take(8 * (size_t)h->latent);
+  o.xb[0] = cv.take(h->latent); o.xb[1] = cv.take(h->latent);
+  o.mb[0] = cv.take(h->latent); o.mb[1] = cv.take(h->latent);
+  o.hb[1] = cv.take(8 * D);
+  o.Xs = cv.take(D + (size_t)h->latent);
+  o.Ms = cv.take(D + (size_t)h->latent);
+  o.NX = o.rpart = o.rtick = HeadWs::none; o.rpart_n = o.rtick_n = 0;
+  o.end = cv.o;
+  return o;
+}
+
+// vv_head_sample_batch(_sde / _cfg): rows [2 B] where the single-utterance form has 2; NX (SDE) carved last, so the ODE layout is a prefix
+static HeadWs head_carve_batch(const vv_head* h, int n_steps, int B, bool sde) {
+  const size_t D = h->D, R = (size_t)2 * B * n_steps, sst = D + (size_t)h->latent;
+  const size_t HR = B <= 4 ? 8 : (size_t)2 * B;          // hidden / act / c0 rows: 8 as ever up to 4 utterances, 2 B beyond
+  HeadWs o;
+  OffCarver cv;
+  o.c0 = cv.take(HR * D);
+  o.c = cv.take(R * D);
+  for (int l = 0; l < 16; ++l) o.mod[l] = l < h->layers ? cv.take(R * 3 * D) : HeadWs::none;
+  o.modf = cv.take(R * 2 * D);
+  o.hb[0] = cv.take(HR * D); o.hb[1] = cv.take(HR * D);
+  o.act = cv.take(HR * (size_t)h->ffn);
+  o.Xs = cv.take((size_t)B * sst);
+  o.Ms = cv.take((size_t)B * sst);
+  o.rpart_n = vv_gemv_rows_part_floats(h->D, 0); o.rtick_n = vv_gemv_rows_tickets(h->ffn);
+  o.rpart = cv.take(o.rpart_n);
+  o.rtick = cv.take(o.rtick_n);
+  o.NX = sde ? cv.take((size_t)B * n_steps * sst) : HeadWs::none;
+  o.v = o.xb[0] = o.xb[1] = o.mb[0] = o.mb[1] = HeadWs::none;
+  o.end = cv.o;
+  return o;
+}
+
 extern "C" size_t vv_head_ws_bytes(const vv_head* h, int n_steps) {
   if (!h || n_steps <= 0) return 0;
+  if (h->layers < 0 || h->layers > 16) return 0;
   VV_WQ_STRIP(vv_head, h);
-  const size_t R = 2 * (size_t)n_steps > 8 ? 2 * (size_t)n_steps : 8;
-  const size_t D = h->D;
-  return al(8 * D) /*c0*/ + al(R * D) /*c*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + al(8 * D) /*hcur*/ +
-         al(8 * (size_t)h->ffn) + al(8 * (size_t)h->latent) /*v*/ + 4 * al(h->latent) /*x, x0 history: double-buffered*/ +
-         al(8 * D) /*second hidden-row buffer*/ + 2 * al(D + (size_t)h->latent) /*fused solver state X, M*/;
+  return head_carve_single(h, n_steps).end;
 }
 
 // shared body: rows R (<= 8), modulation tables mod[l] [*, 3D] / modf [*, 2D] with row offset `mrow`
@@ -361,36 +415,134 @@ extern "C" int vv_head_forward(const vv_head* h, const float* x, const float* te
   return head_body(h, wq, x, h->latent, R, mod, modf, 0, hcur, act, v, stream);
 }
 
+// ---- the samplers' stage choice: one copy, for the launch path and for vv_head_sample_route ----
+// the stage kernels a sampler call takes
+struct HeadRoute {
+  int B;           // 0: vv_head_sample
+  int pre_ku;      // head_pre_kernel<KU>, 0: vv_linear + vv_add_rows_silu(_bf16) (+ head_init_kernel where the fused boundary follows)
+  bool cb;         // conditioning rows c in bf16
+  int mod_nst;     // 12: adaln_lds_kernel<12>, 28: adaln_all_kernel<28, 1>, 0: one vv_linear per adaLN matrix
+  int step_ku;     // head_boundary(_cfg)_kernel<KU, SDE>, 0: the three-launch form (vv_dpm_proj + the FinalLayer vv_linear)
+  bool sde_proj;   // head_sde_proj_kernel in front of the loop (batched form with variance noise)
+  bool sde;        // steps with coef[i].cn != 0 run the SDE instantiation of the boundary
+  bool cfg;        // head_boundary_cfg_kernel
+  bool f32;        // fp32 weights (head_init_kernel<float>)
+};
+
+// vv_head_sample's refusals and choices (noise and latent_out are the caller's to check).  0, or the call's error
+static int head_single_decide(const vv_head* h, const float* cond2, int64_t ld_cond, const float* temb, const vv_dpm_coef* coef, int n_steps,
+                              bool sde_given, const void* ws, HeadRoute* r) {
+  if (!h || !cond2 || !temb || !coef || !ws) return vv_set_error(VV_E_ARG, "vv_head_sample: null pointer");
+  if (n_steps <= 0 || h->layers > 16) return vv_set_error(VV_E_ARG, "vv_head_sample: bad n_steps/layers");
+  VV_WQ_STRIP(vv_head, h);
+  const char* c = reinterpret_cast<const char*>(ws) + head_carve_single(h, n_steps).c;
+  r->B = 0; r->f32 = h->wdt == VV_F32; r->sde_proj = r->sde = r->cfg = false;
+  r->cb = h->wdt == VV_BF16 && 2 * n_steps > 8 && h->D % 32 == 0 && ((uintptr_t)c % 16 == 0);
+  bool ode = !sde_given;
+  for (int i = 0; i < n_steps && ode; ++i) ode = coef[i].cn == 0.f;
+  r->step_ku = (ode && vv_head_boundary_supported(h)) ? vv_head_boundary_decide(h) : 0;
+  r->pre_ku = (r->cb && r->step_ku) ? vv_head_pre_decide(h, cond2, ld_cond, temb, n_steps, c) : 0;
+  r->mod_nst = r->cb ? vv_head_modulations_decide(h, c, 2 * n_steps) : 0;
+  return 0;
+}
+
+// the batched samplers' (fn; sde_fn false: vv_head_sample_batch, which refuses SDE coefficients)
+static int head_batch_decide(const char* fn, bool sde_fn, const vv_head* h, const float* cond, const float* temb, const vv_dpm_coef* coef, int n_steps,
+                             int B, bool sde_given, int64_t ld_sde, bool cfg, const void* ws, HeadRoute* r) {
+  if (!h || !cond || !temb || !coef || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
+  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 8) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..8)", fn, n_steps, h->layers, B);
+  VV_WQ_STRIP(vv_head, h);
+  bool ode = true;
+  for (int i = 0; i < n_steps && ode; ++i) ode = coef[i].cn == 0.f;
+  if (!sde_fn && !ode) return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: the SDE solver is served by vv_head_sample_batch_sde");
+  if (sde_given && ld_sde < (int64_t)n_steps * h->latent) return vv_set_error(VV_E_ARG, "%s: ld_sde=%lld < n_steps * latent", fn, (long long)ld_sde);
+  if (!sde_given && !ode) return vv_set_error(VV_E_ARG, "%s: the SDE solver step needs its variance noise", fn);
+  if (h->wdt != VV_BF16 || !vv_head_boundary_supported(h) || h->D % 32 || !vv_head_boundary_decide(h))
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: needs bf16 weights and the fused solver boundary (vv_head.fused_g)", fn);
+  const char* c = reinterpret_cast<const char*>(ws) + head_carve_batch(h, n_steps, B, sde_given).c;
+  r->B = B; r->f32 = false; r->cb = true; r->pre_ku = 0; r->cfg = cfg;
+  r->mod_nst = vv_head_modulations_decide(h, c, 2 * B * n_steps);
+  r->step_ku = vv_head_boundary_decide(h);
+  r->sde_proj = sde_given; r->sde = sde_given && !ode;
+  return 0;
+}
+
+extern "C" int vv_head_sample_route(const vv_head* h, const float* cond, int64_t ld_cond, const float* temb, const vv_dpm_coef* coef, int n_steps, int B,
+                                    int sde, const float* cfg_rows, const void* ws, char* name, int cap) {
+  if (!name || cap <= 0) return vv_set_error(VV_E_ARG, "vv_head_sample_route: no room for the name");
+  name[0] = 0;
+  HeadRoute r;
+  if (B < 0) return vv_set_error(VV_E_ARG, "vv_head_sample_route: B=%d", B);
+  if (B == 0) {
+    if (cfg_rows) return vv_set_error(VV_E_ARG, "vv_head_sample_route: vv_head_sample takes no cfg_rows");
+    VV_TRY(head_single_decide(h, cond, ld_cond, temb, coef, n_steps, sde != 0, ws, &r));
+  } else {
+    const char* fn = cfg_rows ? "vv_head_sample_batch_cfg" : sde ? "vv_head_sample_batch_sde" : "vv_head_sample_batch";
+    VV_TRY(head_batch_decide(fn, cfg_rows || sde, h, cond, temb, coef, n_steps, B, sde != 0, INT64_MAX, cfg_rows != nullptr, ws, &r));
+  }
+  const char* wt = r.f32 ? "f32" : "bf16";
+  char pre[96], mod[40], step[48];
+  if (r.pre_ku) snprintf(pre, sizeof pre, "head_pre<ku=%d>", r.pre_ku);
+  else
+    snprintf(pre, sizeof pre, "linear+add_rows_silu%s%s%s%s%s%s%s", r.cb ? "_bf16" : "", r.step_ku ? "+head_init<" : "", r.step_ku ? wt : "", r.step_ku ? ">" : "",
+             r.sde_proj ? "+head_sde_proj<" : "", r.sde_proj ? wt : "", r.sde_proj ? ">" : "");
+  if (r.mod_nst == 12) snprintf(mod, sizeof mod, "adaln_lds<nst=12>");
+  else if (r.mod_nst == 28) snprintf(mod, sizeof mod, "adaln_all<nst=28,nm=1>");
+  else snprintf(mod, sizeof mod, "linear");
+  if (r.step_ku) snprintf(step, sizeof step, "boundary<ku=%d,sde=%d,cfg=%d>", r.step_ku, (int)r.sde, (int)r.cfg);
+  else snprintf(step, sizeof step, "dpm_proj");
+  snprintf(name, (size_t)cap, "pre=%s mod=%s step=%s", pre, mod, step);
+  return 0;
+}
+
+extern "C" int vv_head_ws_layout(const vv_head* h, int n_steps, int B, int sde, int64_t* off, int cap) {
+  if (!h || !off) return vv_set_error(VV_E_ARG, "vv_head_ws_layout: null pointer");
+  if (n_steps <= 0 || h->layers < 0 || h->layers > 16 || B < 0 || B > 8) return vv_set_error(VV_E_ARG, "vv_head_ws_layout: n_steps=%d layers=%d B=%d (0..8)", n_steps, h->layers, B);
+  if (B == 0 && sde) return vv_set_error(VV_E_ARG, "vv_head_ws_layout: vv_head_sample keeps no variance noise in its workspace (sde with B = 0)");
+  const int n = h->layers + 10 + (B == 0 ? 5 : 0);
+  if (cap < n) return vv_set_error(VV_E_ARG, "vv_head_ws_layout: room for %d offsets, the layout has %d", cap, n);
+  VV_WQ_STRIP(vv_head, h);
+  const HeadWs o = B == 0 ? head_carve_single(h, n_steps) : head_carve_batch(h, n_steps, B, sde != 0);
+  auto put = [](size_t v) { return v == HeadWs::none ? (int64_t)-1 : (int64_t)v; };
+  int k = 0;
+  off[k++] = put(o.c0); off[k++] = put(o.c);
+  for (int l = 0; l < h->layers; ++l) off[k++] = put(o.mod[l]);
+  off[k++] = put(o.modf); off[k++] = put(o.hb[0]); off[k++] = put(o.hb[1]); off[k++] = put(o.act);
+  off[k++] = put(o.Xs); off[k++] = put(o.Ms); off[k++] = put(o.NX);
+  if (B == 0) { off[k++] = put(o.v); off[k++] = put(o.xb[0]); off[k++] = put(o.xb[1]); off[k++] = put(o.mb[0]); off[k++] = put(o.mb[1]); }
+  off[k++] = put(o.end);
+  return k;
+}
+
 extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_cond, const float* noise, const float* temb,
                               const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, void* ws,
                               const float* sde_noise, vv_stream_t stream) {
-  if (!h || !cond2 || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "vv_head_sample: null pointer");
-  if (n_steps <= 0 || h->layers > 16) return vv_set_error(VV_E_ARG, "vv_head_sample: bad n_steps/layers");
+  if (!noise || !latent_out) return vv_set_error(VV_E_ARG, "vv_head_sample: null pointer");
+  HeadRoute rt;
+  VV_TRY(head_single_decide(h, cond2, ld_cond, temb, coef, n_steps, sde_noise != nullptr, ws, &rt));
   VV_WQ_STRIP(vv_head, h);
   hipStream_t s = (hipStream_t)stream;
   const int D = h->D;
-  const size_t R = 2 * (size_t)n_steps > 8 ? 2 * (size_t)n_steps : 8;
-  Carver cv(ws);
-  float* c0 = cv.take(8 * (size_t)D);
-  float* c = cv.take(R * D);
+  const HeadWs o = head_carve_single(h, n_steps);
+  auto at = [&](size_t off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off); };
+  float* c0 = at(o.c0);
+  float* c = at(o.c);
   float* mod[16];
-  for (int l = 0; l < h->layers; ++l) mod[l] = cv.take(R * 3 * D);
-  float* modf = cv.take(R * 2 * D);
-  float* hcur = cv.take(8 * (size_t)D);
-  float* act = cv.take(8 * (size_t)h->ffn);
-  float* v = cv.take(8 * (size_t)h->latent);
-  float* xb[2] = {cv.take(h->latent), cv.take(h->latent)};       // x and x0-history are double-buffered per step
-  float* mb[2] = {cv.take(h->latent), cv.take(h->latent)};
-  float* hcur2 = cv.take(8 * (size_t)D);
-  float* Xs = cv.take(D + (size_t)h->latent);
-  float* Ms = cv.take(D + (size_t)h->latent);
+  for (int l = 0; l < h->layers; ++l) mod[l] = at(o.mod[l]);
+  float* modf = at(o.modf);
+  float* hcur = at(o.hb[0]);
+  float* act = at(o.act);
+  float* v = at(o.v);
+  float* xb[2] = {at(o.xb[0]), at(o.xb[1])};       // x and x0-history are double-buffered per step
+  float* mb[2] = {at(o.mb[0]), at(o.mb[1])};
+  float* hcur2 = at(o.hb[1]);
+  float* Xs = at(o.Xs);
+  float* Ms = at(o.Ms);
   // step-invariant work hoisted out of the loop: cond_proj, silu(cond_proj(cond) + t_emb(t_i)), all adaLN modulations
-  const bool cb = h->wdt == VV_BF16 && 2 * n_steps > 8 && D % 32 == 0 && ((uintptr_t)c % 16 == 0);
-  bool ode0 = !sde_noise;
-  for (int i = 0; i < n_steps && ode0; ++i) ode0 = coef[i].cn == 0.f;
+  const bool cb = rt.cb;
   // the ODE solver on the fused boundary: cond_proj, the row expansion and the solver-state initialisation are one launch (vv_fused.hip)
   int pre = 0;
-  if (cb && ode0 && vv_head_boundary_supported(h)) {
+  if (rt.pre_ku) {
     pre = vv_head_pre_fused(h, cond2, ld_cond, temb, n_steps, c, noise, Xs, Ms, hcur, D, s);
     if (pre < 0) return pre;
   }
@@ -402,9 +554,7 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
     else VV_TRY(vv_add_rows_silu(c0, D, temb, D, c, 2 * n_steps, 2, D, stream));
   }
   VV_TRY(head_modulations(h, c, 2 * n_steps, mod, modf, true, cb, stream));
-  bool ode = !sde_noise;
-  for (int i = 0; i < n_steps && ode; ++i) ode = coef[i].cn == 0.f;          // the SDE solver (variance noise per step) keeps the three-launch boundary
-  if (ode && vv_head_boundary_supported(h)) {
+  if (rt.step_ku) {          // the SDE solver (variance noise per step) keeps the three-launch boundary
     // one launch per step boundary: FinalLayer + CFG + DPM-Solver++ update + next noisy_images_proj as ONE GEMV over G = [P F ; F]
     // with the solver in its epilogue (vv_fused.hip).  The hidden rows alternate between two buffers: the boundary kernel of step i
     // reads the rows the layers of step i worked on while it writes the rows step i + 1 starts from.
@@ -448,19 +598,16 @@ extern "C" int vv_head_sample(const vv_head* h, const float* cond2, int64_t ld_c
 // B utterances per call: rows [2 B] everywhere the single-utterance sampler has 2; conditioning rows laid out [step][2 B]
 extern "C" size_t vv_head_ws_bytes_batch(const vv_head* h, int n_steps, int B) {
   if (!h || n_steps <= 0 || B <= 0 || B > 8) return 0;
+  if (h->layers < 0 || h->layers > 16) return 0;
   VV_WQ_STRIP(vv_head, h);
-  const size_t R = (size_t)2 * B * n_steps, D = h->D;
-  const size_t HR = B <= 4 ? 8 : (size_t)2 * B;       // hidden / act / c0 rows: 8 as ever up to 4 utterances, 2 B beyond
-  return al(HR * D) /*c0*/ + al(R * D) /*c (bf16 rows fit)*/ + (size_t)h->layers * al(R * 3 * D) + al(R * 2 * D) + 2 * al(HR * D) /*hidden rows x 2*/ +
-         al(HR * (size_t)h->ffn) + 2 * al((size_t)B * (D + h->latent)) /*solver state X, M*/ +
-         al(vv_gemv_rows_part_floats(h->D, 0)) + al(vv_gemv_rows_tickets(h->ffn));
+  return head_carve_batch(h, n_steps, B, false).end;
 }
 
 // the SDE form: the same workspace with the variance noise of every step of every utterance in state space, NX [B][n_steps][D + latent], at its end
 extern "C" size_t vv_head_ws_bytes_batch_sde(const vv_head* h, int n_steps, int B) {
-  const size_t base = vv_head_ws_bytes_batch(h, n_steps, B);
-  if (!base) return 0;
-  return base + al((size_t)B * n_steps * (h->D + h->latent));
+  if (!vv_head_ws_bytes_batch(h, n_steps, B)) return 0;       // its refusals
+  VV_WQ_STRIP(vv_head, h);
+  return head_carve_batch(h, n_steps, B, true).end;
 }
 
 // sde_noise == NULL: the ODE solver (every launch identical to vv_head_sample_batch's); else [B][n_steps][latent] at utterance stride ld_sde,
@@ -470,39 +617,31 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
                              const vv_dpm_coef* coef, int n_steps, float cfg_scale, float* latent_out, int64_t ld_latent, int B, void* ws,
                              const float* sde_noise, int64_t ld_sde, vv_stream_t stream, const float* cfg_rows = nullptr) {
   const char* fn = sde_fn ? sde_fn : "vv_head_sample_batch";
-  if (!h || !cond || !noise || !temb || !coef || !latent_out || !ws) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
-  if (n_steps <= 0 || h->layers > 16 || B <= 0 || B > 8) return vv_set_error(VV_E_ARG, "%s: n_steps=%d layers=%d B=%d (1..8)", fn, n_steps, h->layers, B);
+  if (!noise || !latent_out) return vv_set_error(VV_E_ARG, "%s: null pointer", fn);
+  HeadRoute rt;
+  VV_TRY(head_batch_decide(fn, sde_fn != nullptr, h, cond, temb, coef, n_steps, B, sde_noise != nullptr, ld_sde, cfg_rows != nullptr, ws, &rt));
   VV_WQ_STRIP(vv_head, h);
   const bool f8q = wq == VV_FP8;                  // NF4 companions: the bf16 matrices (and their bf16 fragment-major copies) serve these rows
-  if (!sde_fn)
-    for (int i = 0; i < n_steps; ++i)
-      if (coef[i].cn != 0.f) return vv_set_error(VV_E_UNSUPPORTED, "vv_head_sample_batch: the SDE solver is served by vv_head_sample_batch_sde");
-  if (sde_noise && ld_sde < (int64_t)n_steps * h->latent) return vv_set_error(VV_E_ARG, "%s: ld_sde=%lld < n_steps * latent", fn, (long long)ld_sde);
-  if (!sde_noise)
-    for (int i = 0; i < n_steps; ++i)
-      if (coef[i].cn != 0.f) return vv_set_error(VV_E_ARG, "%s: the SDE solver step needs its variance noise", fn);
-  if (h->wdt != VV_BF16 || !vv_head_boundary_supported(h) || h->D % 32)
-    return vv_set_error(VV_E_UNSUPPORTED, "%s: needs bf16 weights and the fused solver boundary (vv_head.fused_g)", fn);
   hipStream_t s = (hipStream_t)stream;
   const int D = h->D, R2 = 2 * B;
   const size_t R = (size_t)R2 * n_steps;
-  const size_t HR = B <= 4 ? 8 : (size_t)R2;          // as vv_head_ws_bytes_batch
-  Carver cv(ws);
-  float* c0 = cv.take(HR * D);
-  float* c = cv.take(R * D);
+  const HeadWs o = head_carve_batch(h, n_steps, B, sde_noise != nullptr);
+  auto at = [&](size_t off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + off); };
+  float* c0 = at(o.c0);
+  float* c = at(o.c);
   float* mod[16];
-  for (int l = 0; l < h->layers; ++l) mod[l] = cv.take(R * 3 * D);
-  float* modf = cv.take(R * 2 * D);
-  float* hb[2] = {cv.take(HR * D), cv.take(HR * D)};
-  float* act = cv.take(HR * (size_t)h->ffn);
+  for (int l = 0; l < h->layers; ++l) mod[l] = at(o.mod[l]);
+  float* modf = at(o.modf);
+  float* hb[2] = {at(o.hb[0]), at(o.hb[1])};
+  float* act = at(o.act);
   const int64_t sst = D + h->latent;
-  float* Xs = cv.take((size_t)B * sst);
-  float* Ms = cv.take((size_t)B * sst);
-  const size_t rpart_n = vv_gemv_rows_part_floats(h->D, 0), rtick_n = vv_gemv_rows_tickets(h->ffn);
-  float* rpart = cv.take(rpart_n);
-  int* rtick = reinterpret_cast<int*>(cv.take(rtick_n));
+  float* Xs = at(o.Xs);
+  float* Ms = at(o.Ms);
+  const size_t rpart_n = o.rpart_n, rtick_n = o.rtick_n;
+  float* rpart = at(o.rpart);
+  int* rtick = reinterpret_cast<int*>(at(o.rtick));
   if (hipMemsetAsync(rtick, 0, rtick_n * sizeof(int), s) != hipSuccess) return vv_set_error(VV_E_HIP, "%s: memset", fn);
-  float* NX = sde_noise ? cv.take((size_t)B * n_steps * sst) : nullptr;        // carved last: the ODE layout is that of vv_head_ws_bytes_batch
+  float* NX = sde_noise ? at(o.NX) : nullptr;        // carved last: the ODE layout is that of vv_head_ws_bytes_batch
   if (NX) VV_TRY(vv_head_sde_proj_fused(h, sde_noise, ld_sde, n_steps, B, NX, s));
   // step-invariant work: cond_proj on all rows, silu(cond_proj(cond) + t_emb(t_i)) as bf16 rows [step][2 B], every adaLN modulation
   vv_lin_args a = lin_base(cond, ld_cond, R2, h->cond_proj, D, h->cond_dim, h->wdt, c0, D);
