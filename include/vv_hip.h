@@ -157,8 +157,9 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
  * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>", or "gemm_packed<dual=0,obf=0>" for
- * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call; "skinny" or
- * "gemm_f32"; and for the
+ * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call;
+ * "skinny<nst=20,nb=1>" for the resampling convs' skinny GEMM (k = 4 waves x nb bursts x nst steps of 32) and
+ * "gemm_f32<w=bf16,dual=0,vec=1,tile=32>" for the fp32 LDS-tiled GEMM (w f32 | bf16; vec: float4 loads; tile 32 | 64); and for the
  * m <= 8 family (fp8, NF4 and MXFP4 weights included) the kernel itself:
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)

@@ -753,10 +753,10 @@ def test_route_names_other_families():
             a.res, a.ldres = _FAKE["res"], n
         return route_of(a)
 
-    assert route(40, 512, 2560) == "skinny"
+    assert route(40, 512, 2560) == "skinny<nst=20,nb=1>"
     assert route(40, 512, 2560, res=True) == _stream(0, 1, 0, 1)
-    assert route(40, 512, 2560, wdt=L.VV_F32) == "gemm_f32"
-    assert route(33, 70, 56) == "gemm_f32"                          # k % 16 != 0: the matrix-core path declines
+    assert route(40, 512, 2560, wdt=L.VV_F32) == "gemm_f32<w=f32,dual=0,vec=1,tile=32>"
+    assert route(33, 70, 56) == "gemm_f32<w=bf16,dual=0,vec=1,tile=32>"                  # k % 16 != 0: the matrix-core path declines
     # m <= 8: the GEMV kernel itself (tests/test_hip_gemv.py pins the whole family); 5 units at 8 rows split K over 4 waves
     assert route(8, 512, 2560, res=True) == "gemv_stream<m=8,dual=0,ksplit=4,ku=2,rw=2,wq=bf16>"
     assert route(1, 512, 96) == "gemv_stream<m=1,dual=0,ksplit=1,ku=1,rw=2,wq=bf16>"

@@ -165,7 +165,11 @@ void vv_convffn_set_rows(int c, int rows);
 void vv_convffn_set_c128(int on);
 bool vv_convffn_prefers(int wdt, int T, int C);
 int vv_launch_skinny(const vv_lin_args& a, hipStream_t s);       // resampling convs of a streaming frame: 1 launched, 0 not covered
-bool vv_skinny_covers(const vv_lin_args& a);                      // what vv_launch_skinny would launch (the same predicate, no launch)
+// the decision apart from the launch (vv_linear_route prints it): skinny_kernel<nst, nb>, kind 0 = not covered
+struct vv_skinny_route { int kind, nst, nb; };
+vv_skinny_route vv_skinny_decide(const vv_lin_args& a);
+int vv_skinny_route_name(const vv_skinny_route& r, char* name, int cap);
+bool vv_skinny_covers(const vv_lin_args& a);                      // vv_skinny_decide(a).kind != 0
 void vv_skinny_set(int on, int min_m, int max_m);
 int vv_rmsnorm_rows(const float* x, int64_t ldx, const float* w, float eps, int rows, int n, float* out, int64_t ldo, hipStream_t s,
                     const int* sel = nullptr);                    // sel (device int[rows]) or null: output row r normalises input row sel[r]

@@ -557,31 +557,37 @@ void vv_convffn_set_c128(int on) { g_c128 = on; }
 bool vv_convffn_prefers(int wdt, int T, int C) { return g_on && g_c128 && wdt == VV_BF16 && C == 128 && T >= 3 && T <= 1024; }
 void vv_skinny_set(int on, int min_m, int max_m) { g_skinny = on; if (min_m > 0) g_skinny_min_m = min_m; if (max_m > 0) g_skinny_max_m = max_m; }
 
-// what vv_launch_skinny covers (it and the route query share this predicate)
-bool vv_skinny_covers(const vv_lin_args& a) {
-  if (!g_skinny || a.wdt != VV_BF16 || a.w2 || a.pro != VV_PRO_NONE || a.act != VV_ACT_NONE || a.gate || a.res || a.mod_scale || a.flags) return false;
-  if (a.m < g_skinny_min_m || a.m > g_skinny_max_m || a.n % 16 || a.ldx % 4 || a.ldx == 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return false;
-  return a.k == 128 || a.k == 256 || a.k == 512 || a.k == 1024 || a.k == 2048 || a.k == 2560 || a.k == 5120;
+// The skinny_kernel<nst, nb> a call takes, or kind 0: what it covers and the K -> (nst, nb) table live here alone; the launch below, linear_family
+// (through vv_skinny_covers) and vv_linear_route all ask this.  Plain values only: no pointer is followed, nothing is launched.
+vv_skinny_route vv_skinny_decide(const vv_lin_args& a) {
+  vv_skinny_route r = {0, 0, 0};
+  if (!g_skinny || a.wdt != VV_BF16 || a.w2 || a.pro != VV_PRO_NONE || a.act != VV_ACT_NONE || a.gate || a.res || a.mod_scale || a.flags) return r;
+  if (a.m < g_skinny_min_m || a.m > g_skinny_max_m || a.n % 16 || a.ldx % 4 || a.ldx == 0 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return r;
+  // K = 4 waves x nb bursts x nst steps of 32
+  static const int table[7][3] = {{128, 1, 1}, {256, 2, 1}, {512, 4, 1}, {1024, 8, 1}, {2048, 16, 1}, {2560, 20, 1}, {5120, 20, 2}};
+  for (const auto& t : table)
+    if (a.k == t[0]) { r.kind = 1; r.nst = t[1]; r.nb = t[2]; }
+  return r;
 }
 
-// 1 = launched, 0 = not covered
+bool vv_skinny_covers(const vv_lin_args& a) { return vv_skinny_decide(a).kind != 0; }
+
+int vv_skinny_route_name(const vv_skinny_route& r, char* name, int cap) { return snprintf(name, (size_t)cap, "skinny<nst=%d,nb=%d>", r.nst, r.nb); }
+
+// 1 = launched, 0 = not covered (or a route with no kernel: every instantiation is one line here)
 int vv_launch_skinny(const vv_lin_args& a, hipStream_t s) {
-  if (!vv_skinny_covers(a)) return 0;
+  const vv_skinny_route r = vv_skinny_decide(a);
+  if (!r.kind) return 0;
   dim3 grid(a.n / 16, (a.m + 15) / 16);
   const bf16_t* W = reinterpret_cast<const bf16_t*>(a.w);
-#define VV_SK(NSTV, NBV) hipLaunchKernelGGL((skinny_kernel<NSTV, NBV>), grid, dim3(256), 0, s, a.x, a.ldx, a.m, W, a.k, a.bias, a.out, a.ldo)
-  switch (a.k) {
-    case 128: VV_SK(1, 1); break;
-    case 256: VV_SK(2, 1); break;
-    case 512: VV_SK(4, 1); break;
-    case 1024: VV_SK(8, 1); break;
-    case 2048: VV_SK(16, 1); break;
-    case 2560: VV_SK(20, 1); break;
-    case 5120: VV_SK(20, 2); break;
-    default: return 0;
+#define VV_SK(NSTV, NBV)                                                                                                                    \
+  if (r.nst == NSTV && r.nb == NBV) {                                                                                                       \
+    hipLaunchKernelGGL((skinny_kernel<NSTV, NBV>), grid, dim3(256), 0, s, a.x, a.ldx, a.m, W, a.k, a.bias, a.out, a.ldo);                   \
+    return 1;                                                                                                                               \
   }
+  VV_SK(1, 1) VV_SK(2, 1) VV_SK(4, 1) VV_SK(8, 1) VV_SK(16, 1) VV_SK(20, 1) VV_SK(20, 2)
 #undef VV_SK
-  return 1;
+  return 0;
 }
 
 int vv_convffn_init() {

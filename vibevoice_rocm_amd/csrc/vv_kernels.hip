@@ -693,10 +693,24 @@ static int linear_family(const vv_lin_args& a, vv_mfma_route* r) {
   return LIN_FAM_GEMM_F32;
 }
 
+// The gemm_kernel<WT, dual, vec, tile, tile> a LIN_FAM_GEMM_F32 call takes (WT is a.wdt): decided here for the launch below and for vv_linear_route
+// alike.  vec: float4 / 4-weight loads, which need k and ldx in whole float4s and 16-byte aligned x, w (and w2).
+struct gemm_f32_route { int dual, vec, tile; };
+static gemm_f32_route gemm_f32_decide(const vv_lin_args& a) {
+  gemm_f32_route r;
+  r.dual = a.w2 != nullptr;
+  const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!r.dual || (uintptr_t)a.w2 % 16 == 0);
+  r.vec = (a.k % 4 == 0) && (a.ldx % 4 == 0) && ((uintptr_t)a.x % 16 == 0) && w_al16;
+  const long big_tiles = (long)((a.n + 63) / 64) * ((a.m + 63) / 64);
+  r.tile = big_tiles < 192 ? 32 : 64;              // too few 64x64 tiles to fill 256 CUs: use 32x32 tiles
+  return r;
+}
+static int gemm_f32_route_name(const vv_lin_args& a, const gemm_f32_route& r, char* name, int cap) {
+  return snprintf(name, (size_t)cap, "gemm_f32<w=%s,dual=%d,vec=%d,tile=%d>", a.wdt == VV_F32 ? "f32" : "bf16", r.dual, r.vec, r.tile);
+}
+
 template <typename WT>
 static int launch_linear(const vv_lin_args& a, hipStream_t s) {
-  const bool dual = a.w2 != nullptr;
-  const bool w_al16 = ((uintptr_t)a.w % 16 == 0) && (!dual || (uintptr_t)a.w2 % 16 == 0);
   vv_mfma_route route = {};
   const int fam = linear_family(a, &route);
   if (fam < 0) return fam;
@@ -711,21 +725,19 @@ static int launch_linear(const vv_lin_args& a, hipStream_t s) {
     const int rc = vv_launch_mfma_route(a, route, s);
     return rc < 0 ? rc : 0;
   }
-  const bool vec = (a.k % 4 == 0) && (a.ldx % 4 == 0) && ((uintptr_t)a.x % 16 == 0) && w_al16;
-  const long big_tiles = (long)((a.n + 63) / 64) * ((a.m + 63) / 64);
-  const bool small = big_tiles < 192;              // too few 64x64 tiles to fill 256 CUs: use 32x32 tiles
-  const int tm = small ? 32 : 64;
-  dim3 grid((a.n + tm - 1) / tm, (a.m + tm - 1) / tm);
+  const gemm_f32_route g = gemm_f32_decide(a);
+  dim3 grid((a.n + g.tile - 1) / g.tile, (a.m + g.tile - 1) / g.tile);
   if (grid.y > 65535u) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: m=%d rows exceed one launch (split the call)", a.m);
-#define VV_GEMM_LAUNCH(D, V)                                                                                  \
-  do {                                                                                                        \
-    if (small) hipLaunchKernelGGL((gemm_kernel<WT, D, V, 32, 32>), grid, dim3(256), 0, s, a);                 \
-    else hipLaunchKernelGGL((gemm_kernel<WT, D, V, 64, 64>), grid, dim3(256), 0, s, a);                       \
-  } while (0)
-  if (dual) { if (vec) VV_GEMM_LAUNCH(true, true); else VV_GEMM_LAUNCH(true, false); }
-  else { if (vec) VV_GEMM_LAUNCH(false, true); else VV_GEMM_LAUNCH(false, false); }
+  // one line per instantiation: the route's (dual, vec, tile) picks exactly the kernel its name says
+#define VV_GEMM_LAUNCH(D, V, T)                                                                               \
+  if (g.dual == D && g.vec == V && g.tile == T) {                                                             \
+    hipLaunchKernelGGL((gemm_kernel<WT, D != 0, V != 0, T, T>), grid, dim3(256), 0, s, a);                    \
+    return 0;                                                                                                 \
+  }
+  VV_GEMM_LAUNCH(0, 0, 32) VV_GEMM_LAUNCH(0, 1, 32) VV_GEMM_LAUNCH(1, 0, 32) VV_GEMM_LAUNCH(1, 1, 32)
+  VV_GEMM_LAUNCH(0, 0, 64) VV_GEMM_LAUNCH(0, 1, 64) VV_GEMM_LAUNCH(1, 0, 64) VV_GEMM_LAUNCH(1, 1, 64)
 #undef VV_GEMM_LAUNCH
-  return 0;
+  return vv_set_error(VV_E_HIP, "vv_linear: undecided fp32 GEMM route");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -837,7 +849,8 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     if (fam < 0) return fam;
     if (fam == LIN_FAM_MFMA) vv_mfma_route_name(route, name, cap);
     else if (fam == LIN_FAM_PACKED) vv_gemm_packed_route_name(*a, name, cap);
-    else if (fam != LIN_FAM_GEMV) snprintf(name, (size_t)cap, "%s", fam == LIN_FAM_SKINNY ? "skinny" : "gemm_f32");
+    else if (fam == LIN_FAM_SKINNY) vv_skinny_route_name(vv_skinny_decide(*a), name, cap);
+    else if (fam == LIN_FAM_GEMM_F32) gemm_f32_route_name(*a, gemm_f32_decide(*a), name, cap);
   }
   else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (a->flags & VV_LIN_W_MXGEMM) { vv_gemm_mx_route_name(*a, name, cap); return 0; }      // linear_check_args has asked vv_gemm_mx_check
