@@ -20,6 +20,9 @@ OUT = os.path.join(HERE, "libvv_hip.so")
 OBJDIR = os.path.join(HERE, "csrc", "build")
 STAMP = os.path.join(HERE, "libvv_hip.stamp")      # next to the library: travels with it to the GPU box (git-ignored)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# units whose kernels take their leading arguments in user SGPRs at wave launch (kernarg preload): the flag acts on flat leading parameters only
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+UNIT_FLAGS = {"vv_gemv_hot.hip": PRELOAD}
 
 
 def find_hipcc() -> str:
@@ -31,7 +34,7 @@ def find_hipcc() -> str:
 
 def _flavour() -> str:
     """What the library was built from: the translation-unit list and the compiler flags (a changed list or flag set rebuilds)."""
-    return hashlib.sha256("\n".join([os.path.basename(s) for s in SRC] + FLAGS).encode()).hexdigest()[:16]
+    return hashlib.sha256("\n".join([os.path.basename(s) for s in SRC] + FLAGS + [u + " " + " ".join(f) for u, f in sorted(UNIT_FLAGS.items())]).encode()).hexdigest()[:16]
 
 
 def _check_sources():
@@ -70,7 +73,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 6) -> str:
     todo = [s for s in SRC if force or not os.path.exists(_obj(s)) or os.path.getmtime(_obj(s)) < max(os.path.getmtime(s), hdr_t)]
     procs = []
     for s in todo:
-        cmd = [hipcc, *flags, "-c", s, "-o", _obj(s)]
+        cmd = [hipcc, *flags, *UNIT_FLAGS.get(os.path.basename(s), []), "-c", s, "-o", _obj(s)]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd)))

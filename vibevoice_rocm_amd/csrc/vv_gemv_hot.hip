@@ -49,12 +49,25 @@ __device__ __forceinline__ float vv_hot_gate_res(float v, float g, float r) {
   return t + r;
 }
 
+// How the arguments arrive: the leading kernel parameters are exactly what the loads in front of the first wait need, the pointers and then their
+// strides as 32-bit values, at most 14 dwords.  The unit is built with kernarg preload (-mllvm -amdgpu-kernarg-preload-count=16, build.py), which has
+// the command processor place those dwords in user SGPRs at wave launch: a wave's first instructions form addresses and issue global_loads instead of
+// waiting for a scalar round trip to the kernarg segment.  What only the epilogue needs trails in hot_tail (a struct is passed by reference and
+// never preloaded: its s_load is off the critical path).  The bodies read the arguments through hot_view under vv_lin_args' names.
+struct hot_tail { float* out; int64_t ldo; int k; float eps; };
+struct hot_view {     // the fields of vv_lin_args the hot bodies read, under the same names
+  const float* x; int64_t ldx; const float* norm_w; float eps; const float* mod_shift; const float* mod_scale; int64_t ld_mod; const void* w; const void* w2;
+  const float* bias; int k; const float* gate; int64_t gate_ld; const float* res; int64_t ldres; float* out; int64_t ldo;
+};
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // SwiGLU pair (gate / up), K = 1536: RMSNorm (MOD: adaLN shift / scale on top) staged once per block over 256 threads, one weight row
 // of each matrix per wave step, G = ceil(N / 2048) steps all requested at entry.
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int N, bool MOD, bool NT>
-__global__ __launch_bounds__(256, 2) void hot_dual_kernel(const vv_lin_args a) {
+__global__ __launch_bounds__(256, 2) void hot_dual_kernel(const float* x, const float* norm_w, const float* mod_shift, const float* mod_scale, const void* w,
+                                                          const void* w2, int ldx, int ld_mod, const hot_tail t) {
+  const hot_view a{x, ldx, norm_w, t.eps, mod_shift, mod_scale, ld_mod, w, w2, nullptr, t.k, nullptr, 0, nullptr, 0, t.out, t.ldo};
   constexpr int K = 1536, KU = 3, M = 2, T = 256, NCH = 2, NCHUNKS = K / 4;
   constexpr int WAVES = 512 * 4, G = (N + WAVES - 1) / WAVES;
   constexpr bool RAGGED = (N % WAVES) != 0;      // only the last step can be past the end
@@ -185,8 +198,10 @@ __global__ __launch_bounds__(256, 2) void hot_dual_kernel(const vv_lin_args a) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Whole-row kernel, K = 1536, two weight rows per wave, one step: llm.qkv (RMSNorm per wave, + bias) and llm.o (no prologue, + residual).
 // ---------------------------------------------------------------------------------------------------------------------------------
-template <int N, int WPB, bool RMS, bool NT>      // RMS: RMSNorm prologue and bias epilogue; else plain rows and residual epilogue
-__global__ __launch_bounds__(64 * WPB) void hot_rows_kernel(const vv_lin_args a) {
+template <int N, int WPB, bool RMS, bool NT>      // RMS: RMSNorm prologue and bias epilogue (eop = bias); else plain rows and residual epilogue (eop = res)
+__global__ __launch_bounds__(64 * WPB) void hot_rows_kernel(const float* x, const float* norm_w, const float* eop, const void* w, int ldx, int ldres,
+                                                            const hot_tail t) {
+  const hot_view a{x, ldx, norm_w, t.eps, nullptr, nullptr, 0, w, nullptr, eop, t.k, nullptr, 0, eop, ldres, t.out, t.ldo};
   constexpr int K = 1536, KU = 3, M = 2, RW = 2;
   static_assert(N % (RW * WPB) == 0, "every wave of the grid owns one whole row pair");
   const int tid = threadIdx.x, lane = tid & 63;
@@ -292,7 +307,9 @@ __global__ __launch_bounds__(64 * WPB) void hot_rows_kernel(const vv_lin_args a)
 //   GATE: epilogue * gate[m, n] + res[m, n] (head); else + res[m, n] (LLM)
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int N, int K, int R, bool GATE, bool NT>
-__global__ __launch_bounds__(256) void hot_down_kernel(const vv_lin_args a) {
+__global__ __launch_bounds__(256) void hot_down_kernel(const float* x, const float* gate, const float* res, const void* w, int ldx, int gate_ld, int ldres,
+                                                       const hot_tail t) {
+  const hot_view a{x, ldx, nullptr, 0.f, nullptr, nullptr, 0, w, nullptr, nullptr, K, gate, gate_ld, res, ldres, t.out, t.ldo};
   constexpr int M = 2, NW = 4, UNITS = (K + 511) / 512, KU = (UNITS + NW - 1) / NW;
   static_assert(N % R == 0 && R * M <= 64, "whole row sets; the epilogue threads are the first R * M of the block");
   __shared__ float part[NW][R * M];
@@ -387,11 +404,15 @@ const vv_gemv_hot_shape g_table[N_HOT] = {
 constexpr int HOT_DEFAULT = 0x3f;   // the adopted entries (tools/mb_hot.py)
 int g_hot = HOT_DEFAULT;   // tuning hook "gemv_hot": bit i = table entry i takes its hot kernel; bit 8 = the down kernels own 3 rows per block (512 blocks)
 
+bool fits31(int64_t v) { return v >= 0 && v <= INT32_MAX; }
+
 bool matches(const vv_gemv_hot_shape& e, const vv_lin_args& a) {
   return a.m == e.m && a.n == e.n && a.k == e.k && a.wdt == VV_BF16 && (a.w2 != nullptr) == (e.dual != 0) && a.pro == e.pro &&
          (a.pro != VV_PRO_RMSNORM || a.norm_w != nullptr) && (a.mod_scale != nullptr) == (e.mod != 0) && (!e.mod || a.mod_shift != nullptr) &&
          (a.bias != nullptr) == (e.bias != 0) && (a.gate != nullptr) == (e.gate != 0) && (!e.gate || a.gate_ld != 0) &&
-         (a.res != nullptr) == (e.res != 0) && a.act == e.act && a.flags == e.flags;
+         (a.res != nullptr) == (e.res != 0) && a.act == e.act && a.flags == e.flags &&
+         // the kernels take the strides in front of their first loads as 32-bit values: a call they do not fit goes to the template
+         fits31(a.ldx) && (!e.mod || fits31(a.ld_mod)) && (!e.gate || fits31(a.gate_ld)) && (!e.res || fits31(a.ldres));
 }
 
 }  // namespace
@@ -415,19 +436,21 @@ int vv_gemv_hot_covers(const vv_lin_args& a) {
 // modulation rows and ldx % 4 == 0.
 int vv_launch_gemv_hot(const vv_lin_args& a, int id, hipStream_t s) {
   const bool r3 = (g_hot & 256) != 0;
+  const hot_tail t{a.out, a.ldo, a.k, a.eps};
+  const int ldx = (int)a.ldx, ld_mod = (int)a.ld_mod, gate_ld = (int)a.gate_ld, ldres = (int)a.ldres;   // vv_gemv_hot_covers has checked the ones the entry reads
   switch (id) {
-    case 0: hipLaunchKernelGGL((hot_dual_kernel<4608, true, false>), dim3(512), dim3(256), 0, s, a); return 1;
+    case 0: hipLaunchKernelGGL((hot_dual_kernel<4608, true, false>), dim3(512), dim3(256), 0, s, a.x, a.norm_w, a.mod_shift, a.mod_scale, a.w, a.w2, ldx, ld_mod, t); return 1;
     case 1:
-      if (r3) hipLaunchKernelGGL((hot_down_kernel<1536, 4608, 3, true, false>), dim3(512), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((hot_down_kernel<1536, 4608, 6, true, false>), dim3(256), dim3(256), 0, s, a);
+      if (r3) hipLaunchKernelGGL((hot_down_kernel<1536, 4608, 3, true, false>), dim3(512), dim3(256), 0, s, a.x, a.gate, a.res, a.w, ldx, gate_ld, ldres, t);
+      else hipLaunchKernelGGL((hot_down_kernel<1536, 4608, 6, true, false>), dim3(256), dim3(256), 0, s, a.x, a.gate, a.res, a.w, ldx, gate_ld, ldres, t);
       return 1;
-    case 2: hipLaunchKernelGGL((hot_dual_kernel<8960, false, true>), dim3(512), dim3(256), 0, s, a); return 1;
+    case 2: hipLaunchKernelGGL((hot_dual_kernel<8960, false, true>), dim3(512), dim3(256), 0, s, a.x, a.norm_w, a.mod_shift, a.mod_scale, a.w, a.w2, ldx, ld_mod, t); return 1;
     case 3:
-      if (r3) hipLaunchKernelGGL((hot_down_kernel<1536, 8960, 3, false, true>), dim3(512), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((hot_down_kernel<1536, 8960, 6, false, true>), dim3(256), dim3(256), 0, s, a);
+      if (r3) hipLaunchKernelGGL((hot_down_kernel<1536, 8960, 3, false, true>), dim3(512), dim3(256), 0, s, a.x, a.gate, a.res, a.w, ldx, gate_ld, ldres, t);
+      else hipLaunchKernelGGL((hot_down_kernel<1536, 8960, 6, false, true>), dim3(256), dim3(256), 0, s, a.x, a.gate, a.res, a.w, ldx, gate_ld, ldres, t);
       return 1;
-    case 4: hipLaunchKernelGGL((hot_rows_kernel<2048, 4, true, true>), dim3(256), dim3(256), 0, s, a); return 1;
-    case 5: hipLaunchKernelGGL((hot_rows_kernel<1536, 3, false, true>), dim3(256), dim3(192), 0, s, a); return 1;
+    case 4: hipLaunchKernelGGL((hot_rows_kernel<2048, 4, true, true>), dim3(256), dim3(256), 0, s, a.x, a.norm_w, a.bias, a.w, ldx, ldres, t); return 1;
+    case 5: hipLaunchKernelGGL((hot_rows_kernel<1536, 3, false, true>), dim3(256), dim3(192), 0, s, a.x, a.norm_w, a.res, a.w, ldx, ldres, t); return 1;
   }
   return 0;
 }
