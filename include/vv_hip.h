@@ -77,6 +77,29 @@ enum { VV_MXFP4_FRAG = 5 };
  * for every matrix that has a copy; a matrix the form cannot take (N % 16, K % 128) keeps f_* = NULL and the bf16 row-major fallback.  The
  * prefill and the m <= 2 calls are unchanged.  No bf16 fragment copy may sit in f_* under this bit. */
 enum { VV_WQ_FRAG4 = 0x400 };
+/* VV_MXFP6: weight-only OCP Microscaling (MX v1.0) FP6, the e2m3 element type, streaming GEMV only (csrc/vv_gemv_mx6.hip): m <= 2, k % 32 == 0,
+ * k <= 24576 (SwiGLU, w2 != NULL: 16384), no VV_LIN_W_FRAG, no bf16 hand-off, no VV_LIN_W_MXGEMM.  A block is 32 consecutive k of one row with
+ * one E8M0 scale byte e worth 2^(e - 127); an element is a 6-bit code, sign in bit 5, exponent E in bits 4..3, mantissa m in bits 2..0: E == 0
+ * means m / 8, E in 1..3 means (1 + m / 8) * 2^(E - 1), the largest magnitude 7.5.  Effective weight W[n][k] = value(code) * 2^(e - 127): exact
+ * in bf16.  Valid scale bytes are 2 <= e <= 252 (every effective weight is then a finite fp32; under e < 5 the smallest elements are fp32
+ * subnormals, which the kernel delivers exactly); the entry points do not read the bytes.  With G = ceil(N / 4) row groups and B = K / 32 blocks per row (K is never padded):
+ *   w / w2:           codes, 16-byte aligned.  The 32 codes of block b of row 4 q + r form one 192-bit string, code i (k = 32 b + i) in its bits
+ *                     6 i .. 6 i + 5 counted from bit 0 of its first byte (little-endian: the operand of v_cvt_scalef32_pk32_f32_fp6 as six
+ *                     dwords).  Bytes 0..15 of the string lie in PLANE A of the group, bytes 16..23 in PLANE B: group q occupies the 96 B bytes
+ *                     from 96 B q on - plane A [4 rows][B blocks][16 B] in its first 64 B bytes, plane B [4 rows][B blocks][8 B] behind it.
+ *                     So a wave that gives lane l block b0 + l of one row reads 1024 contiguous, 16-byte aligned bytes of plane A and 512
+ *                     contiguous, 8-byte aligned bytes of plane B.
+ *   wscale / w2scale: the ADDRESS of the scale bytes, read as uint8_t (not as float), 4-byte aligned: [G][B blocks][4 rows], i.e. the byte of row
+ *                     4 q + r, block b at (q * B + b) * 4 + r - one 4-byte load per lane carries its block's scale in all four rows
+ * Padding (rows past N) holds code 0 and scale byte 127.  0.78125 bytes per weight.  Any other MXFP6 call (m > 2, k % 32, a longer row, a missing
+ * scale pointer, a misaligned code, scale or activation pointer, VV_LIN_W_FRAG, VV_LIN_X_BF16 / VV_LIN_OUT_BF16, VV_LIN_W_MXGEMM) returns
+ * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, before any launch, the output untouched.  Value 7 is no weight type. */
+enum { VV_MXFP6 = 6 };
+/* VV_WQ_MXFP6: as VV_WQ_MXFP4, for companions that hold MXFP6 (codes in q, the scale bytes' address in scale, the VV_MXFP6 layout above).  The
+ * 1..2-row GEMVs of the LLM, the diffusion head and the tokenizers' one-row stage stream them; every other pass (3 and more rows, the prefill)
+ * uses the bf16 matrices, which hold exactly the same effective values.  There is no fragment-major and no lean form: VV_WQ_FRAG4 means nothing
+ * next to this bit, and composites that refuse quantised companions refuse these. */
+enum { VV_WQ_MXFP6 = 0x800 };
 /* A LEAN MXFP4 LLM (vv_llm with VV_WQ_MXFP4): every layer's five bf16 pointers (wqkv, wo, wgate, wup, wdown) are NULL beside present companions
  * (q_*.q and q_*.scale) - no descriptor bit, the NULL pointers say it; all five of all layers or none (a mix is VV_E_ARG).  hidden, inter and
  * heads * head_dim must be multiples of 128 and the qkv width a multiple of 16 (what VV_LIN_W_MXGEMM takes).  vv_llm_forward and
@@ -149,7 +172,7 @@ typedef struct vv_lin_args {
   float* out;
   int64_t ldo;
   int flags;   /* VV_LIN_* */
-  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4 / VV_MXFP4_FRAG: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
+  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4 / VV_MXFP4_FRAG / VV_MXFP6: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
   const float* w2scale;
 } vv_lin_args;
 
@@ -160,9 +183,10 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
  * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call;
  * "skinny<nst=20,nb=1>" for the resampling convs' skinny GEMM (k = 4 waves x nb bursts x nst steps of 32) and
  * "gemm_f32<w=bf16,dual=0,vec=1,tile=32>" for the fp32 LDS-tiled GEMM (w f32 | bf16; vec: float4 loads; tile 32 | 64); and for the
- * m <= 8 family (fp8, NF4 and MXFP4 weights included) the kernel itself:
+ * m <= 8 family (fp8, NF4, MXFP4 and MXFP6 weights included) the kernel itself:
  *   "gemv_stream<m=2,dual=0,ksplit=4,ku=3,rw=2,wq=bf16>"                   streaming GEMV (m: 1, 2, 4 or 8 = the template's row count; wq bf16 | fp8 | nf4)
  *   "gemv_mx<m=2,dual=0,ksplit=4,ku=3>"                                    streaming GEMV on VV_MXFP4 weights (m: 1 or 2)
+ *   "gemv_mx6<m=2,dual=0,ksplit=5,ku=1>"                                   streaming GEMV on VV_MXFP6 weights (m: 1 or 2; ksplit waves of a block split K, ku units of 2048 k each)
  *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
  *   "gemv_rows_mx<dual=0,nw=4,ks=3,pers=0> ksplit=6 atomic=0"              the same on VV_MXFP4_FRAG weights (ks: 128-wide weight loads per wave)
  *   "gemv_rows16<dual=0,nw=4,ks=3,pers=0> ksplit=5 atomic=0"               9..16 rows on VV_LIN_W_FRAG bf16 weights: two row tiles per weight load (same condition)
@@ -298,8 +322,9 @@ int vv_advance_lens(int* lens, const int* token, int tok_start, int tok_diffusio
  * ------------------------------------------------------------------------------------------------------------ */
 /* Optional weight-only fp8 companion of a matrix for the batch-1/2 decode GEMVs: e4m3fn bytes [N, K] and one
  * fp32 scale per output row.  q == NULL: not quantised.  The bf16 matrix stays the operand of every GEMM-shaped use (prefill, T > 2). */
-/* With VV_WQ_NF4 / VV_WQ_MXFP4 in the descriptor's wdt the same pair holds an NF4 or MXFP4 companion: q = the packed codes, scale = the block absmax
- * (NF4, fp32) or the address of the E8M0 scale bytes (MXFP4, read as uint8_t), in the VV_NF4 / VV_MXFP4 layouts above. */
+/* With VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 in the descriptor's wdt the same pair holds an NF4, MXFP4 or MXFP6 companion: q = the packed codes,
+ * scale = the block absmax (NF4, fp32) or the address of the E8M0 scale bytes (MXFP4, MXFP6, read as uint8_t), in the VV_NF4 / VV_MXFP4 / VV_MXFP6
+ * layouts above. */
 typedef struct vv_w8 { const void* q; const float* scale; } vv_w8;
 
 typedef struct vv_llm_layer {

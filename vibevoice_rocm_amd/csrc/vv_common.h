@@ -43,6 +43,14 @@ struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, b
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
 int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
+// vv_gemv_mx6.hip: gemv_mx6_kernel<m, dual, ksplit, ku>, the VV_MXFP6 weights' streaming GEMV (m <= 2), named gemv_mx6<m, dual, ksplit, ku>.
+// vv_gemv_mx6_refusal is the only copy of what such a call must be (NULL = taken, else what it lacks; no launch, no pointer followed)
+struct vv_mx6_route { int kind, m, dual, ksplit, ku, n_groups, blocks, threads; };
+const char* vv_gemv_mx6_refusal(const vv_lin_args& a);
+vv_mx6_route vv_gemv_mx6_decide(const vv_lin_args& a);
+int vv_launch_gemv_mx6_route(const vv_lin_args& a, const vv_mx6_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0
+int vv_gemv_mx6_route_name(const vv_mx6_route& r, char* name, int cap);
+void vv_gemv_mx6_set_blocks(int b);                               // tuning hook "gemv_blocks", next to the streaming GEMV's
 // vv_gemv_hot.hip: the shape table of the hand-specialised decode GEMVs.  A bf16 vv_linear call whose (m, n, k, dual, prologue kind, epilogue
 // kind, flags) equals an entry runs that entry's own kernel when bit i of vv_tune("gemv_hot") is set; every other call takes the generic
 // template.  dual: w2 != NULL; mod: adaLN shift / scale rows; bias / gate (per row, gate_ld != 0) / res: that operand is present.

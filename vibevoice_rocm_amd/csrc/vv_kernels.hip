@@ -78,7 +78,7 @@ void vv_attn_decode_set_gqa_keys(int k);
 extern "C" int vv_tune(const char* key, int value) {   // developer tuning hooks (not part of the stable ABI surface)
   if (key && !strcmp(key, "gemv_long_cap")) { vv_gemv_stream_set_long(value, 0); return 0; }
   if (key && !strcmp(key, "gemv_long_ku")) { vv_gemv_stream_set_long(0, value); return 0; }
-  if (key && !strcmp(key, "gemv_blocks")) { vv_gemv_stream_set_blocks(value); return 0; }
+  if (key && !strcmp(key, "gemv_blocks")) { vv_gemv_stream_set_blocks(value); vv_gemv_mx6_set_blocks(value); return 0; }
   if (key && !strcmp(key, "gemv_waves")) { vv_gemv_stream_set_waves(value); return 0; }
   if (key && !strcmp(key, "gemv_rows")) { vv_gemv_rows_set(value, 0, -1); return 0; }
   if (key && !strcmp(key, "gemv_rows_blocks")) { vv_gemv_rows_set(-1, value, -1); return 0; }
@@ -500,9 +500,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
 // The m <= 8 family's decision (vv_linear launches it, vv_linear_route prints it): the 3..8-row matrix-core GEMV when the process-wide scratch is
 // on, the weight-streaming GEMV (or a hot kernel), two streaming passes of 4 + rest rows, the LDS-staged gemv_kernel<WT, M, DUAL, KS, NP> or the
 // generic kernel.  Plain values only: no pointer is followed, nothing is launched; the thresholds live here and in the two deciders it calls.
-enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC };
+enum { GEMV_ROWS = 1, GEMV_STREAM, GEMV_SPLIT, GEMV_LDS, GEMV_GENERIC, GEMV_MX6 };
 struct gemv_route {
   int kind;
+  vv_mx6_route mx6;                  // GEMV_MX6: VV_MXFP6 weights (vv_gemv_mx6.hip)
   vv_rows_route rows;                // GEMV_ROWS
   vv_stream_route st, st2;          // GEMV_SPLIT: rows 0..3 and the rest
   int m, dual, ks, np, kc, blocks;  // GEMV_LDS: gemv_kernel<WT, m, dual, ks, np> staging kc columns at a time; GEMV_GENERIC: blocks
@@ -574,6 +575,12 @@ static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights need m <= 2, k %% 32 == 0 (at most 40 units of 512, SwiGLU 24), scale bytes and 16-byte aligned "
                         "codes, scales and activations (m=%d k=%d)", a.m, a.k);
   }
+  if (a.wdt == VV_MXFP6) {
+    // weight-only MXFP6 has a streaming GEMV of its own (<= 2 rows, vv_gemv_mx6.hip) and nothing else; linear_check_args has asked vv_gemv_mx6_refusal
+    g->mx6 = vv_gemv_mx6_decide(a);
+    if (g->mx6.kind) { g->kind = GEMV_MX6; return 0; }
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: no MXFP6 kernel for m=%d k=%d", a.m, a.k);
+  }
   if (a.wdt == VV_FP8 || a.wdt == VV_NF4) {
     // weight-only fp8 / NF4 exist for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix (of the effective weights)
     g->st = vv_gemv_stream_decide(a);
@@ -618,6 +625,7 @@ static void gemv_route_name(const vv_lin_args& a, const gemv_route& g, char* nam
   const char* w = a.wdt == VV_F32 ? "f32" : "bf16";
   if (g.kind == GEMV_ROWS) vv_gemv_rows_route_name(g.rows, name, cap);
   else if (g.kind == GEMV_STREAM) vv_gemv_stream_route_name(g.st, name, cap);
+  else if (g.kind == GEMV_MX6) vv_gemv_mx6_route_name(g.mx6, name, cap);
   else if (g.kind == GEMV_SPLIT) {
     char lo[96], hi[96];
     vv_gemv_stream_route_name(g.st, lo, sizeof(lo));
@@ -667,6 +675,7 @@ static int launch_gemv_route(const vv_lin_args& a, const gemv_route& g, hipStrea
   switch (g.kind) {
     case GEMV_ROWS: return vv_launch_gemv_rows_route(a, g.rows, g_rows_part, g_rows_tk, s) == 1 ? 0 : vv_set_error(VV_E_HIP, "vv_linear: rows GEMV declined its own route");
     case GEMV_STREAM: return vv_launch_gemv_stream_route(a, g.st, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: streaming GEMV declined its own route");
+    case GEMV_MX6: return vv_launch_gemv_mx6_route(a, g.mx6, s) ? 0 : vv_set_error(VV_E_HIP, "vv_linear: MXFP6 GEMV declined its own route");
     case GEMV_SPLIT: {
       vv_lin_args lo = a;
       lo.m = 4;
@@ -822,6 +831,10 @@ static int linear_check_args(const vv_lin_args* a) {
   if (a->wdt == VV_MXFP4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 32 || !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights exist for the streaming GEMV alone: m <= 2, k %% 32 == 0, wscale (w2scale), "
                         "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
+  if (a->wdt == VV_MXFP6) {      // the one copy of what an MXFP6 call must be lives with its kernel
+    const char* lacks = vv_gemv_mx6_refusal(*a);
+    if (lacks) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP6 weights exist for the streaming GEMV alone, which needs %s (m=%d k=%d flags=%d)", lacks, a->m, a->k, a->flags);
+  }
   if (a->wdt == VV_MXFP4_FRAG && (!(a->flags & VV_LIN_W_FRAG) || (a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 128 ||
                                   !a->wscale || (a->w2 && !a->w2scale)))
     return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights exist for the 3..8-row matrix-core GEMV alone: VV_LIN_W_FRAG, 3 <= m <= 8, n %% 16 == 0, "
@@ -852,7 +865,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     else if (fam == LIN_FAM_SKINNY) vv_skinny_route_name(vv_skinny_decide(*a), name, cap);
     else if (fam == LIN_FAM_GEMM_F32) gemm_f32_route_name(*a, gemm_f32_decide(*a), name, cap);
   }
-  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG && a->wdt != VV_MXFP6) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (a->flags & VV_LIN_W_MXGEMM) { vv_gemm_mx_route_name(*a, name, cap); return 0; }      // linear_check_args has asked vv_gemm_mx_check
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
@@ -876,7 +889,7 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   if (a->flags & VV_LIN_W_MXGEMM) rc = vv_launch_gemm_mx(*a, s);      // wdt == VV_MXFP4 and everything else the kernel needs: linear_check_args
   else if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
-  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4 || a->wdt == VV_MXFP4_FRAG) {   // weight-only fp8 / NF4 / MXFP4: the rows or a streaming GEMV, or refused (gemv_decide)
+  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4 || a->wdt == VV_MXFP4_FRAG || a->wdt == VV_MXFP6) {   // weight-only fp8 / NF4 / MXFP4 / MXFP6: the rows or a streaming GEMV, or refused (gemv_decide)
     gemv_route g;
     rc = gemv_decide(*a, &g);
     if (!rc) rc = launch_gemv_route<bf16_t>(*a, g, s);

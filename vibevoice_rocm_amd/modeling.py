@@ -84,7 +84,7 @@ def weight_quant_from_config(quantization_config, weight_quant: Optional[str] = 
             return quantization_config.get(name, default)
         return getattr(quantization_config, name, default)
 
-    built = "built: 4-bit NF4 (load_in_4bit=True, bnb_4bit_quant_type='nf4', or weight_quant='nf4'), weight-only fp8 (weight_quant='fp8') and weight-only OCP MXFP4 (weight_quant='mxfp4')"
+    built = "built: 4-bit NF4 (load_in_4bit=True, bnb_4bit_quant_type='nf4', or weight_quant='nf4'), weight-only fp8 (weight_quant='fp8'), weight-only OCP MXFP4 (weight_quant='mxfp4') and weight-only OCP MXFP6 e2m3 (weight_quant='mxfp6')"
     if get("load_in_8bit", False):
         raise NotImplementedError(f"load_in_8bit is not built; {built}")
     if not get("load_in_4bit", False):
@@ -800,6 +800,8 @@ class VibeVoiceForConditionalGenerationInference:
         # "nf4": weight-only 4-bit NF4 companions for the same GEMVs (batches of >= 2 run on the lanes)
         # "mxfp4": weight-only OCP MXFP4 companions (e2m1 codes, one power-of-two scale byte per 32 k) decoded by the vector ALU's own
         # conversion instruction (batches of >= 2 run on the lanes, sessions refuse it - unless mxfp4_row_batch=True)
+        # "mxfp6": weight-only OCP MXFP6 companions (e2m3 codes, 6.25 bits per weight: fp8's mantissa at 0.78 of its bytes), decoded 32 at a time
+        # by v_cvt_scalef32_pk32_f32_fp6 (batches of >= 2 run on the lanes, sessions refuse it)
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
                              prequant=prequant, kv_cache_dtype=kv_cache_dtype, mxfp4_row_batch=self.mxfp4_row_batch,

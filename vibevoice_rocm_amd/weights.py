@@ -222,6 +222,85 @@ def mxfp4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Di
     return out
 
 
+# OCP Microscaling (MX v1.0) FP6, the e2m3 variant: 1 sign, 2 exponent, 3 mantissa bits (codes 0..31 below, 32..63 the same values negated) -
+# subnormals m / 8 for m = 0..7, normals (1 + m / 8) * 2^(E - 1) for E = 1..3, the largest 7.5; 32-element blocks with one E8M0 scale byte
+MXFP6_VALUES = tuple(m / 8.0 for m in range(8)) + tuple((1.0 + m / 8.0) * 2.0 ** (E - 1) for E in (1, 2, 3) for m in range(8))
+MXFP6_BLOCK = 32
+MXFP6_SCALE_MIN, MXFP6_SCALE_MAX, MXFP6_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
+# Element i of a block sits in bits 6 i .. 6 i + 5 of the 192-bit operand of v_cvt_scalef32_pk32_*_fp6, counted from bit 0 of the first dword
+# (tests/test_hip_mxfp6.py::test_decode_is_exact is the witness: the hardware reads every code back from there)
+
+
+def quantize_mxfp6(w: torch.Tensor):
+    """Weight-only MXFP6 (e2m3) of a [N, K] matrix (K % 32 == 0), the OCP MX v1.0 conversion:
+      * blocks are 32 consecutive weights along K within an output row;
+      * scale byte e = clamp(floor(log2(max |w|)) - 2 + 127, 2, 252), worth 2^(e - 127) (2 = the exponent of e2m3's largest value 7.5 =
+        1.875 * 2^2); an all-zero block gets 127;
+      * element = w / scale rounded to nearest, ties to even, on the e2m3 grid (spacing 1/8 below 2, 1/4 below 4, 1/2 up to 7.5), saturating at
+        +-7.5; a value that rounds to zero takes code 0 (never the negative zero, code 32);
+      * effective weight = value(code) * 2^(e - 127): four significant bits times a power of two, exact in bf16 (and so in fp32).
+    Returns (codes uint8 [N, K] in 0..63, scale bytes uint8 [N, K / 32], effective weights fp32 [N, K])."""
+    n, k = w.shape
+    if k % MXFP6_BLOCK:
+        raise ValueError(f"MXFP6 needs K % {MXFP6_BLOCK} == 0 (K={k})")
+    wf = w.detach().float().reshape(n, k // MXFP6_BLOCK, MXFP6_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    zero = amax == 0
+    ex = torch.frexp(torch.where(zero, torch.ones_like(amax), amax))[1] - 1      # floor(log2(amax)), exact: amax = m 2^ex', m in [0.5, 1)
+    e = torch.where(zero, torch.full_like(ex, MXFP6_SCALE_ONE), (ex - 2 + 127).clamp(MXFP6_SCALE_MIN, MXFP6_SCALE_MAX))
+    # w / 2^(e - 127) in fp64: the quotient by a power of two is exact there for every fp32 w and every scale byte
+    x = wf.double() * torch.exp2((127 - e).double())[..., None]
+    a = x.abs()
+    # round to nearest even on the grid: spacing 1/8 below 2 (subnormals and E = 1), 1/4 below 4, 1/2 above (torch.round is half-to-even)
+    q = torch.where(a < 2.0, torch.round(a * 8.0) / 8.0, torch.where(a < 4.0, torch.round(a * 4.0) / 4.0, torch.round(a * 2.0) / 2.0)).clamp_max(7.5)
+    grid = torch.tensor(MXFP6_VALUES, dtype=torch.float64, device=q.device)
+    mag = torch.searchsorted(grid, q.contiguous()).to(torch.uint8)               # q is on the grid: its index
+    codes = torch.where((x < 0) & (mag > 0), mag + 32, mag).to(torch.uint8)
+    eff = (torch.where(x < 0, -q, q) * torch.exp2((e - 127).double())[..., None]).float()
+    eff = torch.where(mag == 0, torch.zeros_like(eff), eff)                      # +0, as code 0 decodes
+    return codes.reshape(n, k).contiguous(), e.to(torch.uint8).contiguous(), eff.reshape(n, k).contiguous()
+
+
+def pack_mxfp6(codes: torch.Tensor, scales: torch.Tensor):
+    """(codes uint8 [N, K], scale bytes uint8 [N, K / 32]) -> the VV_MXFP6 layout (include/vv_hip.h); rows past N hold code 0 / scale byte 127
+    (K is never padded: K % 32 == 0).  With G = ceil(N / 4) row groups and B = K / 32 blocks per row, a block's 24 bytes (element i in bits
+    6 i .. 6 i + 5) are split into a 16-byte and an 8-byte plane: codes [G][ plane A [4 rows][B][16 B] | plane B [4 rows][B][8 B] ],
+    scale bytes [G][B][4 rows].  Returns (uint8 1-D, uint8 1-D)."""
+    n, k = codes.shape
+    nq, nb = (n + 3) // 4, k // MXFP6_BLOCK
+    c = torch.zeros(nq * 4, k, dtype=torch.uint8, device=codes.device)
+    c[:n] = codes
+    bits = (c.view(nq, 4, nb, 32, 1) >> torch.arange(6, device=c.device, dtype=torch.uint8)) & 1          # [q, r, b, element, bit]: the 192-bit string
+    by = (bits.reshape(nq, 4, nb, 24, 8) << torch.arange(8, device=c.device, dtype=torch.uint8)).sum(dim=-1, dtype=torch.uint8)   # 24 bytes per block
+    packed = torch.cat([by[..., :16].reshape(nq, -1), by[..., 16:].reshape(nq, -1)], dim=1).contiguous().view(-1)
+    s = torch.full((nq * 4, nb), MXFP6_SCALE_ONE, dtype=torch.uint8, device=scales.device)
+    s[:n] = scales
+    sb = s.view(nq, 4, nb).permute(0, 2, 1).contiguous().view(-1)          # [q, block, r]
+    return packed, sb
+
+
+def unpack_mxfp6(packed: torch.Tensor, sb: torch.Tensor, n: int, k: int):
+    """Inverse of pack_mxfp6: (codes uint8 [N, K], scale bytes uint8 [N, K / 32])."""
+    nq, nb = (n + 3) // 4, k // MXFP6_BLOCK
+    p = packed.view(nq, 4 * nb * 24)
+    by = torch.cat([p[:, : 4 * nb * 16].reshape(nq, 4, nb, 16), p[:, 4 * nb * 16:].reshape(nq, 4, nb, 8)], dim=-1)          # [q, r, b, 24 bytes]
+    bits = ((by[..., None] >> torch.arange(8, device=by.device, dtype=torch.uint8)) & 1).reshape(nq, 4, nb, 32, 6)
+    codes = (bits << torch.arange(6, device=by.device, dtype=torch.uint8)).sum(dim=-1, dtype=torch.uint8).reshape(nq * 4, k)[:n].contiguous()
+    scales = sb.view(nq, nb, 4).permute(0, 2, 1).reshape(nq * 4, nb)[:n].contiguous()
+    return codes, scales
+
+
+def mxfp6_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The state dict a weight_quant="mxfp6" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
+    K % 32 == 0 replaced by the effective MXFP6 weights of its bf16 rounding (fp32 tensors; q/k/v quantise the same fused or apart, the blocks
+    lie inside rows).  A matrix with another K is left as it is."""
+    out = dict(sd)
+    for name in fp8_matrix_names(cfg):
+        if sd[name].shape[1] % MXFP6_BLOCK == 0:
+            out[name] = quantize_mxfp6(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
+    return out
+
+
 class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
@@ -249,9 +328,9 @@ class DeviceWeights:
                              "would need a three-way K split, which the row-batched step's partials workspace has no room for")
         self.mxfp4_row_batch = bool(mxfp4_row_batch)
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
-        if quant not in (None, "fp8", "nf4", "mxfp4"):
-            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3), 'nf4' (weight-only 4-bit NF4) or 'mxfp4' (weight-only OCP "
-                             "MXFP4), decode GEMVs, is built")
+        if quant not in (None, "fp8", "nf4", "mxfp4", "mxfp6"):
+            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3), 'nf4' (weight-only 4-bit NF4), 'mxfp4' (weight-only OCP "
+                             "MXFP4) or 'mxfp6' (weight-only OCP MXFP6 e2m3), decode GEMVs, is built")
         if quant is not None and wdtype != torch.bfloat16:
             raise ValueError(f"weight_quant={quant!r} keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
         if prequant and quant != "nf4":
@@ -260,8 +339,8 @@ class DeviceWeights:
         self._pre = dict(prequant or {})
         self._fp8_names = set(fp8_matrix_names(cfg)) if quant is not None else set()     # the matrices that get a companion
         self.wdt = _wdt(wdtype)
-        # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 mark their vv_w8 companions as NF4 / MXFP4 (vv_hip.h); self.wdt stays the plain matrix dtype
-        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else L.VV_WQ_MXFP4 if quant == "mxfp4" else 0)
+        # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 mark their vv_w8 companions as NF4 / MXFP4 / MXFP6 (vv_hip.h); self.wdt stays the plain matrix dtype
+        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else L.VV_WQ_MXFP4 if quant == "mxfp4" else L.VV_WQ_MXFP6 if quant == "mxfp6" else 0)
         # vv_llm / vv_head: VV_WQ_FRAG4 says their layers' f_* copies hold the VV_MXFP4_FRAG form (never a bf16 fragment copy)
         self.desc_wdt_rows = self.desc_wdt | (L.VV_WQ_FRAG4 if self.mxfp4_row_batch else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
@@ -337,7 +416,8 @@ class DeviceWeights:
         """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
         mode it holds the effective weights bf16(table[code] * absmax) and the companion the packed codes and block scales (pack_nf4).
         An NF4 matrix with K % 64 != 0 gets no companion.  In mxfp4 mode the bf16 copy holds value(code) * 2^(e - 127) (exact) and the
-        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion.  lean (a name for
+        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion; mxfp6 mode is mxfp4 mode with
+        quantize_mxfp6 / pack_mxfp6.  lean (a name for
         lean_report, mxfp4 only): the bf16 copy is not made - (None, companion); the effective matrix lives while the codes are packed."""
         w8 = L.W8()
         if self.quant == "nf4" and quantise and t.shape[1] % NF4_BLOCK == 0:
@@ -357,6 +437,13 @@ class DeviceWeights:
                 n, k = t.shape
                 self._lean_dropped.append({"name": lean, "n": int(n), "k": int(k), "bytes": 2 * int(n) * int(k)})
                 return None, w8
+            return self._mat(eff), w8
+        if self.quant == "mxfp6" and quantise and t.shape[1] % MXFP6_BLOCK == 0:
+            codes, sbytes, eff = quantize_mxfp6(t.to(device=self.device, dtype=torch.bfloat16))   # the bf16 weight, widened
+            packed, sb = pack_mxfp6(codes, sbytes)
+            packed, sb = self._aligned(packed), self._aligned(sb)
+            self._keep += [packed, sb]
+            w8.q, w8.scale = L.ptr(packed), L.ptr(sb)          # the address of the scale BYTES, as for MXFP4 (vv_hip.h, VV_MXFP6)
             return self._mat(eff), w8
         if not (quantise and self.quant == "fp8"):
             return self._mat(t), w8
