@@ -33,6 +33,29 @@ struct vv_kv_args8 : vv_kv_args {
   vv_kv_args8(const vv_kv& a) : vv_kv_args(a), kscale(a.kscale), vscale(a.vscale) {}
 };
 
+// The companions' kind that rides on a descriptor's wdt (VV_WQ_*, vv_hip.h), one line per format: the first bit found wins, no bit = fp8, and vv_wq_strip leaves the matrix dtype in *wdt
+static constexpr struct { int bit, wq; } VV_WQ_KINDS[] = {
+  {VV_WQ_MXFP6, VV_MXFP6},
+  {VV_WQ_MXFP4, VV_MXFP4},
+  {VV_WQ_NF4, VV_NF4},
+};
+constexpr int vv_wq_bits() { int bits = VV_WQ_FRAG4; for (const auto& k : VV_WQ_KINDS) bits |= k.bit; return bits; }
+struct vv_wq_kind { int wq; bool frag4; };
+static inline vv_wq_kind vv_wq_strip(int* wdt) {
+  vv_wq_kind r = {VV_FP8, false};
+  for (const auto& k : VV_WQ_KINDS) if (*wdt & k.bit) { r.wq = k.wq; break; }
+  r.frag4 = r.wq == VV_MXFP4 && (*wdt & VV_WQ_FRAG4) != 0;
+  *wdt &= ~vv_wq_bits();
+  return r;
+}
+// The weight-only formats' refusals, one per kernel unit and the only copy of what a call on that unit's formats must be: NULL = taken so far
+// (the unit's decision may still find no kernel at this K), else the words for what the call lacks.  Values and alignments only.  *rc (rc may
+// be NULL) comes in as VV_E_UNSUPPORTED; a refusal makes it VV_E_ARG where the call is malformed, not merely unserved (fp8 with a bf16 hand-off
+// or a shape its fragment-major layout cannot have).  linear_check_args asks them through WQ_FORMATS (vv_kernels.hip), each decision its own.
+const char* vv_gemv_stream_refusal(const vv_lin_args& a, int* rc);   // VV_FP8 (row-major), VV_NF4, VV_MXFP4
+const char* vv_gemv_mx6_refusal(const vv_lin_args& a, int* rc);      // VV_MXFP6
+const char* vv_gemv_rows_refusal(const vv_lin_args& a, int* rc);     // VV_MXFP4_FRAG, VV_FP8 under VV_LIN_W_FRAG
+
 // The decode GEMV family (m <= 8).  Every launcher is a DECISION - a plain struct computed from the arguments and the vv_tune state, no pointer
 // followed, no HIP call, the only copy of the thresholds - and a LAUNCH of that struct; vv_linear_route prints the same struct, so the name it
 // reports is the kernel vv_linear starts.  kind 0 = not covered (the caller falls back).
@@ -43,10 +66,8 @@ struct vv_stream_route { int kind, idx, m, dual, ksplit, ku, rw, wq, n_groups, b
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a);
 int vv_launch_gemv_stream_route(const vv_lin_args& a, const vv_stream_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0 or no such kernel
 int vv_gemv_stream_route_name(const vv_stream_route& r, char* name, int cap);
-// vv_gemv_mx6.hip: gemv_mx6_kernel<m, dual, ksplit, ku>, the VV_MXFP6 weights' streaming GEMV (m <= 2), named gemv_mx6<m, dual, ksplit, ku>.
-// vv_gemv_mx6_refusal is the only copy of what such a call must be (NULL = taken, else what it lacks; no launch, no pointer followed)
+// vv_gemv_mx6.hip: gemv_mx6_kernel<m, dual, ksplit, ku>, the VV_MXFP6 weights' streaming GEMV (m <= 2), named gemv_mx6<m, dual, ksplit, ku>
 struct vv_mx6_route { int kind, m, dual, ksplit, ku, n_groups, blocks, threads; };
-const char* vv_gemv_mx6_refusal(const vv_lin_args& a);
 vv_mx6_route vv_gemv_mx6_decide(const vv_lin_args& a);
 int vv_launch_gemv_mx6_route(const vv_lin_args& a, const vv_mx6_route& r, hipStream_t s);   // 1 = launched, 0 = r.kind == 0
 int vv_gemv_mx6_route_name(const vv_mx6_route& r, char* name, int cap);

@@ -404,8 +404,8 @@ constexpr bool mx6_exists(int m, bool dual, int ksplit, int ku) {
 
 void vv_gemv_mx6_set_blocks(int b) { g_blocks_override = b; }
 
-// The one copy of what a VV_MXFP6 call must be (vv_hip.h): 0 = taken, else the reason it is refused.  Reads values and alignments only.
-const char* vv_gemv_mx6_refusal(const vv_lin_args& a) {
+// The one copy of what a VV_MXFP6 call must be (vv_hip.h): 0 = taken, else the reason it is refused (VV_E_UNSUPPORTED).  Reads values and alignments only.
+const char* vv_gemv_mx6_refusal(const vv_lin_args& a, int*) {
   if (a.flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16 | VV_LIN_W_MXGEMM)) return "no VV_LIN_W_FRAG, bf16 hand-off or VV_LIN_W_MXGEMM";
   if (a.m < 1 || a.m > 2) return "m <= 2";
   if (a.k % 32) return "k % 32 == 0";
@@ -422,7 +422,7 @@ const char* vv_gemv_mx6_refusal(const vv_lin_args& a) {
 // The decision: kind 0 = refused (vv_gemv_mx6_refusal says why).  One wave per 2048-wide unit of the row; 7 waves run as 8, 9 as 10, 11 as 12.
 vv_mx6_route vv_gemv_mx6_decide(const vv_lin_args& a) {
   vv_mx6_route r = {};
-  if (vv_gemv_mx6_refusal(a)) return r;
+  if (vv_gemv_mx6_refusal(a, nullptr)) return r;
   const int units = (a.k + 2047) / 2048;
   r.m = a.m; r.dual = a.w2 != nullptr; r.ku = 1;
   r.ksplit = units <= 6 ? units : (units + 1) & ~1;

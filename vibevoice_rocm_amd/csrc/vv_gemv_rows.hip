@@ -247,6 +247,24 @@ int vv_gemv_rows_init() {
   return 0;
 }
 
+// The one copy of what a call on this unit's weight-only formats must be (vv_common.h): fragment-major fp8 codes and VV_MXFP4_FRAG, 3..8 fp32 rows,
+// whole row groups and weight loads, scales for every matrix; an fp8 call outside that names a layout that does not exist (VV_E_ARG).  What
+// bf16 calls need too (aligned operands, a row pitch) stays with the decision below.
+const char* vv_gemv_rows_refusal(const vv_lin_args& a, int* rc) {
+  const bool fp8 = a.wdt == VV_FP8;
+  const char* lacks = nullptr;
+  if (!fp8 && a.wdt != VV_MXFP4_FRAG) return "VV_FP8 or VV_MXFP4_FRAG weights";
+  if (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) lacks = "fp32 activations and outputs (no bf16 hand-off)";
+  else if (a.m < 3 || a.m > 8) lacks = "3..8 rows";
+  else if (a.n < 16 || a.n % 16) lacks = "n % 16 == 0";
+  else if (a.k % (fp8 ? 64 : 128)) lacks = fp8 ? "k % 64 == 0" : "k % 128 == 0";
+  else if (!a.wscale || (a.w2 && !a.w2scale)) lacks = fp8 ? "wscale (w2scale)" : "scale bytes for w (and w2)";
+  if (lacks) { if (fp8 && rc) *rc = VV_E_ARG; return lacks; }
+  if (!(a.flags & VV_LIN_W_FRAG)) return "VV_LIN_W_FRAG (the fragment-major copy)";
+  if (!fp8 && ((uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4))) return "4-byte aligned scale bytes";
+  return nullptr;
+}
+
 // The decision: which instantiation the call takes, its K split and grid; kind 0 = not covered (the caller falls back).  have_ws: a split-K
 // workspace of part_floats floats and n_tickets tickets exists (without one only shapes that need no K split, or the atomic form, are taken).
 // fp8 and MXFP4 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
@@ -264,18 +282,16 @@ vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t par
   vv_rows_route r = {};
   const int wf = a.wdt == VV_BF16 ? WF_BF16 : a.wdt == VV_FP8 ? WF_FP8 : a.wdt == VV_MXFP4_FRAG ? WF_MXFP4 : -1;
   if (!g_rows_on || wf < 0 || a.m < 3 || a.m > 16) return r;
+  if (wf != WF_BF16 && vv_gemv_rows_refusal(a, nullptr)) return r;
   r.rt = a.m > 8 ? 2 : 1;                             // 9 .. 16 rows: gemv_rows16_kernel, on the fragment-major bf16 copy only
-  if (r.rt == 2 && (wf != WF_BF16 || !(a.flags & VV_LIN_W_FRAG))) return r;
+  if (r.rt == 2 && !(a.flags & VV_LIN_W_FRAG)) return r;
   const int kw = 32 * rows_fpl(wf);                   // k per weight load
   if (a.k % kw || a.k < kw) return r;
   if (a.pro == VV_PRO_SILU || (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a.ldx == 0) return r;
   if ((uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) || (uintptr_t)a.x % 16 || a.ldx % 4) return r;
   if (a.norm_w && (uintptr_t)a.norm_w % 16) return r;
   if (a.mod_scale && ((uintptr_t)a.mod_scale % 16 || (uintptr_t)a.mod_shift % 16 || a.ld_mod % 4)) return r;
-  if (wf == WF_BF16) {
-    if ((a.flags & VV_LIN_W_FRAG) && a.n % 16) return r;
-  } else if (!(a.flags & VV_LIN_W_FRAG) || a.n % 16 || !a.wscale || (a.w2 && !a.w2scale)) return r;
-  if (wf == WF_MXFP4 && (a.n < 16 || (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4))) return r;
+  if (wf == WF_BF16 && (a.flags & VV_LIN_W_FRAG) && a.n % 16) return r;
   const bool dual = a.w2 != nullptr;
   const int steps = a.k / kw, n_groups = (a.n + 15) / 16;
   r.n_groups = n_groups; r.atomic = 0;

@@ -792,22 +792,35 @@ void vv_gemv_stream_set_long(int cap, int ku) { if (cap > 0) g_long_cap = cap; i
 void vv_gemv_stream_set_dual_rw(int r) { g_dual_rw = r; }
 void vv_gemv_stream_set_small_rw(int r) { g_small_rw = r; }
 
+// The one copy of what a call on this unit's weight-only formats must be (vv_common.h): decode rows, whole blocks, scales for every matrix, codes
+// and scales aligned for the format's loads, row-major, fp32 in and out.  The activations' alignment and the reach in K stay with the decision.
+const char* vv_gemv_stream_refusal(const vv_lin_args& a, int* rc) {
+  const bool handoff = (a.flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) != 0, scales = a.wscale && (!a.w2 || a.w2scale);
+  const auto aligned = [&](const void* p, const void* p2, int al) { return (uintptr_t)p % al == 0 && (!a.w2 || (uintptr_t)p2 % al == 0); };
+  if (a.wdt == VV_FP8) {        // e4m3fn codes, one fp32 scale per output row
+    if (handoff) { if (rc) *rc = VV_E_ARG; return "fp32 activations and outputs (the bf16 hand-off is for bf16 weights)"; }
+    if (a.m > 2) return "m <= 2 (3..8 rows read the fragment-major copy, VV_LIN_W_FRAG)";
+    if (a.k % 8) return "k % 8 == 0";
+    if (!scales) return "row scales for w (and w2)";
+    if (!aligned(a.w, a.w2, 8)) return "8-byte aligned rows";
+    return nullptr;
+  }
+  if (a.wdt != VV_NF4 && a.wdt != VV_MXFP4) return "VV_FP8, VV_NF4 or VV_MXFP4 weights";
+  const bool nf4 = a.wdt == VV_NF4;      // NF4: 64-blocks, fp32 absmax; MXFP4: 32-blocks, E8M0 scale bytes read 16 at a time
+  if (handoff || (a.flags & VV_LIN_W_FRAG)) return "no VV_LIN_W_FRAG and no bf16 hand-off";
+  if (a.m < 1 || a.m > 2) return "m <= 2";
+  if (nf4 ? a.k % 64 : a.k % 32) return nf4 ? "k % 64 == 0" : "k % 32 == 0";
+  if (!scales) return nf4 ? "block scales for w (and w2)" : "scale bytes for w (and w2)";
+  if (!aligned(a.w, a.w2, 16)) return "16-byte aligned codes";
+  if (!aligned(a.wscale, a.w2scale, nf4 ? 4 : 16)) return nf4 ? "4-byte aligned block scales" : "16-byte aligned scale bytes";
+  return nullptr;
+}
+
 // The decision: which kernel of this file (or which hot kernel) the call takes, and on what grid.  kind 0 = the shape / alignment is not covered
-// (the caller falls back).  Reads the arguments' values and alignments and the tune state only.
+// (the caller falls back; MXFP4 reaches 40 units of 512, SwiGLU 24).  Reads the arguments' values and alignments and the tune state only.
 vv_stream_route vv_gemv_stream_decide(const vv_lin_args& a) {
   vv_stream_route r = {};
-  if ((a.wdt != VV_BF16 && a.wdt != VV_FP8 && a.wdt != VV_NF4 && a.wdt != VV_MXFP4) || a.m > 8 || a.k % 8) return r;
-  // NF4: decode rows only, whole 64-blocks, scales for every matrix, 16-byte aligned codes (vv_hip.h)
-  if (a.wdt == VV_NF4 && (a.m > 2 || a.k % 64 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 16 || (a.w2 && (uintptr_t)a.w2 % 16) ||
-                          (uintptr_t)a.wscale % 4 || (a.w2 && (uintptr_t)a.w2scale % 4) || (a.flags & VV_LIN_W_FRAG)))
-    return r;
-  if (a.wdt == VV_FP8 && (a.m > 2 || !a.wscale || (a.w2 && !a.w2scale) || (uintptr_t)a.w % 8 || (a.w2 && (uintptr_t)a.w2 % 8))) return r;
-  // MXFP4 (vv_hip.h): decode rows only, whole 32-blocks, a scale array for every matrix, 16-byte aligned codes and scales, no fragment-major flag,
-  // no bf16 hand-off; rows longer than the kernels reach (40 units, SwiGLU 24) find no kernel below
-  if (a.wdt == VV_MXFP4 && (a.m < 1 || a.m > 2 || a.k % 32 || !a.wscale || (a.w2 && !a.w2scale) ||
-                            (a.flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || (uintptr_t)a.w % 16 || (uintptr_t)a.wscale % 16 ||
-                            (a.w2 && ((uintptr_t)a.w2 % 16 || (uintptr_t)a.w2scale % 16))))
-    return r;
+  if (a.wdt == VV_BF16 ? (a.m > 8 || a.k % 8) : vv_gemv_stream_refusal(a, nullptr) != nullptr) return r;
   r.wq = a.wdt == VV_MXFP4 ? 3 : a.wdt == VV_NF4 ? 2 : a.wdt == VV_FP8 ? 1 : 0;
   if (a.m > 4) {
     if (a.w2 || a.wdt != VV_BF16) return r;

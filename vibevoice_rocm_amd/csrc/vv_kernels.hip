@@ -551,42 +551,38 @@ static void lds_decide(const vv_lin_args& a, gemv_route* g) {
   }
 }
 
+// The weight-only formats: one row per format, found by wdt (fp8: the fragment-major row first).  A format exists for one kernel unit alone -
+// GEMM-shaped calls use the bf16 matrix of the same effective weights - and that unit's refusal (vv_common.h) is the only copy of what a call
+// must be.  WQ_ROWS_WS: the rows unit, only while the process-wide split-K scratch is on (rows_scratch), as for bf16; WQ_ROWS: also without.
+enum { WQ_STREAM, WQ_MX6, WQ_ROWS, WQ_ROWS_WS };
+static const char* const WQ_UNIT_NAME[] = {"the weight-streaming GEMV", "the MXFP6 streaming GEMV", "the 3..8-row matrix-core GEMV", "the 3..8-row matrix-core GEMV"};
+static const struct wq_format { int wdt, flags; const char* name; int unit; const char* (*refusal)(const vv_lin_args& a, int* rc); } WQ_FORMATS[] = {   // flags: the row serves the calls that carry them
+  {VV_FP8, VV_LIN_W_FRAG, "fp8 VV_LIN_W_FRAG", WQ_ROWS_WS, vv_gemv_rows_refusal},
+  {VV_FP8, 0, "fp8", WQ_STREAM, vv_gemv_stream_refusal},
+  {VV_NF4, 0, "NF4", WQ_STREAM, vv_gemv_stream_refusal},
+  {VV_MXFP4, 0, "MXFP4", WQ_STREAM, vv_gemv_stream_refusal},
+  {VV_MXFP4_FRAG, 0, "VV_MXFP4_FRAG", WQ_ROWS, vv_gemv_rows_refusal},
+  {VV_MXFP6, 0, "MXFP6", WQ_MX6, vv_gemv_mx6_refusal},
+};
+static const wq_format* wq_format_of(const vv_lin_args& a) {
+  for (const wq_format& f : WQ_FORMATS)
+    if (a.wdt == f.wdt && (a.flags & f.flags) == f.flags) return &f;
+  return nullptr;
+}
+
 // < 0 = error (the call is refused: nothing may be launched)
 static int gemv_decide(const vv_lin_args& a, gemv_route* g) {
   *g = gemv_route{};
-  if (a.wdt == VV_FP8 && (a.flags & VV_LIN_W_FRAG)) {
-    // fp8 fragment-major weights: the 3..8-row matrix-core GEMV (process-wide split-K scratch as for bf16, see rows_scratch)
-    if (g_rows_part) g->rows = vv_gemv_rows_decide(a, true, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
-    if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 VV_LIN_W_FRAG weights not covered by the 3..8-row matrix-core GEMV (m=%d n=%d k=%d)", a.m, a.n, a.k);
-  }
-  if (a.wdt == VV_MXFP4_FRAG) {
-    // fragment-major MXFP4: the 3..8-row matrix-core GEMV and nothing else (process-wide split-K scratch as for bf16)
-    g->rows = vv_gemv_rows_decide(a, g_rows_part != nullptr, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
-    if (g->rows.kind) { g->kind = GEMV_ROWS; return 0; }
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights need VV_LIN_W_FRAG, 3..8 rows, n %% 16 == 0, k %% 128 == 0, scale bytes, 16-byte aligned codes "
-                        "and activations, 4-byte aligned scales, fp32 activations and outputs, and split-K scratch for k > 2048 (m=%d n=%d k=%d flags=%d)",
-                        a.m, a.n, a.k, a.flags);
-  }
-  if (a.wdt == VV_MXFP4) {
-    // weight-only MXFP4 has the weight-streaming GEMV (<= 2 rows, gemv_stream_kernel's format 3) and nothing else
-    g->st = vv_gemv_stream_decide(a);
-    if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights need m <= 2, k %% 32 == 0 (at most 40 units of 512, SwiGLU 24), scale bytes and 16-byte aligned "
-                        "codes, scales and activations (m=%d k=%d)", a.m, a.k);
-  }
-  if (a.wdt == VV_MXFP6) {
-    // weight-only MXFP6 has a streaming GEMV of its own (<= 2 rows, vv_gemv_mx6.hip) and nothing else; linear_check_args has asked vv_gemv_mx6_refusal
-    g->mx6 = vv_gemv_mx6_decide(a);
-    if (g->mx6.kind) { g->kind = GEMV_MX6; return 0; }
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: no MXFP6 kernel for m=%d k=%d", a.m, a.k);
-  }
-  if (a.wdt == VV_FP8 || a.wdt == VV_NF4) {
-    // weight-only fp8 / NF4 exist for the weight-streaming GEMV alone (<= 2 rows); GEMM-shaped calls use the bf16 matrix (of the effective weights)
-    g->st = vv_gemv_stream_decide(a);
-    if (g->st.kind) { g->kind = GEMV_STREAM; return 0; }
-    if (a.wdt == VV_FP8) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: fp8 weights need m <= 2, k %% 8 == 0, scales and 8-byte aligned rows (m=%d k=%d)", a.m, a.k);
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights need m <= 2, k %% 64 == 0, scales and 16-byte aligned codes (m=%d k=%d)", a.m, a.k);
+  if (const wq_format* f = wq_format_of(a)) {      // a weight-only format: its unit's kernel or nothing (linear_check_args has asked the unit's refusal)
+    switch (f->unit) {
+      case WQ_STREAM: g->st = vv_gemv_stream_decide(a); if (g->st.kind) g->kind = GEMV_STREAM; break;
+      case WQ_MX6: g->mx6 = vv_gemv_mx6_decide(a); if (g->mx6.kind) g->kind = GEMV_MX6; break;
+      default:
+        if (g_rows_part || f->unit == WQ_ROWS) g->rows = vv_gemv_rows_decide(a, g_rows_part != nullptr, G_ROWS_PART_FLOATS, G_ROWS_TICKETS);
+        if (g->rows.kind) g->kind = GEMV_ROWS;
+    }
+    if (g->kind) return 0;
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: %s weights not covered by %s: no kernel for m=%d n=%d k=%d (K beyond its reach, misaligned activations or no split-K scratch)", f->name, WQ_UNIT_NAME[f->unit], a.m, a.n, a.k);
   }
   const bool dual = a.w2 != nullptr;
   const size_t wsz = a.wdt == VV_F32 ? sizeof(float) : sizeof(bf16_t);
@@ -820,26 +816,12 @@ static int linear_check_args(const vv_lin_args* a) {
   if (a->act != VV_ACT_SWIGLU && a->w2) return vv_set_error(VV_E_ARG, "vv_linear: w2 given without SWIGLU");
   if (a->mod_scale && (!a->mod_shift || a->pro != VV_PRO_RMSNORM)) return vv_set_error(VV_E_ARG, "vv_linear: modulate needs RMSNORM prologue and shift");
   if (a->m > 8 && a->ldx == 0) return vv_set_error(VV_E_ARG, "vv_linear: broadcast rows (ldx=0) only for m<=8");
-  if ((a->flags & VV_LIN_W_FRAG) && a->wdt == VV_FP8 &&
-      (a->m < 3 || a->m > 8 || a->n % 16 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
-    return vv_set_error(VV_E_ARG, "vv_linear: fp8 VV_LIN_W_FRAG weights need 3..8 rows, n %% 16 == 0, k %% 64 == 0 and wscale (w2scale) (m=%d n=%d k=%d)",
-                        a->m, a->n, a->k);
   if (a->flags & VV_LIN_W_MXGEMM) return vv_gemm_mx_check(*a);      // the GEMM on MXFP4 codes: its own unit says what it takes, every other rule below is for calls without the bit
-  if (a->wdt == VV_NF4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 64 || !a->wscale || (a->w2 && !a->w2scale)))
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: NF4 weights exist for the streaming GEMV alone: m <= 2, k %% 64 == 0, wscale (w2scale), "
-                        "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
-  if (a->wdt == VV_MXFP4 && ((a->flags & (VV_LIN_W_FRAG | VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m > 2 || a->k % 32 || !a->wscale || (a->w2 && !a->w2scale)))
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP4 weights exist for the streaming GEMV alone: m <= 2, k %% 32 == 0, wscale (w2scale), "
-                        "no VV_LIN_W_FRAG / bf16 hand-off (m=%d k=%d flags=%d)", a->m, a->k, a->flags);
-  if (a->wdt == VV_MXFP6) {      // the one copy of what an MXFP6 call must be lives with its kernel
-    const char* lacks = vv_gemv_mx6_refusal(*a);
-    if (lacks) return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: MXFP6 weights exist for the streaming GEMV alone, which needs %s (m=%d k=%d flags=%d)", lacks, a->m, a->k, a->flags);
-  }
-  if (a->wdt == VV_MXFP4_FRAG && (!(a->flags & VV_LIN_W_FRAG) || (a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) || a->m < 3 || a->m > 8 || a->n % 16 || a->k % 128 ||
-                                  !a->wscale || (a->w2 && !a->w2scale)))
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear: VV_MXFP4_FRAG weights exist for the 3..8-row matrix-core GEMV alone: VV_LIN_W_FRAG, 3 <= m <= 8, n %% 16 == 0, "
-                        "k %% 128 == 0, wscale (w2scale), no bf16 hand-off (m=%d n=%d k=%d flags=%d)", a->m, a->n, a->k, a->flags);
-  if ((a->flags & VV_LIN_W_FRAG) && a->wdt != VV_FP8 && a->wdt != VV_MXFP4_FRAG && (a->wdt != VV_BF16 || a->m < 3 || a->m > 16 || a->n % 16 || a->k % 32))
+  int rc = VV_E_UNSUPPORTED;
+  const wq_format* f = wq_format_of(*a);      // a weight-only format: what a call must be is written once, next to the kernels of the format's unit
+  const char* lacks = f ? f->refusal(*a, &rc) : nullptr;
+  if (lacks) return vv_set_error(rc, "vv_linear: %s weights need %s: they exist for %s alone (m=%d n=%d k=%d flags=%d)", f->name, lacks, WQ_UNIT_NAME[f->unit], a->m, a->n, a->k, a->flags);
+  if ((a->flags & VV_LIN_W_FRAG) && !f && (a->wdt != VV_BF16 || a->m < 3 || a->m > 16 || a->n % 16 || a->k % 32))
     return vv_set_error(VV_E_ARG, "vv_linear: VV_LIN_W_FRAG needs bf16 weights, 3..16 rows, n %% 16 == 0 and k %% 32 == 0");
   if ((a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && (a->wdt != VV_BF16 || a->m <= 8 || a->k % 16))
     return vv_set_error(VV_E_ARG, "vv_linear: bf16 activation hand-off needs bf16 weights, m > 8 and k %% 16 == 0");
@@ -865,7 +847,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     else if (fam == LIN_FAM_SKINNY) vv_skinny_route_name(vv_skinny_decide(*a), name, cap);
     else if (fam == LIN_FAM_GEMM_F32) gemm_f32_route_name(*a, gemm_f32_decide(*a), name, cap);
   }
-  else if (a->wdt != VV_FP8 && a->wdt != VV_NF4 && a->wdt != VV_MXFP4 && a->wdt != VV_MXFP4_FRAG && a->wdt != VV_MXFP6) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  else if (!wq_format_of(*a)) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
   if (a->flags & VV_LIN_W_MXGEMM) { vv_gemm_mx_route_name(*a, name, cap); return 0; }      // linear_check_args has asked vv_gemm_mx_check
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
@@ -889,7 +871,7 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
   if (a->flags & VV_LIN_W_MXGEMM) rc = vv_launch_gemm_mx(*a, s);      // wdt == VV_MXFP4 and everything else the kernel needs: linear_check_args
   else if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
-  else if (a->wdt == VV_FP8 || a->wdt == VV_NF4 || a->wdt == VV_MXFP4 || a->wdt == VV_MXFP4_FRAG || a->wdt == VV_MXFP6) {   // weight-only fp8 / NF4 / MXFP4 / MXFP6: the rows or a streaming GEMV, or refused (gemv_decide)
+  else if (wq_format_of(*a)) {      // a weight-only format (WQ_FORMATS): its unit's GEMV, or refused (gemv_decide)
     gemv_route g;
     rc = gemv_decide(*a, &g);
     if (!rc) rc = launch_gemv_route<bf16_t>(*a, g, s);

@@ -42,12 +42,12 @@ static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q
 }
 
 // VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 (vv_hip.h) ride on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
-// the matrix dtype, and keeps the companions' kind in `wq`; `frag4`: VV_WQ_FRAG4, the layers' f_* copies hold the VV_MXFP4_FRAG form
+// the matrix dtype, and keeps the companions' kind in `wq` (vv_wq_strip, vv_common.h); `frag4`: VV_WQ_FRAG4, the layers' f_* copies hold the VV_MXFP4_FRAG form
 #define VV_WQ_STRIP(T, p)                                                   \
   T p##_plain_ = *(p);                                                      \
-  const int wq = (p##_plain_.wdt & VV_WQ_MXFP6) ? VV_MXFP6 : (p##_plain_.wdt & VV_WQ_MXFP4) ? VV_MXFP4 : (p##_plain_.wdt & VV_WQ_NF4) ? VV_NF4 : VV_FP8; \
-  const bool frag4 = wq == VV_MXFP4 && (p##_plain_.wdt & VV_WQ_FRAG4) != 0; \
-  p##_plain_.wdt &= ~(VV_WQ_NF4 | VV_WQ_MXFP4 | VV_WQ_MXFP6 | VV_WQ_FRAG4);  \
+  const vv_wq_kind p##_kind_ = vv_wq_strip(&p##_plain_.wdt);                \
+  const int wq = p##_kind_.wq;                                              \
+  const bool frag4 = p##_kind_.frag4;                                       \
   p = &p##_plain_;                                                          \
   (void)wq; (void)frag4
 
@@ -1138,7 +1138,7 @@ inline int r64(size_t n) { return (int)((n + 63) & ~(size_t)63); }
 int rows_shape(const char* who, const vv_convnet* net0, int decoder, RowsPlan* p) {
   p->net = *net0;
   vv_convnet& n = p->net;
-  if (n.wdt & (VV_WQ_NF4 | VV_WQ_MXFP4 | VV_WQ_MXFP6 | VV_WQ_FRAG4)) return vv_set_error(VV_E_UNSUPPORTED, "%s: quantised companions are not served", who);
+  if (n.wdt & vv_wq_bits()) return vv_set_error(VV_E_UNSUPPORTED, "%s: quantised companions are not served", who);
   if (n.wdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "%s: bf16 weights only", who);
   if (n.n_stages < 2 || n.n_stages > VV_MAX_STAGES) return vv_set_error(VV_E_UNSUPPORTED, "%s: %d stages", who, n.n_stages);
   if (!convnet_streaming(&n)) return vv_set_error(VV_E_UNSUPPORTED, "%s: a streaming net (every conv with its state) only", who);

@@ -13,7 +13,9 @@ Matrix weights are stored in `wdtype` (fp32 for graded parity, bf16 for the benc
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+import functools
+import math
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -62,15 +64,6 @@ def fp8_matrix_names(cfg: VVConfig):
     return names
 
 
-def fp8_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """The state dict a weight_quant="fp8" engine computes with (for the checker side of parity tests): the listed matrices replaced
-    by code * scale (q/k/v are quantised as the fused [q|k|v] matrix, row scales make that identical to quantising them apart)."""
-    out = dict(sd)
-    for name in fp8_matrix_names(cfg):
-        out[name] = quantize_e4m3_pow2(sd[name])[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
-    return out
-
-
 # bitsandbytes' NF4 code book (index = 4-bit code), in this order
 NF4_TABLE = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
              -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
@@ -108,51 +101,76 @@ def quantize_nf4(w: torch.Tensor):
     return codes.reshape(n, k).contiguous(), absmax.contiguous(), eff.reshape(n, k).contiguous()
 
 
-def pack_nf4(codes: torch.Tensor, absmax: torch.Tensor):
-    """(codes uint8 [N, K], absmax fp32 [N, K / 64]) -> the streaming GEMV's VV_NF4 layout (include/vv_hip.h), padded with code 0 / scale 0:
-    codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B] - nibble i of dword r of lane l's 16 bytes is code (4 q + r, 512 u + 8 l + i) -
-    and absmax [ceil(N/4)][ceil(K/512)][4 rows][8 blocks].  Returns (uint8 1-D, fp32 1-D)."""
+def _pack_nibbles(codes: torch.Tensor) -> torch.Tensor:
+    """4-bit codes uint8 [N, K] -> the streaming GEMV's code layout (VV_NF4 and VV_MXFP4 share it, include/vv_hip.h), padded with code 0:
+    [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B] - nibble i of dword r of lane l's 16 bytes is code (4 q + r, 512 u + 8 l + i).  uint8 1-D."""
     n, k = codes.shape
     nq, ku = (n + 3) // 4, (k + 511) // 512
     c = torch.zeros(nq * 4, ku * 512, dtype=torch.uint8, device=codes.device)
     c[:n, :k] = codes
     c = c.view(nq, 4, ku, 64, 4, 2).permute(0, 2, 3, 1, 4, 5)           # [q, u, lane, r, byte, nibble]
-    packed = (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
+    return (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
+
+
+def _unpack_nibbles(packed: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Inverse of _pack_nibbles: codes uint8 [N, K]."""
+    nq, ku = (n + 3) // 4, (k + 511) // 512
+    b = packed.view(nq, ku, 64, 4, 4)
+    c = torch.stack([b & 15, b >> 4], dim=-1)                           # [q, u, lane, r, byte, nibble]
+    return c.permute(0, 3, 1, 2, 4, 5).reshape(nq * 4, ku * 512)[:n, :k].contiguous()
+
+
+def pack_nf4(codes: torch.Tensor, absmax: torch.Tensor):
+    """(codes uint8 [N, K], absmax fp32 [N, K / 64]) -> the streaming GEMV's VV_NF4 layout (include/vv_hip.h), padded with code 0 / scale 0:
+    the codes as _pack_nibbles lays them out and absmax [ceil(N/4)][ceil(K/512)][4 rows][8 blocks].  Returns (uint8 1-D, fp32 1-D)."""
+    n, k = codes.shape
+    nq, ku = (n + 3) // 4, (k + 511) // 512
     s = torch.zeros(nq * 4, ku * 8, dtype=torch.float32, device=absmax.device)
     s[:n, : k // NF4_BLOCK] = absmax
-    scales = s.view(nq, 4, ku, 8).permute(0, 2, 1, 3).contiguous().view(-1)
-    return packed, scales
+    return _pack_nibbles(codes), s.view(nq, 4, ku, 8).permute(0, 2, 1, 3).contiguous().view(-1)
 
 
 def unpack_nf4(packed: torch.Tensor, scales: torch.Tensor, n: int, k: int):
     """Inverse of pack_nf4: (codes uint8 [N, K], absmax fp32 [N, K / 64])."""
     nq, ku = (n + 3) // 4, (k + 511) // 512
-    b = packed.view(nq, ku, 64, 4, 4)
-    c = torch.stack([b & 15, b >> 4], dim=-1)                           # [q, u, lane, r, byte, nibble]
-    codes = c.permute(0, 3, 1, 2, 4, 5).reshape(nq * 4, ku * 512)[:n, :k].contiguous()
-    absmax = scales.view(nq, ku, 4, 8).permute(0, 2, 1, 3).reshape(nq * 4, ku * 8)[:n, : k // NF4_BLOCK].contiguous()
-    return codes, absmax
-
-
-def nf4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """The state dict a weight_quant="nf4" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
-    K % 64 == 0 replaced by the effective NF4 weights of its bf16 rounding bf16(table[code] * absmax) (fp32 tensors; q/k/v quantise the same fused or apart, the
-    blocks lie inside rows)."""
-    out = dict(sd)
-    for name in fp8_matrix_names(cfg):
-        if sd[name].shape[1] % NF4_BLOCK == 0:
-            out[name] = quantize_nf4(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
-    return out
+    return _unpack_nibbles(packed, n, k), scales.view(nq, ku, 4, 8).permute(0, 2, 1, 3).reshape(nq * 4, ku * 8)[:n, : k // NF4_BLOCK].contiguous()
 
 
 # OCP Microscaling (MX v1.0) FP4: e2m1 element values by code (codes 8..15 are the negated values), 32-element blocks with one E8M0 scale byte
 MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 MXFP4_BLOCK = 32
-MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
+# the E8M0 scale bytes the engine writes, for every MX format; 127 = 2^0 (padding, all-zero blocks)
+MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = MXFP6_SCALE_MIN, MXFP6_SCALE_MAX, MXFP6_SCALE_ONE = 2, 252, 127
 # limits of the MX rows kernel's decision (csrc/vv_gemv_rows.hip, vv_gemv_rows_decide) that the host acts on: the adaLN-modulated prologue
 # is served on whole rows only (K <= 2048); the SwiGLU pair splits K two ways at most inside the row-batched step's partials workspace
 # (csrc/vv_model.hip, rows_part_floats), 2 slices x 8 waves x 2 loads x 128 = 4096
 MXFP4_ROWS_MOD_K, MXFP4_ROWS_MAX_HIDDEN = 2048, 4096
+
+
+def _quantize_mx(w: torch.Tensor, values, block: int, sign_code: int):
+    """What quantize_mxfp4 / quantize_mxfp6 define, for an e2mX grid `values` (magnitudes by code; sign_code: the negative zero's code, a code's
+    top bit).  The grid's spacing is values[1] below 2 (subnormals and the first binade) and doubles per binade up to the largest value's."""
+    n, k = w.shape
+    if k % block:
+        raise ValueError(f"MXFP{sign_code.bit_length()} needs K % {block} == 0 (K={k})")
+    top, emax = values[-1], math.frexp(values[-1])[1] - 1                        # emax: the exponent of the largest value, 2 for e2m1 and e2m3
+    wf = w.detach().float().reshape(n, k // block, block)
+    amax = wf.abs().amax(dim=2)
+    zero = amax == 0
+    ex = torch.frexp(torch.where(zero, torch.ones_like(amax), amax))[1] - 1      # floor(log2(amax)), exact: amax = m 2^ex', m in [0.5, 1)
+    e = torch.where(zero, torch.full_like(ex, MXFP4_SCALE_ONE), (ex - emax + 127).clamp(MXFP4_SCALE_MIN, MXFP4_SCALE_MAX))
+    # w / 2^(e - 127) in fp64: the quotient by a power of two is exact there for every fp32 w and every scale byte
+    x = wf.double() * torch.exp2((127 - e).double())[..., None]
+    a = x.abs()
+    # round to nearest even on the grid (torch.round is half-to-even; a quotient by the power-of-two spacing is exact); above the top saturates
+    step = values[1] * torch.exp2((torch.frexp(a)[1] - 1).clamp(0, emax).double())
+    q = (torch.round(a / step) * step).clamp_max(top)
+    grid = torch.tensor(values, dtype=torch.float64, device=q.device)
+    mag = torch.searchsorted(grid, q.contiguous()).to(torch.uint8)               # q is on the grid: its index
+    codes = torch.where((x < 0) & (mag > 0), mag + sign_code, mag).to(torch.uint8)
+    eff = (torch.where(x < 0, -q, q) * torch.exp2((e - 127).double())[..., None]).float()
+    eff = torch.where(mag == 0, torch.zeros_like(eff), eff)                      # +0, as code 0 decodes
+    return codes.reshape(n, k).contiguous(), e.to(torch.uint8).contiguous(), eff.reshape(n, k).contiguous()
 
 
 def quantize_mxfp4(w: torch.Tensor):
@@ -164,69 +182,29 @@ def quantize_mxfp4(w: torch.Tensor):
         rounds to zero takes code 0 (never the negative zero, code 8);
       * effective weight = value(code) * 2^(e - 127): exact in bf16 (and so in fp32).
     Returns (codes uint8 [N, K], scale bytes uint8 [N, K / 32], effective weights fp32 [N, K])."""
-    n, k = w.shape
-    if k % MXFP4_BLOCK:
-        raise ValueError(f"MXFP4 needs K % {MXFP4_BLOCK} == 0 (K={k})")
-    wf = w.detach().float().reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
-    amax = wf.abs().amax(dim=2)
-    zero = amax == 0
-    ex = torch.frexp(torch.where(zero, torch.ones_like(amax), amax))[1] - 1      # floor(log2(amax)), exact: amax = m 2^ex', m in [0.5, 1)
-    e = torch.where(zero, torch.full_like(ex, MXFP4_SCALE_ONE), (ex - 2 + 127).clamp(MXFP4_SCALE_MIN, MXFP4_SCALE_MAX))
-    # w / 2^(e - 127) in fp64: the quotient by a power of two is exact there for every fp32 w and every scale byte
-    x = wf.double() * torch.exp2((127 - e).double())[..., None]
-    a = x.abs()
-    # round to nearest even on the grid: spacing 0.5 below 2, 1 below 4, 2 below 6 (torch.round is half-to-even); above 6 saturates
-    q = torch.where(a < 2.0, torch.round(a * 2.0) / 2.0, torch.where(a < 4.0, torch.round(a), torch.round(a / 2.0) * 2.0)).clamp_max(6.0)
-    grid = torch.tensor(MXFP4_VALUES, dtype=torch.float64, device=q.device)
-    mag = torch.searchsorted(grid, q.contiguous()).to(torch.uint8)               # q is on the grid: its index
-    codes = torch.where((x < 0) & (mag > 0), mag + 8, mag).to(torch.uint8)
-    eff = (torch.where(x < 0, -q, q) * torch.exp2((e - 127).double())[..., None]).float()
-    eff = torch.where(mag == 0, torch.zeros_like(eff), eff)                      # +0, as code 0 decodes
-    return codes.reshape(n, k).contiguous(), e.to(torch.uint8).contiguous(), eff.reshape(n, k).contiguous()
+    return _quantize_mx(w, MXFP4_VALUES, MXFP4_BLOCK, 8)
 
 
 def pack_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
     """(codes uint8 [N, K], scale bytes uint8 [N, K / 32]) -> the VV_MXFP4 layout (include/vv_hip.h), padded with code 0 / scale byte 127:
-    codes [ceil(N/4)][ceil(K/512)][64 lanes][4 rows][4 B] - nibble i of dword r of lane l's 16 bytes is code (4 q + r, 512 u + 8 l + i) -
-    and scale bytes [ceil(N/4)][ceil(K/512)][16 blocks][4 rows].  Returns (uint8 1-D, uint8 1-D)."""
+    the codes as _pack_nibbles lays them out and scale bytes [ceil(N/4)][ceil(K/512)][16 blocks][4 rows].  Returns (uint8 1-D, uint8 1-D)."""
     n, k = codes.shape
     nq, ku = (n + 3) // 4, (k + 511) // 512
-    c = torch.zeros(nq * 4, ku * 512, dtype=torch.uint8, device=codes.device)
-    c[:n, :k] = codes
-    c = c.view(nq, 4, ku, 64, 4, 2).permute(0, 2, 3, 1, 4, 5)           # [q, u, lane, r, byte, nibble]
-    packed = (c[..., 0] | (c[..., 1] << 4)).contiguous().view(-1)
     s = torch.full((nq * 4, ku * 16), MXFP4_SCALE_ONE, dtype=torch.uint8, device=scales.device)
     s[:n, : k // MXFP4_BLOCK] = scales
-    sb = s.view(nq, 4, ku, 16).permute(0, 2, 3, 1).contiguous().view(-1)  # [q, u, block, r]
-    return packed, sb
+    return _pack_nibbles(codes), s.view(nq, 4, ku, 16).permute(0, 2, 3, 1).contiguous().view(-1)  # [q, u, block, r]
 
 
 def unpack_mxfp4(packed: torch.Tensor, sb: torch.Tensor, n: int, k: int):
     """Inverse of pack_mxfp4: (codes uint8 [N, K], scale bytes uint8 [N, K / 32])."""
     nq, ku = (n + 3) // 4, (k + 511) // 512
-    b = packed.view(nq, ku, 64, 4, 4)
-    c = torch.stack([b & 15, b >> 4], dim=-1)                           # [q, u, lane, r, byte, nibble]
-    codes = c.permute(0, 3, 1, 2, 4, 5).reshape(nq * 4, ku * 512)[:n, :k].contiguous()
-    scales = sb.view(nq, ku, 16, 4).permute(0, 3, 1, 2).reshape(nq * 4, ku * 16)[:n, : k // MXFP4_BLOCK].contiguous()
-    return codes, scales
-
-
-def mxfp4_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """The state dict a weight_quant="mxfp4" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
-    K % 32 == 0 replaced by the effective MXFP4 weights of its bf16 rounding (fp32 tensors; q/k/v quantise the same fused or apart, the blocks
-    lie inside rows).  A matrix with another K is left as it is."""
-    out = dict(sd)
-    for name in fp8_matrix_names(cfg):
-        if sd[name].shape[1] % MXFP4_BLOCK == 0:
-            out[name] = quantize_mxfp4(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
-    return out
+    return _unpack_nibbles(packed, n, k), sb.view(nq, ku, 16, 4).permute(0, 3, 1, 2).reshape(nq * 4, ku * 16)[:n, : k // MXFP4_BLOCK].contiguous()
 
 
 # OCP Microscaling (MX v1.0) FP6, the e2m3 variant: 1 sign, 2 exponent, 3 mantissa bits (codes 0..31 below, 32..63 the same values negated) -
 # subnormals m / 8 for m = 0..7, normals (1 + m / 8) * 2^(E - 1) for E = 1..3, the largest 7.5; 32-element blocks with one E8M0 scale byte
 MXFP6_VALUES = tuple(m / 8.0 for m in range(8)) + tuple((1.0 + m / 8.0) * 2.0 ** (E - 1) for E in (1, 2, 3) for m in range(8))
 MXFP6_BLOCK = 32
-MXFP6_SCALE_MIN, MXFP6_SCALE_MAX, MXFP6_SCALE_ONE = 2, 252, 127     # the scale bytes the engine writes; 127 = 2^0 (padding, all-zero blocks)
 # Element i of a block sits in bits 6 i .. 6 i + 5 of the 192-bit operand of v_cvt_scalef32_pk32_*_fp6, counted from bit 0 of the first dword
 # (tests/test_hip_mxfp6.py::test_decode_is_exact is the witness: the hardware reads every code back from there)
 
@@ -240,25 +218,7 @@ def quantize_mxfp6(w: torch.Tensor):
         +-7.5; a value that rounds to zero takes code 0 (never the negative zero, code 32);
       * effective weight = value(code) * 2^(e - 127): four significant bits times a power of two, exact in bf16 (and so in fp32).
     Returns (codes uint8 [N, K] in 0..63, scale bytes uint8 [N, K / 32], effective weights fp32 [N, K])."""
-    n, k = w.shape
-    if k % MXFP6_BLOCK:
-        raise ValueError(f"MXFP6 needs K % {MXFP6_BLOCK} == 0 (K={k})")
-    wf = w.detach().float().reshape(n, k // MXFP6_BLOCK, MXFP6_BLOCK)
-    amax = wf.abs().amax(dim=2)
-    zero = amax == 0
-    ex = torch.frexp(torch.where(zero, torch.ones_like(amax), amax))[1] - 1      # floor(log2(amax)), exact: amax = m 2^ex', m in [0.5, 1)
-    e = torch.where(zero, torch.full_like(ex, MXFP6_SCALE_ONE), (ex - 2 + 127).clamp(MXFP6_SCALE_MIN, MXFP6_SCALE_MAX))
-    # w / 2^(e - 127) in fp64: the quotient by a power of two is exact there for every fp32 w and every scale byte
-    x = wf.double() * torch.exp2((127 - e).double())[..., None]
-    a = x.abs()
-    # round to nearest even on the grid: spacing 1/8 below 2 (subnormals and E = 1), 1/4 below 4, 1/2 above (torch.round is half-to-even)
-    q = torch.where(a < 2.0, torch.round(a * 8.0) / 8.0, torch.where(a < 4.0, torch.round(a * 4.0) / 4.0, torch.round(a * 2.0) / 2.0)).clamp_max(7.5)
-    grid = torch.tensor(MXFP6_VALUES, dtype=torch.float64, device=q.device)
-    mag = torch.searchsorted(grid, q.contiguous()).to(torch.uint8)               # q is on the grid: its index
-    codes = torch.where((x < 0) & (mag > 0), mag + 32, mag).to(torch.uint8)
-    eff = (torch.where(x < 0, -q, q) * torch.exp2((e - 127).double())[..., None]).float()
-    eff = torch.where(mag == 0, torch.zeros_like(eff), eff)                      # +0, as code 0 decodes
-    return codes.reshape(n, k).contiguous(), e.to(torch.uint8).contiguous(), eff.reshape(n, k).contiguous()
+    return _quantize_mx(w, MXFP6_VALUES, MXFP6_BLOCK, 32)
 
 
 def pack_mxfp6(codes: torch.Tensor, scales: torch.Tensor):
@@ -290,15 +250,39 @@ def unpack_mxfp6(packed: torch.Tensor, sb: torch.Tensor, n: int, k: int):
     return codes, scales
 
 
-def mxfp6_effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """The state dict a weight_quant="mxfp6" engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names with
-    K % 32 == 0 replaced by the effective MXFP6 weights of its bf16 rounding (fp32 tensors; q/k/v quantise the same fused or apart, the blocks
-    lie inside rows).  A matrix with another K is left as it is."""
+class WeightFormat(NamedTuple):
+    block: Optional[int]       # weights per scale along K (a matrix whose K it does not divide gets no companion); None: fp8's one scale per output
+    quantize: Callable         # row, the one format that quantises the matrix as given - the blockwise ones quantise its bf16 rounding
+    pack: Optional[Callable]   # (codes, scales) -> the companion's layout (include/vv_hip.h); None: the codes are streamed as quantize gives them
+    wq: int                    # the VV_WQ_* bit of the descriptors' wdt
+    what: str
+
+
+# weight_quant -> its format: the one place on this side that lists them (csrc/vv_kernels.hip has the kernels' table)
+WEIGHT_FORMATS: Dict[str, WeightFormat] = {
+    "fp8": WeightFormat(None, quantize_e4m3_pow2, None, 0, "weight-only e4m3"),
+    "nf4": WeightFormat(NF4_BLOCK, quantize_nf4, pack_nf4, L.VV_WQ_NF4, "weight-only 4-bit NF4"),
+    "mxfp4": WeightFormat(MXFP4_BLOCK, quantize_mxfp4, pack_mxfp4, L.VV_WQ_MXFP4, "weight-only OCP MXFP4"),
+    "mxfp6": WeightFormat(MXFP6_BLOCK, quantize_mxfp6, pack_mxfp6, L.VV_WQ_MXFP6, "weight-only OCP MXFP6 e2m3"),
+}
+
+
+def effective_state_dict(cfg: VVConfig, sd: Dict[str, torch.Tensor], quant: str) -> Dict[str, torch.Tensor]:
+    """The state dict a weight_quant=quant engine computes with (the checker side of parity tests): every matrix of fp8_matrix_names that the
+    format takes replaced by its effective weights (fp32 tensors; q/k/v quantise the same fused or apart: the scales lie inside rows).  A
+    matrix whose K the format's block does not divide is left as it is."""
+    f = WEIGHT_FORMATS[quant]
     out = dict(sd)
     for name in fp8_matrix_names(cfg):
-        if sd[name].shape[1] % MXFP6_BLOCK == 0:
-            out[name] = quantize_mxfp6(sd[name].to(torch.bfloat16))[2].to(sd[name].dtype if sd[name].dtype == torch.float32 else torch.float32)
+        if not (f.block and sd[name].shape[1] % f.block):
+            out[name] = f.quantize(sd[name] if f.block is None else sd[name].to(torch.bfloat16))[2]
     return out
+
+
+fp8_effective_state_dict = functools.partial(effective_state_dict, quant="fp8")       # (cfg, sd) -> state dict, one per format as ever
+nf4_effective_state_dict = functools.partial(effective_state_dict, quant="nf4")
+mxfp4_effective_state_dict = functools.partial(effective_state_dict, quant="mxfp4")
+mxfp6_effective_state_dict = functools.partial(effective_state_dict, quant="mxfp6")
 
 
 class DeviceWeights:
@@ -328,9 +312,9 @@ class DeviceWeights:
                              "would need a three-way K split, which the row-batched step's partials workspace has no room for")
         self.mxfp4_row_batch = bool(mxfp4_row_batch)
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
-        if quant not in (None, "fp8", "nf4", "mxfp4", "mxfp6"):
-            raise ValueError(f"weight_quant {quant!r}: only None, 'fp8' (weight-only e4m3), 'nf4' (weight-only 4-bit NF4), 'mxfp4' (weight-only OCP "
-                             "MXFP4) or 'mxfp6' (weight-only OCP MXFP6 e2m3), decode GEMVs, is built")
+        if quant is not None and quant not in WEIGHT_FORMATS:
+            raise ValueError(f"weight_quant {quant!r}: only None, " + " or ".join(f"{name!r} ({f.what})" for name, f in WEIGHT_FORMATS.items()) +
+                             ", decode GEMVs, is built")
         if quant is not None and wdtype != torch.bfloat16:
             raise ValueError(f"weight_quant={quant!r} keeps bf16 copies for the GEMM-shaped uses: torch_dtype must be bfloat16")
         if prequant and quant != "nf4":
@@ -340,7 +324,7 @@ class DeviceWeights:
         self._fp8_names = set(fp8_matrix_names(cfg)) if quant is not None else set()     # the matrices that get a companion
         self.wdt = _wdt(wdtype)
         # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 mark their vv_w8 companions as NF4 / MXFP4 / MXFP6 (vv_hip.h); self.wdt stays the plain matrix dtype
-        self.desc_wdt = self.wdt | (L.VV_WQ_NF4 if quant == "nf4" else L.VV_WQ_MXFP4 if quant == "mxfp4" else L.VV_WQ_MXFP6 if quant == "mxfp6" else 0)
+        self.desc_wdt = self.wdt | (WEIGHT_FORMATS[quant].wq if quant else 0)
         # vv_llm / vv_head: VV_WQ_FRAG4 says their layers' f_* copies hold the VV_MXFP4_FRAG form (never a bf16 fragment copy)
         self.desc_wdt_rows = self.desc_wdt | (L.VV_WQ_FRAG4 if self.mxfp4_row_batch else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
@@ -413,44 +397,25 @@ class DeviceWeights:
         return self._mat(t), w8
 
     def _mat_q(self, t: torch.Tensor, quantise: bool, lean: Optional[str] = None):
-        """(bf16 matrix, vv_w8 companion): in fp8 mode the bf16 copy holds the dequantised values (exact, power-of-two scales); in nf4
-        mode it holds the effective weights bf16(table[code] * absmax) and the companion the packed codes and block scales (pack_nf4).
-        An NF4 matrix with K % 64 != 0 gets no companion.  In mxfp4 mode the bf16 copy holds value(code) * 2^(e - 127) (exact) and the
-        companion the packed codes and scale bytes (pack_mxfp4); a matrix with K % 32 != 0 gets no companion; mxfp6 mode is mxfp4 mode with
-        quantize_mxfp6 / pack_mxfp6.  lean (a name for
+        """(bf16 matrix, vv_w8 companion) in the model's format (WEIGHT_FORMATS): the companion holds the codes and scales in the format's layout,
+        the bf16 copy the effective weights - exact in bf16 in every format (fp8: power-of-two row scales; nf4: bf16(table[code] * absmax);
+        mxfp4 / mxfp6: value(code) * 2^(e - 127)).  A matrix whose K the format's block does not divide gets no companion.  lean (a name for
         lean_report, mxfp4 only): the bf16 copy is not made - (None, companion); the effective matrix lives while the codes are packed."""
         w8 = L.W8()
-        if self.quant == "nf4" and quantise and t.shape[1] % NF4_BLOCK == 0:
-            codes, absmax, eff = quantize_nf4(t.to(device=self.device, dtype=torch.bfloat16))    # the bf16 weight, widened
-            packed, scales = pack_nf4(codes, absmax)
-            packed = self._aligned(packed)
-            self._keep.append(packed)
-            w8.q, w8.scale = L.ptr(packed), L.ptr(self._vec(scales))
-            return self._mat(eff), w8
-        if self.quant == "mxfp4" and quantise and t.shape[1] % MXFP4_BLOCK == 0:
-            codes, sbytes, eff = quantize_mxfp4(t.to(device=self.device, dtype=torch.bfloat16))   # the bf16 weight, widened
-            packed, sb = pack_mxfp4(codes, sbytes)
-            packed, sb = self._aligned(packed), self._aligned(sb)
-            self._keep += [packed, sb]
-            w8.q, w8.scale = L.ptr(packed), L.ptr(sb)          # vv_w8.scale carries the address of the scale BYTES (vv_hip.h, VV_MXFP4)
-            if lean is not None:
-                n, k = t.shape
-                self._lean_dropped.append({"name": lean, "n": int(n), "k": int(k), "bytes": 2 * int(n) * int(k)})
-                return None, w8
-            return self._mat(eff), w8
-        if self.quant == "mxfp6" and quantise and t.shape[1] % MXFP6_BLOCK == 0:
-            codes, sbytes, eff = quantize_mxfp6(t.to(device=self.device, dtype=torch.bfloat16))   # the bf16 weight, widened
-            packed, sb = pack_mxfp6(codes, sbytes)
-            packed, sb = self._aligned(packed), self._aligned(sb)
-            self._keep += [packed, sb]
-            w8.q, w8.scale = L.ptr(packed), L.ptr(sb)          # the address of the scale BYTES, as for MXFP4 (vv_hip.h, VV_MXFP6)
-            return self._mat(eff), w8
-        if not (quantise and self.quant == "fp8"):
+        f = WEIGHT_FORMATS[self.quant] if quantise and self.quant else None
+        if f is None or (f.block and t.shape[1] % f.block):
             return self._mat(t), w8
-        codes, scale, eff = quantize_e4m3_pow2(t.to(self.device))
-        codes = self._aligned(codes.to(self.device))
-        self._keep.append(codes)
-        w8.q, w8.scale = L.ptr(codes), L.ptr(self._vec(scale))
+        # the blockwise formats quantise the bf16 weight, widened; fp8 the matrix as given
+        codes, scales, eff = f.quantize(t.to(self.device) if f.block is None else t.to(device=self.device, dtype=torch.bfloat16))
+        if f.pack:
+            codes, scales = f.pack(codes, scales)
+        codes, scales = self._aligned(codes.to(self.device)), self._aligned(scales.to(self.device))
+        self._keep += [codes, scales]
+        w8.q, w8.scale = L.ptr(codes), L.ptr(scales)      # scale: fp32 scales (fp8, nf4) or the address of the E8M0 scale BYTES (vv_hip.h)
+        if lean is not None and self.quant == "mxfp4":
+            n, k = t.shape
+            self._lean_dropped.append({"name": lean, "n": int(n), "k": int(k), "bytes": 2 * int(n) * int(k)})
+            return None, w8
         return self._mat(eff), w8
 
     def _vec(self, t: torch.Tensor) -> torch.Tensor:
