@@ -6,7 +6,8 @@ matched by their template arguments, the weight format as a number (gemv_rows_ke
 the streaming GEMV's (gemv_stream_kernel by its six arguments, a gemv_mx_kernel<M, DUAL, KSPLIT, KU> -> <M, DUAL, KSPLIT, KU, 4, 3>),
 and the conv tokenizers' row-in kernels by theirs with the row count in front (a row_in_kernel<NT> -> row_in_rows_kernel<1, NT>, the earlier
 row_in_rows_kernel<BT> -> <BT, 0>): a kernel
-whose stream differs is listed with the registers, LDS, scratch and spill counts of its metadata on both sides."""
+whose stream differs is listed with the registers, LDS, scratch and spill counts of its metadata on both sides, a kernel (or device function)
+that only one set holds with the side it is on.  Exit status 1 when a kernel differs or is missing from the new set, else 0."""
 import re
 import sys
 
@@ -73,9 +74,11 @@ old, new = bodies(sys.argv[1]), bodies(sys.argv[2])
 mo, mn = meta(sys.argv[1]), meta(sys.argv[2])
 pool = list(new)
 same = diff = 0
+only_old = []
 for n, b in old:
     cands = [i for i, (m, _) in enumerate(pool) if base(m) == base(n)]
     if not cands:
+        only_old.append(base(n))
         continue
     hit = next((i for i in cands if pool[i][1] == b), None)
     if hit is None:
@@ -87,4 +90,10 @@ for n, b in old:
         same += 1
         print(f"identical  {base(n)}: {len(b)} lines")
         pool.pop(hit)
-print(f"{same} identical, {diff} different; only in new: {sorted(set(base(m) for m, _ in pool if 'kernel' in base(m)))[:8]}")
+pool = [(m, b) for m, b in pool if base(m) not in {base(n) for n, _ in old}]     # what is left of a matched name is listed above as DIFFERENT
+only_new = sorted(set(base(m) for m, _ in pool))
+for side, names in (("old", sorted(set(only_old))), ("new", only_new)):
+    for name in names:
+        print(f"ONLY IN {side.upper()}  {name}")
+print(f"{same} identical, {diff} different, {len(only_old)} only in old, {len(pool)} only in new")
+sys.exit(1 if diff or only_old else 0)

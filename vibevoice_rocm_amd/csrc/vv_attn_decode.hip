@@ -26,10 +26,6 @@ namespace {
 
 typedef unsigned int att_raw __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void unpack8(const att_raw v, float (&o)[8]) {
-  o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u); o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-  o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u); o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
-}
 __device__ __forceinline__ float gsum16(float v) {       // sum over the 16 lanes of a DPP row, result in every lane of the row
 #define VV_DPP_ADD(ctrl) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, true))
   VV_DPP_ADD(0xB1); VV_DPP_ADD(0x4E); VV_DPP_ADD(0x141); VV_DPP_ADD(0x140);
@@ -37,10 +33,6 @@ __device__ __forceinline__ float gsum16(float v) {       // sum over the 16 lane
   return v;
 }
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ unsigned bf16_bits(float f) {   // round to nearest even (finite inputs: projections of finite activations)
-  const unsigned u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // phase timing of block (0,0,0) / thread 0, debug builds only (-DVV_CF_TIMING, tools/convffn_phase.py attn)
 #ifdef VV_CF_TIMING
@@ -290,13 +282,10 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* qkv, 
 // are those of the bf16 kernel on the dequantised cache, bit for bit.  The new token takes part in its own step at fp32 as before and is
 // appended as codes saturated to +-448 under the head's scale.
 // ---------------------------------------------------------------------------------------------------------------------------------------
-typedef __bf16 gq_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float gq_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int gq_u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned gq_pk(float a, float b) { return bf16_bits(a) | (bf16_bits(b) << 16); }
 __device__ __forceinline__ float gq_bf_round(float a) { return __uint_as_float(bf16_bits(a) << 16); }
-__device__ __forceinline__ gq_bf16x8 gq_frag(att_raw v) { return __builtin_bit_cast(gq_bf16x8, v); }
+__device__ __forceinline__ bf16x8 gq_frag(att_raw v) { return __builtin_bit_cast(bf16x8, v); }
 // split 8 floats into bf16 hi and lo fragments: hi + lo reproduces the fp32 value to 2^-17 relative
 __device__ __forceinline__ void gq_split(const float (&x)[8], att_raw& hi, att_raw& lo) {
   float h[8], l[8];
@@ -306,17 +295,16 @@ __device__ __forceinline__ void gq_split(const float (&x)[8], att_raw& hi, att_r
   lo.x = gq_pk(l[0], l[1]); lo.y = gq_pk(l[2], l[3]); lo.z = gq_pk(l[4], l[5]); lo.w = gq_pk(l[6], l[7]);
 }
 
-typedef __bf16 gq_bf16x2 __attribute__((ext_vector_type(2)));
 // cache bits of one fragment -> the MFMA operand bits: bf16 as they are; e4m3fn codes widened with the head's scale
 __device__ __forceinline__ att_raw gq_widen(att_raw v, float) { return v; }
-__device__ __forceinline__ att_raw gq_widen(gq_u32x2 v, float sc) {
-  const gq_bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, true);
-  const gq_bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, true);
-  return __builtin_bit_cast(att_raw, gq_bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]});
+__device__ __forceinline__ att_raw gq_widen(u32x2 v, float sc) {
+  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.x, sc, true);
+  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v.y, sc, true);
+  return __builtin_bit_cast(att_raw, bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]});
 }
 __device__ __forceinline__ float gq_pow2_inv(float sc) { return __uint_as_float(0x7f000000u - __float_as_uint(sc)); }     // 1 / 2^p, exact
-__device__ __forceinline__ gq_u32x2 gq_codes8(const float (&x)[8], float inv) {
-  gq_u32x2 o;
+__device__ __forceinline__ u32x2 gq_codes8(const float (&x)[8], float inv) {
+  u32x2 o;
   o.x = vv_e4m3_sat(x[0] * inv) | (vv_e4m3_sat(x[1] * inv) << 8) | (vv_e4m3_sat(x[2] * inv) << 16) | (vv_e4m3_sat(x[3] * inv) << 24);
   o.y = vv_e4m3_sat(x[4] * inv) | (vv_e4m3_sat(x[5] * inv) << 8) | (vv_e4m3_sat(x[6] * inv) << 16) | (vv_e4m3_sat(x[7] * inv) << 24);
   return o;
@@ -331,7 +319,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
   constexpr int d = 128;
   constexpr bool F8 = std::is_same<KVA, vv_kv_args8>::value;
   using elem_t = typename std::conditional<F8, uint8_t, bf16_t>::type;      // one cache element
-  using raw_t = typename std::conditional<F8, gq_u32x2, att_raw>::type;     // one fragment of 8 elements as it is loaded
+  using raw_t = typename std::conditional<F8, u32x2, att_raw>::type;     // one fragment of 8 elements as it is loaded
   __shared__ __attribute__((aligned(16))) float so[NW][GQ_MAXG][GQ_PITCH];     // per wave and query: O[128], then m, l
   __shared__ float s_new[GQ_MAXG];
   __shared__ int s_last;
@@ -431,7 +419,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if constexpr (F8) {
-        *reinterpret_cast<gq_u32x2*>(kc + (int64_t)pos * d + 32 * s + 8 * g) = gq_codes8(kn[s], gq_pow2_inv(ksc));
+        *reinterpret_cast<u32x2*>(kc + (int64_t)pos * d + 32 * s + 8 * g) = gq_codes8(kn[s], gq_pow2_inv(ksc));
       } else {
         att_raw pk;
         pk.x = gq_pk(kn[s][0], kn[s][1]); pk.y = gq_pk(kn[s][2], kn[s][3]); pk.z = gq_pk(kn[s][4], kn[s][5]); pk.w = gq_pk(kn[s][6], kn[s][7]);
@@ -442,15 +430,15 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
   ASTAMP(1);                                       // q / k / rope landed, RoPE, split, new token
   // ---- key tiles ----------------------------------------------------------------------------------------------------------------------------
   issue(1, ks + 32 * (wave + NW), kv.s_max - 1);      // second tile of this wave: requested once the fp32 q / k registers are free
-  gq_f32x4 oacc[8];
+  f32x4 oacc[8];
 #pragma unroll
-  for (int dt = 0; dt < 8; ++dt) oacc[dt] = gq_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < 8; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_part = 0.f;
   auto consume = [&](int buf, int key0) {
-    gq_f32x4 sc[2];
+    f32x4 sc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      sc[t] = gq_f32x4{0.f, 0.f, 0.f, 0.f};
+      sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const att_raw kf = gq_widen(kraw[buf][t][s], ksc);
@@ -488,7 +476,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_gqa_kernel(const float* q
       const att_raw vf = gq_widen(vraw[buf][dt], vsc);
       att_raw a;
       a.x = vf.x & a0; a.y = vf.y & a1; a.z = vf.z & a2; a.w = vf.w & a3;
-      gq_f32x4 o = oacc[dt];
+      f32x4 o = oacc[dt];
       o[0] *= corr; o[1] *= corr; o[2] *= corr; o[3] *= corr;
       o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(a), gq_frag(phi), o, 0, 0, 0);
       o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gq_frag(a), gq_frag(plo), o, 0, 0, 0);
@@ -725,7 +713,7 @@ __global__ __launch_bounds__(256) void kvq_absmax_kernel(vv_kv_args src, vv_kv_a
 __device__ __forceinline__ att_raw kvq_codes16(const att_raw a, const att_raw b, float inv) {
   float x[8], y[8];
   unpack8(a, x); unpack8(b, y);
-  const gq_u32x2 lo = gq_codes8(x, inv), hi = gq_codes8(y, inv);
+  const u32x2 lo = gq_codes8(x, inv), hi = gq_codes8(y, inv);
   return att_raw{lo.x, lo.y, hi.x, hi.y};
 }
 

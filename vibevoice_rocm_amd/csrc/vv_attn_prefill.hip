@@ -25,12 +25,6 @@
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pk2(float a, float b) {      // two floats -> packed bf16 pair, round to nearest even
-  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-  return ((ua + 0x7fffu + ((ua >> 16) & 1u)) >> 16) | (((ub + 0x7fffu + ((ub >> 16) & 1u)) >> 16) << 16);
-}
 __device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
 __global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int64_t ld, int heads, vv_kv_args kv, int layer, const int* lens, const int* cache_rows,
@@ -56,7 +50,7 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int6
   for (int s = 0; s < 8; ++s) {
     const float4 a = *reinterpret_cast<const float4*>(qp + 16 * s), b = *reinterpret_cast<const float4*>(qp + 16 * s + 4);
     u32x4 p;
-    p.x = pk2(a.x * qsc, a.y * qsc); p.y = pk2(a.z * qsc, a.w * qsc); p.z = pk2(b.x * qsc, b.y * qsc); p.w = pk2(b.z * qsc, b.w * qsc);
+    p.x = bf16_bits2(a.x * qsc, a.y * qsc); p.y = bf16_bits2(a.z * qsc, a.w * qsc); p.z = bf16_bits2(b.x * qsc, b.y * qsc); p.w = bf16_bits2(b.z * qsc, b.w * qsc);
     qf[s] = as_frag(p);
   }
   unsigned long long todo = __ballot(1);
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(const float* qkv, int6
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       u32x4 w;
-      w.x = pk2(p[8 * s + 0], p[8 * s + 1]); w.y = pk2(p[8 * s + 2], p[8 * s + 3]); w.z = pk2(p[8 * s + 4], p[8 * s + 5]); w.w = pk2(p[8 * s + 6], p[8 * s + 7]);
+      w.x = bf16_bits2(p[8 * s + 0], p[8 * s + 1]); w.y = bf16_bits2(p[8 * s + 2], p[8 * s + 3]); w.z = bf16_bits2(p[8 * s + 4], p[8 * s + 5]); w.w = bf16_bits2(p[8 * s + 6], p[8 * s + 7]);
       pf[s] = as_frag(w);
     }
     // O^T += V^T P

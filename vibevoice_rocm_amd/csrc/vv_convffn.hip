@@ -27,7 +27,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // phase timing of workgroup (0, 0) / thread 0, debug builds only (-DVV_CF_TIMING, tools/convffn_phase.py)
 #ifdef VV_CF_TIMING

@@ -222,7 +222,6 @@ __global__ __launch_bounds__(256) void conv_ctx_scatter_kernel(const CtxArgs a) 
 struct AdaTab { const bf16_t* w[17]; float* out[17]; int nblk[17]; int ldo[17]; int n; };
 
 typedef __bf16 ad_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float ad_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int ad_u32x4 __attribute__((ext_vector_type(4)));
 
 template <int NST, int NM>
@@ -244,9 +243,9 @@ __global__ __launch_bounds__(256) void adaln_all_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int s = 0; s < NST; ++s) xf[t][s] = *reinterpret_cast<const ad_u32x4*>(xr + 32 * s);
   }
-  ad_f32x4 acc[NM];
+  f32x4 acc[NM];
 #pragma unroll
-  for (int t = 0; t < NM; ++t) acc[t] = ad_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < NST; ++s)
 #pragma unroll
@@ -333,9 +332,9 @@ __global__ __launch_bounds__(256) void adaln_lds_kernel(const bf16_t* __restrict
 #pragma unroll
       for (int s = 0; s < NST; ++s) wnn[s] = *reinterpret_cast<const ad_u32x4*>(wr + 32 * s);
     }
-    ad_f32x4 acc[NM];
+    f32x4 acc[NM];
 #pragma unroll
-    for (int t = 0; t < NM; ++t) acc[t] = ad_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < NM; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < NST; ++s)
 #pragma unroll
@@ -588,10 +587,7 @@ __global__ __launch_bounds__(256) void head_pre_kernel(const HeadPreArgs a) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const float v0 = c0[0][r] + te[ps][0], v1 = c0[1][r] + te[ps][1];
-          const float s0 = v0 / (1.0f + expf(-v0)), s1 = v1 / (1.0f + expf(-v1));
-          const unsigned u0 = __float_as_uint(s0), u1 = __float_as_uint(s1);        // round to nearest even, as kv_store<bf16_t>
-          const unsigned pk = ((u0 + 0x7fffu + ((u0 >> 16) & 1u)) >> 16) | (((u1 + 0x7fffu + ((u1 >> 16) & 1u)) >> 16) << 16);
-          *reinterpret_cast<unsigned*>(a.c_out + ((int64_t)(i * 2 + r)) * D + n) = pk;
+          *reinterpret_cast<unsigned*>(a.c_out + ((int64_t)(i * 2 + r)) * D + n) = bf16_bits2(vv_silu(v0), vv_silu(v1));     // rounds as kv_store<bf16_t>
         }
       }
     }

@@ -26,9 +26,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int MX_TM = 64;                        // rows of a workgroup's tile
 constexpr int MX_TN = 128;                       // channels of a workgroup's tile: 2 waves x 16 quads x 4 rows
 constexpr int MX_BK = 128;                       // K elements per slab: a row is 256 bytes = 16 pieces of 16, four 32-wide MFMA steps
@@ -36,28 +33,6 @@ constexpr int MX_STEPS = MX_BK / 32;
 constexpr int MX_SLAB = MX_TM * MX_BK * 2;       // bytes of one activation slab (16 KB)
 constexpr int MX_PIECES = MX_SLAB / (16 * 256);  // DMA instructions per thread per slab (4)
 constexpr int MX_RT = 2;                         // 16-row tiles per wave
-
-// 8 e2m1 codes (one dword of a lane's load) under scale byte e -> one bf16 MFMA fragment of a 32-wide k step (mx_frag of vv_gemv_rows.hip)
-__device__ __forceinline__ bf16x8 mxg_frag(unsigned codes, unsigned e) {
-  const float s = __uint_as_float(e << 23);
-  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 0);
-  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 1);
-  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 2);
-  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 3);
-  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
-
-__device__ __forceinline__ unsigned int mxg_pack2(float a, float b) {
-  const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
-  return (unsigned int)(*reinterpret_cast<const bf16_t*>(&x)) | ((unsigned int)(*reinterpret_cast<const bf16_t*>(&y)) << 16);
-}
-
-// pk_xcd_remap of vv_gemm_packed.hip: the workgroups one XCD receives (ids = x mod 8) own consecutive tiles, so the row tiles of one weight
-// panel meet in one L2.  Bijective for every nwg
-__device__ __forceinline__ int mxg_xcd_remap(int orig, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
 
 // one slab's codes and scale dwords of one matrix, as a lane holds them
 struct MxW { u32x4 c[MX_STEPS]; unsigned e[MX_STEPS]; };
@@ -69,7 +44,7 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const vv_lin_args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = a.m, K = a.k, N = a.n;
   const int mtiles = (M + MX_TM - 1) / MX_TM;
-  const int wg = mxg_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int wg = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   const int n0 = (wg / mtiles) * MX_TN, m0 = (wg % mtiles) * MX_TM;          // consecutive workgroups share the weight panel
   // piece p = 256 i + tid of a slab: LDS row p >> 4, slot p & 15 <- the row's k piece (p & 15) ^ (row & 15)
   const bf16_t* xg[MX_PIECES];
@@ -132,9 +107,9 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const vv_lin_args a) {
         if (r < nrt) fb[r] = *reinterpret_cast<const u32x4*>(xs + brow + r * 16 * 256 + (((4 * s + fc) ^ fj) << 4));
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x8 fa = mxg_frag(cw.c[s][i], (cw.e[s] >> (8 * i)) & 0xffu);
+        const bf16x8 fa = mx_frag(cw.c[s][i], (cw.e[s] >> (8 * i)) & 0xffu);
         bf16x8 fa2;
-        if (DUAL) fa2 = mxg_frag(cw2.c[s][i], (cw2.e[s] >> (8 * i)) & 0xffu);
+        if (DUAL) fa2 = mx_frag(cw2.c[s][i], (cw2.e[s] >> (8 * i)) & 0xffu);
 #pragma unroll
         for (int r = 0; r < MX_RT; ++r)
           if (r < nrt) {
@@ -161,7 +136,7 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const vv_lin_args a) {
       if (a.bias) { const float4 b = *reinterpret_cast<const float4*>(a.bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
       if (DUAL) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = v[i] / (1.0f + expf(-v[i])) * acc2[i][r][e];
+        for (int i = 0; i < 4; ++i) v[i] = vv_silu(v[i]) * acc2[i][r][e];
       }
       if (a.res) {
         const float4 rs = *reinterpret_cast<const float4*>(a.res + (int64_t)m * a.ldres + n);
@@ -169,8 +144,8 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const vv_lin_args a) {
       }
       if (OBF) {
         uint2 p;
-        p.x = mxg_pack2(v[0], v[1]);
-        p.y = mxg_pack2(v[2], v[3]);
+        p.x = pack2(v[0], v[1]);
+        p.y = pack2(v[2], v[3]);
         *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.out) + (int64_t)m * a.ldo + n) = p;
       } else {
         *reinterpret_cast<float4*>(a.out + (int64_t)m * a.ldo + n) = make_float4(v[0], v[1], v[2], v[3]);

@@ -32,18 +32,6 @@ constexpr int PK_PIECES = PK_SLAB / (16 * 256);  // DMA instructions per thread 
 constexpr int PK_ROWS_DEFAULT = 2640;
 int g_packed_rows = PK_ROWS_DEFAULT;             // fewest rows for this kernel (tuning hook "gemm_packed_rows"; 0 = never, < 0 = back to the default)
 
-__device__ __forceinline__ unsigned int pk_pack2(float a, float b) {
-  const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
-  return (unsigned int)(*reinterpret_cast<const bf16_t*>(&x)) | ((unsigned int)(*reinterpret_cast<const bf16_t*>(&y)) << 16);
-}
-
-// the workgroup's place in a grid of nwg, renumbered so that the workgroups one XCD receives (ids = x mod 8) own consecutive tiles.  Bijective
-// for every nwg: the first nwg % 8 XCDs hold one workgroup more than the others
-__device__ __forceinline__ int pk_xcd_remap(int orig, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
-
 template <bool DUAL, bool OBF>
 __global__ __launch_bounds__(256) void gemm_packed_kernel(const vv_lin_args a) {
   constexpr int NOP = DUAL ? 3 : 2;              // operand slabs per buffer: x, w (, w2)
@@ -52,7 +40,7 @@ __global__ __launch_bounds__(256) void gemm_packed_kernel(const vv_lin_args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = a.m, K = a.k;
   const int mtiles = (M + PK_T - 1) / PK_T;
-  const int wg = pk_xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int wg = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   const int n0 = (wg / mtiles) * PK_T, m0 = (wg % mtiles) * PK_T;        // consecutive workgroups share the weight panel
   // piece p = 256 i + tid: LDS row p >> 3, slot p & 7 <- the row's k piece (p & 7) ^ ((row >> 1) & 7)
   const bf16_t* xg[PK_PIECES]; const bf16_t* wg1[PK_PIECES]; const bf16_t* wg2[PK_PIECES];
@@ -136,7 +124,7 @@ __global__ __launch_bounds__(256) void gemm_packed_kernel(const vv_lin_args a) {
         if (a.bias) { const float4 b = *reinterpret_cast<const float4*>(a.bias + n); v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
         if (DUAL) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + expf(-v[e])) * acc2[i][j][4 * g + e];
+          for (int e = 0; e < 4; ++e) v[e] = vv_silu(v[e]) * acc2[i][j][4 * g + e];
         }
         if (a.res) {
           const float4 r = *reinterpret_cast<const float4*>(a.res + (int64_t)m * a.ldres + n);
@@ -144,8 +132,8 @@ __global__ __launch_bounds__(256) void gemm_packed_kernel(const vv_lin_args a) {
         }
         if (OBF) {
           uint2 p;
-          p.x = pk_pack2(v[0], v[1]);
-          p.y = pk_pack2(v[2], v[3]);
+          p.x = pack2(v[0], v[1]);
+          p.y = pack2(v[2], v[3]);
           *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(a.out) + (int64_t)m * a.ldo + n) = p;
         } else {
           *reinterpret_cast<float4*>(a.out + (int64_t)m * a.ldo + n) = make_float4(v[0], v[1], v[2], v[3]);

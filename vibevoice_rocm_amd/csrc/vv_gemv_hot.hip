@@ -27,8 +27,6 @@
 
 namespace {
 
-__device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
-
 // ldw<NT> (vv_device.h), NT: streamed once per frame (LLM); otherwise the matrix is re-read by the next solver step (head) and stays cacheable
 
 // one lane's 8 weights of one K unit against both activation rows: even / odd k accumulate separately (v_pk_fma_f32), j ascending
@@ -39,14 +37,6 @@ __device__ __forceinline__ void fma_unit(const u32x4 wv, const float (&x0)[8], c
   for (int j = 0; j < 8; j += 2) p0 = __builtin_elementwise_fma(vf2{w[j], w[j + 1]}, vf2{x0[j], x0[j + 1]}, p0);
 #pragma unroll
   for (int j = 0; j < 8; j += 2) p1 = __builtin_elementwise_fma(vf2{w[j], w[j + 1]}, vf2{x1[j], x1[j + 1]}, p1);
-}
-
-// v * gate + res as the generic epilogue rounds it: a product and a sum (its operands sit behind run-time selects there and are never
-// contracted into one FMA)
-__device__ __forceinline__ float vv_hot_gate_res(float v, float g, float r) {
-#pragma clang fp contract(off)
-  const float t = v * g;
-  return t + r;
 }
 
 // How the arguments arrive: the leading kernel parameters are exactly what the loads in front of the first wait need, the pointers and then their
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void hot_dual_kernel(const float* x, const 
     }
     if (lane < M) {                                // lane m keeps (row n, m)
       const float v = lane == 0 ? acc[0] : acc[1], v2 = lane == 0 ? acc2[0] : acc2[1];
-      a.out[(int64_t)lane * a.ldo + n] = silu1(v) * v2;
+      a.out[(int64_t)lane * a.ldo + n] = vv_silu(v) * v2;
     }
   }
 }
@@ -383,7 +373,7 @@ __global__ __launch_bounds__(256) void hot_down_kernel(const float* x, const flo
 #pragma unroll
     for (int w4 = 0; w4 < NW; ++w4) s += part[w4][tid];
     float v = s;
-    if constexpr (GATE) v = vv_hot_gate_res(v, eg, er);
+    if constexpr (GATE) v = gate_res(v, eg, er);
     else v += er;
     a.out[(int64_t)eo_m * a.ldo + eo_n] = v;
   }

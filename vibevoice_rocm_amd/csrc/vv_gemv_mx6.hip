@@ -31,36 +31,13 @@
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
 typedef float f32x32 __attribute__((ext_vector_type(32)));
 
-__device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
-// epilogue operands (bias / gate / residual) of one output, fetched a row group ahead (loads return in order: an operand load issued at epilogue
-// time would wait for itself alone, but on the critical path).  Straight-line and use-free: an absent operand reads x[0] (always a valid
-// address), the values are only looked at in epi_store.
-struct EpiOp { float b, g, r; };
-__device__ __forceinline__ EpiOp epi_load(const vv_lin_args& a, int m, int n) {
-  EpiOp e;
-  const float* pb = a.bias ? a.bias + n : a.x;
-  const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)m * a.gate_ld + n : (int64_t)n) : a.x;
-  const float* pr = a.res ? a.res + (int64_t)m * a.ldres + n : a.x;
-  e.b = *pb; e.g = *pg; e.r = *pr;
-  return e;
+// the epilogue operands (bias / gate / residual) of one output are fetched a row group ahead: EpiOp<false>, epi_load (vv_device.h)
+__device__ __forceinline__ void epi_store(const vv_lin_args& a, int m, int n, float v, float v2, const EpiOp<false>& e) {
+  a.out[(int64_t)m * a.ldo + n] = vv_epi_value(a, v, v2, e);
 }
-__device__ __forceinline__ void epi_store(const vv_lin_args& a, int m, int n, float v, float v2, const EpiOp& e) {
-  if (a.bias) v += e.b;
-  if (a.act == VV_ACT_GELU) v = gelu1(v);
-  else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
-  if (a.gate) v *= e.g;
-  if (a.res) v += e.r;
-  a.out[(int64_t)m * a.ldo + n] = v;
-}
-
-// sum over the 64 lanes, in every lane (vv_wave_sum: DPP row reductions, fixed order)
-__device__ __forceinline__ float wsum(float v) { return vv_wave_sum(v); }
 
 // the 32 weights of one block: its 24 bytes (16 from plane A, 8 from plane B) under scale byte e
 __device__ __forceinline__ f32x32 decode32(const u32x4 lo, const u32x2 hi, unsigned int e) {
@@ -143,9 +120,9 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 256 : 64 * KSPLIT) void gemv_mx6_kern
   const int eid = (KSPLIT == 1) ? lane : tid;
   const int eo_id = eid < RW * M ? eid : 0;          // lanes that own no output fetch output 0's operands: no divergent branch around the loads
   const int eo_r = eo_id / M, eo_m = (eo_id - eo_r * M) < mr ? (eo_id - eo_r * M) : mr - 1;
-  EpiOp eo_cur = {0.f, 1.f, 0.f};
-  auto load_eo = [&](EpiOp& e, int grp) {
-    if (has_eo) e = epi_load(a, eo_m, min(grp * RW + eo_r, N - 1));
+  EpiOp<false> eo_cur = {{0.f, 1.f, 0.f}};
+  auto load_eo = [&](EpiOp<false>& e, int grp) {
+    if (has_eo) e = epi_load<false>(a, eo_m, min(grp * RW + eo_r, N - 1));
   };
 
   // ---- activations: this lane's 32 k of every unit, after the prologue, as the packed FMA's operand pairs ---------------------------
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 256 : 64 * KSPLIT) void gemv_mx6_kern
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           float4& p = xv[m][u][j];
-          p.x = silu1(p.x); p.y = silu1(p.y); p.z = silu1(p.z); p.w = silu1(p.w);
+          p.x = vv_silu(p.x); p.y = vv_silu(p.y); p.z = vv_silu(p.z); p.w = vv_silu(p.w);
         }
   }
   if (rms) {
@@ -229,7 +206,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 256 : 64 * KSPLIT) void gemv_mx6_kern
           const float4 p = xv[m][u][j];
           t = fmaf(p.x, p.x, t); t = fmaf(p.y, p.y, t); t = fmaf(p.z, p.z, t); t = fmaf(p.w, p.w, t);
         }
-      ss[m] = wsum(t);                               // KSPLIT == 1: the wave holds the whole row
+      ss[m] = vv_wave_sum(t);                               // KSPLIT == 1: the wave holds the whole row
     }
     if (KSPLIT != 1) {
       if (lane == 0) {
@@ -347,8 +324,8 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 256 : 64 * KSPLIT) void gemv_mx6_kern
       }
 #pragma unroll
       for (int m = 0; m < M; ++m) {
-        const float s = wsum(pacc[m].x + pacc[m].y);
-        const float s2 = DUAL ? wsum(pacc2[m].x + pacc2[m].y) : 0.f;
+        const float s = vv_wave_sum(pacc[m].x + pacc[m].y);
+        const float s2 = DUAL ? vv_wave_sum(pacc2[m].x + pacc2[m].y) : 0.f;
         if (KSPLIT == 1) {
           if (lane == r * M + m) { own = s; own2 = s2; }
         } else if (lane == 0) {

@@ -55,17 +55,6 @@
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned bf_bits(float f) {     // round to nearest even (finite activations)
-  const unsigned u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
 struct RowsAux {
   int atomic;        // ksplit > 1 with a linear epilogue whose residual already sits in `out` (res == out): every K slice adds gate * (partial [+ bias])
                      // to out with fp32 atomics - no partial tiles, no ticket, nothing to wait for (the summation ORDER of the slices then varies from
@@ -79,8 +68,6 @@ struct RowsAux {
 
 constexpr int MAXSPLIT = 16;
 
-struct EpiOps { float b, g, r; };
-
 // 16 e4m3fn codes (one fp8 fragment-major lane load) -> the bf16 B fragments of two 32-wide k steps, times the row scale s (a power of two)
 __device__ __forceinline__ void fp8_frags(const u32x4 w, float s, bf16x8& b0, bf16x8& b1) {
   bf16x2 p[8];
@@ -91,16 +78,6 @@ __device__ __forceinline__ void fp8_frags(const u32x4 w, float s, bf16x8& b0, bf
   }
   b0 = bf16x8{p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], p[3][0], p[3][1]};
   b1 = bf16x8{p[4][0], p[4][1], p[5][0], p[5][1], p[6][0], p[6][1], p[7][0], p[7][1]};
-}
-
-// 8 e2m1 codes (one dword of a lane's MXFP4 load) under scale byte e -> the bf16 B fragment of one 32-wide k step
-__device__ __forceinline__ bf16x8 mx_frag(unsigned codes, unsigned e) {
-  const float s = __uint_as_float(e << 23);
-  const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 0);
-  const bf16x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 1);
-  const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 2);
-  const bf16x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 3);
-  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
 // The weight format WF (vv_rows_route.wf) owns the width of a weight load, the addresses `issue` computes, the decode in front of the MFMA and the

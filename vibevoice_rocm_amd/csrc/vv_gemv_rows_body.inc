@@ -61,9 +61,9 @@
   const int em = (tid >> 4) & (MR - 1), en = tid & 15;
   const int emr = em < mr ? em : mr - 1;
   auto load_eo = [&](int grp) {
-    EpiOps e;
     int egn = min(grp, n_groups - 1) * 16 + en;
     if constexpr (!MX) egn = min(egn, N - 1);       // MXFP4: N % 16 == 0, in bounds as it is
+    EpiOp<false> e;
     const float* pb = a.bias ? a.bias + egn : a.x;
     const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)emr * a.gate_ld + egn : (int64_t)egn) : a.x;
     const float* pr = a.res ? a.res + (int64_t)emr * a.ldres + egn : a.x;
@@ -122,7 +122,7 @@
   u32x4 wn[PERS ? KS : 1], wn2[(PERS && DUAL) ? KS : 1];
   unsigned ec[MX ? KS : 1], ec2[(MX && DUAL) ? KS : 1];                       // MXFP4: the loads' scale dwords
   unsigned en_[(MX && PERS) ? KS : 1], en2[(MX && PERS && DUAL) ? KS : 1];
-  EpiOps eo = load_eo(g), eo_n = eo;
+  EpiOp<false> eo = load_eo(g), eo_n = eo;
   float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;                         // fp8: the row scales
   if constexpr (F8) { sc = wscale_of(a.wscale, g); if (DUAL) sc2 = wscale_of(a.w2scale, g); }
   issue(wc, ec, wc2, ec2, g);
@@ -329,13 +329,12 @@
     }
     if (tid < ET) {
       const int gn = g * 16 + en;
+      // the shared sequence on this thread's output.  The shape is the one that leaves the instruction streams as they were: v assigned in two
+      // blocks and the operands handed over by value.  With eo by reference, or v initialised and used in one block, the persistent DUAL
+      // kernels come out with the same instructions on other registers (4 .. 8 of the 44; DESIGN.md, "One epilogue, one set of device helpers")
+      float v = s * rs, v2 = s2 * rs;
       if (em < mr && gn < N) {
-        float v = s * rs, v2 = s2 * rs;
-        if (a.bias) v += eo.b;
-        if (a.act == VV_ACT_GELU) v = gelu1(v);
-        else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
-        if (a.gate) v *= eo.g;
-        if (a.res) v += eo.r;
+        v = vv_epi_value(a, v, v2, EpiHeld{eo.b, eo.g, eo.r});
         a.out[(int64_t)em * a.ldo + gn] = v;
       }
     }

@@ -28,12 +28,12 @@
           }
         }
         if (!cval[cc] || 8 * t + m >= mr) v = make_float4(0.f, 0.f, 0.f, 0.f);
-        const unsigned h0 = bf_bits(v.x), h1 = bf_bits(v.y), h2 = bf_bits(v.z), h3 = bf_bits(v.w);
+        const unsigned h0 = bf16_bits(v.x), h1 = bf16_bits(v.y), h2 = bf16_bits(v.z), h3 = bf16_bits(v.w);
         const float l0 = v.x - __uint_as_float(h0 << 16), l1 = v.y - __uint_as_float(h1 << 16);
         const float l2 = v.z - __uint_as_float(h2 << 16), l3 = v.w - __uint_as_float(h3 << 16);
         u32x2 hi, lo;
         hi.x = h0 | (h1 << 16); hi.y = h2 | (h3 << 16);
-        lo.x = bf_bits(l0) | (bf_bits(l1) << 16); lo.y = bf_bits(l2) | (bf_bits(l3) << 16);
+        lo.x = bf16_bits(l0) | (bf16_bits(l1) << 16); lo.y = bf16_bits(l2) | (bf16_bits(l3) << 16);
         *reinterpret_cast<u32x2*>(base + (size_t)m * 16) = hi;               // fragment row m: high parts
         *reinterpret_cast<u32x2*>(base + (size_t)(m + 8) * 16) = lo;         // fragment row m + 8: low parts
       }

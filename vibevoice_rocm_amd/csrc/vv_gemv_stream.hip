@@ -22,42 +22,16 @@
 
 namespace {
 
-__device__ __forceinline__ float wsum(float v) { return vv_wave_sum(v); }   // DPP row reduction, all 64 lanes active
-__device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
 // 8 e4m3fn weights in the low 8 bytes of the tile register (fp8 weight-only mode: 8-byte loads per lane)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void unpack8_f8(const u32x4 v, float (&o)[8]) {
   const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true);
   const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true);
   o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y; o[4] = c.x; o[5] = c.y; o[6] = d.x; o[7] = d.y;
 }
 
-// epilogue operands (bias / adaLN gate / residual) of one output: their addresses are known before the dot product is, so
-// they are loaded one row group ahead, in front of the weight loads that follow them in the queue (loads return in order: an
-// operand load issued at epilogue time would sit behind two row groups of prefetched weights)
-// ROWSC: the instantiation can meet fp8 row scales at all (every format but MXFP4).  For the others the fp8 loads and multiplies hang on the
-// run-time test a.wdt == VV_FP8; the MXFP4 kernels carry none of them: their EpiOp is b, g, r.
-template <bool ROWSC> struct EpiOp { float b, g, r, s, s2; };   // bias, gate, residual, fp8 row scales (raw loads; absent operands are ignored at use)
-template <> struct EpiOp<false> { float b, g, r; };
-template <bool ROWSC>
-__device__ __forceinline__ EpiOp<ROWSC> epi_load(const vv_lin_args& a, int m, int n) {
-  // straight-line and use-free: an absent operand reads x[0] (always a valid address), the values are only looked at in epi_pre.
-  // With a select per operand here the compiler waited for each dword right away - draining every load issued before it - and a
-  // uniform branch per operand cut the issue sequence into blocks it then reordered.
-  EpiOp<ROWSC> e;
-  const bool f8s = ROWSC && a.wdt == VV_FP8, f8d = f8s && a.w2;
-  const float* pb = a.bias ? a.bias + n : a.x;
-  const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)m * a.gate_ld + n : (int64_t)n) : a.x;
-  const float* pr = a.res ? a.res + (int64_t)m * a.ldres + n : a.x;
-  const float* ps = f8s ? a.wscale + n : a.x;
-  const float* ps2 = f8d ? a.w2scale + n : a.x;
-  e.b = *pb; e.g = *pg; e.r = *pr;
-  if constexpr (ROWSC) { e.s = *ps; e.s2 = *ps2; }
-  return e;
-}
+// epilogue operands (bias / adaLN gate / residual) of one output are loaded one row group ahead, in front of the weight loads that follow them in
+// the queue: EpiOp<ROWSC>, epi_load (vv_device.h).  ROWSC: the instantiation can meet fp8 row scales at all (every format but MXFP4).  For the
+// others the fp8 loads and multiplies hang on the run-time test a.wdt == VV_FP8; the MXFP4 kernels carry none of them: their EpiOp is b, g, r.
 __device__ __forceinline__ EpiOp<true> epi_load_cond(const vv_lin_args& a, int m, int n) {   // one uniform branch per operand (owner lanes only)
   EpiOp<true> e;
   e.b = a.bias ? a.bias[n] : 0.f;
@@ -72,12 +46,7 @@ __device__ __forceinline__ void epi_pre(const vv_lin_args& a, int m, int n, floa
   if constexpr (ROWSC) {
     if (a.wdt == VV_FP8) { v *= e.s; if (a.w2) v2 *= e.s2; }      // fp8 codes carry a row scale
   }
-  if (a.bias) v += e.b;
-  if (a.act == VV_ACT_GELU) v = gelu1(v);
-  else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
-  if (a.gate) v *= e.g;
-  if (a.res) v += e.r;
-  a.out[(int64_t)m * a.ldo + n] = v;
+  a.out[(int64_t)m * a.ldo + n] = vv_epi_value(a, v, v2, e);
 }
 
 // NF4 (VV_NF4, weight-only 4-bit): the instantiation streams FOUR weight rows per step so that each lane's 16-byte load carries the 32 codes
@@ -89,13 +58,12 @@ __constant__ float c_nf4_table[16] = {-1.0f, -0.6961928009986877f, -0.5250730514
                                       -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,
                                       0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f,
                                       0.7229568362236023f, 1.0f};
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void nf4_build_lut(float s, unsigned int* dst) {   // dst: this lane's 8 dwords (16 bf16) in the wave's LDS slot
   unsigned int e[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const f32x2 v = {c_nf4_table[2 * j] * s, c_nf4_table[2 * j + 1] * s};
-    e[j] = __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_t));   // v_cvt_pk_bf16_f32: round to nearest even
+    e[j] = __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32: round to nearest even
   }
   *reinterpret_cast<u32x4*>(dst) = u32x4{e[0], e[1], e[2], e[3]};
   *reinterpret_cast<u32x4*>(dst + 4) = u32x4{e[4], e[5], e[6], e[7]};
@@ -325,7 +293,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
         const float4 v = xv[m][c];
         s1 += (tid + c * T < nchunks) ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
       }
-      ss[m] = wsum(s1);
+      ss[m] = vv_wave_sum(s1);
     }
     if (lane == 0) {
 #pragma unroll
@@ -410,7 +378,7 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     }
     if (rms) {
 #pragma unroll
-      for (int m = 0; m < M; ++m) ss[m] = wsum(ss[m]);   // KSPLIT == 1: every wave holds the whole row
+      for (int m = 0; m < M; ++m) ss[m] = vv_wave_sum(ss[m]);   // KSPLIT == 1: every wave holds the whole row
       if (KSPLIT != 1) {
         if (lane == 0) {
 #pragma unroll
@@ -459,13 +427,13 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
       }
       if (a.pro == VV_PRO_SILU) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) xr[m][u][j] = silu1(xr[m][u][j]);
+        for (int j = 0; j < 8; ++j) xr[m][u][j] = vv_silu(xr[m][u][j]);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) ss = fmaf(xr[m][u][j], xr[m][u][j], ss);
     }
     if (a.pro == VV_PRO_RMSNORM) {
-      ss = wsum(ss);                               // KSPLIT == 1: every wave holds the whole row
+      ss = vv_wave_sum(ss);                               // KSPLIT == 1: every wave holds the whole row
       if (KSPLIT != 1) {
         if (lane == 0) red[wave * M + m] = ss;
         __syncthreads();
@@ -597,8 +565,8 @@ __global__ __launch_bounds__(KSPLIT == 1 ? 512 : 64 * KSPLIT) void gemv_stream_k
     for (int r = 0; r < RW; ++r)
 #pragma unroll
       for (int m = 0; m < M; ++m) {
-        acc[r][m] = wsum(pacc[r][m].x + pacc[r][m].y);
-        if (DUAL) acc2[r][m] = wsum(pacc2[r][m].x + pacc2[r][m].y);
+        acc[r][m] = vv_wave_sum(pacc[r][m].x + pacc[r][m].y);
+        if (DUAL) acc2[r][m] = vv_wave_sum(pacc2[r][m].x + pacc2[r][m].y);
       }
     if (KSPLIT == 1) {
       if (lane < RW * M) {                         // every lane holds all sums: lane r * M + m keeps (r, m)

@@ -128,9 +128,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float wave_sum_dpp(float v) { return vv_wave_sum(v); }   // all 64 lanes active
-__device__ __forceinline__ float silu_f(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 template <typename WT> struct WL;
 template <> struct WL<float> {
@@ -148,10 +145,7 @@ template <> struct WL<float> {
 template <> struct WL<bf16_t> {
   static __device__ __forceinline__ void load8(const bf16_t* p, float (&o)[8]) {
     const uint4 v = *reinterpret_cast<const uint4*>(p);
-    o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-    o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-    o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);
-    o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
+    unpack8(u32x4{v.x, v.y, v.z, v.w}, o);
   }
   static __device__ __forceinline__ void load4(const bf16_t* p, float (&o)[4]) {
     const uint2 v = *reinterpret_cast<const uint2*>(p);
@@ -162,12 +156,7 @@ template <> struct WL<bf16_t> {
 };
 
 __device__ __forceinline__ void lin_epilogue(const vv_lin_args& a, int m, int n, float v, float v2) {
-  if (a.bias) v += a.bias[n];
-  if (a.act == VV_ACT_GELU) v = gelu_f(v);
-  else if (a.act == VV_ACT_SWIGLU) v = silu_f(v) * v2;
-  if (a.gate) v *= a.gate_ld ? a.gate[(int64_t)m * a.gate_ld + n] : a.gate[n];
-  if (a.res) v += a.res[(int64_t)m * a.ldres + n];
-  a.out[(int64_t)m * a.ldo + n] = v;
+  a.out[(int64_t)m * a.ldo + n] = vv_epi_value(a, v, v2, EpiAtUse{a, m, n});
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -217,7 +206,7 @@ __device__ __forceinline__ void stage_chunk(const vv_lin_args& a, float* xs, int
         if (a.norm_w) v *= a.norm_w[k];
         if (a.mod_scale) v = v * (1.0f + a.mod_scale[(int64_t)m * a.ld_mod + k]) + a.mod_shift[(int64_t)m * a.ld_mod + k];
       } else if (a.pro == VV_PRO_SILU) {
-        v = silu_f(v);
+        v = vv_silu(v);
       }
     }
     xs[idx] = v;
@@ -345,7 +334,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_generic_kernel(const vv_lin
           v *= rstd;
           if (a.norm_w) v *= a.norm_w[k];
           if (a.mod_scale) v = v * (1.0f + a.mod_scale[(int64_t)m * a.ld_mod + k]) + a.mod_shift[(int64_t)m * a.ld_mod + k];
-        } else if (a.pro == VV_PRO_SILU) v = silu_f(v);
+        } else if (a.pro == VV_PRO_SILU) v = vv_silu(v);
         s = fmaf(WL<WT>::load1(W + (int64_t)n * a.k + k), v, s);
         if (W2) s2 = fmaf(WL<WT>::load1(W2 + (int64_t)n * a.k + k), v, s2);
       }
@@ -428,7 +417,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const vv_lin_args a) {
         }
       } else if (a.pro == VV_PRO_SILU) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) av[i] = silu_f(av[i]);
+        for (int i = 0; i < 4; ++i) av[i] = vv_silu(av[i]);
       }
     }
     if (doW && n0 + lr < N) {
@@ -1569,7 +1558,7 @@ __global__ __launch_bounds__(256) void block_mixer_kernel(const float* __restric
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float tot = wave_sum_dpp(ss[u]);
+      const float tot = vv_wave_sum(ss[u]);
       if (lane == 0 && rb + u < nrow) rstd_s[rb + u] = xr[u] ? rsqrtf(tot / (float)C + eps) : 1.f;   // history rows are stored normalised
     }
   }
@@ -1608,7 +1597,7 @@ __global__ __launch_bounds__(256) void block_mixer_kernel(const float* __restric
         const float* xs = x + (int64_t)src * C;
         float q = 0.f;
         for (int c = lane; c < C; c += 64) { const float v = xs[c]; q = fmaf(v, v, q); }
-        const float rstd = rsqrtf(wave_sum_dpp(q) / (float)C + eps);
+        const float rstd = rsqrtf(vv_wave_sum(q) / (float)C + eps);
         for (int c = lane; c < cs; c += 64) dst[c] = xs[c0 + c] * rstd * norm_w[c0 + c];
       }
     }
@@ -1666,7 +1655,7 @@ __global__ __launch_bounds__(256) void mixer_rows_kernel(const float* __restrict
   for (int i = 0; i < MIXR_NI; ++i) {
     const int e0 = 256 * i + 64 * wave;              // first element of this wave's 64: one row per wave step (C4 is a multiple of 64)
     if (e0 < nel) {
-      const float s = wave_sum_dpp(v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w);
+      const float s = vv_wave_sum(v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w);
       const int w = e0 / C4;
       if (lane == 0) part[w * 8 + ((e0 - w * C4) >> 6)] = s;
     }
@@ -1724,7 +1713,7 @@ __global__ __launch_bounds__(256) void mixer_rows_kernel(const float* __restrict
         const float* xs = x + (int64_t)src * C;
         float q = 0.f;
         for (int c = lane * 4; c < C; c += 256) { const float4 a = *reinterpret_cast<const float4*>(xs + c); q += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w; }
-        const float rstd = rsqrtf(wave_sum_dpp(q) / (float)C + eps);
+        const float rstd = rsqrtf(vv_wave_sum(q) / (float)C + eps);
         for (int c = lane * 4; c < C; c += 256) {
           const float4 a = *reinterpret_cast<const float4*>(xs + c), nw = *reinterpret_cast<const float4*>(norm_w + c);
           *reinterpret_cast<float4*>(dst + c) = make_float4(a.x * rstd * nw.x, a.y * rstd * nw.y, a.z * rstd * nw.z, a.w * rstd * nw.w);
@@ -1864,7 +1853,7 @@ __global__ void add_rows_kernel(const float* a, int64_t lda, const float* b, int
 }
 __global__ void add_rows_silu_kernel(const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int rows, int rows_b, int n) {
   const int r = blockIdx.x, i = r / rows_b, j = r - i * rows_b;
-  for (int c = threadIdx.x; c < n; c += blockDim.x) out[(int64_t)r * n + c] = silu_f(a[(int64_t)j * lda + c] + b[(int64_t)i * ldb + c]);
+  for (int c = threadIdx.x; c < n; c += blockDim.x) out[(int64_t)r * n + c] = vv_silu(a[(int64_t)j * lda + c] + b[(int64_t)i * ldb + c]);
 }
 extern "C" int vv_add_rows_silu(const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int rows, int rows_b, int n, vv_stream_t stream) {
   if (!a || !b || !out || rows <= 0 || rows_b <= 0 || rows % rows_b || n <= 0) return vv_set_error(VV_E_ARG, "vv_add_rows_silu: bad args");
@@ -1875,7 +1864,7 @@ extern "C" int vv_add_rows_silu(const float* a, int64_t lda, const float* b, int
 // bf16 output: the operand of the hoisted adaLN GEMMs (rounded to bf16 by the matrix-core path anyway)
 __global__ void add_rows_silu_bf16_kernel(const float* a, int64_t lda, const float* b, int64_t ldb, bf16_t* out, int rows, int rows_b, int n) {
   const int r = blockIdx.x, i = r / rows_b, j = r - i * rows_b;
-  for (int c = threadIdx.x; c < n; c += blockDim.x) kv_store<bf16_t>(out + (int64_t)r * n + c, silu_f(a[(int64_t)j * lda + c] + b[(int64_t)i * ldb + c]));
+  for (int c = threadIdx.x; c < n; c += blockDim.x) kv_store<bf16_t>(out + (int64_t)r * n + c, vv_silu(a[(int64_t)j * lda + c] + b[(int64_t)i * ldb + c]));
 }
 extern "C" int vv_add_rows_silu_bf16(const float* a, int64_t lda, const float* b, int64_t ldb, void* out, int rows, int rows_b, int n, vv_stream_t stream) {
   if (!a || !b || !out || rows <= 0 || rows_b <= 0 || rows % rows_b || n <= 0) return vv_set_error(VV_E_ARG, "vv_add_rows_silu_bf16: bad args");
@@ -2090,7 +2079,7 @@ __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const float* x, int
     float s = 0.f;
 #pragma unroll 4
     for (int c = tid; c < n; c += 256) { const float v = xr[c]; s = fmaf(v, v, s); }
-    s = wave_sum_dpp(s);
+    s = vv_wave_sum(s);
     if (lane == 0) red[wave] = s;
     __syncthreads();
     rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)n + eps);
@@ -2152,7 +2141,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const float* x, int64
   const float* xr = x + (int64_t)(sel ? sel[r] : r) * ldx;
   float s = 0.f;
   for (int c = tid; c < n; c += blockDim.x) s += xr[c] * xr[c];
-  s = wave_sum_dpp(s);
+  s = vv_wave_sum(s);
   if (lane == 0) red[wave] = s;
   __syncthreads();
   const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)n + eps);

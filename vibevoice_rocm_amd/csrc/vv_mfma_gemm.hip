@@ -38,14 +38,8 @@ template <int MT> struct Tile {                 // MT 32-row tiles per workgroup
   static constexpr size_t LDS = (XS_BYTES > RED_BYTES ? XS_BYTES : RED_BYTES) + ROWS * 4 + 64;
 };
 
-__device__ __forceinline__ float silu1(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float gelu1(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ void epi1(const vv_lin_args& a, int m, int n, float v, float v2) {
-  if (a.bias) v += a.bias[n];
-  if (a.act == VV_ACT_GELU) v = gelu1(v);
-  else if (a.act == VV_ACT_SWIGLU) v = silu1(v) * v2;
-  if (a.gate) v *= a.gate_ld ? a.gate[(int64_t)m * a.gate_ld + n] : a.gate[n];
-  if (a.res) v += a.res[(int64_t)m * a.ldres + n];
+  v = vv_epi_value(a, v, v2, EpiAtUse{a, m, n});
   if (a.flags & VV_LIN_OUT_BF16) {
     const __hip_bfloat16 b = __float2bfloat16(v);
     reinterpret_cast<bf16_t*>(a.out)[(int64_t)m * a.ldo + n] = *reinterpret_cast<const bf16_t*>(&b);
@@ -70,11 +64,11 @@ __device__ __forceinline__ void epi4(const vv_lin_args& a, bool vec_ok, int m, i
       for (int i = 0; i < 4; ++i) v[i] = vv_gelu_as(v[i]);
     } else {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = gelu1(v[i]);
+      for (int i = 0; i < 4; ++i) v[i] = vv_gelu(v[i]);
     }
   } else if (a.act == VV_ACT_SWIGLU) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = silu1(v[i]) * v2[i];
+    for (int i = 0; i < 4; ++i) v[i] = vv_silu(v[i]) * v2[i];
   }
   if (a.gate) {
     const float4 g = *reinterpret_cast<const float4*>(a.gate + (a.gate_ld ? (int64_t)m * a.gate_ld : 0) + n);
@@ -218,7 +212,7 @@ __global__ __launch_bounds__(256) void mfma_linear_kernel(const vv_lin_args a) {
                 v.w = v.w * (1.f + a.mod_scale[mo + 3]) + a.mod_shift[mo + 3];
               }
             } else if (a.pro == VV_PRO_SILU) {
-              v.x = silu1(v.x); v.y = silu1(v.y); v.z = silu1(v.z); v.w = silu1(v.w);
+              v.x = vv_silu(v.x); v.y = vv_silu(v.y); v.z = vv_silu(v.z); v.w = vv_silu(v.w);
             }
             uint2 p;
             p.x = pack2(v.x, v.y);
