@@ -93,13 +93,39 @@ enum { VV_WQ_FRAG4 = 0x400 };
  *                     4 q + r, block b at (q * B + b) * 4 + r - one 4-byte load per lane carries its block's scale in all four rows
  * Padding (rows past N) holds code 0 and scale byte 127.  0.78125 bytes per weight.  Any other MXFP6 call (m > 2, k % 32, a longer row, a missing
  * scale pointer, a misaligned code, scale or activation pointer, VV_LIN_W_FRAG, VV_LIN_X_BF16 / VV_LIN_OUT_BF16, VV_LIN_W_MXGEMM) returns
- * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, before any launch, the output untouched.  Value 7 is no weight type. */
+ * VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, before any launch, the output untouched.  Value 7 is no weight type.  The 3..8-row
+ * matrix-core GEMV reads the same codes in another order, VV_MXFP6_FRAG below: a weight type of its own. */
 enum { VV_MXFP6 = 6 };
 /* VV_WQ_MXFP6: as VV_WQ_MXFP4, for companions that hold MXFP6 (codes in q, the scale bytes' address in scale, the VV_MXFP6 layout above).  The
  * 1..2-row GEMVs of the LLM, the diffusion head and the tokenizers' one-row stage stream them; every other pass (3 and more rows, the prefill)
- * uses the bf16 matrices, which hold exactly the same effective values.  There is no fragment-major and no lean form: VV_WQ_FRAG4 means nothing
- * next to this bit, and composites that refuse quantised companions refuse these. */
+ * uses the bf16 matrices, which hold exactly the same effective values - unless VV_WQ_FRAG6 (below) rides along: the 3..8-row decode passes then
+ * stream the VV_MXFP6_FRAG copies.  There is no lean form (the bf16 matrices are always resident), VV_WQ_FRAG4 means nothing next to this bit,
+ * and composites that refuse quantised companions refuse these. */
 enum { VV_WQ_MXFP6 = 0x800 };
+/* VV_MXFP6_FRAG: the same OCP MXFP6 e2m3 values (6-bit codes, E8M0 scale bytes 2..252, effective weight value(code) * 2^(e - 127)) in FRAGMENT-MAJOR
+ * order, for the 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows_mx6.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding
+ * occurs), fp32 activations and outputs, no VV_LIN_W_MXGEMM.  gfx950 decodes fp6 32 codes at a time (v_cvt_scalef32_pk32_bf16_fp6), so a LANE OWNS A
+ * WHOLE MX BLOCK: lane 16 c + n of 128-wide step J of row group g owns block 4 J + c of row 16 g + n - the 32 codes of k = 128 J + 32 c .. + 31 as
+ * the 192-bit string of VV_MXFP6 (code i in bits 6 i .. 6 i + 5, little-endian).  One wave load carries 16 rows x 128 k.
+ *   w / w2:           16-byte aligned, (N K 3 / 4 bytes).  Plane A [N / 16][K / 128][64 lanes][16 B]: bytes 0..15 of the lane's string at
+ *                     ((g * K/128 + J) * 64 + 16 c + n) * 16.  Plane B [N / 16][K / 128][64 lanes][8 B], at byte offset N * K / 2: bytes 16..23 at
+ *                     N K / 2 + ((g * K/128 + J) * 64 + 16 c + n) * 8.  Every wave load is contiguous and naturally aligned (1 KB, 512 B).
+ *   wscale / w2scale: the ADDRESS of the scale bytes, read as uint8_t, 4-byte aligned: [N / 16][K / 128][16 rows][4 B] (VV_MXFP4_FRAG's
+ *                     arrangement), i.e. byte c of the dword at ((g * K/128 + J) * 16 + n) * 4 is the E8M0 byte of block 4 J + c of row 16 g + n
+ * K order: the decoded block is four B fragments - MFMA h (0..3) of the load takes elements 8 h .. 8 h + 7 of every lane's block, the k set
+ * {128 J + 32 c + 8 h + i}; the kernel lays the activation fragments out to match.  The summation order is fixed (results repeat bit for bit under
+ * vv_tune("gemv_rows_atomic", 0)) but is not the bf16 rows kernel's: against the bf16 fragment-major form of the same effective matrix results
+ * agree to fp32 reassociation, never bit for bit.  0.78125 bytes per weight.  Any other call with this code (m <= 2, m > 8, the flag missing, n % 16,
+ * k % 128, a missing scale pointer, misaligned codes or scale bytes, VV_LIN_X_BF16 / VV_LIN_OUT_BF16, VV_LIN_W_MXGEMM, k > 2048 without split-K
+ * scratch) returns VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, before any launch, the output untouched. */
+enum { VV_MXFP6_FRAG = 8 };
+/* VV_WQ_FRAG6: ORed into vv_llm.wdt / vv_head.wdt next to VV_WQ_MXFP6, the counterpart of VV_WQ_FRAG4 - a layer's f_* pointers then hold the
+ * VV_MXFP6_FRAG form of its MXFP6 companions: plane A, plane B at byte offset N * K / 2 and the scale bytes at N * K * 3 / 4, one allocation.
+ * vv_llm_forward with R in 3..8, vv_linear_ws, vv_head_sample_batch(_sde / _cfg) and the row-batched step around vv_llm_tail_batch then run
+ * gemv_rows_mx6_kernel for every matrix that has a copy; a matrix the form cannot take (N % 16, K % 128) keeps f_* = NULL and the bf16 row-major
+ * fallback.  1..2 rows and the prefill are unchanged, 9..16 rows stay bf16-only (two passes of 5..8 rows here).  No bf16 fragment copy may sit in
+ * f_* under this bit. */
+enum { VV_WQ_FRAG6 = 0x1000 };
 /* A LEAN MXFP4 LLM (vv_llm with VV_WQ_MXFP4): every layer's five bf16 pointers (wqkv, wo, wgate, wup, wdown) are NULL beside present companions
  * (q_*.q and q_*.scale) - no descriptor bit, the NULL pointers say it; all five of all layers or none (a mix is VV_E_ARG).  hidden, inter and
  * heads * head_dim must be multiples of 128 and the qkv width a multiple of 16 (what VV_LIN_W_MXGEMM takes).  vv_llm_forward and
@@ -172,7 +198,7 @@ typedef struct vv_lin_args {
   float* out;
   int64_t ldo;
   int flags;   /* VV_LIN_* */
-  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4 / VV_MXFP4_FRAG / VV_MXFP6: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
+  const float* wscale;   /* wdt == VV_FP8: out = (W8 x) * wscale[n] (+ bias ...); VV_NF4: block absmax; VV_MXFP4 / VV_MXFP4_FRAG / VV_MXFP6 / VV_MXFP6_FRAG: the address of the E8M0 scale bytes, read as uint8_t; else ignored */
   const float* w2scale;
 } vv_lin_args;
 
@@ -189,6 +215,7 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
  *   "gemv_mx6<m=2,dual=0,ksplit=5,ku=1>"                                   streaming GEMV on VV_MXFP6 weights (m: 1 or 2; ksplit waves of a block split K, ku units of 2048 k each)
  *   "gemv_rows<dual=0,nw=4,ks=6,pers=0,f8=0> ksplit=5 atomic=0"           3..8-row matrix-core GEMV (taken while vv_tune("gemv_rows_scratch", 1) holds)
  *   "gemv_rows_mx<dual=0,nw=4,ks=3,pers=0> ksplit=6 atomic=0"              the same on VV_MXFP4_FRAG weights (ks: 128-wide weight loads per wave)
+ *   "gemv_rows_mx6<dual=0,nw=4,ks=3,pers=0> ksplit=6 atomic=0"             the same on VV_MXFP6_FRAG weights (gemv_rows_mx6_kernel, csrc/vv_gemv_rows_mx6.hip)
  *   "gemv_rows16<dual=0,nw=4,ks=3,pers=0> ksplit=5 atomic=0"               9..16 rows on VV_LIN_W_FRAG bf16 weights: two row tiles per weight load (same condition)
  *   "gemv_hot<3>", "conv_hot_gemv<0>"                                      hot kernels, by table index
  *   "gemv_stream<m=4,...> + gemv_stream<m=2,...>"                          5..8 rows as two streaming passes of 4 + rest rows
@@ -346,7 +373,9 @@ typedef struct vv_llm_layer {
    *   q_*.scale), [N / 16][K / 64][4][16][2][8] bytes, i.e. code (16 g + n, 64 j + 32 h + 8 c + e) at ((g * K/64 + j) * 64 + 16 c + n) * 16 +
    *   8 h + e - one 1 KB wave load carries the B fragments of two 32-wide k steps.  N % 16 == 0, K % 64 == 0.  Never a bf16 copy.
    *   MXFP4 (VV_WQ_FRAG4 in the descriptor's wdt): f_* is the VV_MXFP4_FRAG form of the MXFP4 companion, codes then scale bytes.  N % 16 == 0,
-   *   K % 128 == 0.  Never a bf16 copy. */
+   *   K % 128 == 0.  Never a bf16 copy.
+   *   MXFP6 (VV_WQ_FRAG6 in the descriptor's wdt): f_* is the VV_MXFP6_FRAG form of the MXFP6 companion, plane A, plane B, then scale bytes.
+   *   N % 16 == 0, K % 128 == 0.  Never a bf16 copy. */
   const void* f_qkv; const void* f_o; const void* f_gate; const void* f_up; const void* f_down;
 } vv_llm_layer;
 

@@ -13,10 +13,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvv_hip.so")
 
 VV_F32, VV_BF16, VV_FP8, VV_NF4, VV_MXFP4, VV_MXFP4_FRAG, VV_MXFP6 = 0, 1, 2, 3, 4, 5, 6
+VV_MXFP6_FRAG = 8       # 7 is no weight type (include/vv_hip.h)
 VV_WQ_NF4 = 0x100      # ORed into vv_llm / vv_head / vv_convnet .wdt: their vv_w8 companions hold NF4 (include/vv_hip.h)
 VV_WQ_MXFP4 = 0x200    # likewise: the companions hold OCP MXFP4 (e2m1 codes, E8M0 scale bytes per 32 k)
 VV_WQ_MXFP6 = 0x800    # likewise: the companions hold OCP MXFP6 (e2m3 codes in two planes, E8M0 scale bytes per 32 k)
 VV_WQ_FRAG4 = 0x400    # next to VV_WQ_MXFP4 on vv_llm / vv_head: the layers' f_* copies hold the VV_MXFP4_FRAG form (codes, then scale bytes)
+VV_WQ_FRAG6 = 0x1000   # next to VV_WQ_MXFP6: the layers' f_* copies hold the VV_MXFP6_FRAG form (plane A, plane B, then scale bytes)
 PRO_NONE, PRO_RMSNORM, PRO_SILU = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SWIGLU = 0, 1, 2
 LIN_X_BF16, LIN_OUT_BF16, LIN_W_REUSED, LIN_W_FRAG, LIN_PACKED, LIN_W_MXGEMM = 1, 2, 4, 8, 16, 32

@@ -34,17 +34,18 @@ struct vv_kv_args8 : vv_kv_args {
 };
 
 // The companions' kind that rides on a descriptor's wdt (VV_WQ_*, vv_hip.h), one line per format: the first bit found wins, no bit = fp8, and vv_wq_strip leaves the matrix dtype in *wdt
-static constexpr struct { int bit, wq; } VV_WQ_KINDS[] = {
-  {VV_WQ_MXFP6, VV_MXFP6},
-  {VV_WQ_MXFP4, VV_MXFP4},
-  {VV_WQ_NF4, VV_NF4},
+// frag_bit / frag_wdt: the bit beside it that says the f_* copies hold the format's fragment-major form, and that form's weight type (0: it has none)
+static constexpr struct { int bit, wq, frag_bit, frag_wdt; } VV_WQ_KINDS[] = {
+  {VV_WQ_MXFP6, VV_MXFP6, VV_WQ_FRAG6, VV_MXFP6_FRAG},
+  {VV_WQ_MXFP4, VV_MXFP4, VV_WQ_FRAG4, VV_MXFP4_FRAG},
+  {VV_WQ_NF4, VV_NF4, 0, 0},
 };
-constexpr int vv_wq_bits() { int bits = VV_WQ_FRAG4; for (const auto& k : VV_WQ_KINDS) bits |= k.bit; return bits; }
-struct vv_wq_kind { int wq; bool frag4; };
+constexpr int vv_wq_bits() { int bits = VV_WQ_FRAG4 | VV_WQ_FRAG6; for (const auto& k : VV_WQ_KINDS) bits |= k.bit; return bits; }
+struct vv_wq_kind { int wq; int fragq; };      // fragq: 0, or the weight type the layers' f_* copies hold - VV_MXFP4_FRAG (VV_WQ_FRAG4) / VV_MXFP6_FRAG (VV_WQ_FRAG6)
 static inline vv_wq_kind vv_wq_strip(int* wdt) {
-  vv_wq_kind r = {VV_FP8, false};
+  vv_wq_kind r = {VV_FP8, 0};
   for (const auto& k : VV_WQ_KINDS) if (*wdt & k.bit) { r.wq = k.wq; break; }
-  r.frag4 = r.wq == VV_MXFP4 && (*wdt & VV_WQ_FRAG4) != 0;
+  for (const auto& k : VV_WQ_KINDS) if (r.wq == k.wq && k.frag_bit && (*wdt & k.frag_bit)) r.fragq = k.frag_wdt;
   *wdt &= ~vv_wq_bits();
   return r;
 }
@@ -55,6 +56,7 @@ static inline vv_wq_kind vv_wq_strip(int* wdt) {
 const char* vv_gemv_stream_refusal(const vv_lin_args& a, int* rc);   // VV_FP8 (row-major), VV_NF4, VV_MXFP4
 const char* vv_gemv_mx6_refusal(const vv_lin_args& a, int* rc);      // VV_MXFP6
 const char* vv_gemv_rows_refusal(const vv_lin_args& a, int* rc);     // VV_MXFP4_FRAG, VV_FP8 under VV_LIN_W_FRAG
+const char* vv_gemv_rows_mx6_refusal(const vv_lin_args& a, int* rc); // VV_MXFP6_FRAG
 
 // The decode GEMV family (m <= 8).  Every launcher is a DECISION - a plain struct computed from the arguments and the vv_tune state, no pointer
 // followed, no HIP call, the only copy of the thresholds - and a LAUNCH of that struct; vv_linear_route prints the same struct, so the name it
@@ -93,7 +95,7 @@ void vv_conv_hot_set(int mask);                                   // tuning hook
 // left zero) or null
 int vv_launch_gemv_rows(const vv_lin_args& a, float* part, size_t part_floats, int* tickets, size_t n_tickets, hipStream_t s);
 // the same, decision apart from launch: gemv_rows_kernel<dual, nw, ks, pers, wf> on (gx, ksplit) blocks, spw weight loads per wave (wf: the weight
-// format, 0 = bf16, 1 = fp8, 2 = MXFP4: 32-, 64-, 128-wide loads); atomic: the K slices add into out.  have_ws: the caller has a partials workspace
+// format, 0 = bf16, 1 = fp8, 2 = MXFP4, 3 = MXFP6: 32-, 64-, 128-, 128-wide loads); atomic: the K slices add into out.  have_ws: the caller has a partials workspace
 // and tickets (their sizes follow); kind 1 = covered
 struct vv_rows_route { int kind, dual, nw, ks, pers, wf, ksplit, spw, atomic, n_groups, gx, rt; };   // rt: row tiles of 8 (2 = gemv_rows16_kernel)
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets);
@@ -102,11 +104,16 @@ int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap);
 size_t vv_gemv_rows_part_floats(int n, int dual);
 size_t vv_gemv_rows_tickets(int n);
 int vv_gemv_rows_init();
+// vv_gemv_rows_mx6.hip: the same kernel text on VV_MXFP6_FRAG weights, gemv_rows_mx6_kernel<dual, nw, ks, pers> (route wf = 3, named
+// gemv_rows_mx6<dual, nw, ks, pers>).  vv_gemv_rows_decide decides and asks which instantiations exist; vv_launch_gemv_rows_route hands over the launch
+bool vv_gemv_rows_mx6_built(int dual, int nw, int ks, int pers);
+int vv_launch_gemv_rows_mx6_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s);   // 1 = launched
+int vv_gemv_rows_mx6_init();                                     // called by vv_gemv_rows_init
 void vv_gemv_rows_set(int on, int blocks, int pers);            // tuning hooks (negative / zero: keep)
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets,
-                 vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr, bool frag4 = false);
+                 vv_stream_t stream, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr, int fragq = 0);
                  // vv_kernels.hip: f1 / f2 = fragment-major copies of a->w / a->w2 or null; with fp8 companions q1 / q2 (q != NULL) of the fp8 codes;
-                 // frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form, codes then scale bytes at byte offset n * k / 2
+                 // fragq (VV_WQ_FRAG4 / VV_WQ_FRAG6): f1 / f2 hold the VV_MXFP4_FRAG / VV_MXFP6_FRAG form, codes then scale bytes at byte offset n * k / 2 (n * k * 3 / 4)
 int vv_launch_mfma_gemm(const vv_lin_args& a, hipStream_t s);     // vv_mfma_gemm.hip: 1 launched, 0 not covered, <0 error
 // the kernel of vv_mfma_gemm.hip a call takes, decided apart from the launch (vv_linear_route reports it without launching): kind 0 = not covered,
 // < 0 = error; stream: mfma_linear_kernel<dual, ksplit, xb, mt>, tiled: mfma_tiled_kernel<dual, bk, tm>

@@ -52,40 +52,11 @@
 #include "vv_hip.h"
 #include "vv_common.h"
 #include "vv_device.h"
+#include "vv_gemv_rows.h"
 
 namespace {
 
-struct RowsAux {
-  int atomic;        // ksplit > 1 with a linear epilogue whose residual already sits in `out` (res == out): every K slice adds gate * (partial [+ bias])
-                     // to out with fp32 atomics - no partial tiles, no ticket, nothing to wait for (the summation ORDER of the slices then varies from
-                     // run to run: results reproduce to fp32 rounding, ~1e-7, not bit for bit; vv_tune("gemv_rows_atomic", 0) keeps the ticket)
-  int dbg;           // timing experiments (wrong results; bf16 and fp8 only): 2 = no ticket merge, 4 = no activation loads
-  float* part;       // [n_groups][ksplit][PST] partial tiles (ksplit > 1)
-  int* tickets;      // [n_groups], zero on entry, left zero
-  int ksplit, spw;   // K slices per row group; weight loads per wave (32-wide k steps, 64-wide for fp8, 128-wide for MXFP4)
-  int n_groups;
-};
-
-constexpr int MAXSPLIT = 16;
-
-// 16 e4m3fn codes (one fp8 fragment-major lane load) -> the bf16 B fragments of two 32-wide k steps, times the row scale s (a power of two)
-__device__ __forceinline__ void fp8_frags(const u32x4 w, float s, bf16x8& b0, bf16x8& b1) {
-  bf16x2 p[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    p[2 * i] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], s, false);
-    p[2 * i + 1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], s, true);
-  }
-  b0 = bf16x8{p[0][0], p[0][1], p[1][0], p[1][1], p[2][0], p[2][1], p[3][0], p[3][1]};
-  b1 = bf16x8{p[4][0], p[4][1], p[5][0], p[5][1], p[6][0], p[6][1], p[7][0], p[7][1]};
-}
-
-// The weight format WF (vv_rows_route.wf) owns the width of a weight load, the addresses `issue` computes, the decode in front of the MFMA and the
-// scale registers of the persistent walk - nothing else: prologue, LDS layout, fold, atomic form and epilogue are one text for all three.
-constexpr int WF_BF16 = 0;      // row-major or fragment-major bf16: a load is one 32-wide k step
-constexpr int WF_FP8 = 1;       // fragment-major e4m3fn codes, a row scale: a load is two 32-wide k steps
-constexpr int WF_MXFP4 = 2;     // fragment-major e2m1 codes, a scale dword beside each load: a load is four 32-wide k steps
-constexpr int rows_fpl(int wf) { return 1 << wf; }    // 32-wide A fragments per weight load
+// RowsAux, MAXSPLIT, the weight formats WF_* and rows_fpl, fp8_frags: vv_gemv_rows.h (shared with vv_gemv_rows_mx6.hip)
 
 // The text of both kernels below (vv_gemv_rows_body.inc): KS weight loads per wave against KA = rows_fpl(WF) * KS activation fragments per row tile.  RT row tiles of 8
 // activation rows each: every B fragment meets RT A fragments (tile t = the hi / lo parts of rows 8 t .. 8 t + 7), RT MFMAs per weight load.
@@ -186,7 +157,7 @@ bool rows_split(const vv_lin_args& a, int steps, int n_groups, int NW, int kscap
 
 // The smallest built KS that holds spw loads per wave.  wide: the 8-wave kernels (whole rows, SwiGLU K split); else the 4-wave single-matrix K split.
 int rows_ks(int wf, bool wide, int spw) {
-  if (wf == WF_MXFP4) return spw;                       // every KS the decision can ask for is built
+  if (wf == WF_MXFP4 || wf == WF_MXFP6) return spw;     // every KS the decision can ask for is built (MXFP6: the decision asks vv_gemv_rows_mx6_built)
   if (wf == WF_FP8) return spw <= 2 ? 2 : spw <= 4 || wide ? 4 : spw <= 6 ? 6 : 8;
   if (wide) return spw <= 4 ? 4 : spw <= 6 ? 6 : 8;
   return spw <= 3 ? 3 : spw <= 6 ? 6 : spw <= 9 ? 9 : 12;
@@ -221,7 +192,7 @@ int vv_gemv_rows_init() {
     return vv_set_error(VV_E_HIP, "gemv_rows16: cannot raise the dynamic LDS limit");
   VV_ROWS16_ALL(VV_ROWS16_ATTR)
 #undef VV_ROWS16_ATTR
-  return 0;
+  return vv_gemv_rows_mx6_init();      // gemv_rows_mx6_kernel (vv_gemv_rows_mx6.hip)
 }
 
 // The one copy of what a call on this unit's weight-only formats must be (vv_common.h): fragment-major fp8 codes and VV_MXFP4_FRAG, 3..8 fp32 rows,
@@ -244,22 +215,23 @@ const char* vv_gemv_rows_refusal(const vv_lin_args& a, int* rc) {
 
 // The decision: which instantiation the call takes, its K split and grid; kind 0 = not covered (the caller falls back).  have_ws: a split-K
 // workspace of part_floats floats and n_tickets tickets exists (without one only shapes that need no K split, or the atomic form, are taken).
-// fp8 and MXFP4 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
+// fp8, MXFP4 and MXFP6 weights: fragment-major only (VV_LIN_W_FRAG).  Reads the arguments' values and alignments and the tune state only.
 //
-// The three formats share the pattern and differ in the width of a weight load (32, 64, 128 k) and in what a load costs in registers:
+// The formats share the pattern and differ in the width of a weight load (32, 64, 128 k) and in what a load costs in registers:
 //   bf16    4 VGPRs per load and matrix, 4 of activation fragment: 8 loads hold the whole K <= 2048 row in 8 waves; the single-matrix split-K
 //           form goes up to 12 loads per wave.
 //   fp8     a 64-wide load costs 4 VGPRs per matrix (8 in flight per persistent buffer pair) and its two activation fragments 8: KS = 4 holds the
 //           whole row and leaves the persistent dual form 64 weight + 32 fragment VGPRs, so fp8 runs persistent at every whole-row width; the
 //           single-matrix split-K form goes up to 8 loads (8 KB in flight per wave, as the bf16 form's 8 - 12).
+//   MXFP6   (VV_MXFP6_FRAG, the kernels of vv_gemv_rows_mx6.hip) MXFP4's rules: a 128-wide load costs 6 VGPRs of codes + 1 of scale bytes per matrix
 //   MXFP4   a 128-wide load costs 4 VGPRs of codes + 1 of scale bytes per matrix and 16 of activation fragments, and 4 KB of LDS per wave: two loads
 //           hold the whole row (one chunk per thread: the adaLN prologue fits), the single-matrix split-K form goes up to 4 loads per wave
 //           (64 fragment VGPRs, 64 KB of LDS per block).
 vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t part_floats, size_t n_tickets) {
   vv_rows_route r = {};
-  const int wf = a.wdt == VV_BF16 ? WF_BF16 : a.wdt == VV_FP8 ? WF_FP8 : a.wdt == VV_MXFP4_FRAG ? WF_MXFP4 : -1;
+  const int wf = a.wdt == VV_BF16 ? WF_BF16 : a.wdt == VV_FP8 ? WF_FP8 : a.wdt == VV_MXFP4_FRAG ? WF_MXFP4 : a.wdt == VV_MXFP6_FRAG ? WF_MXFP6 : -1;
   if (!g_rows_on || wf < 0 || a.m < 3 || a.m > 16) return r;
-  if (wf != WF_BF16 && vv_gemv_rows_refusal(a, nullptr)) return r;
+  if (wf != WF_BF16 && (wf == WF_MXFP6 ? vv_gemv_rows_mx6_refusal(a, nullptr) : vv_gemv_rows_refusal(a, nullptr))) return r;
   r.rt = a.m > 8 ? 2 : 1;                             // 9 .. 16 rows: gemv_rows16_kernel, on the fragment-major bf16 copy only
   if (r.rt == 2 && !(a.flags & VV_LIN_W_FRAG)) return r;
   const int kw = 32 * rows_fpl(wf);                   // k per weight load
@@ -279,15 +251,17 @@ vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t par
     // persistent when the row groups outnumber the blocks aimed for; bf16: 8 steps x 2 matrices x 2 buffers do not fit the registers
     const bool pers = dual && n_groups > g_rows_pers && (wf != WF_BF16 || r.spw <= 6);
     rows_cfg(r, dual, 8, rows_ks(wf, true, r.spw), pers, wf);
+    if (wf == WF_MXFP6 && !vv_gemv_rows_mx6_built(r.dual, r.nw, r.ks, r.pers)) r.kind = 0;
     return r;
   }
   // long rows: K slices across blocks, folded by the last arriver
   if (a.mod_scale) return r;                          // the modulated prologue needs the whole row's statistic up front
   // loads per wave the split aims for and accepts at most, [format][dual], and the few loads below which more blocks are not worth another slice
-  static const int KSCAP[3][2] = {{9, 8}, {6, 4}, {3, 2}}, KSMAX[3][2] = {{12, 8}, {8, 4}, {4, 2}}, FEW[3] = {3, 2, 1};
+  static const int KSCAP[4][2] = {{9, 8}, {6, 4}, {3, 2}, {3, 2}}, KSMAX[4][2] = {{12, 8}, {8, 4}, {4, 2}, {4, 2}}, FEW[4] = {3, 2, 1, 1};
   const int NW = dual ? 8 : 4;
   if (!rows_split(a, steps, n_groups, NW, KSCAP[wf][dual], KSMAX[wf][dual], FEW[wf], have_ws, part_floats, n_tickets, r)) return r;
   rows_cfg(r, dual, NW, rows_ks(wf, dual, r.spw), 0, wf);
+  if (wf == WF_MXFP6 && !vv_gemv_rows_mx6_built(r.dual, r.nw, r.ks, r.pers)) r.kind = 0;
   return r;
 }
 
@@ -295,6 +269,7 @@ vv_rows_route vv_gemv_rows_decide(const vv_lin_args& a, bool have_ws, size_t par
 // the decision was told about (tickets zeroed by the caller once; every launch leaves them zero) or null.
 int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, float* part, int* tickets, hipStream_t s) {
   if (r.kind != 1) return 0;
+  if (r.wf == WF_MXFP6) return vv_launch_gemv_rows_mx6_route(a, r, part, tickets, s);      // the kernels of vv_gemv_rows_mx6.hip
   RowsAux x;
   x.part = part; x.tickets = tickets; x.dbg = g_rows_dbg; x.n_groups = r.n_groups; x.atomic = r.atomic; x.ksplit = r.ksplit; x.spw = r.spw;
   if (r.rt == 2) {
@@ -315,6 +290,8 @@ int vv_launch_gemv_rows_route(const vv_lin_args& a, const vv_rows_route& r, floa
 int vv_gemv_rows_route_name(const vv_rows_route& r, char* name, int cap) {
   if (r.rt == 2)
     return snprintf(name, (size_t)cap, "gemv_rows16<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
+  if (r.wf == WF_MXFP6)
+    return snprintf(name, (size_t)cap, "gemv_rows_mx6<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
   if (r.wf == WF_MXFP4)
     return snprintf(name, (size_t)cap, "gemv_rows_mx<dual=%d,nw=%d,ks=%d,pers=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.ksplit, r.atomic);
   return snprintf(name, (size_t)cap, "gemv_rows<dual=%d,nw=%d,ks=%d,pers=%d,f8=%d> ksplit=%d atomic=%d", r.dual, r.nw, r.ks, r.pers, r.wf, r.ksplit, r.atomic);

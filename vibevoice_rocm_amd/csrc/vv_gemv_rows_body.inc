@@ -1,7 +1,7 @@
 // vv_gemv_rows_body.inc - the body of gemv_rows_kernel (RT = 1 row tile, 3 .. 8 rows) and gemv_rows16_kernel (RT = 2, 9 .. 16 rows), included by both
-// in vv_gemv_rows.hip, which describes it.  The includer provides DUAL, NW, KS, PERS, WF, RT and the kernel arguments `a` (vv_lin_args) and `x`
+// in vv_gemv_rows.hip, which describes it, and of gemv_rows_mx6_kernel (vv_gemv_rows_mx6.hip: WF_MXFP6, RT = 1).  The includer provides DUAL, NW, KS, PERS, WF, RT and the kernel arguments `a` (vv_lin_args) and `x`
 // (RowsAux).  Included text, not a device function template: behind a call the 8-row kernels come out with another register allocation.
-  constexpr bool F8 = WF == WF_FP8, MX = WF == WF_MXFP4;
+  constexpr bool F8 = WF == WF_FP8, MX6 = WF == WF_MXFP6, MX = WF == WF_MXFP4 || MX6;      // MX: 128-wide loads, a scale dword beside each (both MX formats)
   constexpr int T = NW * 64;
   static_assert(RT == 1 || (RT == 2 && WF == WF_BF16), "two row tiles: the bf16 form only");
   constexpr int MR = 8 * RT;                        // activation rows
@@ -62,7 +62,7 @@
   const int emr = em < mr ? em : mr - 1;
   auto load_eo = [&](int grp) {
     int egn = min(grp, n_groups - 1) * 16 + en;
-    if constexpr (!MX) egn = min(egn, N - 1);       // MXFP4: N % 16 == 0, in bounds as it is
+    if constexpr (!MX) egn = min(egn, N - 1);       // MXFP4, MXFP6: N % 16 == 0, in bounds as it is
     EpiOp<false> e;
     const float* pb = a.bias ? a.bias + egn : a.x;
     const float* pg = a.gate ? a.gate + (a.gate_ld ? (int64_t)emr * a.gate_ld + egn : (int64_t)egn) : a.x;
@@ -81,7 +81,9 @@
   // fp8: the row scale of this lane's weight row (n) in row group grp; N % 16 == 0, so the clamped group is in bounds
   auto wscale_of = [&](const float* sc, int grp) { return F8 ? sc[min(grp, n_groups - 1) * 16 + n] : 1.0f; };
   // a load that is not live (past the row's end, past the last row group, j >= spw) reads the first load of the matrix: a valid address
-  auto issue = [&](u32x4 (&w)[KS], unsigned (&e)[MX ? KS : 1], u32x4 (&w2)[DUAL ? KS : 1], unsigned (&e2)[(MX && DUAL) ? KS : 1], int grp) {
+  // MXFP6: wb / wb2 take the blocks' bytes 16 .. 23 (plane B, behind the N K / 2 bytes of plane A)
+  auto issue = [&](u32x4 (&w)[KS], unsigned (&e)[MX ? KS : 1], u32x4 (&w2)[DUAL ? KS : 1], unsigned (&e2)[(MX && DUAL) ? KS : 1],
+                   u32x2 (&wb)[MX6 ? KS : 1], u32x2 (&wb2)[(MX6 && DUAL) ? KS : 1], int grp) {
     const bool glive = grp < n_groups;
     int64_t base = 0;                               // in bf16 elements (fp8: two codes per element)
     if constexpr (!MX) {
@@ -100,6 +102,12 @@
         q1 = reinterpret_cast<const unsigned*>(S + (ld * 16 + n) * 4);
         p2 = reinterpret_cast<const u32x4*>(WB2 + (ld * 64 + lane) * 16);
         q2 = reinterpret_cast<const unsigned*>(S2 + (ld * 16 + n) * 4);
+        if constexpr (MX6) {
+          const int64_t pb = (int64_t)N * K / 2 + (ld * 64 + lane) * 8;
+          const u32x2 *r1 = reinterpret_cast<const u32x2*>(WB + pb), *r2 = reinterpret_cast<const u32x2*>(WB2 + pb);
+          if (reused) { wb[j] = *r1; if (DUAL) wb2[j] = *r2; }
+          else { wb[j] = __builtin_nontemporal_load(r1); if (DUAL) wb2[j] = __builtin_nontemporal_load(r2); }
+        }
       } else {
         const int64_t off = live ? base + (int64_t)(sbw + j) * sstep : 0;
         p1 = reinterpret_cast<const u32x4*>(W + off);
@@ -122,14 +130,15 @@
   u32x4 wn[PERS ? KS : 1], wn2[(PERS && DUAL) ? KS : 1];
   unsigned ec[MX ? KS : 1], ec2[(MX && DUAL) ? KS : 1];                       // MXFP4: the loads' scale dwords
   unsigned en_[(MX && PERS) ? KS : 1], en2[(MX && PERS && DUAL) ? KS : 1];
+  u32x2 bc[MX6 ? KS : 1], bc2[(MX6 && DUAL) ? KS : 1], bn[(MX6 && PERS) ? KS : 1], bn2[(MX6 && PERS && DUAL) ? KS : 1];      // MXFP6: plane B
   EpiOp<false> eo = load_eo(g), eo_n = eo;
   float sc = 1.0f, sc2 = 1.0f, sn = 1.0f, sn2 = 1.0f;                         // fp8: the row scales
   if constexpr (F8) { sc = wscale_of(a.wscale, g); if (DUAL) sc2 = wscale_of(a.w2scale, g); }
-  issue(wc, ec, wc2, ec2, g);
+  issue(wc, ec, wc2, ec2, bc, bc2, g);
   if constexpr (PERS && RT == 1) {
     eo_n = load_eo(g + gstride);
     if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-    issue(wn, en_, wn2, en2, g + gstride);
+    issue(wn, en_, wn2, en2, bn, bn2, g + gstride);
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -178,9 +187,12 @@
   for (int cc = 0; cc < NCH; ++cc) {
     const int q = tid + cc * T;
     if (q >= NW * KA * 8) continue;
-    const int js = q >> 3, wv = js / spa, j = js - wv * spa;        // block-relative k step -> (wave, step of the wave)
+    const int js = q >> 3, wv = js / spa, jk = js - wv * spa;       // block-relative k step -> (wave, step of the wave)
     if (wv >= NW) continue;
-    const int cq = (q & 7) >> 1, half = q & 1;
+    // MXFP6: MFMA h of a load meets elements 8 h .. 8 h + 7 of the block of lane quarter c, k = 128 J + 32 c + 8 h + i: the 8-wide piece that
+    // is quarter cq of step 4 J + h in k order goes to quarter h of fragment 4 J + cq
+    const int j = MX6 ? (jk & ~3) | ((q & 7) >> 1) : jk;
+    const int cq = MX6 ? jk & 3 : (q & 7) >> 1, half = q & 1;
     {
       constexpr int t = 0;
 #include "vv_gemv_rows_tile.inc"
@@ -192,7 +204,7 @@
   }
   if constexpr (PERS && RT == 2) {                  // two tiles: the next row group's weights are requested here, once the prologue's registers are free
     eo_n = load_eo(g + gstride);
-    issue(wn, en_, wn2, en2, g + gstride);
+    issue(wn, en_, wn2, en2, bn, bn2, g + gstride);
   }
   __syncthreads();
   u32x4 af[RT][KA];
@@ -220,6 +232,19 @@
             fp8_frags(wc2[j], sc2, b0, b1);
             acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][2 * j]), b0, acc2, 0, 0, 0);
             acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][2 * j + 1]), b1, acc2, 0, 0, 0);
+          }
+        } else if constexpr (MX6) {      // the lane's whole block decoded at once; MFMA h takes its elements 8 h .. 8 h + 7 (the fragments' k order above)
+          const bf16x32 b = mx6_block(wc[j], bc[j], (ec[j] >> (8 * c)) & 0xffu);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 0]), __builtin_shufflevector(b, b, 0, 1, 2, 3, 4, 5, 6, 7), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 1]), __builtin_shufflevector(b, b, 8, 9, 10, 11, 12, 13, 14, 15), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 2]), __builtin_shufflevector(b, b, 16, 17, 18, 19, 20, 21, 22, 23), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 3]), __builtin_shufflevector(b, b, 24, 25, 26, 27, 28, 29, 30, 31), acc, 0, 0, 0);
+          if (DUAL) {
+            const bf16x32 b2 = mx6_block(wc2[j], bc2[j], (ec2[j] >> (8 * c)) & 0xffu);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 0]), __builtin_shufflevector(b2, b2, 0, 1, 2, 3, 4, 5, 6, 7), acc2, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 1]), __builtin_shufflevector(b2, b2, 8, 9, 10, 11, 12, 13, 14, 15), acc2, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 2]), __builtin_shufflevector(b2, b2, 16, 17, 18, 19, 20, 21, 22, 23), acc2, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[0][4 * j + 3]), __builtin_shufflevector(b2, b2, 24, 25, 26, 27, 28, 29, 30, 31), acc2, 0, 0, 0);
           }
         } else if constexpr (MX) {       // the four 32-wide steps of the load in k order: the summation order of the bf16 kernel
 #pragma unroll
@@ -349,11 +374,12 @@
       for (int j = 0; j < KS; ++j) {
         wc[j] = wn[j]; if (DUAL) wc2[j] = wn2[j];
         if constexpr (MX) { ec[j] = en_[j]; if (DUAL) ec2[j] = en2[j]; }
+        if constexpr (MX6) { bc[j] = bn[j]; if (DUAL) bc2[j] = bn2[j]; }
       }
       if (g + gstride < n_groups) {
         eo_n = load_eo(g + gstride);
         if constexpr (F8) { sn = wscale_of(a.wscale, g + gstride); if (DUAL) sn2 = wscale_of(a.w2scale, g + gstride); }
-        issue(wn, en_, wn2, en2, g + gstride);
+        issue(wn, en_, wn2, en2, bn, bn2, g + gstride);
       }
     }
   }

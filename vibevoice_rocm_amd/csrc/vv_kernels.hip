@@ -552,6 +552,7 @@ static const struct wq_format { int wdt, flags; const char* name; int unit; cons
   {VV_MXFP4, 0, "MXFP4", WQ_STREAM, vv_gemv_stream_refusal},
   {VV_MXFP4_FRAG, 0, "VV_MXFP4_FRAG", WQ_ROWS, vv_gemv_rows_refusal},
   {VV_MXFP6, 0, "MXFP6", WQ_MX6, vv_gemv_mx6_refusal},
+  {VV_MXFP6_FRAG, 0, "VV_MXFP6_FRAG", WQ_ROWS, vv_gemv_rows_mx6_refusal},
 };
 static const wq_format* wq_format_of(const vv_lin_args& a) {
   for (const wq_format& f : WQ_FORMATS)
@@ -874,40 +875,40 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 
 // vv_linear for the composites of a row-batched step: 3..8 rows go to the matrix-core GEMV with the caller's split-K workspace, on the
 // fragment-major copies f1 / f2 of w / w2 when the model has them; shapes that kernel does not cover take vv_linear on the row-major matrices.
-// 9..16 rows: the 16-row form of that GEMV, on bf16 fragment-major copies only (no fp8 companions, no VV_WQ_FRAG4); else two passes of 5..8 rows.
+// 9..16 rows: the 16-row form of that GEMV, on bf16 fragment-major copies only (no fp8 companions, no VV_WQ_FRAG4 / VV_WQ_FRAG6); else two passes of 5..8 rows.
 // q1 / q2 (or NULL): the matrices' fp8 companions - when present, f1 / f2 are fragment-major copies of their CODES (vv_llm_layer.f_*).
-// frag4 (VV_WQ_FRAG4): f1 / f2 hold the VV_MXFP4_FRAG form (codes, scale bytes behind them) for the same kernel; a matrix without
+// fragq (VV_WQ_FRAG4 / VV_WQ_FRAG6): f1 / f2 hold the VV_MXFP4_FRAG / VV_MXFP6_FRAG form (codes, scale bytes behind them) for the same kernel; a matrix without
 // such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
-                 const vv_w8* q1, const vv_w8* q2, bool frag4) {
+                 const vv_w8* q1, const vv_w8* q2, int fragq) {
   // a lean MXFP4 model's matrix (vv_hip.h: w == NULL, for a SwiGLU pair w2 too): its VV_MXFP4_FRAG copy serves the call or nothing does
   vv_lin_args lean_a;
   const bool lean = a && !a->w && a->x && a->out;
   if (lean) {
     const bool dual = a->act == VV_ACT_SWIGLU;
-    if (!frag4 || !f1 || (dual && !f2) || a->m < 3 || a->m > 8 || a->wdt != VV_BF16)
+    if (fragq != VV_MXFP4_FRAG || !f1 || (dual && !f2) || a->m < 3 || a->m > 8 || a->wdt != VV_BF16)
       return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean mxfp4 model (no bf16 matrix is resident): m=%d rows need the matrix's VV_MXFP4_FRAG copy and 3..8 rows", a->m);
     lean_a = *a;
     lean_a.w = f1; lean_a.w2 = dual ? f2 : nullptr;
     a = &lean_a;
   }
-  const bool wide_ok = a && !frag4 && !(q1 && q1->q) && f1 && (!a->w2 || f2);
+  const bool wide_ok = a && !fragq && !(q1 && q1->q) && f1 && (!a->w2 || f2);
   if (a && a->wdt == VV_BF16 && a->m > 2 && (a->m <= 8 || (a->m <= 16 && wide_ok)) && a->x && a->w && a->out) {
     vv_lin_args b = *a;
-    const bool f8 = !frag4 && q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
-    const bool mx = frag4 && f1 && (!b.w2 || f2);
-    if (mx) {                 // VV_WQ_FRAG4: the copies are VV_MXFP4_FRAG codes, their scale bytes behind them in the same allocation
-      const size_t codes = (size_t)b.n * b.k / 2;
-      b.w = f1; b.wscale = reinterpret_cast<const float*>(static_cast<const char*>(f1) + codes); b.wdt = VV_MXFP4_FRAG; b.flags |= VV_LIN_W_FRAG;
+    const bool f8 = !fragq && q1 && q1->q && q1->scale && (!b.w2 || (q2 && q2->q && q2->scale));
+    const bool mx = fragq && f1 && (!b.w2 || f2);
+    if (mx) {                 // VV_WQ_FRAG4 / VV_WQ_FRAG6: the copies are VV_MXFP4_FRAG / VV_MXFP6_FRAG codes, their scale bytes behind them in the same allocation
+      const size_t codes = (size_t)b.n * b.k / 4 * (fragq == VV_MXFP6_FRAG ? 3 : 2);
+      b.w = f1; b.wscale = reinterpret_cast<const float*>(static_cast<const char*>(f1) + codes); b.wdt = fragq; b.flags |= VV_LIN_W_FRAG;
       if (b.w2) { b.w2 = f2; b.w2scale = reinterpret_cast<const float*>(static_cast<const char*>(f2) + codes); }
     } else if (f8) {          // fp8 companions: their fragment-major codes or nothing (never a bf16 read of an fp8 copy)
       if (f1 && (!b.w2 || f2)) {
         b.w = f1; b.wscale = q1->scale; b.wdt = VV_FP8; b.flags |= VV_LIN_W_FRAG;
         if (b.w2) { b.w2 = f2; b.w2scale = q2->scale; }
       }
-    } else if (!frag4 && f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
-    ProfRec pr;               // vv_prof_begin: a VV_WQ_FRAG4 model's rows launches are recorded under the weight type they stream (other models: none, as before)
-    const bool prof = frag4 && prof_wanted();
+    } else if (!fragq && f1 && (!b.w2 || f2)) { b.w = f1; if (b.w2) b.w2 = f2; b.flags |= VV_LIN_W_FRAG; }
+    ProfRec pr;               // vv_prof_begin: a VV_WQ_FRAG4 / VV_WQ_FRAG6 model's rows launches are recorded under the weight type they stream (other models: none, as before)
+    const bool prof = fragq && prof_wanted();
     if (prof) {
       pr.m = b.m; pr.n = b.n; pr.k = b.k; pr.dual = b.w2 != nullptr; pr.wdt = b.wdt;
       if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
@@ -930,8 +931,8 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
     vv_lin_args lo = *a;
     lo.m = a->m / 2;
     const vv_lin_args hi = split_hi(*a, lo.m);
-    VV_TRY(vv_linear_ws(&lo, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, frag4));
-    return vv_linear_ws(&hi, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, frag4);
+    VV_TRY(vv_linear_ws(&lo, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, fragq));
+    return vv_linear_ws(&hi, f1, f2, part, part_floats, tickets, n_tickets, stream, q1, q2, fragq);
   }
   return vv_linear(a, stream);
 }

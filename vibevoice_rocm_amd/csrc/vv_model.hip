@@ -42,14 +42,14 @@ static inline void use_w8(vv_lin_args& a, int wq, const vv_w8& q, const vv_w8* q
 }
 
 // VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 (vv_hip.h) ride on a descriptor's wdt: every composite strips it once at entry into a local copy, so each wdt test below reads
-// the matrix dtype, and keeps the companions' kind in `wq` (vv_wq_strip, vv_common.h); `frag4`: VV_WQ_FRAG4, the layers' f_* copies hold the VV_MXFP4_FRAG form
+// the matrix dtype, and keeps the companions' kind in `wq` (vv_wq_strip, vv_common.h); `fragq`: 0, or - VV_WQ_FRAG4 / VV_WQ_FRAG6 - the weight type the layers' f_* copies hold (VV_MXFP4_FRAG / VV_MXFP6_FRAG)
 #define VV_WQ_STRIP(T, p)                                                   \
   T p##_plain_ = *(p);                                                      \
   const vv_wq_kind p##_kind_ = vv_wq_strip(&p##_plain_.wdt);                \
   const int wq = p##_kind_.wq;                                              \
-  const bool frag4 = p##_kind_.frag4;                                       \
+  const int fragq = p##_kind_.fragq;                                        \
   p = &p##_plain_;                                                          \
-  (void)wq; (void)frag4
+  (void)wq; (void)fragq
 
 // from this many rows on, a bf16-weight LLM forward is a prompt prefill: activations are cast to bf16 once per GEMM and both
 // operands stream from global on the matrix cores with 128-row tiles (every weight fragment reused by 4 row tiles)
@@ -127,7 +127,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   if (lean && decode && R > 2 && R < VV_PREFILL_ROWS) {
     // lean: no bf16 matrix is resident, so a 3..8-row decode pass runs on the VV_MXFP4_FRAG copies or not at all, and 9..16 rows not at all -
     // said here, before the first launch
-    bool copies = frag4 && R <= 8;
+    bool copies = fragq == VV_MXFP4_FRAG && R <= 8;
     for (int l = 0; copies && l < m->layers; ++l) {
       const vv_llm_layer& L = m->layer[l];
       copies = L.f_qkv && L.f_o && L.f_gate && L.f_up && L.f_down;
@@ -152,8 +152,8 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   float* att_part = c.take(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (d + 2));
   int* att_tickets = reinterpret_cast<int*>(c.take(att_rows(R) * m->heads));
   // contexts beyond ~1K keys: one block per (row, q head) would pull all of its K / V through a single CU (~95 GB/s: 8 us at S = 3000)
-  // 9..16 rows: two row tiles of the same GEMV, when every layer has the bf16 fragment-major copies (no VV_WQ_FRAG4, whose copies are MXFP4 codes)
-  bool rows16 = decode && R > 8 && R <= 16 && m->wdt == VV_BF16 && !frag4;
+  // 9..16 rows: two row tiles of the same GEMV, when every layer has the bf16 fragment-major copies (no VV_WQ_FRAG4 / VV_WQ_FRAG6, whose copies are MX codes)
+  bool rows16 = decode && R > 8 && R <= 16 && m->wdt == VV_BF16 && !fragq;
   for (int l = 0; rows16 && l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
     rows16 = L.f_qkv && L.f_o && L.f_gate && L.f_up && L.f_down;
@@ -186,8 +186,8 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   auto lin = [&](vv_lin_args& a, const void* f1, const void* f2, const vv_w8* q1 = nullptr, const vv_w8* q2 = nullptr) -> int {
     if (!rows8) return vv_linear(&a, stream);
     // NF4 / MXFP4 companions never reach the 3..8-row kernel: f1 / f2 are then bf16 fragment-major copies of the effective matrices (or NULL) -
-    // or, under VV_WQ_FRAG4, the VV_MXFP4_FRAG form of the MXFP4 companions
-    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr, frag4);
+    // or, under VV_WQ_FRAG4 / VV_WQ_FRAG6, the VV_MXFP4_FRAG / VV_MXFP6_FRAG form of the MX companions
+    return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr, fragq);
   };
   // lean, outside the rows kernel: the matrix is its MXFP4 companion - under VV_LIN_W_MXGEMM in the prefill branch, as the streaming GEMV's
   // operand at 1..2 rows (what use_w8 does for a model that has both)
@@ -645,7 +645,7 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
   if (NX) VV_TRY(vv_head_sde_proj_fused(h, sde_noise, ld_sde, n_steps, B, NX, s));
   // step-invariant work: cond_proj on all rows, silu(cond_proj(cond) + t_emb(t_i)) as bf16 rows [step][2 B], every adaLN modulation
   vv_lin_args a = lin_base(cond, ld_cond, R2, h->cond_proj, D, h->cond_dim, h->wdt, c0, D);
-  VV_TRY(vv_linear_ws(&a, nullptr, nullptr, rpart, rpart_n, rtick, rtick_n, stream, nullptr, nullptr, frag4));   // no companion, no copy: bf16 rows; frag4 only for the profiler's record
+  VV_TRY(vv_linear_ws(&a, nullptr, nullptr, rpart, rpart_n, rtick, rtick_n, stream, nullptr, nullptr, fragq));   // no companion, no copy: bf16 rows; fragq only for the profiler's record
   VV_TRY(vv_add_rows_silu_bf16(c0, D, temb, D, c, (int)R, R2, D, stream));
   VV_TRY(head_modulations(h, c, (int)R, mod, modf, true, true, stream));
   for (int b = 0; b < B; ++b)
@@ -659,10 +659,10 @@ static int head_sample_batch(const char* sde_fn, const vv_head* h, const float* 
       a.pro = VV_PRO_RMSNORM; a.norm_w = L.norm_w; a.eps = h->eps;
       a.mod_shift = ml; a.mod_scale = ml + D; a.ld_mod = 3 * D;
       a.w2 = L.wup; a.act = VV_ACT_SWIGLU; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_gate : nullptr, f8q ? &L.q_up : nullptr, frag4));
+      VV_TRY(vv_linear_ws(&a, L.f_gate, L.f_up, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_gate : nullptr, f8q ? &L.q_up : nullptr, fragq));
       a = lin_base(act, h->ffn, R2, L.wdown, D, h->ffn, h->wdt, hc, D);
       a.gate = ml + 2 * D; a.gate_ld = 3 * D; a.res = hc; a.ldres = D; a.flags = VV_LIN_W_REUSED;
-      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_down : nullptr, nullptr, frag4));
+      VV_TRY(vv_linear_ws(&a, L.f_down, nullptr, rpart, rpart_n, rtick, rtick_n, stream, f8q ? &L.q_down : nullptr, nullptr, fragq));
     }
     const float* mf = modf + (size_t)R2 * i * 2 * D;
     VV_TRY(vv_head_boundary_batch(h, hc, D, mf, mf + D, 2 * D, cfg_scale, &coef[i], Xs, Ms, sst, hb[(i + 1) & 1], D, latent_out, ld_latent, B, s,

@@ -27,6 +27,7 @@ from .batchloop import VibeVoiceGenerationOutput, _BatchCoupling      # noqa: F4
 from .config import VVConfig
 from .engine import Engine, check_kv_cache_dtype
 from .synth import state_dict_shapes
+from .weights import MXFP6_ROWS_MAX_HIDDEN
 from .voice_prefix import VoicePrefix      # noqa: F401  (public name of this module)
 
 LANES_IN_FLIGHT = 4       # lock-step batches: lanes (one HIP stream each) enqueued concurrently; see _LaneDriver
@@ -723,7 +724,7 @@ class VibeVoiceForConditionalGenerationInference:
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
                  kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
                  seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS,
-                 batched_conv_rows: bool = False, mxfp4_lean: bool = False):
+                 batched_conv_rows: bool = False, mxfp4_lean: bool = False, mxfp6_row_batch: bool = False):
         # batched_conv_rows: a row batch runs the one-row stage (C = 2048) of the acoustic decoder and the semantic encoder, and the connectors,
         # once for all its dialogues - one pass over 78 % of the tokenizers' weights instead of one per dialogue (csrc/vv_conv_hot.hip, DESIGN.md
         # section 5o).  bf16 weights without companions only.  Off by default; generate(batched_conv_rows=) overrides it per call, a session
@@ -767,6 +768,15 @@ class VibeVoiceForConditionalGenerationInference:
         if mxfp4_lean and weight_quant != "mxfp4":
             raise ValueError(f"mxfp4_lean=True needs weight_quant='mxfp4', not {weight_quant!r}")
         self.mxfp4_lean = bool(mxfp4_lean)
+        # mxfp6_row_batch=True (weight_quant="mxfp6" only): batches of row_batch_min..4 dialogues per row batch and serving sessions run the
+        # row-batched path on fragment-major copies of the MXFP6 codes and scale bytes (csrc/vv_gemv_rows_mx6.hip; +0.78 B
+        # per copied weight).  Off by default: the batch then runs on the lanes and open_session refuses the mode, as before.  row_batch_width=8
+        # and batched_conv_rows=True have refused every weight_quant above, this one included
+        if mxfp6_row_batch and weight_quant != "mxfp6":
+            raise ValueError(f"mxfp6_row_batch=True needs weight_quant='mxfp6', not {weight_quant!r}")
+        if mxfp6_row_batch and config.hidden > MXFP6_ROWS_MAX_HIDDEN:
+            raise ValueError(f"mxfp6_row_batch=True serves LLM hidden sizes up to {MXFP6_ROWS_MAX_HIDDEN}, not {config.hidden}")
+        self.mxfp6_row_batch = bool(mxfp6_row_batch)
         missing = [k for k in shapes if k not in state_dict and k not in (prequant or {})]
         if missing:
             raise KeyError(f"state dict is missing {len(missing)} tensors, e.g. {missing[:4]}")
@@ -801,11 +811,11 @@ class VibeVoiceForConditionalGenerationInference:
         # "mxfp4": weight-only OCP MXFP4 companions (e2m1 codes, one power-of-two scale byte per 32 k) decoded by the vector ALU's own
         # conversion instruction (batches of >= 2 run on the lanes, sessions refuse it - unless mxfp4_row_batch=True)
         # "mxfp6": weight-only OCP MXFP6 companions (e2m3 codes, 6.25 bits per weight: fp8's mantissa at 0.78 of its bytes), decoded 32 at a time
-        # by v_cvt_scalef32_pk32_f32_fp6 (batches of >= 2 run on the lanes, sessions refuse it)
+        # by v_cvt_scalef32_pk32_f32_fp6 (batches of >= 2 run on the lanes, sessions refuse it - unless mxfp6_row_batch=True)
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
                              prequant=prequant, kv_cache_dtype=kv_cache_dtype, mxfp4_row_batch=self.mxfp4_row_batch,
-                             mxfp4_lean=self.mxfp4_lean)
+                             mxfp4_lean=self.mxfp4_lean, mxfp6_row_batch=self.mxfp6_row_batch)
         self.device = self.engine.device
         # batches run in lock step on one Engine per sample (own HIP stream, KV cache and conv state; matrices already in the streamed
         # dtype on the device are shared, not copied): lanes beyond the first are built on first use from this state dict
@@ -857,7 +867,7 @@ class VibeVoiceForConditionalGenerationInference:
                    mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False),
                    row_batch_width=kw.get("row_batch_width", 4), packed_prefill=kw.get("packed_prefill", False),
                    packed_prefill_rows=kw.get("packed_prefill_rows", PACKED_PREFILL_ROWS), batched_conv_rows=kw.get("batched_conv_rows", False),
-                   mxfp4_lean=kw.get("mxfp4_lean", False))
+                   mxfp4_lean=kw.get("mxfp4_lean", False), mxfp6_row_batch=kw.get("mxfp6_row_batch", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):
@@ -962,8 +972,9 @@ class VibeVoiceForConditionalGenerationInference:
         return vp
 
     def _rows_quant_ok(self) -> bool:
-        """the row-batched decode path serves this model's weights: bf16, weight-only fp8, or MXFP4 with the fragment-major opt-in"""
-        return self.weight_quant in (None, "fp8") or (self.weight_quant == "mxfp4" and self.mxfp4_row_batch)
+        """the row-batched decode path serves this model's weights: bf16, weight-only fp8, or MXFP4 / MXFP6 with the fragment-major opt-in"""
+        from .rowbatch import row_batch_ok
+        return row_batch_ok(self.weight_quant, getattr(self, "mxfp4_row_batch", False), getattr(self, "mxfp6_row_batch", False))
 
     # ---- serving sessions ---------------------------------------------------------------------------------------
     def open_session(self, tokenizer=None, slots: int = 8, max_context: Optional[int] = None, generation_config=None, device_noise: bool = True,
@@ -971,7 +982,7 @@ class VibeVoiceForConditionalGenerationInference:
         """Open a serving session: `slots` (2..16) row-batch slots - ceil(slots / 4) row batches, as a batched generate() partitions them - whose
         KV caches are sized once for `max_context` tokens per dialogue (required).  Dialogues are submitted to the session one by one and a
         finished one frees its slot for the next between two steps (VibeVoiceSession, batchloop.Session).  Needs what row batching needs -
-        bf16, weight_quant None or "fp8" (or "mxfp4" on a model built with mxfp4_row_batch=True), a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
+        bf16, weight_quant None or "fp8" (or "mxfp4" / "mxfp6" on a model built with mxfp4_row_batch=True / mxfp6_row_batch=True), a bf16 KV cache, graphs on - and raises ValueError otherwise: there is no lanes fallback.  One session
         per model; generate() raises RuntimeError until it is closed.  seeded_tokens=True: every request may bring its own generation_config and token_seed
         (submit), greedy and sampled requests share the one graph A, and a dialogue's tokens do not depend on who shares the session.
         packed_prefill=True: the requests queued when a step begins are admitted together and prefilled in one weight pass per row batch

@@ -6,7 +6,7 @@ B dialogues (2 <= B <= 4 per RowBatch, up to 8 on a row_batch_width=8 model; gen
   graph A   Qwen2 decode step with R = 2 B rows (dialogue b = rows {2 b: positive, 2 b + 1: negative} of x, lens and one KV cache with 2 B
             rows): every weight matrix is read once for all dialogues (4..8 rows, and 10..16 on bf16 weights: the matrix-core GEMV of csrc/vv_gemv_rows.hip on
             fragment-major weight copies - of the e4m3 codes with weight_quant="fp8", of the MXFP4 codes and scale bytes with weight_quant="mxfp4" and
-            mxfp4_row_batch=True (csrc/vv_gemv_rows.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
+            mxfp4_row_batch=True (csrc/vv_gemv_rows.hip), MXFP6 ones with mxfp6_row_batch=True (csrc/vv_gemv_rows_mx6.hip)), then vv_llm_tail_batch = final norm, constrained logits, argmax / forced token and position
             bookkeeping per dialogue.  With do_sample it splits as Engine.step_decode does: A1 = the decode step and the constrained logits
             (no position bookkeeping), one host read-back of every row batch's logits, the tokens drawn on the host, A2 = the bookkeeping with
             those tokens as forced tokens;
@@ -96,6 +96,12 @@ class ConvRowsBook:
         self.owed = set()
 
 
+def row_batch_ok(quant, mxfp4_row_batch: bool = False, mxfp6_row_batch: bool = False) -> bool:
+    """Does the row-batched decode step serve weights of this weight_quant?  bf16 and weight-only fp8 as they are; MXFP4 / MXFP6 with their
+    fragment-major opt-in (DeviceWeights.ensure_frag builds the copies the 3..8-row kernels stream); NF4 never."""
+    return quant in (None, "fp8") or (quant == "mxfp4" and bool(mxfp4_row_batch)) or (quant == "mxfp6" and bool(mxfp6_row_batch))
+
+
 class RowBatch:
     def __init__(self, lanes: List[Engine], stream: Optional[torch.cuda.Stream] = None):
         """lanes: one Engine per dialogue (conv state, conv graphs, its stream).  stream: the stream graphs A and H run on (default: lanes[0]'s);
@@ -108,8 +114,9 @@ class RowBatch:
         self.lib, self.cfg, self.device, self.stream = eng.lib, eng.cfg, eng.device, (stream or eng.stream)
         self._on_main = [e.stream.cuda_stream == self.stream.cuda_stream for e in lanes]
         if eng.dtype != torch.bfloat16 or eng.kv_dtype != torch.bfloat16 or getattr(eng, "kv_fp8", False) or \
-                not (eng.w.quant in (None, "fp8") or (eng.w.quant == "mxfp4" and eng.w.mxfp4_row_batch)):
-            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions, or MXFP4 ones with mxfp4_row_batch=True) and a bf16 KV cache "
+                not row_batch_ok(eng.w.quant, eng.w.mxfp4_row_batch, eng.w.mxfp6_row_batch):
+            raise L.VVError("row batching needs bf16 weights (or their weight-only fp8 companions, or MXFP4 / MXFP6 ones with mxfp4_row_batch=True / "
+                            "mxfp6_row_batch=True) and a bf16 KV cache "
                             "(kv_cache_dtype='fp8' batches run on the lanes: the row-batched decode step has no fp8-KV form)")
         if B > 4 and eng.w.quant is not None:
             raise L.VVError("row batches of 5..8 dialogues (10..16 rows) need bf16 weights without companions: the 16-row matrix-core GEMV has no quantized form")

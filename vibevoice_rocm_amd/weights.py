@@ -145,6 +145,8 @@ MXFP4_SCALE_MIN, MXFP4_SCALE_MAX, MXFP4_SCALE_ONE = MXFP6_SCALE_MIN, MXFP6_SCALE
 # is served on whole rows only (K <= 2048); the SwiGLU pair splits K two ways at most inside the row-batched step's partials workspace
 # (csrc/vv_model.hip, rows_part_floats), 2 slices x 8 waves x 2 loads x 128 = 4096
 MXFP4_ROWS_MOD_K, MXFP4_ROWS_MAX_HIDDEN = 2048, 4096
+# MXFP6 rows (csrc/vv_gemv_rows_mx6.hip): the same decision with the same 128-wide loads, so the same two limits
+MXFP6_ROWS_MOD_K, MXFP6_ROWS_MAX_HIDDEN = MXFP4_ROWS_MOD_K, MXFP4_ROWS_MAX_HIDDEN
 
 
 def _quantize_mx(w: torch.Tensor, values, block: int, sign_code: int):
@@ -289,10 +291,12 @@ class DeviceWeights:
     """Owns every device tensor of the model and the C descriptors (vv_llm, vv_head, vv_convnet x3, vv_connector x2)."""
 
     def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None,
-                 prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False, mxfp4_lean: bool = False):
+                 prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False, mxfp4_lean: bool = False,
+                 mxfp6_row_batch: bool = False):
         """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
         are imported as they are (vv_nf4_import) and need quant="nf4".  mxfp4_row_batch (quant="mxfp4" only): the 3..8-row paths stream the
         MXFP4 companions in fragment-major form (VV_WQ_FRAG4 on the LLM's and the head's descriptors; ensure_frag builds the copies).
+        mxfp6_row_batch (quant="mxfp6" only): the same for the MXFP6 companions (VV_WQ_FRAG6, the VV_MXFP6_FRAG form); the bf16 matrices stay.
         mxfp4_lean (quant="mxfp4" only): the LLM's matrices exist as MXFP4 codes alone - no bf16 copy is uploaded, their descriptor pointers are
         NULL and every pass of 3 or more prompt rows runs the GEMM on the codes (csrc/vv_gemm_mx.hip; lean_report lists what was dropped).
         Kept in bf16, because something still reads them in that form:
@@ -311,6 +315,12 @@ class DeviceWeights:
             raise ValueError(f"mxfp4_row_batch=True serves LLM hidden sizes up to {MXFP4_ROWS_MAX_HIDDEN}, not {cfg.hidden}: beyond, the SwiGLU pair "
                              "would need a three-way K split, which the row-batched step's partials workspace has no room for")
         self.mxfp4_row_batch = bool(mxfp4_row_batch)
+        if mxfp6_row_batch and quant != "mxfp6":
+            raise ValueError(f"mxfp6_row_batch=True serves the MXFP6 companions on the row-batched path: it needs weight_quant='mxfp6', not {quant!r}")
+        if mxfp6_row_batch and cfg.hidden > MXFP6_ROWS_MAX_HIDDEN:
+            raise ValueError(f"mxfp6_row_batch=True serves LLM hidden sizes up to {MXFP6_ROWS_MAX_HIDDEN}, not {cfg.hidden}: beyond, the SwiGLU pair "
+                             "would need a three-way K split, which the row-batched step's partials workspace has no room for")
+        self.mxfp6_row_batch = bool(mxfp6_row_batch)
         self.cfg, self.device, self.wdtype = cfg, torch.device(device), wdtype
         if quant is not None and quant not in WEIGHT_FORMATS:
             raise ValueError(f"weight_quant {quant!r}: only None, " + " or ".join(f"{name!r} ({f.what})" for name, f in WEIGHT_FORMATS.items()) +
@@ -325,13 +335,14 @@ class DeviceWeights:
         self.wdt = _wdt(wdtype)
         # the descriptors' wdt: VV_WQ_NF4 / VV_WQ_MXFP4 / VV_WQ_MXFP6 mark their vv_w8 companions as NF4 / MXFP4 / MXFP6 (vv_hip.h); self.wdt stays the plain matrix dtype
         self.desc_wdt = self.wdt | (WEIGHT_FORMATS[quant].wq if quant else 0)
-        # vv_llm / vv_head: VV_WQ_FRAG4 says their layers' f_* copies hold the VV_MXFP4_FRAG form (never a bf16 fragment copy)
-        self.desc_wdt_rows = self.desc_wdt | (L.VV_WQ_FRAG4 if self.mxfp4_row_batch else 0)
+        # vv_llm / vv_head: VV_WQ_FRAG4 / VV_WQ_FRAG6 say their layers' f_* copies hold the VV_MXFP4_FRAG / VV_MXFP6_FRAG form (never a bf16 fragment copy)
+        self.desc_wdt_rows = self.desc_wdt | (L.VV_WQ_FRAG4 if self.mxfp4_row_batch else 0) | (L.VV_WQ_FRAG6 if self.mxfp6_row_batch else 0)
         self._keep: List[object] = []     # tensors / ctypes arrays that must outlive the descriptors
         # the fragment-major copies (ensure_frag) live here: one dict object shared by every fork, as the ctypes layer arrays they are
         # written into are, so they are built once per process whichever fork asks first
-        # mxfp4_*: the VRAM record of the VV_MXFP4_FRAG copies - weights copied, bytes they take (0.5 + 1 / 32 = 0.53125 B per weight)
-        self._frag_state: Dict[str, object] = {"done": False, "tensors": [], "mxfp4_weights": 0, "mxfp4_bytes": 0}
+        # mxfp4_* / mxfp6_*: the VRAM record of the VV_MXFP4_FRAG / VV_MXFP6_FRAG copies - weights copied, bytes they take (0.5 + 1 / 32 = 0.53125,
+        # 0.75 + 1 / 32 = 0.78125 B per weight)
+        self._frag_state: Dict[str, object] = {"done": False, "tensors": [], "mxfp4_weights": 0, "mxfp4_bytes": 0, "mxfp6_weights": 0, "mxfp6_bytes": 0}
         self._sd = sd
         self.state_tensors: Dict[str, List[torch.Tensor]] = {"acoustic_dec": [], "semantic_enc": []}
         # every streaming-state tensor (conv left contexts, mixer histories) is a 256-byte aligned view into ONE arena, so the
@@ -507,6 +518,34 @@ class DeviceWeights:
         scales = f[n * k // 2:].view(n // 16, k // 128, 16, 4).permute(0, 2, 1, 3).reshape(n, k // MXFP4_BLOCK).contiguous()
         return codes, scales
 
+    @staticmethod
+    def frag_major_mxfp6(codes: torch.Tensor, scales: torch.Tensor) -> Optional[torch.Tensor]:
+        """(e2m3 codes uint8 [N, K] in 0..63, E8M0 scale bytes uint8 [N, K / 32]) -> the VV_MXFP6_FRAG form (include/vv_hip.h) as ONE uint8 tensor.
+        Lane 16 c + n of 128-wide step J of row group g owns block 4 J + c of row 16 g + n: its 24 bytes (code i in bits 6 i .. 6 i + 5, the
+        string of VV_MXFP6) are split into plane A [N / 16][K / 128][64 lanes][16 B] (bytes 0..15) and, at byte offset N K / 2, plane B
+        [N / 16][K / 128][64 lanes][8 B] (bytes 16..23); then, at N K 3 / 4, the scale bytes [N / 16][K / 128][16 rows][4 B] - byte c of the
+        dword of (g, J, n) is the byte of block 4 J + c of row 16 g + n.  None when N % 16 or K % 128."""
+        n, k = codes.shape
+        if n % 16 or k % 128 or codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or tuple(scales.shape) != (n, k // MXFP6_BLOCK):
+            return None
+        dev = codes.device
+        bits = (codes.view(n // 16, 16, k // 128, 4, 32, 1) >> torch.arange(6, device=dev, dtype=torch.uint8)) & 1      # [g, n, J, c, element, bit]
+        by = (bits.reshape(n // 16, 16, k // 128, 4, 24, 8) << torch.arange(8, device=dev, dtype=torch.uint8)).sum(dim=-1, dtype=torch.uint8)
+        by = by.permute(0, 2, 3, 1, 4)                                                          # [g, J, c, n, 24 bytes]: lane 16 c + n
+        sb = scales.view(n // 16, 16, k // 128, 4).permute(0, 2, 1, 3)                          # [g, J, n, c]
+        return torch.cat([by[..., :16].reshape(-1), by[..., 16:].reshape(-1), sb.reshape(-1)])
+
+    @staticmethod
+    def unfrag_mxfp6(f: torch.Tensor, n: int, k: int):
+        """Inverse of frag_major_mxfp6: (codes uint8 [N, K], scale bytes uint8 [N, K / 32])."""
+        g, kj = n // 16, k // 128
+        by = torch.cat([f[: n * k // 2].view(g, kj, 4, 16, 16), f[n * k // 2: n * k * 3 // 4].view(g, kj, 4, 16, 8)], dim=-1)      # [g, J, c, n, 24 bytes]
+        bits = ((by[..., None] >> torch.arange(8, device=f.device, dtype=torch.uint8)) & 1).reshape(g, kj, 4, 16, 32, 6)
+        codes = (bits << torch.arange(6, device=f.device, dtype=torch.uint8)).sum(dim=-1, dtype=torch.uint8)                    # [g, J, c, n, element]
+        codes = codes.permute(0, 3, 1, 2, 4).reshape(n, k).contiguous()
+        scales = f[n * k * 3 // 4:].view(g, kj, 16, 4).permute(0, 2, 1, 3).reshape(n, k // MXFP6_BLOCK).contiguous()
+        return codes, scales
+
     def ensure_frag(self) -> None:
         """Fragment-major copies of the LLM's and the diffusion head's per-frame matrices for the row-batched decode step (rowbatch.py): built
         once per process (for this weight set and all its forks), on first use, next to the row-major matrices (which the prefill GEMMs and the
@@ -516,24 +555,28 @@ class DeviceWeights:
         mxfp4_row_batch: the VV_MXFP4_FRAG form of the MXFP4 companions (frag_major_mxfp4: +0.53 B per copied weight, recorded in
         _frag_state["mxfp4_weights"] / ["mxfp4_bytes"] and counted by nbytes()), never a bf16 copy: a matrix without a companion or with
         N % 16 / K % 128 keeps f_* = NULL and the row-major bf16 fallback, and so does the head's gate / up pair beyond K = 2048 (MXFP4_ROWS_MOD_K:
-        it is called with the adaLN prologue, which the MX rows kernel serves on whole rows only - a copy would never be read)."""
+        it is called with the adaLN prologue, which the MX rows kernel serves on whole rows only - a copy would never be read).
+        weight_quant="mxfp6" with mxfp6_row_batch: the same with the VV_MXFP6_FRAG form (frag_major_mxfp6: +0.78 B per copied weight, recorded
+        in _frag_state["mxfp6_weights"] / ["mxfp6_bytes"]), under the same two rules."""
         st = self._frag_state
         if st["done"] or self.wdtype != torch.bfloat16:
             return
         by_ptr = {t.data_ptr(): t for t in self._keep if isinstance(t, torch.Tensor)}
+        mx = "mxfp4" if self.mxfp4_row_batch else "mxfp6" if self.mxfp6_row_batch else None      # the MX row-batch opt-in, if any: no bf16 copy then
+        mx_frag, mx_unpack = (self.frag_major_mxfp4, unpack_mxfp4) if mx == "mxfp4" else (self.frag_major_mxfp6, unpack_mxfp6)
 
         def frag_of(p, w8, n, k):
-            if self.mxfp4_row_batch:            # MXFP4 companion: its codes and scale bytes, re-laid (the companion's own layout is pack_mxfp4's)
+            if mx:                              # MX companion: its codes and scale bytes, re-laid (the companion's own layout is pack_mxfp4's / pack_mxfp6's)
                 packed, sb = by_ptr.get(int(w8.q or 0)), by_ptr.get(int(w8.scale or 0))
                 if packed is None or sb is None or k % MXFP4_BLOCK:
                     return None
-                f = self.frag_major_mxfp4(*unpack_mxfp4(packed, sb, n, k))
+                f = mx_frag(*mx_unpack(packed, sb, n, k))
                 if f is None:
                     return None
                 f = self._aligned(f)
                 st["tensors"].append(f)
-                st["mxfp4_weights"] += n * k
-                st["mxfp4_bytes"] += f.numel()
+                st[mx + "_weights"] += n * k
+                st[mx + "_bytes"] += f.numel()
                 return f.data_ptr()
             if w8.q and self.quant == "fp8":    # fp8 companion: the copy is of its codes, or none (NF4: the bf16 effective matrix)
                 t, fm = by_ptr.get(int(w8.q)), self.frag_major_fp8
@@ -559,7 +602,7 @@ class DeviceWeights:
             lay.f_down = frag_of(lay.wdown, lay.q_down, cfg.hidden, cfg.inter)
         for l in range(cfg.head_layers):
             lay = self.head.layer[l]
-            if self.mxfp4_row_batch and cfg.head_hidden > MXFP4_ROWS_MOD_K:     # no MX rows route takes the modulated pair at this K: no copy
+            if mx and cfg.head_hidden > MXFP4_ROWS_MOD_K:     # no MX rows route takes the modulated pair at this K: no copy
                 lay.f_gate = lay.f_up = None
             else:
                 lay.f_gate = frag_of(lay.wgate, lay.q_gate, cfg.head_ffn, cfg.head_hidden)
