@@ -99,8 +99,8 @@ enum { VV_MXFP6 = 6 };
 /* VV_WQ_MXFP6: as VV_WQ_MXFP4, for companions that hold MXFP6 (codes in q, the scale bytes' address in scale, the VV_MXFP6 layout above).  The
  * 1..2-row GEMVs of the LLM, the diffusion head and the tokenizers' one-row stage stream them; every other pass (3 and more rows, the prefill)
  * uses the bf16 matrices, which hold exactly the same effective values - unless VV_WQ_FRAG6 (below) rides along: the 3..8-row decode passes then
- * stream the VV_MXFP6_FRAG copies.  There is no lean form (the bf16 matrices are always resident), VV_WQ_FRAG4 means nothing next to this bit,
- * and composites that refuse quantised companions refuse these. */
+ * stream the VV_MXFP6_FRAG copies - and unless the model is LEAN (below, after VV_WQ_FRAG6): its LLM has no bf16 matrices and runs those passes
+ * on the codes.  VV_WQ_FRAG4 means nothing next to this bit, and composites that refuse quantised companions refuse these. */
 enum { VV_WQ_MXFP6 = 0x800 };
 /* VV_MXFP6_FRAG: the same OCP MXFP6 e2m3 values (6-bit codes, E8M0 scale bytes 2..252, effective weight value(code) * 2^(e - 127)) in FRAGMENT-MAJOR
  * order, for the 3..8-row matrix-core GEMV only (csrc/vv_gemv_rows_mx6.hip): VV_LIN_W_FRAG set, 3 <= m <= 8, n % 16 == 0, k % 128 == 0 (no padding
@@ -126,13 +126,15 @@ enum { VV_MXFP6_FRAG = 8 };
  * fallback.  1..2 rows and the prefill are unchanged, 9..16 rows stay bf16-only (two passes of 5..8 rows here).  No bf16 fragment copy may sit in
  * f_* under this bit. */
 enum { VV_WQ_FRAG6 = 0x1000 };
-/* A LEAN MXFP4 LLM (vv_llm with VV_WQ_MXFP4): every layer's five bf16 pointers (wqkv, wo, wgate, wup, wdown) are NULL beside present companions
- * (q_*.q and q_*.scale) - no descriptor bit, the NULL pointers say it; all five of all layers or none (a mix is VV_E_ARG).  hidden, inter and
- * heads * head_dim must be multiples of 128 and the qkv width a multiple of 16 (what VV_LIN_W_MXGEMM takes).  vv_llm_forward and
- * vv_llm_prefill_packed then run every non-decode pass of R >= 3 rows as the prefill (activations cast to bf16 once per GEMM) on
- * VV_LIN_W_MXGEMM; R <= 2 streams the companions as ever; a decode pass (cache_rows == NULL) of 3..8 rows runs on the VV_MXFP4_FRAG copies under
- * VV_WQ_FRAG4.  A pass that would need a matrix that is not resident - a 3..8-row decode pass without those copies, a 9..16-row decode pass -
- * returns VV_E_UNSUPPORTED naming the lean mode before anything is launched.  vv_llm_ws_bytes counts the bf16 staging buffer from R = 3 on. */
+/* A LEAN MX LLM (vv_llm with VV_WQ_MXFP4 or VV_WQ_MXFP6): every layer's five bf16 pointers (wqkv, wo, wgate, wup, wdown) are NULL beside present
+ * companions (q_*.q and q_*.scale) - no descriptor bit, the NULL pointers say it; all five of all layers or none (a mix is VV_E_ARG).  hidden,
+ * inter and heads * head_dim must be multiples of 128 and the qkv width a multiple of 16 (what VV_LIN_W_MXGEMM and VV_LIN_W_MX6GEMM take).
+ * vv_llm_forward and vv_llm_prefill_packed then run every non-decode pass of R >= 3 rows as the prefill (activations cast to bf16 once per GEMM)
+ * on VV_MXFP4 + VV_LIN_W_MXGEMM or VV_MXFP6 + VV_LIN_W_MX6GEMM; R <= 2 streams the companions as ever; a decode pass (cache_rows == NULL) of 3..8
+ * rows runs on the VV_MXFP4_FRAG copies under VV_WQ_FRAG4 or the VV_MXFP6_FRAG copies under VV_WQ_FRAG6.  A pass that would need a matrix that is
+ * not resident - a 3..8-row decode pass without those copies, a 9..16-row decode pass - returns VV_E_UNSUPPORTED naming the lean mode before
+ * anything is launched; no kernel is ever launched on a NULL weight.  vv_llm_ws_bytes counts the bf16 staging buffer from R = 3 on for either
+ * lean form. */
 enum { VV_OK = 0, VV_E_ARG = -1, VV_E_HIP = -2, VV_E_UNSUPPORTED = -3 };
 enum { VV_PRO_NONE = 0, VV_PRO_RMSNORM = 1, VV_PRO_SILU = 2 };
 enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
@@ -154,6 +156,17 @@ enum { VV_ACT_NONE = 0, VV_ACT_GELU = 1, VV_ACT_SWIGLU = 2 };
  * wdt, fp32 x, a prologue, m < 3, n % 16, k % 128, missing scales, a misaligned operand) returns VV_E_UNSUPPORTED from vv_linear and
  * vv_linear_route alike, nothing launched; every VV_MXFP4 / VV_MXFP4_FRAG call without the bit is taken or refused exactly as before */
 enum { VV_LIN_X_BF16 = 1, VV_LIN_OUT_BF16 = 2, VV_LIN_W_REUSED = 4, VV_LIN_W_FRAG = 8, VV_LIN_PACKED = 16, VV_LIN_W_MXGEMM = 32 };
+/* VV_LIN_W_MX6GEMM: the matrix-core GEMM on MXFP6 CODES (csrc/vv_gemm_mx6.hip), the counterpart of VV_LIN_W_MXGEMM with the same contract - w / w2
+ * and wscale / w2scale are a VV_MXFP6 companion (wdt == VV_MXFP6, the two-plane layout above), x is bf16 (VV_LIN_X_BF16, no prologue), m >= 3,
+ * n % 16 == 0, k % 128 == 0, the epilogue is bias / residual (its own array or out) / VV_ACT_SWIGLU with w2 (+ VV_LIN_OUT_BF16), no gate.  Codes, x,
+ * out, bias and res 16-byte aligned, scale bytes 4-byte aligned, ldx % 8 == 0, ldo % 4 == 0, ldres % 4 == 0.  A lane decodes one whole MX block
+ * in registers (v_cvt_scalef32_pk32_bf16_fp6); no bf16 copy of the matrix is read.  No atomics, no split K and one fixed K order (the 128-wide
+ * steps ascending, inside a step k = 32 c + 8 h + i with h = 0..3 ascending): a row's result does not depend on the other rows of the call, bit
+ * for bit.  The bit is a flag of its own because VV_MXFP6 with VV_LIN_W_MXGEMM is refused, and stays refused.  Any other call with the bit
+ * (another wdt, VV_LIN_W_MXGEMM or VV_LIN_W_FRAG beside it, fp32 x, a prologue, m < 3, n % 16, k % 128, missing scales, a gate, a misaligned
+ * operand) returns VV_E_UNSUPPORTED from vv_linear and vv_linear_route alike, nothing launched; every call without the bit is taken or refused
+ * exactly as before */
+enum { VV_LIN_W_MX6GEMM = 64 };
 
 const char* vv_last_error(void);
 int vv_abi_version(void);
@@ -206,7 +219,7 @@ int vv_linear(const vv_lin_args* a, vv_stream_t stream);
 /* The kernel family vv_linear would launch for *a under the current vv_tune state, written to name[cap]: decided by the very code vv_linear
  * launches through, without a launch and without touching the device (pointers count for their alignment only).  For the many-row matrix-core
  * GEMM the instantiation, "mfma_stream<dual=0,ksplit=1,xb=1,mt=4>" or "mfma_tiled<dual=0,bk=128,tm=64>", or "gemm_packed<dual=0,obf=0>" for
- * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call;
+ * a VV_LIN_PACKED call its kernel takes (dual: w2 given, obf: VV_LIN_OUT_BF16), "gemm_mx<dual=0,obf=0>" for a VV_LIN_W_MXGEMM call, "gemm_mx6<dual=0,obf=0>" for a VV_LIN_W_MX6GEMM call;
  * "skinny<nst=20,nb=1>" for the resampling convs' skinny GEMM (k = 4 waves x nb bursts x nst steps of 32) and
  * "gemm_f32<w=bf16,dual=0,vec=1,tile=32>" for the fp32 LDS-tiled GEMM (w f32 | bf16; vec: float4 loads; tile 32 | 64); and for the
  * m <= 8 family (fp8, NF4, MXFP4 and MXFP6 weights included) the kernel itself:

@@ -22,6 +22,7 @@ VV_WQ_FRAG6 = 0x1000   # next to VV_WQ_MXFP6: the layers' f_* copies hold the VV
 PRO_NONE, PRO_RMSNORM, PRO_SILU = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SWIGLU = 0, 1, 2
 LIN_X_BF16, LIN_OUT_BF16, LIN_W_REUSED, LIN_W_FRAG, LIN_PACKED, LIN_W_MXGEMM = 1, 2, 4, 8, 16, 32
+LIN_W_MX6GEMM = 64     # the matrix-core GEMM on VV_MXFP6 codes (csrc/vv_gemm_mx6.hip); a bit of its own: VV_MXFP6 with LIN_W_MXGEMM stays refused
 VV_MAX_STAGES = 8
 KVQ_DERIVE_SCALES = 1  # vv_kv_quantize flags
 

@@ -9,7 +9,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("vv_kernels.hip", "vv_gemv_stream.hip", "vv_gemv_mx6.hip", "vv_gemv_hot.hip", "vv_conv_hot.hip", "vv_gemv_rows.hip", "vv_gemv_rows_mx6.hip", "vv_mfma_gemm.hip", "vv_gemm_packed.hip", "vv_gemm_mx.hip", "vv_block1d.hip", "vv_convffn.hip",
+SRC = [os.path.join(HERE, "csrc", f) for f in ("vv_kernels.hip", "vv_gemv_stream.hip", "vv_gemv_mx6.hip", "vv_gemv_hot.hip", "vv_conv_hot.hip", "vv_gemv_rows.hip", "vv_gemv_rows_mx6.hip", "vv_mfma_gemm.hip", "vv_gemm_packed.hip", "vv_gemm_mx.hip", "vv_gemm_mx6.hip", "vv_block1d.hip", "vv_convffn.hip",
                                                "vv_fused.hip", "vv_attn_decode.hip", "vv_attn_prefill.hip", "vv_model.hip",
                                                "vv_nf4_import.hip", "vv_kv_copy.hip", "vv_noise.hip")]
 HDR = [os.path.join(ROOT, "include", "vv_hip.h"), os.path.join(HERE, "csrc", "vv_common.h"), os.path.join(HERE, "csrc", "vv_device.h"),

@@ -135,6 +135,10 @@ int vv_gemm_packed_init();
 int vv_gemm_mx_check(const vv_lin_args& a);
 int vv_launch_gemm_mx(const vv_lin_args& a, hipStream_t s);
 int vv_gemm_mx_route_name(const vv_lin_args& a, char* name, int cap);
+// vv_gemm_mx6.hip: the same for VV_MXFP6 codes (gemm_mx6_kernel<dual, obf>), taken by VV_LIN_W_MX6GEMM calls alone
+int vv_gemm_mx6_check(const vv_lin_args& a);
+int vv_launch_gemm_mx6(const vv_lin_args& a, hipStream_t s);
+int vv_gemm_mx6_route_name(const vv_lin_args& a, char* name, int cap);
 // vv_attn_decode.hip: bf16 KV cache, head_dim 128; part / tickets = split-key workspace ([R, heads, nsplit, 130] floats, [R, heads] zeroed ints) or null
 // part_cap: splits the partials workspace has room for (>= nsplit); the grouped kernel may use more splits than the per-head kernel's nsplit
 int vv_launch_attn_decode(const float* qkv, int64_t ld_qkv, int R, int heads, const vv_kv* kv, int layer, const float2* rope, const int* lens, float* out,

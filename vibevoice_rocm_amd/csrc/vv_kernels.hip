@@ -806,6 +806,7 @@ static int linear_check_args(const vv_lin_args* a) {
   if (a->act != VV_ACT_SWIGLU && a->w2) return vv_set_error(VV_E_ARG, "vv_linear: w2 given without SWIGLU");
   if (a->mod_scale && (!a->mod_shift || a->pro != VV_PRO_RMSNORM)) return vv_set_error(VV_E_ARG, "vv_linear: modulate needs RMSNORM prologue and shift");
   if (a->m > 8 && a->ldx == 0) return vv_set_error(VV_E_ARG, "vv_linear: broadcast rows (ldx=0) only for m<=8");
+  if (a->flags & VV_LIN_W_MX6GEMM) return vv_gemm_mx6_check(*a);    // the GEMM on MXFP6 codes, likewise (it refuses VV_LIN_W_MXGEMM beside its own bit)
   if (a->flags & VV_LIN_W_MXGEMM) return vv_gemm_mx_check(*a);      // the GEMM on MXFP4 codes: its own unit says what it takes, every other rule below is for calls without the bit
   int rc = VV_E_UNSUPPORTED;
   const wq_format* f = wq_format_of(*a);      // a weight-only format: what a call must be is written once, next to the kernels of the format's unit
@@ -838,6 +839,7 @@ extern "C" int vv_linear_route(const vv_lin_args* a, char* name, int cap) {
     else if (fam == LIN_FAM_GEMM_F32) gemm_f32_route_name(*a, gemm_f32_decide(*a), name, cap);
   }
   else if (!wq_format_of(*a)) return vv_set_error(VV_E_ARG, "vv_linear: bad wdt %d", a->wdt);
+  if (a->flags & VV_LIN_W_MX6GEMM) { vv_gemm_mx6_route_name(*a, name, cap); return 0; }    // linear_check_args has asked vv_gemm_mx6_check
   if (a->flags & VV_LIN_W_MXGEMM) { vv_gemm_mx_route_name(*a, name, cap); return 0; }      // linear_check_args has asked vv_gemm_mx_check
   if (fam == LIN_FAM_GEMV) {
     gemv_route g;
@@ -858,7 +860,8 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
     if (hipEventCreate(&pr.e0) != hipSuccess || hipEventCreate(&pr.e1) != hipSuccess) return vv_set_error(VV_E_HIP, "vv_linear: event create");
     (void)hipEventRecord(pr.e0, s);
   }
-  if (a->flags & VV_LIN_W_MXGEMM) rc = vv_launch_gemm_mx(*a, s);      // wdt == VV_MXFP4 and everything else the kernel needs: linear_check_args
+  if (a->flags & VV_LIN_W_MX6GEMM) rc = vv_launch_gemm_mx6(*a, s);    // wdt == VV_MXFP6 and everything else the kernel needs: linear_check_args
+  else if (a->flags & VV_LIN_W_MXGEMM) rc = vv_launch_gemm_mx(*a, s);      // wdt == VV_MXFP4 and everything else the kernel needs: linear_check_args
   else if (a->wdt == VV_F32) rc = launch_linear<float>(*a, s);
   else if (a->wdt == VV_BF16) rc = launch_linear<bf16_t>(*a, s);
   else if (wq_format_of(*a)) {      // a weight-only format (WQ_FORMATS): its unit's GEMV, or refused (gemv_decide)
@@ -881,13 +884,14 @@ extern "C" int vv_linear(const vv_lin_args* a, vv_stream_t stream) {
 // such a copy runs the bf16 rows kernel on its row-major matrix
 int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* part, size_t part_floats, int* tickets, size_t n_tickets, vv_stream_t stream,
                  const vv_w8* q1, const vv_w8* q2, int fragq) {
-  // a lean MXFP4 model's matrix (vv_hip.h: w == NULL, for a SwiGLU pair w2 too): its VV_MXFP4_FRAG copy serves the call or nothing does
+  // a lean MXFP4 / MXFP6 model's matrix (vv_hip.h: w == NULL, for a SwiGLU pair w2 too): its VV_MXFP4_FRAG / VV_MXFP6_FRAG copy serves the call or nothing does
   vv_lin_args lean_a;
   const bool lean = a && !a->w && a->x && a->out;
   if (lean) {
     const bool dual = a->act == VV_ACT_SWIGLU;
-    if (fragq != VV_MXFP4_FRAG || !f1 || (dual && !f2) || a->m < 3 || a->m > 8 || a->wdt != VV_BF16)
-      return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean mxfp4 model (no bf16 matrix is resident): m=%d rows need the matrix's VV_MXFP4_FRAG copy and 3..8 rows", a->m);
+    if ((fragq != VV_MXFP4_FRAG && fragq != VV_MXFP6_FRAG) || !f1 || (dual && !f2) || a->m < 3 || a->m > 8 || a->wdt != VV_BF16)
+      return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean %s model (no bf16 matrix is resident): m=%d rows need the matrix's %s copy and 3..8 rows",
+                          fragq == VV_MXFP6_FRAG ? "mxfp6" : "mxfp4", a->m, fragq == VV_MXFP6_FRAG ? "VV_MXFP6_FRAG" : "VV_MXFP4_FRAG");
     lean_a = *a;
     lean_a.w = f1; lean_a.w2 = dual ? f2 : nullptr;
     a = &lean_a;
@@ -923,7 +927,8 @@ int vv_linear_ws(const vv_lin_args* a, const void* f1, const void* f2, float* pa
     if (rc == 1) { VV_CHECK_LAUNCH("vv_linear(rows)"); return 0; }
   }
   if (lean)       // w stands in for a matrix that does not exist: no row-major route may read it
-    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean mxfp4 model (no bf16 matrix is resident): the MXFP4 rows kernel does not take m=%d n=%d k=%d", a->m, a->n, a->k);
+    return vv_set_error(VV_E_UNSUPPORTED, "vv_linear_ws: lean %s model (no bf16 matrix is resident): the MX rows kernel does not take m=%d n=%d k=%d",
+                        fragq == VV_MXFP6_FRAG ? "mxfp6" : "mxfp4", a->m, a->n, a->k);
   if (a && a->wdt == VV_BF16 && a->m > 8 && a->m <= 16 && a->ldx != 0 && !(a->flags & (VV_LIN_X_BF16 | VV_LIN_OUT_BF16)) && a->x && a->w && a->out) {
     // 9..16 rows the 16-row GEMV does not take (no bf16 fragment-major copy, a K it does not cover): two passes of 5..8 rows, each on the route
     // the 8-row step takes for this matrix - vv_linear at these row counts would round the activations to bf16 once on the matrix-core GEMM

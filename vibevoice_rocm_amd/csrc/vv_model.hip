@@ -74,7 +74,7 @@ static size_t rows_tickets(const vv_llm* m) {
   return vv_gemv_rows_tickets(n > m->hidden ? n : m->hidden);
 }
 
-// A lean MXFP4 LLM (vv_hip.h): the layers' bf16 pointers are NULL beside present MXFP4 companions.  1 = lean, 0 = every matrix resident, < 0 = a
+// A lean MXFP4 / MXFP6 LLM (vv_hip.h): the layers' bf16 pointers are NULL beside present MX companions.  1 = lean, 0 = every matrix resident, < 0 = a
 // descriptor that is neither (VV_E_ARG) or a lean one whose shapes the GEMM on the codes does not take (VV_E_UNSUPPORTED).  Host only
 static int llm_lean(const char* who, const vv_llm* m) {
   if (!m->layer || m->layers <= 0) return 0;
@@ -84,17 +84,19 @@ static int llm_lean(const char* who, const vv_llm* m) {
     nul += !L.wqkv + !L.wo + !L.wgate + !L.wup + !L.wdown;
   }
   if (!nul) return 0;
-  if (nul != 5 * m->layers) return vv_set_error(VV_E_ARG, "%s: %d of %d LLM matrices are NULL: a lean mxfp4 model has none of them, any other model all", who, nul, 5 * m->layers);
-  if (!(m->wdt & VV_WQ_MXFP4) || (m->wdt & 0xff) != VV_BF16) return vv_set_error(VV_E_ARG, "%s: NULL LLM matrices (the lean mode) need VV_BF16 | VV_WQ_MXFP4", who);
+  if (nul != 5 * m->layers) return vv_set_error(VV_E_ARG, "%s: %d of %d LLM matrices are NULL: a lean mxfp4 / mxfp6 model has none of them, any other model all", who, nul, 5 * m->layers);
+  const bool mx4 = (m->wdt & VV_WQ_MXFP4) != 0, mx6 = (m->wdt & VV_WQ_MXFP6) != 0;
+  if (mx4 == mx6 || (m->wdt & 0xff) != VV_BF16) return vv_set_error(VV_E_ARG, "%s: NULL LLM matrices (the lean mode) need VV_BF16 | VV_WQ_MXFP4 or VV_BF16 | VV_WQ_MXFP6", who);
+  const char* fmt = mx6 ? "mxfp6" : "mxfp4";
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];
     for (const vv_w8* q : {&L.q_qkv, &L.q_o, &L.q_gate, &L.q_up, &L.q_down})
-      if (!q->q || !q->scale) return vv_set_error(VV_E_ARG, "%s: lean mxfp4 model: layer %d has neither a bf16 matrix nor an MXFP4 companion", who, l);
+      if (!q->q || !q->scale) return vv_set_error(VV_E_ARG, "%s: lean %s model: layer %d has neither a bf16 matrix nor an MX companion", who, fmt, l);
   }
   const int qd = m->heads * m->head_dim, qkvd = (m->heads + 2 * m->kv_heads) * m->head_dim;
   if (m->hidden % 128 || m->inter % 128 || qd % 128 || qkvd % 16)
-    return vv_set_error(VV_E_UNSUPPORTED, "%s: lean mxfp4 model: hidden=%d inter=%d q width=%d must be multiples of 128 and the qkv width %d of 16 "
-                        "(the GEMM on the codes takes n %% 16 == 0, k %% 128 == 0)", who, m->hidden, m->inter, qd, qkvd);
+    return vv_set_error(VV_E_UNSUPPORTED, "%s: lean %s model: hidden=%d inter=%d q width=%d must be multiples of 128 and the qkv width %d of 16 "
+                        "(the GEMM on the codes takes n %% 16 == 0, k %% 128 == 0)", who, fmt, m->hidden, m->inter, qd, qkvd);
   return 1;
 }
 
@@ -125,16 +127,18 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   const int H = m->hidden, d = m->head_dim, qd = m->heads * d, qkvd = (m->heads + 2 * m->kv_heads) * d;
   const bool decode = (cache_rows == nullptr && R <= kv->rows);
   if (lean && decode && R > 2 && R < VV_PREFILL_ROWS) {
-    // lean: no bf16 matrix is resident, so a 3..8-row decode pass runs on the VV_MXFP4_FRAG copies or not at all, and 9..16 rows not at all -
-    // said here, before the first launch
-    bool copies = fragq == VV_MXFP4_FRAG && R <= 8;
+    // lean: no bf16 matrix is resident, so a 3..8-row decode pass runs on the VV_MXFP4_FRAG / VV_MXFP6_FRAG copies or not at all, and 9..16 rows
+    // not at all - said here, before the first launch
+    const bool six = wq == VV_MXFP6;
+    bool copies = fragq == (six ? VV_MXFP6_FRAG : VV_MXFP4_FRAG) && R <= 8;
     for (int l = 0; copies && l < m->layers; ++l) {
       const vv_llm_layer& L = m->layer[l];
       copies = L.f_qkv && L.f_o && L.f_gate && L.f_up && L.f_down;
     }
     if (!copies)
-      return vv_set_error(VV_E_UNSUPPORTED, "%s: lean mxfp4 model (no bf16 LLM matrices): a decode pass of %d rows needs the VV_MXFP4_FRAG copies of every layer "
-                          "(VV_WQ_FRAG4, mxfp4_row_batch=True) and 3..8 rows; 9..16 rows need bf16 copies, which the lean mode does not keep", who, R);
+      return vv_set_error(VV_E_UNSUPPORTED, "%s: lean %s model (no bf16 LLM matrices): a decode pass of %d rows needs the %s copies of every layer "
+                          "(%s=True) and 3..8 rows; 9..16 rows need bf16 copies, which the lean mode does not keep", who, six ? "mxfp6" : "mxfp4", R,
+                          six ? "VV_MXFP6_FRAG" : "VV_MXFP4_FRAG", six ? "VV_WQ_FRAG6, mxfp6_row_batch" : "VV_WQ_FRAG4, mxfp4_row_batch");
   }
   Carver c(ws);
   float* h = c.take((size_t)R * H);
@@ -146,7 +150,7 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   const float* hin = x;
   int64_t ldh = ldx;
   VV_TRY(vv_rope_table(lens, m->inv_freq, R, d, rope, stream));
-  // a lean model casts from 3 rows on in every non-decode pass: its matrices exist as codes alone, which the GEMM of vv_gemm_mx.hip reads
+  // a lean model casts from 3 rows on in every non-decode pass: its matrices exist as codes alone, which the GEMMs of vv_gemm_mx.hip / vv_gemm_mx6.hip read
   const bool prefill = (R >= VV_PREFILL_ROWS || (lean && R > 2 && !decode)) && m->wdt == VV_BF16 && H % 16 == 0 && m->inter % 16 == 0 && qd % 16 == 0;
   void* xb = prefill ? (void*)c.take((size_t)R * (m->inter > H ? m->inter : H) / 2 + 64) : nullptr;
   float* att_part = c.take(att_rows(R) * m->heads * VV_ATT_PART_SPLITS * (d + 2));
@@ -189,13 +193,13 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
     // or, under VV_WQ_FRAG4 / VV_WQ_FRAG6, the VV_MXFP4_FRAG / VV_MXFP6_FRAG form of the MX companions
     return vv_linear_ws(&a, f1, f2, rpart, rpart_n, rtick, rtick_n, stream, wq == VV_FP8 ? q1 : nullptr, wq == VV_FP8 ? q2 : nullptr, fragq);
   };
-  // lean, outside the rows kernel: the matrix is its MXFP4 companion - under VV_LIN_W_MXGEMM in the prefill branch, as the streaming GEMV's
-  // operand at 1..2 rows (what use_w8 does for a model that has both)
+  // lean, outside the rows kernel: the matrix is its MXFP4 / MXFP6 companion - under VV_LIN_W_MXGEMM / VV_LIN_W_MX6GEMM in the prefill branch, as the
+  // streaming GEMV's operand at 1..2 rows (what use_w8 does for a model that has both)
   auto lean_w = [&](vv_lin_args& a, const vv_w8& q, const vv_w8* q2 = nullptr) {
     if (!lean || rows8) return;
-    a.w = q.q; a.wscale = q.scale; a.wdt = VV_MXFP4;
+    a.w = q.q; a.wscale = q.scale; a.wdt = wq;      // VV_MXFP4 or VV_MXFP6: llm_lean admits no other kind
     if (q2) { a.w2 = q2->q; a.w2scale = q2->scale; }
-    if (prefill) a.flags |= VV_LIN_W_MXGEMM;
+    if (prefill) a.flags |= wq == VV_MXFP6 ? VV_LIN_W_MX6GEMM : VV_LIN_W_MXGEMM;
   };
   for (int l = 0; l < m->layers; ++l) {
     const vv_llm_layer& L = m->layer[l];

@@ -69,7 +69,7 @@ class Engine:
                  kv_dtype: Optional[torch.dtype] = None, use_graphs: bool = True, bf16_timestep_quirk: Optional[bool] = None,
                  weight_quant: Optional[str] = None, stream: Optional[torch.cuda.Stream] = None, weights_from: Optional["Engine"] = None,
                  prequant: Optional[dict] = None, kv_cache_dtype: Optional[str] = None, mxfp4_row_batch: bool = False, mxfp4_lean: bool = False,
-                 mxfp6_row_batch: bool = False):
+                 mxfp6_row_batch: bool = False, mxfp6_lean: bool = False):
         self.kv_fp8 = check_kv_cache_dtype(kv_cache_dtype, dtype, cfg.head_dim)
         self.lib = L.load()
         self.cfg = cfg
@@ -99,7 +99,7 @@ class Engine:
                 self.w = weights_from.w.fork()
             else:
                 self.w = DeviceWeights(cfg, state_dict, self.device, dtype, quant=weight_quant, prequant=prequant, mxfp4_row_batch=mxfp4_row_batch,
-                                       mxfp4_lean=mxfp4_lean, mxfp6_row_batch=mxfp6_row_batch)
+                                       mxfp4_lean=mxfp4_lean, mxfp6_row_batch=mxfp6_row_batch, mxfp6_lean=mxfp6_lean)
             H = cfg.hidden
             f32 = dict(dtype=torch.float32, device=self.device)
             self.x2 = torch.zeros(2, H, **f32)            # input embedding of the step, rows {positive, negative}

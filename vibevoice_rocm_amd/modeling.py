@@ -724,7 +724,7 @@ class VibeVoiceForConditionalGenerationInference:
                  attn_implementation: str = "hip_gfx950", use_graphs: bool = True, weight_quant: Optional[str] = None, prequant=None,
                  kv_cache_dtype: Optional[str] = None, device_sampling: bool = False, device_noise: bool = False, mxfp4_row_batch: bool = False,
                  seeded_tokens: bool = False, row_batch_width: int = 4, packed_prefill: bool = False, packed_prefill_rows: int = PACKED_PREFILL_ROWS,
-                 batched_conv_rows: bool = False, mxfp4_lean: bool = False, mxfp6_row_batch: bool = False):
+                 batched_conv_rows: bool = False, mxfp4_lean: bool = False, mxfp6_row_batch: bool = False, mxfp6_lean: bool = False):
         # batched_conv_rows: a row batch runs the one-row stage (C = 2048) of the acoustic decoder and the semantic encoder, and the connectors,
         # once for all its dialogues - one pass over 78 % of the tokenizers' weights instead of one per dialogue (csrc/vv_conv_hot.hip, DESIGN.md
         # section 5o).  bf16 weights without companions only.  Off by default; generate(batched_conv_rows=) overrides it per call, a session
@@ -777,6 +777,12 @@ class VibeVoiceForConditionalGenerationInference:
         if mxfp6_row_batch and config.hidden > MXFP6_ROWS_MAX_HIDDEN:
             raise ValueError(f"mxfp6_row_batch=True serves LLM hidden sizes up to {MXFP6_ROWS_MAX_HIDDEN}, not {config.hidden}")
         self.mxfp6_row_batch = bool(mxfp6_row_batch)
+        # mxfp6_lean=True (weight_quant="mxfp6" only): the LLM's matrices are held as MXFP6 codes alone - no bf16 copies - and the prompt passes
+        # run a matrix-core GEMM on the codes (csrc/vv_gemm_mx6.hip).  Memory is the point: -2 B per LLM weight.  Composes
+        # with every other option of an mxfp6 model; without mxfp6_row_batch batches run on the lanes and sessions are refused, as without it
+        if mxfp6_lean and weight_quant != "mxfp6":
+            raise ValueError(f"mxfp6_lean=True needs weight_quant='mxfp6', not {weight_quant!r}")
+        self.mxfp6_lean = bool(mxfp6_lean)
         missing = [k for k in shapes if k not in state_dict and k not in (prequant or {})]
         if missing:
             raise KeyError(f"state dict is missing {len(missing)} tensors, e.g. {missing[:4]}")
@@ -815,7 +821,7 @@ class VibeVoiceForConditionalGenerationInference:
         self.weight_quant = weight_quant
         self.engine = Engine(config, state_dict, device=device, dtype=torch_dtype, use_graphs=use_graphs, weight_quant=weight_quant,
                              prequant=prequant, kv_cache_dtype=kv_cache_dtype, mxfp4_row_batch=self.mxfp4_row_batch,
-                             mxfp4_lean=self.mxfp4_lean, mxfp6_row_batch=self.mxfp6_row_batch)
+                             mxfp4_lean=self.mxfp4_lean, mxfp6_row_batch=self.mxfp6_row_batch, mxfp6_lean=self.mxfp6_lean)
         self.device = self.engine.device
         # batches run in lock step on one Engine per sample (own HIP stream, KV cache and conv state; matrices already in the streamed
         # dtype on the device are shared, not copied): lanes beyond the first are built on first use from this state dict
@@ -867,7 +873,7 @@ class VibeVoiceForConditionalGenerationInference:
                    mxfp4_row_batch=kw.get("mxfp4_row_batch", False), seeded_tokens=kw.get("seeded_tokens", False),
                    row_batch_width=kw.get("row_batch_width", 4), packed_prefill=kw.get("packed_prefill", False),
                    packed_prefill_rows=kw.get("packed_prefill_rows", PACKED_PREFILL_ROWS), batched_conv_rows=kw.get("batched_conv_rows", False),
-                   mxfp4_lean=kw.get("mxfp4_lean", False), mxfp6_row_batch=kw.get("mxfp6_row_batch", False))
+                   mxfp4_lean=kw.get("mxfp4_lean", False), mxfp6_row_batch=kw.get("mxfp6_row_batch", False), mxfp6_lean=kw.get("mxfp6_lean", False))
 
     @classmethod
     def from_synthetic(cls, config: VVConfig, seed: int = 1234, device="cuda:0", torch_dtype=torch.bfloat16, numpy_weights=False, **kw):

@@ -292,13 +292,14 @@ class DeviceWeights:
 
     def __init__(self, cfg: VVConfig, sd: Dict[str, torch.Tensor], device, wdtype=torch.bfloat16, streaming_state=True, quant=None,
                  prequant: Optional[Dict[str, object]] = None, mxfp4_row_batch: bool = False, mxfp4_lean: bool = False,
-                 mxfp6_row_batch: bool = False):
+                 mxfp6_row_batch: bool = False, mxfp6_lean: bool = False):
         """prequant: the matrices a pre-quantized bitsandbytes NF4 checkpoint holds in 4-bit form ({weight key: bnb.BnbNF4}, not in `sd`); they
         are imported as they are (vv_nf4_import) and need quant="nf4".  mxfp4_row_batch (quant="mxfp4" only): the 3..8-row paths stream the
         MXFP4 companions in fragment-major form (VV_WQ_FRAG4 on the LLM's and the head's descriptors; ensure_frag builds the copies).
-        mxfp6_row_batch (quant="mxfp6" only): the same for the MXFP6 companions (VV_WQ_FRAG6, the VV_MXFP6_FRAG form); the bf16 matrices stay.
+        mxfp6_row_batch (quant="mxfp6" only): the same for the MXFP6 companions (VV_WQ_FRAG6, the VV_MXFP6_FRAG form); the bf16 matrices stay unless mxfp6_lean drops the LLM's.
         mxfp4_lean (quant="mxfp4" only): the LLM's matrices exist as MXFP4 codes alone - no bf16 copy is uploaded, their descriptor pointers are
         NULL and every pass of 3 or more prompt rows runs the GEMM on the codes (csrc/vv_gemm_mx.hip; lean_report lists what was dropped).
+        mxfp6_lean (quant="mxfp6" only): the same for the MXFP6 codes (csrc/vv_gemm_mx6.hip), with the same list of what is kept.
         Kept in bf16, because something still reads them in that form:
           * matrices without a companion (embeddings / lm_head, the head's projections and adaLN, connectors, the tokenizers' convs);
           * a companion-set matrix whose shape the GEMM refuses (N % 16, K % 128) - then none of the LLM's is dropped, a model is lean as a whole;
@@ -308,6 +309,9 @@ class DeviceWeights:
         if mxfp4_lean and quant != "mxfp4":
             raise ValueError(f"mxfp4_lean=True drops the bf16 copies of the MXFP4 matrices: it needs weight_quant='mxfp4', not {quant!r}")
         self.mxfp4_lean = bool(mxfp4_lean)
+        if mxfp6_lean and quant != "mxfp6":
+            raise ValueError(f"mxfp6_lean=True drops the bf16 copies of the MXFP6 matrices: it needs weight_quant='mxfp6', not {quant!r}")
+        self.mxfp6_lean = bool(mxfp6_lean)
         self._lean_dropped: List[Dict[str, object]] = []      # lean_report(): {"name", "n", "k", "bytes"} per matrix that has no bf16 copy
         if mxfp4_row_batch and quant != "mxfp4":
             raise ValueError(f"mxfp4_row_batch=True serves the MXFP4 companions on the row-batched path: it needs weight_quant='mxfp4', not {quant!r}")
@@ -411,7 +415,7 @@ class DeviceWeights:
         """(bf16 matrix, vv_w8 companion) in the model's format (WEIGHT_FORMATS): the companion holds the codes and scales in the format's layout,
         the bf16 copy the effective weights - exact in bf16 in every format (fp8: power-of-two row scales; nf4: bf16(table[code] * absmax);
         mxfp4 / mxfp6: value(code) * 2^(e - 127)).  A matrix whose K the format's block does not divide gets no companion.  lean (a name for
-        lean_report, mxfp4 only): the bf16 copy is not made - (None, companion); the effective matrix lives while the codes are packed."""
+        lean_report, mxfp4 / mxfp6 only): the bf16 copy is not made - (None, companion); the effective matrix lives while the codes are packed."""
         w8 = L.W8()
         f = WEIGHT_FORMATS[self.quant] if quantise and self.quant else None
         if f is None or (f.block and t.shape[1] % f.block):
@@ -423,7 +427,7 @@ class DeviceWeights:
         codes, scales = self._aligned(codes.to(self.device)), self._aligned(scales.to(self.device))
         self._keep += [codes, scales]
         w8.q, w8.scale = L.ptr(codes), L.ptr(scales)      # scale: fp32 scales (fp8, nf4) or the address of the E8M0 scale BYTES (vv_hip.h)
-        if lean is not None and self.quant == "mxfp4":
+        if lean is not None and self.quant in ("mxfp4", "mxfp6"):
             n, k = t.shape
             self._lean_dropped.append({"name": lean, "n": int(n), "k": int(k), "bytes": 2 * int(n) * int(k)})
             return None, w8
@@ -620,8 +624,8 @@ class DeviceWeights:
         return t
 
     def lean_report(self) -> List[Dict[str, object]]:
-        """The matrices an mxfp4_lean model holds as MXFP4 codes alone: [{"name", "n", "k", "bytes"}], bytes = 2 n k = the bf16 copy that was not
-        uploaded (nbytes() of the same model without mxfp4_lean is larger by exactly their sum).  Empty without the mode."""
+        """The matrices an mxfp4_lean / mxfp6_lean model holds as MX codes alone: [{"name", "n", "k", "bytes"}], bytes = 2 n k = the bf16 copy that
+        was not uploaded (nbytes() of the same model without the keyword is larger by exactly their sum).  Empty without the mode."""
         return [dict(d) for d in self._lean_dropped]
 
     def nbytes(self) -> int:
@@ -639,7 +643,7 @@ class DeviceWeights:
         # lean: all of the LLM's matrices or none (csrc/vv_model.hip takes a model whose five pointers are NULL in every layer) - every one of
         # them must be a shape the GEMM on the codes takes: N % 16 == 0, K % 128 == 0
         qd, qkvd = cfg.heads * cfg.head_dim, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim
-        lean = self.mxfp4_lean and not (cfg.hidden % 128 or cfg.inter % 128 or qd % 128 or qkvd % 16)
+        lean = (self.mxfp4_lean or self.mxfp6_lean) and not (cfg.hidden % 128 or cfg.inter % 128 or qd % 128 or qkvd % 16)
         for l in range(cfg.layers):
             q = f"{p}layers.{l}."
             qz = self.quant is not None
