@@ -242,7 +242,8 @@ int vv_linear_route(const vv_lin_args* a, char* name, int cap);
  * KV cache layout: k, v = [layers][rows][kv_heads][s_max][head_dim], dtype kvdt.
  * Each of the R query rows carries lens[r] (device int: its absolute position == number of tokens cached before
  * it) and cache_rows[r] (device int or NULL = r): decode uses rows {positive, negative}; prefill uses R prompt
- * tokens that all append to cache row 0 with lens = pos0 + r.
+ * tokens that all append to cache row 0 with lens = pos0 + r.  cache_rows == NULL with R > kv->rows names cache rows the
+ * cache does not have: vv_rope_store, vv_attn, vv_llm_forward return VV_E_ARG before anything is launched.
  * vv_rope_store: RoPE (half rotation, fp32 cos/sin from inv_freq) on q and k of qkv[R, (heads+2 kv_heads)*d]
  *   in place, and store k, v at slot lens[r] of the cache.
  * vv_attn: out[r, h*d ..] = softmax(q k^T / sqrt(d)) v over slots 0..lens[r] (inclusive), GQA, fp32 softmax.

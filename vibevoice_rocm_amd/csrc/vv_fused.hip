@@ -424,7 +424,8 @@ __global__ __launch_bounds__(256) void conn_fc2_pair_kernel(const ConnPairArgs a
     nv[0][c] = *reinterpret_cast<const float4*>(a.nw_a + kk);
     nv[1][c] = *reinterpret_cast<const float4*>(a.nw_s + kk);
   }
-  // this wave's rows: gw, gw + nwaves, ... (at most 2 at the shipped shapes); the first row's weights are requested before the prologue
+  // this wave's rows: gw, gw + nwaves, ... - rows_per_wave = ceil(H / 768) rounds: 2 at H = 1536, 5 at H = 3584, where the last round is ragged
+  // (512 of its 768 waves have a row; the others load row 0 and store nothing); the first row's weights are requested before the prologue
   const int nwaves = gridDim.x * 4, gw = blockIdx.x * 4 + wave;
   uint4 wa[KU], wsm[KU];
   auto issue = [&](int row) {

@@ -1012,6 +1012,7 @@ extern "C" int vv_rope_store(float* qkv, int64_t ld_qkv, int R, int heads, const
   const float2* inv_freq = reinterpret_cast<const float2*>(rope_table);
   if (!qkv || !kv || !inv_freq || !lens) return vv_set_error(VV_E_ARG, "vv_rope_store: null pointer");
   if (layer < 0 || layer >= kv->layers || R <= 0) return vv_set_error(VV_E_ARG, "vv_rope_store: bad layer/R");
+  if (!cache_rows && R > kv->rows) return vv_set_error(VV_E_ARG, "vv_rope_store: cache_rows == NULL means row r owns cache row r, but R=%d > %d cache rows", R, kv->rows);
   if (kv->head_dim % 2) return vv_set_error(VV_E_ARG, "vv_rope_store: odd head_dim");
   if (kv->kvdt != VV_F32 && kv->kvdt != VV_BF16) return vv_set_error(VV_E_UNSUPPORTED, "vv_rope_store: an fp8 KV cache is written by vv_kv_quantize and vv_attn_decode only (kv dtype %d)", kv->kvdt);
   hipStream_t s = (hipStream_t)stream;
@@ -1292,6 +1293,7 @@ extern "C" int vv_attn(const float* qkv, int64_t ld_qkv, int R, int heads, const
   if (layer < 0 || layer >= kv->layers) return vv_set_error(VV_E_ARG, "vv_attn: bad layer/R/heads");
   const vv_attn_route_t rt = vv_attn_decide(qkv, ld_qkv, R, heads, kv, out, ldo);
   if (rt.kind < 0) return rt.kind;
+  if (!cache_rows && R > kv->rows) return vv_set_error(VV_E_ARG, "vv_attn: cache_rows == NULL means row r reads cache row r, but R=%d > %d cache rows", R, kv->rows);
   hipStream_t s = (hipStream_t)stream;
   if (rt.kind == VV_ATTN_PREFILL) return vv_launch_attn_prefill(qkv, ld_qkv, R, heads, kv, layer, lens, cache_rows, out, ldo, s);
   if (rt.kind == VV_ATTN_GROUP) {

@@ -119,13 +119,15 @@ static int llm_forward(const char* who, const vv_llm* m, const vv_kv* kv, const 
   if (R <= 0) return vv_set_error(VV_E_ARG, "%s: R=%d", who, R);
   if (kv->layers != m->layers || kv->kv_heads != m->kv_heads || kv->head_dim != m->head_dim)
     return vv_set_error(VV_E_ARG, "%s: kv cache shape does not match the model", who);
+  // cache_rows == NULL means row r owns cache row r (vv_hip.h): more rows than the cache has would be stored outside it
+  if (!cache_rows && R > kv->rows) return vv_set_error(VV_E_ARG, "%s: cache_rows == NULL (row r owns cache row r) with R=%d > %d cache rows", who, R, kv->rows);
   const int lean_rc = llm_lean(who, m);
   if (lean_rc < 0) return lean_rc;
   const bool lean = lean_rc == 1;
   VV_WQ_STRIP(vv_llm, m);
   hipStream_t s = (hipStream_t)stream;
   const int H = m->hidden, d = m->head_dim, qd = m->heads * d, qkvd = (m->heads + 2 * m->kv_heads) * d;
-  const bool decode = (cache_rows == nullptr && R <= kv->rows);
+  const bool decode = cache_rows == nullptr;      // R <= kv->rows: checked above
   if (lean && decode && R > 2 && R < VV_PREFILL_ROWS) {
     // lean: no bf16 matrix is resident, so a 3..8-row decode pass runs on the VV_MXFP4_FRAG / VV_MXFP6_FRAG copies or not at all, and 9..16 rows
     // not at all - said here, before the first launch
